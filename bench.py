@@ -42,6 +42,7 @@ HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md "Chip-leve
 THRESHOLD = 0.5
 SEED = 42
 CHECK_ROWS = 2_000_000  # prefix every --workload is checked on against the oracle
+DUMP_MAX_BYTES = 64 << 20
 
 
 KERNEL_SOURCES = ("rdf_spec_kernel.hip.h", "rdf_spec.hip", "rdf_common.hip.h", "rdf_expr.hip.h", "rdf_gspec_kernel.hip.h", "rdf_groupby.hip", "rdf_eval.hip")
@@ -175,6 +176,19 @@ def _close(a, b, rtol=1e-6):
     return a == b or abs(a - b) <= rtol * max(abs(a), abs(b))
 
 
+def dump_outputs(path, arrays):
+    """--dump-outputs: what the timed path handed its caller in the last step, one float64 DIR/<name>.npy per array (a NULL
+    scalar as NaN).  The inputs are seeded, so two builds run with the same arguments can be compared output for output."""
+    import numpy as np
+    arrays = {k: np.atleast_1d(np.asarray(np.nan if v is None else v, dtype=np.float64)) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        sys.exit(f"bench.py --dump-outputs: {total} bytes of outputs, more than the {DUMP_MAX_BYTES} allowed")
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def workload_c3(torch, lib, api, A, sharding, dev, comm_dev, rank, rows, first, total, opts):
     """C3: fused a*b+c -> min/max/count and the i64 key's min/max/count, one pass over 4 columns (32 B/row)."""
     g = Gen(torch, lib, dev)
@@ -261,14 +275,20 @@ def workload_c4(torch, lib, api, A, sharding, dev, comm_dev, rank, rows, first, 
         last["groups"] = (mk_, ms_, mc_)
         return {"groups_owned": mk_.length, "exchange": "partial groups", **ex.stats}
 
-    def check(res, world_):
-        import numpy as np
+    L = lib.load()
+
+    def host_groups():
+        """The groups this rank owns after the last step, copied to the host: keys, sums, counts."""
         gk, gs, gc = last["groups"]
         n = gk.length
         hk = torch.empty(n, dtype=torch.int64); hs = torch.empty(n, dtype=torch.float64); hc = torch.empty(n, dtype=torch.int64)
-        L = lib.load()
         L.rdf_copy_d2h(hk.data_ptr(), gk.values_ptr, n * 8); L.rdf_copy_d2h(hs.data_ptr(), gs.values_ptr, n * 8); L.rdf_copy_d2h(hc.data_ptr(), gc.values_ptr, n * 8)
-        hk, hs, hc = hk.numpy(), hs.numpy(), hc.numpy()
+        return hk, hs, hc
+
+    def check(res, world_):
+        import numpy as np
+        hk, hs, hc = (t.numpy() for t in host_groups())
+        n = len(hk)
         # invariants of the full-size result: no key twice, every count positive, counts add up to the rows and the
         # group sums to the column sum (all ranks' shares together when N > 1)
         e = A.Expr()
@@ -302,6 +322,25 @@ def workload_c4(torch, lib, api, A, sharding, dev, comm_dev, rank, rows, first, 
             out["cpu_baseline"] = {"value": m / dt_o, "unit": "rows/s", "cores": 1, "kind": "port",
                                    "sample": f"rows [0,{m}): hash GROUP BY key -> sum, count (oracle), median of 3 warmed runs"}
         return out
+
+    def outputs():
+        """Every rank's groups in one key-ascending set (collective when N > 1): placed by key into dense columns and summed over
+        the ranks, which is exact because every key is owned by one rank only."""
+        hk, hs, hc = host_groups()
+        sums = torch.zeros(ngroups, dtype=torch.float64)
+        counts = torch.zeros(ngroups, dtype=torch.float64)
+        sums[hk] = hs
+        counts[hk] = hc.to(torch.float64)
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized():
+            on = comm_dev if comm_dev is not None else "cpu"
+            sums, counts = sums.to(on), counts.to(on)
+            dist.all_reduce(sums)
+            dist.all_reduce(counts)
+            sums, counts = sums.cpu(), counts.cpu()
+        keys = counts.nonzero().flatten()
+        return {"keys": keys.numpy(), "sums": sums[keys].numpy(), "counts": counts[keys].numpy()}
+    opts["outputs"] = outputs
     return step, 16.0 * rows, f"C4: hash GROUP BY key -> sum(val), {ngroups:.0e} keys over {rows:.0e} rows per GPU", check
 
 
@@ -410,7 +449,7 @@ def run_ref_bench(args, lib, api, A):
                 return False
         return True
 
-    calls = max(1000, args.steps)
+    calls = args.steps
     res = {}
     for name, x in (("gpu", api), ("cpu", o)):
         outs, carr, call = caller(x)
@@ -425,6 +464,12 @@ def run_ref_bench(args, lib, api, A):
         t_all = time.perf_counter() - t_all
         res[name] = {"median_us": statistics.median(ts) * 1e6, "mean_us": t_all / calls * 1e6, "min_us": min(ts) * 1e6,
                      "p99_us": sorted(ts)[int(0.99 * (calls - 1))] * 1e6, "parity": bool(ok(outs, carr))}
+        if name == "gpu" and args.dump_outputs:
+            prod = np.full((n, 5), np.nan)         # the 380 product arrays of the last call, NULL as NaN
+            for i, q in enumerate(outs):
+                m = q.valid_mask()
+                prod[i, m] = q.to_numpy()[m]
+            dump_outputs(args.dump_outputs, {"product": prod})
     g, c_ = res["gpu"], res["cpu"]
     line = {"metric": "calls/s par_multiply::<Int32Type>, 380 chunks x 5 values (the reference's bench_multiply_i32)", "value": 1e6 / g["median_us"], "unit": "calls/s",
             "n_gpus": 1, "steps": calls, "warmup": max(20, args.warmup), "ms_per_step": g["median_us"] * 1e-3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -460,7 +505,7 @@ def _self_launch(args):
     import socket
     import subprocess
     with socket.socket() as s_:
-        s_.bind(("127.0.0.1", 0))
+        s_.bind(("", 0))          # free on every address: the rendezvous store listens on all of them
         port = s_.getsockname()[1]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", RDF_BENCH_SELF_LAUNCHED="1")
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -523,7 +568,11 @@ def main():
     ap.add_argument("--workload", default="headline", choices=["headline", "ref_bench"] + sorted(WORKLOADS),
                     help="headline = BASELINE.json's metric (the default, what the driver runs); c3 / c4 / q1 = the other configs; "
                          "ref_bench = the reference's own bench_multiply_i32 shape (380 chunks x 5 Int32 values), device path end to end against the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned to its caller as DIR/<name>.npy (float64, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world == 1 and args.gpus > 1 and "RANK" not in os.environ:
@@ -550,22 +599,22 @@ def main():
         sharding.FORCE_COLLECTIVES = bool(args.force_exchange)
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+        store = None
         if world == 1:
-            import socket
-            with socket.socket() as s_:
-                s_.bind(("127.0.0.1", 0))
-                os.environ.setdefault("MASTER_PORT", str(s_.getsockname()[1]))
+            # one rank meets nobody: an in-process store, no TCP port (a port probed free on the loopback address can still be
+            # taken on another address of the host when the store binds it on all of them)
+            store = dist.HashStore()
             os.environ.setdefault("RANK", "0")
             os.environ.setdefault("WORLD_SIZE", "1")
         want_native = args.backend == "nccl" and args.comm == "native"
         if want_native:
             # CPU tensors (the unique id, barriers, the max-over-ranks clock) travel over gloo; torch's own RCCL communicator is
             # created only if the library's cannot be (CUDA tensors of the fallback harness)
-            dist.init_process_group("cpu:gloo,cuda:nccl", rank=rank, world_size=world)
+            dist.init_process_group("cpu:gloo,cuda:nccl", rank=rank, world_size=world, store=store)
         elif args.backend == "nccl":
-            dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local_rank))
+            dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local_rank), store=store)
         else:
-            dist.init_process_group(args.backend, rank=rank, world_size=world)
+            dist.init_process_group(args.backend, rank=rank, world_size=world, store=store)
     lib.set_device(local_rank)
     api = lib.api()
     dev = torch.device("cuda", local_rank)
@@ -649,14 +698,13 @@ def main():
         if fused_combine:
             # N > 1, the library's communicator: kernel, all-gather of the partials and their fold in ONE call, all on the device
             # (rdf_pipeline_dist / rdf_pipeline_frame_dist): the host waits once per step
-            tot = native.pipeline_dist(e, frame, [c], pred)[0]
-            return tot.sum, tot.count
+            return native.pipeline_dist(e, frame, [c], pred)[0]
         local = api.pipeline(e, frame, [c], pred)          # fused filter -> {sum,min,max,count}, one pass over HBM
         tc = time.perf_counter()
         # N > 1: all-gather the partials (RCCL), fold in rank order — rdf_agg_combine inside the library, or the torch harness
         tot = (native.agg_combine(local) if native is not None else sharding.all_combine(local, device=comm_dev))[0]
         combine_s[0] += time.perf_counter() - tc
-        return tot.sum, tot.count
+        return tot
 
     def sync():
         torch.cuda.synchronize()
@@ -672,7 +720,7 @@ def main():
     combine_s[0] = 0.0          # (the warm-up steps carry the communicator's lazy initialisation)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        res = step()
+        tot = step()
     sync()
     barrier()
     sync()
@@ -680,6 +728,9 @@ def main():
     kern_ms, kern_n = lib.kernel_timing_get()
     kernel_name = lib.last_kernel()
     lib.kernel_timing_reset(False)
+    res = (tot.sum, tot.count)
+    if args.dump_outputs and rank == 0:      # (every rank holds the same combined result)
+        dump_outputs(args.dump_outputs, {"sum": tot.sum, "min": tot.min, "max": tot.max, "count": tot.count})
     per_rank = None
     if dist is not None:
         # every rank's own share of the result (its shard alone, one more untimed call) travels with its times: the shares must add up
@@ -857,6 +908,11 @@ def run_other(args, torch, lib, api, A, sharding, dev, comm_dev, dist, rank, wor
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
     chk = check(res, world)     # untimed; collective when N > 1 (every rank takes part)
+    if args.dump_outputs:
+        # opts["outputs"]: the arrays the last step's caller received, when they are more than the step's result (collective when N > 1)
+        arrays = opts["outputs"]() if "outputs" in opts else res
+        if rank == 0:
+            dump_outputs(args.dump_outputs, arrays)
     if native is not None:
         native.destroy()
     if dist is not None:

@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -26,7 +27,7 @@ def _run(workload, gpus, rows, port, launcher="torchrun", flags=(), **extra_env)
     if gpus > 1 and launcher == "torchrun":
         import socket
         with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as sk:   # a port nobody listens on (the number passed in is only a label)
-            sk.bind(("127.0.0.1", 0))
+            sk.bind(("", 0))            # on any address: the rendezvous store listens on all of them
             port = sk.getsockname()[1]
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={gpus}", "--master-addr", "127.0.0.1",
                "--master-port", str(port)] + base + ["--backend", "gloo", "--share-gpu"]
@@ -77,23 +78,24 @@ def test_c4_two_ranks_row_shuffle():
     assert cfg["groups_total"] == 1_000_000 and cfg["result"].get("exchange") == "rows", cfg
 
 
-def test_eight_ranks_small_shards_through_bench_main():
-    """The driver's N = 8 command line end to end through bench.py's own main() at 1e6 rows per rank (eight processes on the one
-    GPU, gloo): every rank's share of the result is gathered and must add up to the combined count before the line is printed;
-    the line carries every rank's step time, kernel time and roofline fraction.  C4 at eight ranks: every key owned once."""
-    h8 = _run("headline", 8, 1_000_000, 0)
-    h1 = _run("headline", 1, 8_000_000, 0)
-    cfg = h8["config"]
-    assert h8["n_gpus"] == 8 and cfg["total_rows"] == 8_000_000 and cfg["result_count"] == h1["config"]["result_count"]
+def test_four_ranks_small_shards_through_bench_main():
+    """The driver's N > 2 command line end to end through bench.py's own main() at 1e6 rows per rank (four processes on the one
+    GPU, gloo; with the launcher's and the test's own processes that is the most a shared GPU may have open at once): every
+    rank's share of the result is gathered and must add up to the combined count before the line is printed; the line carries
+    every rank's step time, kernel time and roofline fraction.  C4 at four ranks: every key owned once."""
+    h4 = _run("headline", 4, 1_000_000, 0)
+    h1 = _run("headline", 1, 4_000_000, 0)
+    cfg = h4["config"]
+    assert h4["n_gpus"] == 4 and cfg["total_rows"] == 4_000_000 and cfg["result_count"] == h1["config"]["result_count"]
     assert abs(cfg["result_sum"] - h1["config"]["result_sum"]) <= 1e-12 * h1["config"]["result_sum"]
     pr = cfg["per_rank"]
-    assert len(pr["result_count"]) == 8 and sum(pr["result_count"]) == cfg["result_count"] and min(pr["result_count"]) > 0
-    assert len(pr["roofline_frac"]) == 8 and all(f is not None and 0 < f < 1 for f in pr["roofline_frac"]), pr
-    assert h8["roofline"]["frac_wall"] <= h8["roofline"]["frac"] * 1.05
-    c8 = _run("c4", 8, 1_000_000, 0)
-    cc = c8["config"]
-    assert c8["n_gpus"] == 8 and cc["self_check"] is True and cc["parity_on_sample"] is True, cc
-    assert cc["check_totals"]["sum_of_group_counts"] == 8_000_000
+    assert len(pr["result_count"]) == 4 and sum(pr["result_count"]) == cfg["result_count"] and min(pr["result_count"]) > 0
+    assert len(pr["roofline_frac"]) == 4 and all(f is not None and 0 < f < 1 for f in pr["roofline_frac"]), pr
+    assert h4["roofline"]["frac_wall"] <= h4["roofline"]["frac"] * 1.05
+    c4 = _run("c4", 4, 1_000_000, 0)
+    cc = c4["config"]
+    assert c4["n_gpus"] == 4 and cc["self_check"] is True and cc["parity_on_sample"] is True, cc
+    assert cc["check_totals"]["sum_of_group_counts"] == 4_000_000
 
 
 def test_q1_two_ranks_equal_one():
@@ -170,3 +172,36 @@ def test_exchange_in_rounds():
         assert cfg["self_check"] is True and cfg["parity_on_sample"] is True and 999_000 < cfg["groups_total"] <= 1_000_000, cfg
         one = _run("c4", 1, 12_000_000, 0, flags=["--force-exchange", "--backend", "nccl"], RDF_A2A_MAX_BYTES=str(1 << 20), **env)
         assert one["config"]["self_check"] is True and one["config"]["groups_total"] == cfg["groups_total"], one["config"]
+
+
+# ------------------------------------------------------------------ --dump-outputs, --steps
+def test_dump_outputs_hold_the_last_steps_results(tmp_path):
+    """--dump-outputs DIR: what the last timed step handed its caller, one float64 .npy per array — the headline's combined
+    aggregate, C4's groups in key order (the same groups from one rank and from two), Q1's six groups, ref_bench's 380 products;
+    the inputs are seeded, so a second run writes the same values.  --steps is the number of timed steps (kernel launches)."""
+    def run(name, workload, gpus, rows):
+        out = _run(workload, gpus, rows, 0, flags=["--dump-outputs", str(tmp_path / name)])
+        return out, {f[:-len(".npy")]: np.load(tmp_path / name / f) for f in os.listdir(tmp_path / name)}
+
+    h, d = run("headline", "headline", 1, 4_000_000)
+    assert h["steps"] == 2 and h["roofline"]["launches"] == 2, h["roofline"]
+    assert sorted(d) == ["count", "max", "min", "sum"] and all(a.dtype == np.float64 and a.shape == (1,) for a in d.values()), d
+    assert d["sum"][0] == h["config"]["result_sum"] and d["count"][0] == h["config"]["result_count"]
+    assert 0.5 < d["min"][0] <= d["max"][0] < 1.0
+    _, again = run("headline_again", "headline", 1, 4_000_000)
+    assert all(np.array_equal(d[k], again[k]) for k in d), (d, again)
+
+    c1, g1 = run("c4_one_rank", "c4", 1, 4_000_000)
+    _, g2 = run("c4_two_ranks", "c4", 2, 2_000_000)
+    assert sorted(g1) == ["counts", "keys", "sums"] and len(g1["keys"]) == c1["config"]["groups_total"]
+    assert np.all(np.diff(g1["keys"]) > 0) and g1["counts"].sum() == 4_000_000
+    assert abs(g1["sums"].sum() - c1["config"]["check_totals"]["column_sum"]) <= 1e-9 * c1["config"]["check_totals"]["column_sum"]
+    assert np.array_equal(g1["keys"], g2["keys"]) and np.array_equal(g1["counts"], g2["counts"])
+    assert np.allclose(g1["sums"], g2["sums"], rtol=1e-12, atol=0)
+
+    q, dq = run("q1", "q1", 1, 2_000_000)
+    assert sorted(dq) == sorted(q["config"]["result"]) and all(list(dq[k]) == q["config"]["result"][k] for k in dq), (dq, q["config"]["result"])
+
+    r, dr = run("ref_bench", "ref_bench", 1, 0)
+    assert r["steps"] == 2 and dr["product"].shape == (380, 5)
+    assert np.array_equal(dr["product"], np.tile([np.nan, 40000.0, np.nan, 65536.0, np.nan], (380, 1)), equal_nan=True)
