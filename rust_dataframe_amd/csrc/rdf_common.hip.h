@@ -210,8 +210,9 @@ __device__ __forceinline__ void block_reduce_agg(int cls, uint64_t sum, uint64_t
 // out directly: Cody-Waite reduction by pi/2 in four FMA steps (the first three constants hold 33 bits each, so
 // k * constant is exact for |k| < 2^16 and the chain keeps the RELATIVE accuracy of r even next to a zero of the
 // function), then a polynomial kernel.  tan divides the two degree-13 / degree-12 minimax kernels of fdlibm's k_sin.c /
-// k_cos.c on |r| <= pi/4.  Checked on the host against glibc over 2e7 points incl. the neighbourhood of every multiple of
-// pi/2 below 1e5: <= 2 ulp, relative error <= 3.2e-16.  Arguments with |x| >= 1e5, infinities and NaNs take the libm path.
+// k_cos.c on |r| <= pi/4.  tests/test_float_accuracy_gpu.py holds tan to <= 4 ulp of the exact value (measured on the device:
+// 3.84, at x = 46639.304862655372).
+// Arguments with |x| >= 1e5, infinities and NaNs take the libm path.
 __device__ __forceinline__ void trig_reduce(double x, double& r, int& q) {
     const double kd = rint(x * 6.36619772367581382433e-01);   // 2 / pi
     q = (int)kd;
@@ -235,7 +236,8 @@ __device__ __forceinline__ double trig_kcos(double r) {
 // sin / cos use ONE odd polynomial on [-pi/2, pi/2] instead (x = m * pi/2 + r with m even for sin, odd for cos; the sign is
 // the parity of m / 2): sin r = r + r z P(z), P of degree 7 in z = r^2 fitted at Chebyshev nodes in 60-digit arithmetic
 // (relative error 3.6e-17 before rounding).  About half the arithmetic of evaluating both quarter-pi kernels and
-// selecting; same host check: <= 2 ulp, relative error <= 2.7e-16, cos(0) == 1, sin(-0.0) == -0.0.
+// selecting.  Held to <= 2.5 ulp of the exact value by tests/test_float_accuracy_gpu.py (measured on the device: 2.37 for sin
+// at x = -75885.045330917957, 2.23 for cos); cos(0) == 1, sin(-0.0) == -0.0.
 __device__ __forceinline__ double trig_reduce_m(double x, double md) {
     double t = fma(-md, 1.57079632673412561417e+00, x);
     t = fma(-md, 6.07710050630396597660e-11, t);
@@ -282,7 +284,8 @@ __device__ __forceinline__ double rdf_tan(double x) {
 // fence each row's ~20-deep FMA chain off from its neighbours.  Here ONE wave-wide test covers all R rows (a single lane
 // holding one large argument sends the wave's R rows down the per-row path — rare, and still correct), and the common path
 // is branch-free: R independent chains the scheduler interleaves, the tiny-argument result picked by a select.
-// KIND 0 = sin, 1 = cos, 2 = tan.  Same arithmetic per element as the scalar functions: bit-identical results.
+// KIND 0 = sin, 1 = cos, 2 = tan.  Same arithmetic per element as the scalar functions: bit-identical results (tested, with
+// and without a wave-mate on the per-row path).
 // (the per-row path is a real call: inlined R times, libm's Payne-Hanek reduction set the kernel's register count — 117
 // VGPRs, 4 waves per SIMD — for a path that almost never runs)
 template <int KIND>
@@ -326,8 +329,8 @@ __device__ __forceinline__ void rdf_trig_rows(const double (&a)[R], double (&out
 // — two FMAs against pi split in two doubles, good for every |x| < 1e9 with the relative accuracy of r kept next to the zeros
 // of the function — and ONE odd polynomial of degree 9 runs in f32 on [-pi/2, pi/2] (weighted least squares at Chebyshev nodes
 // in 50-digit arithmetic; the error is the f32 rounding of its evaluation).  14 vector instructions against the device libm's
-// ~40 with its own branches.  Checked on the host against (float)sin((double)x) over 2.4e8 points incl. every multiple of pi/2
-// below 6e6 and its neighbours: <= 2.0 ulp, relative error <= 1.2e-7; sin(-0.0f) == -0.0f, cos(0) == 1.  |x| >= 1e9, inf, NaN: libm.
+// ~40 with its own branches.  Held to <= 2 ulp of the exact value by tests/test_float_accuracy_gpu.py (every f32 within 4 ulps
+// of k pi/2, k <= 4e6: measured 1.97 sin, 1.98 cos); sin(-0.0f) == -0.0f, cos(0) == 1.  |x| >= 1e9, inf, NaN: libm.
 __device__ __forceinline__ float trigf_psin(float r, int k) {
     const float z = r * r;
     float p = 2.6052944122056942e-06f;

@@ -192,7 +192,7 @@ __device__ __forceinline__ double unary_f64(int op, double x) {
             case RDF_OP_COS: return rdf_cos(x);
             case RDF_OP_COSH: return cosh(x);
             case RDF_OP_EXP: return exp(x);
-            case RDF_OP_EXPM1: return expm1(x);
+            case RDF_OP_EXPM1: return x == 0.0 ? x : expm1(x);      // (the device libm returns +0 for -0; C99 F.9.3.5 keeps the sign)
             case RDF_OP_LOG10: return log10(x);
             case RDF_OP_LOG2: return log2(x);
             case RDF_OP_SIN: return rdf_sin(x);
@@ -228,7 +228,7 @@ __device__ __forceinline__ float unary_f32(int op, float x) {
             case RDF_OP_COS: return rdf_cos(x);
             case RDF_OP_COSH: return coshf(x);
             case RDF_OP_EXP: return expf(x);
-            case RDF_OP_EXPM1: return expm1f(x);
+            case RDF_OP_EXPM1: return x == 0.0f ? x : expm1f(x);
             case RDF_OP_LOG10: return log10f(x);
             case RDF_OP_LOG2: return log2f(x);
             case RDF_OP_SIN: return rdf_sin(x);

@@ -207,7 +207,7 @@ struct Un {
         else if constexpr (OP == RDF_OP_COSH) return cosh(x);
         else if constexpr (OP == RDF_OP_DEGREES) return x * (180.0 / 3.14159265358979323846264338327950288);
         else if constexpr (OP == RDF_OP_EXP) return exp(x);
-        else if constexpr (OP == RDF_OP_EXPM1) return expm1(x);
+        else if constexpr (OP == RDF_OP_EXPM1) return x == (T)0 ? x : expm1(x);   // (the device libm returns +0 for -0; C99 F.9.3.5 keeps the sign)
         else if constexpr (OP == RDF_OP_FLOOR) return floor(x);
         else if constexpr (OP == RDF_OP_LOG10) return log10(x);
         else if constexpr (OP == RDF_OP_LOG2) return log2(x);

@@ -3,6 +3,7 @@
 Mirrors the reference's own test style (in-file unit tests per kernel) with two-sided
 checks: integers/bitmaps bit-exact, floats within util.RTOL = 1e-6 relative.
 """
+import math
 import os
 
 import numpy as np
@@ -187,6 +188,10 @@ def test_aggregates(gpu, ora, dtype):
             mag = sum(float(np.abs(ch.to_numpy()[ch.valid_mask()].astype(np.float64)).sum()) for ch in a)
             n = sum(ch.length for ch in a)
             assert abs(gpu.sum(a) - ora.sum(a)) <= max(1e-6 * abs(ora.sum(a)), n * 2.0 ** -24 * mag), "sum " + what
+            # the device side against the exact sum: the f64 fold's bound plus the one rounding to f32
+            exact = math.fsum(float(t) for ch in a for t in ch.to_numpy()[ch.valid_mask()])
+            half_ulp = 0.5 * float(np.spacing(np.float32(abs(exact)))) if exact else 2.0 ** -150
+            assert abs(gpu.sum(a) - exact) <= half_ulp + n * 2.0 ** -53 * mag, "exact sum " + what
         else:
             assert_scalar_close(gpu.sum(a), ora.sum(a), dtype, "sum " + what)
         assert_scalar_close(gpu.min(a), ora.min(a), dtype, "min " + what)
