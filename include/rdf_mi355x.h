@@ -369,6 +369,40 @@ rdf_status rdf_list_intersect(const rdf_list_array* a, const rdf_list_array* b, 
 rdf_status rdf_list_union(const rdf_list_array* a, const rdf_list_array* b, rdf_out* out_offsets, rdf_out* out_values);
 rdf_status rdf_list_repeat(const rdf_list_array* list, int32_t count, rdf_out* out_offsets, rdf_out* out_values);
 
+/* ------------------------------------------------------------------ Utf8 (StringArray) columns */
+
+/* A StringArray (Utf8, Int32 offsets): row i is the bytes data[offsets[i] .. offsets[i+1]).  `offsets` is an RDF_I32
+ * array of rows + 1 elements whose validity / offset / null_count describe the ROWS; `data` is an RDF_U8 array of the
+ * value bytes (its validity is ignored).  Bytes are valid UTF-8 (Arrow's guarantee; not re-checked). */
+typedef struct { rdf_array offsets; rdf_array data; } rdf_utf8_array;
+
+/* Column::filter / Column::take and the string ScalarFunctions over chunked StringArrays.  `chunks[i]` is chunk i; the
+ * outputs are out_offsets[i] (RDF_I32, rows + 1 entries starting at 0, row validity in its `validity` and `null_count`)
+ * and out_data[i] (RDF_U8).  A NULL input row gives a NULL output row of zero bytes (StringBuilder::append(false)).
+ * Sizing, one rule for all of them: on return out_data[i].length holds the bytes of chunk i (out_offsets[i].length its
+ * rows + 1).  If any out_data[i].capacity (or, for filter, out_offsets[i].capacity) is too small the call returns
+ * RDF_MEMORY_ERROR with those lengths set for every chunk and nothing written: values == NULL, capacity == 0 is the
+ * sizing call.  Input bytes bound the output of filter, trim and substring, 3 x input bytes that of lower / upper.
+ * An output chunk beyond 2^31-1 bytes is RDF_COMPUTE_ERROR (Int32 offsets).  Input offsets are used as given (offset
+ * by the row `offset`, the first not necessarily 0); the first and last must lie within data.length.  An output whose
+ * rows can be NULL needs out_offsets[i].validity.
+ *   filter:    Column::filter (src/table.rs:97-107): per chunk the rows whose mask bit is set AND valid, order and chunk
+ *              boundaries kept; mask[i].length == rows of chunk i.
+ *   take:      Column::take (src/table.rs:213-241): gather over the virtual concatenation of the chunks; `indices` is one
+ *              RDF_U32 / RDF_U64 array; a NULL index gives NULL, out of range RDF_COMPUTE_ERROR.  ONE output chunk.
+ *   trim / ltrim / rtrim: str::trim / trim_start / trim_end: Unicode White_Space (Rust's char::is_whitespace) stripped.
+ *   substring: chars().skip(pos).take(len) (scalar.rs:428-441), counted in code points; pos, len >= 0.
+ *   lower / upper: str::to_lowercase / to_uppercase: full Unicode case mapping (one-to-many mappings, Final_Sigma), from
+ *              the Unicode version recorded in rdf_unicode_case.h. */
+rdf_status rdf_utf8_filter(const rdf_utf8_array* chunks, const rdf_array* mask, int64_t nchunks, rdf_out* out_offsets, rdf_out* out_data);
+rdf_status rdf_utf8_take(const rdf_utf8_array* chunks, int64_t nchunks, const rdf_array* indices, rdf_out* out_offsets, rdf_out* out_data);
+rdf_status rdf_utf8_trim(const rdf_utf8_array* chunks, int64_t nchunks, rdf_out* out_offsets, rdf_out* out_data);
+rdf_status rdf_utf8_ltrim(const rdf_utf8_array* chunks, int64_t nchunks, rdf_out* out_offsets, rdf_out* out_data);
+rdf_status rdf_utf8_rtrim(const rdf_utf8_array* chunks, int64_t nchunks, rdf_out* out_offsets, rdf_out* out_data);
+rdf_status rdf_utf8_substring(const rdf_utf8_array* chunks, int64_t nchunks, int64_t pos, int64_t len, rdf_out* out_offsets, rdf_out* out_data);
+rdf_status rdf_utf8_lower(const rdf_utf8_array* chunks, int64_t nchunks, rdf_out* out_offsets, rdf_out* out_data);
+rdf_status rdf_utf8_upper(const rdf_utf8_array* chunks, int64_t nchunks, rdf_out* out_offsets, rdf_out* out_data);
+
 /* ------------------------------------------------------------------ fused batch loop */
 
 typedef enum {

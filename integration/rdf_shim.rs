@@ -57,6 +57,7 @@ pub mod sys {
     pub struct rdf_group_result { pub sum_f64: f64, pub sum_i64: i64, pub count: i64, pub is_some: i32, pub dtype: i32 }
     #[repr(C)] #[derive(Clone, Copy)] pub struct rdf_sort_options { pub descending: i32, pub nulls_first: i32 }
     #[repr(C)] #[derive(Clone, Copy)] pub struct rdf_list_array { pub offsets: rdf_array, pub values: rdf_array }
+    #[repr(C)] #[derive(Clone, Copy)] pub struct rdf_utf8_array { pub offsets: rdf_array, pub data: rdf_array }
     #[repr(C)] pub struct rdf_frame { _opaque: [u8; 0] }
     #[repr(C)] pub struct rdf_comm { _opaque: [u8; 0] }
     #[repr(C)] #[derive(Clone, Copy, Default)]
@@ -155,6 +156,15 @@ pub mod sys {
         pub fn rdf_list_intersect(a: *const rdf_list_array, b: *const rdf_list_array, out_offsets: *mut rdf_out, out_values: *mut rdf_out) -> i32;
         pub fn rdf_list_union(a: *const rdf_list_array, b: *const rdf_list_array, out_offsets: *mut rdf_out, out_values: *mut rdf_out) -> i32;
         pub fn rdf_list_repeat(list: *const rdf_list_array, count: i32, out_offsets: *mut rdf_out, out_values: *mut rdf_out) -> i32;
+        // Utf8 (StringArray) columns: Column::filter / take and the string ScalarFunctions; one sizing rule for all (header)
+        pub fn rdf_utf8_filter(chunks: *const rdf_utf8_array, mask: *const rdf_array, nchunks: i64, out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
+        pub fn rdf_utf8_take(chunks: *const rdf_utf8_array, nchunks: i64, indices: *const rdf_array, out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
+        pub fn rdf_utf8_trim(chunks: *const rdf_utf8_array, nchunks: i64, out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
+        pub fn rdf_utf8_ltrim(chunks: *const rdf_utf8_array, nchunks: i64, out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
+        pub fn rdf_utf8_rtrim(chunks: *const rdf_utf8_array, nchunks: i64, out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
+        pub fn rdf_utf8_substring(chunks: *const rdf_utf8_array, nchunks: i64, pos: i64, len: i64, out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
+        pub fn rdf_utf8_lower(chunks: *const rdf_utf8_array, nchunks: i64, out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
+        pub fn rdf_utf8_upper(chunks: *const rdf_utf8_array, nchunks: i64, out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
         // the fused batch loop (src/evaluation.rs:66-96); host-resident frames above one slab are streamed (rdf_stream_stats says how)
         pub fn rdf_jit_status() -> *const c_char;          // the run-time compiler: found or not, cache directory, counts
         pub fn rdf_stream_stats(slabs: *mut i64, bytes_staged: *mut i64, bytes_direct: *mut i64) -> i32;
@@ -202,7 +212,7 @@ pub mod sys {
 // (2) views over Arrow arrays, output buffers, error mapping
 
 use self::sys::*;
-use arrow::array::{Array, ArrayData, ArrayRef, BooleanArray, ListArray, PrimitiveArray, UInt32Array};
+use arrow::array::{Array, ArrayData, ArrayRef, BooleanArray, ListArray, PrimitiveArray, StringArray, UInt32Array};
 use arrow::buffer::MutableBuffer;
 use arrow::datatypes::{ArrowNumericType, ArrowPrimitiveType, DataType};
 use arrow::error::ArrowError;
@@ -423,6 +433,75 @@ pub fn array_contains<T: ArrowNumericType>(array: &ListArray, val: T::Native) ->
     let mut out = buf.as_out();
     status(unsafe { rdf_list_contains(&l, &val as *const T::Native as *const c_void, &mut out) })?;
     Ok(buf.finish(&out))
+}
+
+/// A StringArray travels as two views, nothing copied: its value_offsets (Int32, len + 1, carrying the row validity and the
+/// row offset of a slice) and its value bytes.
+pub fn utf8_view(array: &StringArray) -> rdf_utf8_array {
+    let data = array.data();
+    let bytes = data.buffers()[1].len();
+    rdf_utf8_array {
+        offsets: rdf_array { values: data.buffers()[0].raw_data() as *const c_void,
+                             validity: data.null_buffer().map_or(std::ptr::null(), |b| b.raw_data()),
+                             offset: data.offset() as i64, length: array.len() as i64 + 1, null_count: -1, dtype: RDF_I32, mem: RDF_MEM_HOST },
+        data: rdf_array { values: data.buffers()[1].raw_data() as *const c_void, validity: std::ptr::null(), offset: 0,
+                          length: bytes as i64, null_count: 0, dtype: RDF_U8, mem: RDF_MEM_HOST },
+    }
+}
+/// One rdf_utf8_* call made twice: the sizing call (no data buffers), then into buffers of exactly the reported sizes.
+fn utf8_call(rows: &[usize], nullable: &[bool], call: &dyn Fn(*mut rdf_out, *mut rdf_out) -> i32) -> Result<Vec<ArrayRef>, ArrowError> {
+    let mut obufs: Vec<OutBuf> = rows.iter().zip(nullable).map(|(r, n)| OutBuf::new(DataType::Int32, r + 1, *n)).collect();
+    let mut oo: Vec<rdf_out> = obufs.iter_mut().map(|b| b.as_out()).collect();
+    let mut od: Vec<rdf_out> = rows.iter().map(|_| rdf_out { values: std::ptr::null_mut(), validity: std::ptr::null_mut(), capacity: 0,
+                                                           length: 0, null_count: 0, dtype: RDF_U8, mem: RDF_MEM_HOST }).collect();
+    let code = call(oo.as_mut_ptr(), od.as_mut_ptr());
+    if code != RDF_OK && code != RDF_MEMORY_ERROR { status(code)?; }
+    let mut dbufs: Vec<OutBuf> = od.iter().map(|o| OutBuf::new(DataType::UInt8, o.length as usize, false)).collect();
+    if code == RDF_MEMORY_ERROR {
+        let mut oo2: Vec<rdf_out> = obufs.iter_mut().map(|b| b.as_out()).collect();
+        let mut od2: Vec<rdf_out> = dbufs.iter_mut().map(|b| b.as_out()).collect();
+        status(call(oo2.as_mut_ptr(), od2.as_mut_ptr()))?;
+        oo = oo2; od = od2;
+    }
+    Ok(obufs.into_iter().zip(dbufs).zip(oo.iter().zip(od.iter())).map(|((ob, db), (o, d))| {
+        let offs = ob.finish(o);
+        let bytes = db.finish(d);
+        let b = ArrayData::builder(DataType::Utf8).len(o.length as usize - 1).null_count(o.null_count as usize)
+            .add_buffer(offs.data().buffers()[0].clone()).add_buffer(bytes.data().buffers()[0].clone());
+        let b = match offs.data().null_buffer() { Some(v) => b.null_bit_buffer(v.clone()), None => b };
+        arrow::array::make_array(b.build())
+    }).collect())
+}
+/// ScalarFunctions::{lower, upper, trim, ltrim, rtrim} (src/functions/scalar.rs:315-427) over the chunks of a column.
+pub fn utf8_unary(op: &str, chunks: &[&StringArray]) -> Result<Vec<ArrayRef>, ArrowError> {
+    let v: Vec<rdf_utf8_array> = chunks.iter().map(|c| utf8_view(c)).collect();
+    let f = match op { "lower" => rdf_utf8_lower, "upper" => rdf_utf8_upper, "trim" => rdf_utf8_trim, "ltrim" => rdf_utf8_ltrim,
+                       "rtrim" => rdf_utf8_rtrim, _ => return Err(ArrowError::ComputeError(format!("no Utf8 function {}", op))) };
+    let rows: Vec<usize> = chunks.iter().map(|c| c.len()).collect();
+    let nullable: Vec<bool> = chunks.iter().map(|c| c.null_count() > 0 || c.data().null_buffer().is_some()).collect();
+    utf8_call(&rows, &nullable, &|oo, od| unsafe { f(v.as_ptr(), v.len() as i64, oo, od) })
+}
+/// substring (scalar.rs:428-441): chars().skip(pos).take(len).
+pub fn utf8_substring(chunks: &[&StringArray], pos: usize, len: usize) -> Result<Vec<ArrayRef>, ArrowError> {
+    let v: Vec<rdf_utf8_array> = chunks.iter().map(|c| utf8_view(c)).collect();
+    let rows: Vec<usize> = chunks.iter().map(|c| c.len()).collect();
+    let nullable: Vec<bool> = chunks.iter().map(|c| c.data().null_buffer().is_some()).collect();
+    utf8_call(&rows, &nullable, &|oo, od| unsafe { rdf_utf8_substring(v.as_ptr(), v.len() as i64, pos as i64, len as i64, oo, od) })
+}
+/// Column::filter (src/table.rs:97-107) of a Utf8 column by one BooleanArray per chunk.
+pub fn utf8_filter(chunks: &[&StringArray], masks: &[&BooleanArray]) -> Result<Vec<ArrayRef>, ArrowError> {
+    let v: Vec<rdf_utf8_array> = chunks.iter().map(|c| utf8_view(c)).collect();
+    let m: Vec<rdf_array> = masks.iter().map(|b| view(*b)).collect();
+    let rows: Vec<usize> = chunks.iter().map(|c| c.len()).collect();
+    let nullable: Vec<bool> = chunks.iter().map(|c| c.data().null_buffer().is_some()).collect();
+    utf8_call(&rows, &nullable, &|oo, od| unsafe { rdf_utf8_filter(v.as_ptr(), m.as_ptr(), v.len() as i64, oo, od) })
+}
+/// Column::take (src/table.rs:213-241) of a Utf8 column: one output chunk.
+pub fn utf8_take(chunks: &[&StringArray], indices: &UInt32Array) -> Result<ArrayRef, ArrowError> {
+    let v: Vec<rdf_utf8_array> = chunks.iter().map(|c| utf8_view(c)).collect();
+    let idx = view(indices);
+    let nullable = indices.data().null_buffer().is_some() || chunks.iter().any(|c| c.data().null_buffer().is_some());
+    Ok(utf8_call(&[indices.len()], &[nullable], &|oo, od| unsafe { rdf_utf8_take(v.as_ptr(), v.len() as i64, &idx, oo, od) })?.remove(0))
 }
 
 // Evaluate::evaluate (src/evaluation.rs:66-96): fuse each maximal run of Calculate / Filter steps into ONE rdf_pipeline call —

@@ -98,6 +98,10 @@ class rdf_list_array(C.Structure):
     _fields_ = [("offsets", rdf_array), ("values", rdf_array)]
 
 
+class rdf_utf8_array(C.Structure):
+    _fields_ = [("offsets", rdf_array), ("data", rdf_array)]
+
+
 class rdf_exchange_stats(C.Structure):
     _fields_ = [("exchange", C.c_int32), ("rounds", C.c_int32), ("local_groups", C.c_int64), ("rows_sent", C.c_int64),
                 ("rows_sent_remote", C.c_int64), ("rows_received", C.c_int64), ("bytes_sent", C.c_int64),
@@ -301,6 +305,117 @@ class DeviceList:
 
 
 # ---------------------------------------------------------------- expression trees
+
+@dataclass
+class HostUtf8:
+    """A StringArray (Utf8, Int32 offsets) in host memory: value_offsets (rows + 1 from row `offset` on), optional row
+    validity sharing that offset, and the value bytes, whose byte 0 is `data[data_offset]`."""
+    offsets: np.ndarray                # int32
+    data: np.ndarray                   # uint8
+    validity: Optional[np.ndarray] = None
+    offset: int = 0
+    length: int = 0
+    data_offset: int = 0
+    null_count: int = -1
+
+    @staticmethod
+    def from_pylist(rows, row_offset: int = 0, data_offset: int = 0) -> "HostUtf8":
+        """rows: list of (str | None).  row_offset leading junk rows and data_offset leading junk bytes make it look like
+        a sliced Arrow array (the first value offset is then not 0)."""
+        pre = ["j" * (i % 3 + 1) for i in range(row_offset)]
+        enc = [b"" if r is None else r.encode("utf-8") for r in pre + list(rows)]
+        offs = np.zeros(len(enc) + 1, dtype=np.int64)
+        offs[1:] = np.cumsum([len(b) for b in enc]) if enc else []
+        if offs[-1] > 2**31 - 1:
+            raise ValueError("more than 2^31-1 bytes: not a Utf8 (Int32 offsets) array")
+        data = np.frombuffer(b"\xff" * data_offset + b"".join(enc) + b"\0" * 8, dtype=np.uint8).copy()
+        valid = None
+        nulls = sum(r is None for r in rows)
+        if nulls:
+            valid = pack_bits(np.array([True] * row_offset + [r is not None for r in rows], dtype=bool))
+        return HostUtf8(offs.astype(np.int32), data, valid, row_offset, len(rows), data_offset, nulls)
+
+    @staticmethod
+    def from_arrow(arr) -> "HostUtf8":
+        """A pyarrow.StringArray (sliced arrays included: their row offset is kept, nothing is copied but the buffers' views)."""
+        vbuf, obuf, dbuf = arr.buffers()[:3]
+        offs = np.frombuffer(obuf, dtype=np.int32)
+        data = np.frombuffer(dbuf, dtype=np.uint8) if dbuf is not None and dbuf.size else np.zeros(8, dtype=np.uint8)
+        valid = None
+        if vbuf is not None and arr.null_count:
+            vb = np.frombuffer(vbuf, dtype=np.uint8)
+            valid = np.zeros(((len(vb) + 7) // 8) * 8 + 8, dtype=np.uint8)   # readable to the next 8-byte boundary
+            valid[:len(vb)] = vb
+        return HostUtf8(offs, data, valid, arr.offset, len(arr), 0, arr.null_count)
+
+    def c_struct(self) -> "rdf_utf8_array":
+        o = rdf_array(self.offsets.ctypes.data, self.validity.ctypes.data if self.validity is not None else None, self.offset,
+                      self.length + 1, self.null_count if self.validity is not None else 0, I32, MEM_HOST)
+        d = rdf_array(self.data.ctypes.data, None, self.data_offset, len(self.data) - self.data_offset, 0, U8, MEM_HOST)
+        return rdf_utf8_array(o, d)
+
+    def valid_mask(self) -> np.ndarray:
+        if self.validity is None:
+            return np.ones(self.length, dtype=bool)
+        return unpack_bits(self.validity, self.offset, self.length)
+
+    def to_pylist(self) -> list:
+        o = self.offsets[self.offset:self.offset + self.length + 1].astype(np.int64) + self.data_offset
+        raw = self.data.tobytes()
+        return [raw[o[i]:o[i + 1]].decode("utf-8") if ok else None for i, ok in enumerate(self.valid_mask())]
+
+    def to_arrow(self):
+        import pyarrow as pa
+        o = self.offsets[self.offset:self.offset + self.length + 1].astype(np.int64)
+        first, last = int(o[0]) if len(o) else 0, int(o[-1]) if len(o) else 0
+        offs = (o - first).astype(np.int32)
+        data = self.data[self.data_offset + first:self.data_offset + last]
+        valid = None
+        if self.validity is not None:
+            valid = pa.py_buffer(pack_bits(self.valid_mask(), pad_words=False).tobytes())
+        return pa.StringArray.from_buffers(self.length, pa.py_buffer(offs.tobytes()), pa.py_buffer(data.tobytes()), valid)
+
+
+@dataclass
+class DeviceUtf8:
+    """A StringArray resident in HBM (offsets / validity / data device pointers); `keep` holds whatever owns the memory."""
+    offsets_ptr: int
+    data_ptr: int
+    data_length: int
+    length: int
+    validity_ptr: Optional[int] = None
+    offset: int = 0
+    data_offset: int = 0
+    null_count: int = -1
+    keep: object = None
+
+    @staticmethod
+    def from_host(h: "HostUtf8", device: str = "cuda") -> "DeviceUtf8":
+        """Copies the buffers of a HostUtf8 to the device with torch (tests and tools)."""
+        import torch
+        ot = torch.from_numpy(np.ascontiguousarray(h.offsets)).to(device)
+        dt = torch.from_numpy(np.ascontiguousarray(h.data)).to(device)
+        vt = torch.from_numpy(np.ascontiguousarray(h.validity)).to(device) if h.validity is not None else None
+        return DeviceUtf8(ot.data_ptr(), dt.data_ptr(), len(h.data) - h.data_offset, h.length, vt.data_ptr() if vt is not None else None,
+                          h.offset, h.data_offset, h.null_count, keep=(ot, dt, vt))
+
+    def c_struct(self) -> "rdf_utf8_array":
+        o = rdf_array(self.offsets_ptr, self.validity_ptr, self.offset, self.length + 1,
+                      self.null_count if self.validity_ptr else 0, I32, MEM_DEVICE)
+        d = rdf_array(self.data_ptr, None, self.data_offset, self.data_length, 0, U8, MEM_DEVICE)
+        return rdf_utf8_array(o, d)
+
+    def to_host(self) -> "HostUtf8":
+        t_off, t_data, t_valid = self.keep[:3]
+        offs = t_off.cpu().numpy()[:self.offset + self.length + 1].copy()
+        data = t_data.cpu().numpy().copy() if t_data is not None else np.zeros(8, dtype=np.uint8)
+        valid = t_valid.cpu().numpy().copy() if t_valid is not None and self.validity_ptr else None
+        return HostUtf8(offs, data, valid, self.offset, self.length, self.data_offset, self.null_count)
+
+
+UTF8_UNARY = ("trim", "ltrim", "rtrim", "substring", "lower", "upper")
+
+
 class Expr:
     """Builder for rdf_expr_node arrays; mirrors BooleanFilter / Scalar (src/expression.rs:718-763)."""
 
@@ -953,6 +1068,100 @@ class Api:
         cv = (rdf_out * 1)(ov.out_struct())
         self._check(self._fn("list_sort")(C.byref(lst.c_struct()), cv))
         return self._finish([ov], cv)[0]
+
+    # ---- Utf8 columns (Column::filter / Column::take, the string ScalarFunctions); bound lazily: only the product has them
+    def _utf8_fn(self, name):
+        fn = self._fn(name)
+        fn.restype = C.c_int
+        return fn
+
+    @staticmethod
+    def _utf8_outs(chunks, rows_out, nullable, device: bool, caps=None):
+        """Output buffers for one call: offsets of rows + 1 entries, data of caps[i] bytes (0: the sizing call)."""
+        outs, keep = [], []
+        for i, (r, nl) in enumerate(zip(rows_out, nullable)):
+            cap = caps[i] if caps is not None else 0
+            if device:
+                import torch
+                ot = torch.zeros(r + 1, dtype=torch.int32, device="cuda")
+                vt = torch.zeros(((r + 63) // 64) * 8 + 8, dtype=torch.uint8, device="cuda") if nl else None
+                dt = torch.zeros(cap + 64, dtype=torch.uint8, device="cuda") if cap else None
+                o_off = rdf_out(ot.data_ptr(), vt.data_ptr() if vt is not None else None, r + 1, 0, 0, I32, MEM_DEVICE)
+                o_dat = rdf_out(dt.data_ptr() if dt is not None else None, None, cap, 0, 0, U8, MEM_DEVICE)
+                keep.append((ot, dt, vt))
+            else:
+                ob = np.zeros(r + 1, dtype=np.int32)
+                vb = np.zeros(((r + 63) // 64) * 8 + 8, dtype=np.uint8) if nl else None
+                db = np.zeros(max(cap, 1), dtype=np.uint8) if cap else None
+                o_off = rdf_out(ob.ctypes.data, vb.ctypes.data if vb is not None else None, r + 1, 0, 0, I32, MEM_HOST)
+                o_dat = rdf_out(db.ctypes.data if db is not None else None, None, cap, 0, 0, U8, MEM_HOST)
+                keep.append((ob, db, vb))
+            outs.append((o_off, o_dat))
+        co = (rdf_out * max(1, len(outs)))(*[o[0] for o in outs])
+        cd = (rdf_out * max(1, len(outs)))(*[o[1] for o in outs])
+        return co, cd, keep
+
+    def _utf8_run(self, call, chunks, rows_out, nullable, as_arrow=False):
+        """The sizing call, then the call into exactly sized buffers -> one HostUtf8 / DeviceUtf8 per output chunk
+        (python lists / pyarrow arrays with as_arrow="pylist" / True)."""
+        device = any(isinstance(c, DeviceUtf8) for c in chunks)
+        co, cd, keep = self._utf8_outs(chunks, rows_out, nullable, device)
+        st = call(co, cd)
+        if st not in (RDF_OK, RDF_MEMORY_ERROR):
+            self._check(st)
+        if st == RDF_MEMORY_ERROR and all(cd[i].capacity >= cd[i].length for i in range(len(rows_out))):
+            self._check(st)   # not the data buffers: a genuine error
+        caps = [cd[i].length for i in range(len(rows_out))]
+        if st == RDF_MEMORY_ERROR:
+            co, cd, keep = self._utf8_outs(chunks, rows_out, nullable, device, caps)
+            self._check(call(co, cd))
+        res = []
+        for i in range(len(rows_out)):
+            rows = co[i].length - 1
+            if device:
+                ot, dt, vt = keep[i]
+                r = DeviceUtf8(ot.data_ptr(), dt.data_ptr() if dt is not None else 0, cd[i].length, rows,
+                               vt.data_ptr() if vt is not None else None, 0, 0, co[i].null_count, keep=(ot, dt, vt))
+            else:
+                ob, db, vb = keep[i]
+                r = HostUtf8(ob, db if db is not None else np.zeros(8, dtype=np.uint8), vb, 0, rows, 0, co[i].null_count)
+            if as_arrow:
+                h = r.to_host() if device else r
+                r = h.to_pylist() if as_arrow == "pylist" else h.to_arrow()
+            res.append(r)
+        return res
+
+    def utf8_filter(self, chunks: Sequence, mask: Sequence, as_arrow=False):
+        """Column::filter over StringArray chunks: one result per chunk."""
+        n = len(chunks)
+        carr = (rdf_utf8_array * max(1, n))(*[c.c_struct() for c in chunks])
+        marr = _flat([mask], n)
+        fn = self._utf8_fn("utf8_filter")
+        return self._utf8_run(lambda co, cd: fn(carr, marr, C.c_int64(n), co, cd), chunks,
+                              [c.length for c in chunks], [c.validity is not None if isinstance(c, HostUtf8) else bool(c.validity_ptr) for c in chunks], as_arrow)
+
+    def utf8_take(self, chunks: Sequence, indices, as_arrow=False):
+        """Column::take: ONE result chunk of indices.length rows."""
+        n = len(chunks)
+        carr = (rdf_utf8_array * max(1, n))(*[c.c_struct() for c in chunks])
+        idx = (rdf_array * 1)(indices.c_struct())
+        nullable = indices.validity is not None or any((c.validity is not None) if isinstance(c, HostUtf8) else bool(c.validity_ptr) for c in chunks)
+        fn = self._utf8_fn("utf8_take")
+        return self._utf8_run(lambda co, cd: fn(carr, C.c_int64(n), idx, co, cd), chunks, [indices.length], [nullable], as_arrow)[0]
+
+    def utf8_unary(self, op: str, chunks: Sequence, pos: int = 0, length: int = 0, as_arrow=False):
+        """trim / ltrim / rtrim / substring(pos, length) / lower / upper: one result per chunk."""
+        if op not in UTF8_UNARY:
+            raise ValueError(f"unknown Utf8 function {op!r}")
+        n = len(chunks)
+        carr = (rdf_utf8_array * max(1, n))(*[c.c_struct() for c in chunks])
+        fn = self._utf8_fn("utf8_" + op)
+        if op == "substring":
+            call = lambda co, cd: fn(carr, C.c_int64(n), C.c_int64(pos), C.c_int64(length), co, cd)  # noqa: E731
+        else:
+            call = lambda co, cd: fn(carr, C.c_int64(n), co, cd)  # noqa: E731
+        return self._utf8_run(call, chunks, [c.length for c in chunks],
+                              [c.validity is not None if isinstance(c, HostUtf8) else bool(c.validity_ptr) for c in chunks], as_arrow)
 
     # ---- fused grouped aggregation over a small dense domain (TPC-H Q1 shape)
     def group_pipeline(self, expr: Expr, cols: Sequence[Sequence], value_roots: Sequence[int], group_root: int, ngroups: int,

@@ -26,6 +26,7 @@
 
 #include "rdf_device.h"
 #include "rdf_stage_copy.h"
+#include "rdf_utf8.h"
 
 using namespace rdfk;
 
@@ -4492,6 +4493,7 @@ rdf_status legacy_groupby_sum(const rdf_array* keys, const rdf_array* values, in
 #include "rdf_capi_frame.inc"
 #include "rdf_capi_stream.inc"
 #include "rdf_capi_comm.inc"
+#include "rdf_capi_utf8.inc"
 
 extern "C" {
 

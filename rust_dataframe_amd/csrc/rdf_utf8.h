@@ -1,0 +1,81 @@
+// rdf_utf8.h — device-side argument blocks of the Utf8 kernels (rdf_utf8.hip) and their launchers.  Host side:
+// rdf_capi_utf8.inc.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+enum : int32_t {
+    UTF8_FILTER = 0, UTF8_TAKE = 1, UTF8_TRIM = 2, UTF8_LTRIM = 3, UTF8_RTRIM = 4, UTF8_SUBSTRING = 5,
+    UTF8_LOWER = 6, UTF8_UPPER = 7
+};
+// per-row flags of the span pass
+enum : uint8_t { UTF8_ROW_VALID = 1, UTF8_ROW_WIDE = 2 };   // WIDE: lower / upper of a row with a byte >= 0x80
+
+constexpr int kUtf8CopyThreads = 256;
+constexpr int kUtf8CopyTile = kUtf8CopyThreads * 16;   // output bytes per copy block: 16 per lane
+constexpr int kUtf8WindowRows = 1024;                  // rows of a copy tile held in LDS; more (empty rows) -> searched in HBM
+
+// One input chunk as the kernels see it.  data[o] is the byte at value offset o; [lo, hi] are the first and last value
+// offsets of the chunk and every row's span is clamped into them, so no kernel reads outside the bytes the host checked.
+struct Utf8Chunk {
+    const uint8_t* data;
+    const int32_t* offs;        // value_offsets of row 0 (the row offset applied): rows + 1 entries
+    const uint8_t* valid;       // row validity, nullptr = all valid
+    int64_t        valid_off;   // bit of row 0
+    const uint8_t* mask;        // filter: mask values / validity (same bit offset), else nullptr
+    const uint8_t* mask_valid;
+    int64_t        mask_off;
+    int64_t        row_start;   // global number of row 0 over the virtual concatenation of the chunks
+    int64_t        rows;
+    int32_t        lo, hi;
+};
+
+// One output chunk (device pointers: the caller's buffers, or staging space for host outputs).
+struct Utf8OutChunk {
+    int32_t* offs;        // rows + 1 entries
+    uint8_t* valid;       // nullptr = not requested
+    uint8_t* data;
+    int64_t  row_start;   // global output row of row 0
+    int64_t  rows;
+    int64_t  byte_start;  // global output byte of byte 0 (in the scan of the row lengths)
+    int64_t  bytes;
+    int64_t  tile_start;  // first copy tile
+};
+
+struct Utf8Args {
+    const Utf8Chunk* chunks;
+    int64_t          nchunks;
+    int32_t          op;
+    int64_t          n;            // candidate rows: the input rows, or the indices for take
+    // take
+    const void*      idx;
+    const uint8_t*   idx_valid;
+    int64_t          idx_off;
+    int32_t          idx64;
+    int64_t          total_rows;
+    // substring
+    int32_t          pos, len;
+    // per candidate row
+    int64_t*         keep;         // filter: 1 = kept (scanned into rscan)
+    int64_t*         blen;         // output bytes (scanned into bscan)
+    uint64_t*        src;          // address of the first source byte
+    uint8_t*         flags;        // UTF8_ROW_*
+    const int64_t*   rscan;        // n + 1 entries (filter)
+    const int64_t*   bscan;        // n + 1 entries
+    uint32_t*        err;          // [0]: an index out of range
+    int64_t*         tot;          // per output chunk: bytes, rows
+    // outputs
+    const Utf8OutChunk* outs;
+    int64_t          nout;
+    int64_t          ntiles;
+    uint64_t*        osrc;         // per global output row: source address
+    int64_t*         tile_row;     // per copy tile: the output row (of its chunk) that holds the tile's first byte
+    uint8_t*         oflags;
+    unsigned long long* null_counts;   // per output chunk
+    int32_t*         bounds;       // per input chunk: first, last value offset (device-resident inputs)
+};
+
+hipError_t launch_utf8_bounds(const Utf8Args& a, hipStream_t s);   // bounds[2c], bounds[2c+1] = offs[0], offs[rows]
+hipError_t launch_utf8_span(const Utf8Args& a, hipStream_t s);     // keep / blen / src / flags, err
+hipError_t launch_utf8_totals(const Utf8Args& a, hipStream_t s);   // tot
+hipError_t launch_utf8_write(const Utf8Args& a, hipStream_t s);    // offsets, validity, null counts, the bytes
