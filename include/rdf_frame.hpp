@@ -2051,6 +2051,8 @@ class DataFrame {
     struct SortCriteria { std::string column; bool descending = false; bool nulls_first = false; };
     DataFrame sort(const std::vector<SortCriteria>& criteria) const {
         if (criteria.empty()) throw DataFrameError(DataFrameError::ComputeError, "Sort criteria cannot be empty");
+        for (auto& c : criteria)
+            if (column_by_name(c.column).data_type() == DataType::Utf8) return take(lexsort_indices(criteria));
         std::vector<rdf_array> cols;
         std::vector<rdf_sort_options> opts;
         for (auto& c : criteria) {
@@ -2062,6 +2064,62 @@ class DataFrame {
         check(rdf_sort_to_indices(cols.data(), (int32_t)criteria.size(), (int64_t)num_chunks(), opts.data(), &ov));
         idx->length = ov.length;
         return take(idx);
+    }
+    // lexsort_to_indices when a criterion is a Utf8 column (rdf_lexsort_to_indices: byte order, NULLs last, stable).  A text
+    // column's chunks go as offsets + bytes built from the mirror's strings; they are copied to the device when the frame's
+    // numeric columns live there (one memory space per call, and the take that follows wants indices beside the columns).
+    ArrayRef lexsort_indices(const std::vector<SortCriteria>& criteria) const {
+        bool host = true;
+        for (auto& c : columns_)
+            if (c.data_type() != DataType::Utf8)
+                for (auto& a : c.data().chunks()) host &= a->host;
+        const int32_t mem = host ? RDF_MEM_HOST : RDF_MEM_DEVICE;
+        struct Text { std::vector<int32_t> offs; std::string bytes; std::vector<uint8_t> valid; std::vector<std::shared_ptr<DeviceBuffer>> dev; };
+        std::vector<std::unique_ptr<Text>> keep;
+        std::vector<std::vector<rdf_array>> num(criteria.size());
+        std::vector<std::vector<rdf_utf8_array>> txt(criteria.size());
+        std::vector<rdf_sort_key> keys(criteria.size());
+        auto place = [&](Text& t, const void* src, int64_t bytes) -> const void* {   // host bytes, or a device copy of them
+            if (host) return src;
+            t.dev.push_back(std::make_shared<DeviceBuffer>(bytes));
+            if (bytes > 0) check(rdf_copy_h2d(t.dev.back()->data(), src, bytes));
+            return t.dev.back()->data();
+        };
+        for (size_t k = 0; k < criteria.size(); ++k) {
+            const Column& col = column_by_name(criteria[k].column);
+            if (col.data_type() != DataType::Utf8) {
+                for (auto& a : col.data().chunks()) num[k].push_back(a->view());
+            } else {
+                for (auto& a : col.data().chunks()) {
+                    keep.push_back(std::make_unique<Text>());
+                    Text& t = *keep.back();
+                    t.offs.reserve((size_t)a->length + 1);
+                    t.offs.push_back(0);
+                    for (int64_t r = 0; r < a->length; ++r) {
+                        t.bytes += (*a->strings)[(size_t)(a->offset + r)];
+                        if (t.bytes.size() > (size_t)INT32_MAX) throw DataFrameError(DataFrameError::ComputeError, "sort: a Utf8 chunk above 2^31-1 bytes");
+                        t.offs.push_back((int32_t)t.bytes.size());
+                    }
+                    if (a->validity) t.valid = pack_bits(a->valid_to_host());
+                    rdf_utf8_array u;
+                    u.offsets.values = place(t, t.offs.data(), (int64_t)t.offs.size() * 4);
+                    u.offsets.validity = t.valid.empty() ? nullptr : (const uint8_t*)place(t, t.valid.data(), (int64_t)t.valid.size());
+                    u.offsets.offset = 0; u.offsets.length = a->length + 1; u.offsets.null_count = -1; u.offsets.dtype = RDF_I32; u.offsets.mem = mem;
+                    u.data.values = place(t, t.bytes.data(), (int64_t)t.bytes.size());
+                    u.data.validity = nullptr;
+                    u.data.offset = 0; u.data.length = (int64_t)t.bytes.size(); u.data.null_count = 0; u.data.dtype = RDF_U8; u.data.mem = mem;
+                    txt[k].push_back(u);
+                }
+            }
+            keys[k].values = num[k].empty() ? nullptr : num[k].data();
+            keys[k].utf8 = txt[k].empty() ? nullptr : txt[k].data();
+            keys[k].options = rdf_sort_options{criteria[k].descending ? 1 : 0, 0};
+        }
+        auto idx = Array::make_out(DataType::UInt32, num_rows(), false, host);
+        rdf_out ov = idx->out_view(num_rows());
+        check(rdf_lexsort_to_indices(keys.data(), (int32_t)keys.size(), (int64_t)num_chunks(), &ov));
+        idx->length = ov.length;
+        return idx;
     }
     // sort_by_indices (:216-222): Column::take of every column (chunk size 4096 as in the reference)
     DataFrame take(const ArrayRef& indices) const {

@@ -403,6 +403,27 @@ rdf_status rdf_utf8_substring(const rdf_utf8_array* chunks, int64_t nchunks, int
 rdf_status rdf_utf8_lower(const rdf_utf8_array* chunks, int64_t nchunks, rdf_out* out_offsets, rdf_out* out_data);
 rdf_status rdf_utf8_upper(const rdf_utf8_array* chunks, int64_t nchunks, rdf_out* out_offsets, rdf_out* out_data);
 
+/* DataFrame::sort (src/dataframe.rs:194-222) whose criteria may be Utf8 columns: arrow's lexsort_to_indices over numeric
+ * and StringArray columns alike.  keys[k] is criterion k (key 0 most significant) and sets exactly one of
+ *   values  nchunks numeric chunks (one dtype), ordered as by rdf_sort_to_indices, or
+ *   utf8    nchunks Utf8 chunks (rdf_utf8_array conventions: row `offset`, value offsets that need not start at 0,
+ *           validity at any bit offset, Int32 offsets per chunk; the bytes of all chunks together may exceed 2^31).
+ * Utf8 values compare byte by byte as unsigned bytes (Rust's str Ord, code-point order); a proper prefix sorts first and
+ * 0x00 is an ordinary byte ("a" < "a\0" < "a\0b" < "b"); the bytes are not validated as UTF-8.  `descending` reverses
+ * the order of non-NULL values; NULL rows sort last in both directions (nulls_first is ignored, as for the numeric
+ * sort).  The sort is stable: rows equal on every key keep ascending row order.  out_indices: ONE RDF_U32 array over the
+ * concatenation of the chunks.  Inputs and output all in host memory or all in device memory.  With numeric keys only
+ * the result is rdf_sort_to_indices' on the same columns, bit for bit.
+ * Errors: no keys RDF_COMPUTE_ERROR; a key setting both pointers or neither, wrong dtypes, mixed memory kinds
+ * RDF_INVALID_ARGUMENT; chunk row counts that differ between keys RDF_COMPUTE_ERROR; 2^32 rows or more
+ * RDF_INVALID_ARGUMENT; output capacity below the rows RDF_MEMORY_ERROR. */
+typedef struct {
+    const rdf_array*      values;   /* nchunks numeric chunks of this criterion, or NULL */
+    const rdf_utf8_array* utf8;     /* nchunks Utf8 chunks of this criterion, or NULL  */
+    rdf_sort_options      options;
+} rdf_sort_key;
+rdf_status rdf_lexsort_to_indices(const rdf_sort_key* keys, int32_t nkeys, int64_t nchunks, rdf_out* out_indices);
+
 /* ------------------------------------------------------------------ fused batch loop */
 
 typedef enum {

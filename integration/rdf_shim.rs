@@ -58,6 +58,9 @@ pub mod sys {
     #[repr(C)] #[derive(Clone, Copy)] pub struct rdf_sort_options { pub descending: i32, pub nulls_first: i32 }
     #[repr(C)] #[derive(Clone, Copy)] pub struct rdf_list_array { pub offsets: rdf_array, pub values: rdf_array }
     #[repr(C)] #[derive(Clone, Copy)] pub struct rdf_utf8_array { pub offsets: rdf_array, pub data: rdf_array }
+    // one criterion of rdf_lexsort_to_indices: exactly one of values / utf8 points at nchunks chunks
+    #[repr(C)] #[derive(Clone, Copy)]
+    pub struct rdf_sort_key { pub values: *const rdf_array, pub utf8: *const rdf_utf8_array, pub options: rdf_sort_options }
     #[repr(C)] pub struct rdf_frame { _opaque: [u8; 0] }
     #[repr(C)] pub struct rdf_comm { _opaque: [u8; 0] }
     #[repr(C)] #[derive(Clone, Copy, Default)]
@@ -103,6 +106,8 @@ pub mod sys {
         // sort / join (src/dataframe.rs:194-222, src/functions/join.rs:19-137)
         pub fn rdf_sort_to_indices(cols: *const rdf_array, ncols: i32, nchunks: i64, opts: *const rdf_sort_options,
                                    out_indices: *mut rdf_out) -> i32;
+        // DataFrame::sort whose criteria may be StringArray columns (byte order, NULLs last, stable)
+        pub fn rdf_lexsort_to_indices(keys: *const rdf_sort_key, nkeys: i32, nchunks: i64, out_indices: *mut rdf_out) -> i32;
         pub fn rdf_equijoin_indices(left_keys: *const rdf_array, left_nchunks: i64, right_keys: *const rdf_array, right_nchunks: i64,
                                     join_type: i32, out_left: *mut rdf_out, out_right: *mut rdf_out, out_rows: *mut i64) -> i32;
         pub fn rdf_equijoin_indices_multi(left_keys: *const rdf_array, left_nchunks: i64, right_keys: *const rdf_array,
@@ -502,6 +507,30 @@ pub fn utf8_take(chunks: &[&StringArray], indices: &UInt32Array) -> Result<Array
     let idx = view(indices);
     let nullable = indices.data().null_buffer().is_some() || chunks.iter().any(|c| c.data().null_buffer().is_some());
     Ok(utf8_call(&[indices.len()], &[nullable], &|oo, od| unsafe { rdf_utf8_take(v.as_ptr(), v.len() as i64, &idx, oo, od) })?.remove(0))
+}
+
+/// DataFrame::sort (src/dataframe.rs:194-222) when criteria are StringArray columns: lexsort_to_indices over the chunks of
+/// every criterion (`None` for a Utf8 column's numeric views, and the other way round), byte order, NULLs last, stable.
+pub fn lexsort_to_indices(criteria: &[(Vec<&dyn Array>, bool)]) -> Result<ArrayRef, ArrowError> {   // (a UInt32Array)
+    let nchunks = criteria.first().map_or(0, |c| c.0.len());
+    let rows: usize = criteria.first().map_or(0, |c| c.0.iter().map(|a| a.len()).sum());
+    let mut num: Vec<Vec<rdf_array>> = Vec::new();
+    let mut txt: Vec<Vec<rdf_utf8_array>> = Vec::new();
+    for (chunks, _) in criteria {
+        match chunks.first().map(|a| a.data_type()) {
+            Some(DataType::Utf8) => { txt.push(chunks.iter().map(|a| utf8_view(a.as_any().downcast_ref::<StringArray>().unwrap())).collect()); num.push(Vec::new()); }
+            _ => { num.push(chunks.iter().map(|a| view(*a)).collect()); txt.push(Vec::new()); }
+        }
+    }
+    let keys: Vec<rdf_sort_key> = criteria.iter().enumerate().map(|(k, (_, desc))| rdf_sort_key {
+        values: if num[k].is_empty() { std::ptr::null() } else { num[k].as_ptr() },
+        utf8: if txt[k].is_empty() { std::ptr::null() } else { txt[k].as_ptr() },
+        options: rdf_sort_options { descending: *desc as i32, nulls_first: 0 },
+    }).collect();
+    let mut buf = OutBuf::new(DataType::UInt32, rows, false);
+    let mut out = buf.as_out();
+    status(unsafe { rdf_lexsort_to_indices(keys.as_ptr(), keys.len() as i32, nchunks as i64, &mut out) })?;
+    Ok(buf.finish(&out))
 }
 
 // Evaluate::evaluate (src/evaluation.rs:66-96): fuse each maximal run of Calculate / Filter steps into ONE rdf_pipeline call —

@@ -102,6 +102,10 @@ class rdf_utf8_array(C.Structure):
     _fields_ = [("offsets", rdf_array), ("data", rdf_array)]
 
 
+class rdf_sort_key(C.Structure):
+    _fields_ = [("values", C.POINTER(rdf_array)), ("utf8", C.POINTER(rdf_utf8_array)), ("options", rdf_sort_options)]
+
+
 class rdf_exchange_stats(C.Structure):
     _fields_ = [("exchange", C.c_int32), ("rounds", C.c_int32), ("local_groups", C.c_int64), ("rows_sent", C.c_int64),
                 ("rows_sent_remote", C.c_int64), ("rows_received", C.c_int64), ("bytes_sent", C.c_int64),
@@ -868,6 +872,33 @@ class Api:
         opts = (rdf_sort_options * len(cols))(*[rdf_sort_options(int(d), 0) for d in descending])
         carr = (rdf_out * 1)(out.out_struct())
         self._check(self._fn("sort_to_indices")(_flat(cols, nchunks), C.c_int32(len(cols)), C.c_int64(nchunks), opts, carr))
+        return self._finish([out], carr)[0]
+
+    def lexsort_to_indices(self, keys: Sequence, out=None):
+        """DataFrame::sort over numeric and Utf8 criteria (rdf_lexsort_to_indices).  keys[k] = (chunks, descending): the
+        chunks are HostArray / DeviceArray (numeric) or HostUtf8 / DeviceUtf8 (Utf8), one kind per key; key 0 is the most
+        significant.  -> ONE UInt32 array of row numbers over the concatenation of the chunks."""
+        keys = [(k, False) if not isinstance(k, tuple) else k for k in keys]
+        nchunks = len(keys[0][0]) if keys else 0
+        first = keys[0][0] if keys else []
+        n = sum(c.length for c in first)
+        if out is None:
+            out = HostArray.empty_out(U32, n, False)
+        ck = (rdf_sort_key * max(1, len(keys)))()
+        keep = []
+        for i, (chunks, desc) in enumerate(keys):
+            utf8 = len(chunks) > 0 and all(isinstance(c, (HostUtf8, DeviceUtf8)) for c in chunks)
+            if utf8:
+                arr = (rdf_utf8_array * max(1, len(chunks)))(*[c.c_struct() for c in chunks])
+                ck[i] = rdf_sort_key(None, C.cast(arr, C.POINTER(rdf_utf8_array)), rdf_sort_options(int(desc), 0))
+            else:
+                arr = (rdf_array * max(1, len(chunks)))(*[c.c_struct(getattr(c, "_unknown_nc", False)) for c in chunks])
+                ck[i] = rdf_sort_key(C.cast(arr, C.POINTER(rdf_array)), None, rdf_sort_options(int(desc), 0))
+            keep.append(arr)
+        carr = (rdf_out * 1)(out.out_struct())
+        fn = self._fn("lexsort_to_indices")
+        fn.restype = C.c_int
+        self._check(fn(ck if keys else None, C.c_int32(len(keys)), C.c_int64(nchunks), carr))
         return self._finish([out], carr)[0]
 
     # ---- join (calc_equijoin_indices)

@@ -72,6 +72,7 @@ struct Ctx {
     int    opt_gb_debug = 0;        // ablations of the partitioned GROUP BY (tools/bench_kernels.py): 1 = aggregate without LDS work, 2 = scatter without stores
     int    opt_sort_gen = 3;        // radix passes: 3 = one read + one write of the pairs per digit, decoupled look-back between 4096-pair tiles (rdf_sort.hip, default); 2 = count -> scan -> scatter over static tile ranges with the same wave-ranked tiles (A/B: slower, see rdf_sort.hip); 1 = first generation (rdf_kernels.hip)
     bool   sort_used_local = false; // the last sort finished at least one column with os_local_kernel
+    int64_t utf8_sort_rounds = 0;   // the last sort: refinement rounds its Utf8 criteria took (round 0 included), summed
     int    opt_sort_super = 1;      // the digit passes of rdf_sort.hip: 1 = a tile per ticket, decoupled look-back between tiles (os_scatter_kernel, default); K > 1 = a ticket is up to K consecutive tiles, counted together, ONE look-back, then ranked and written one by one (os_scatter4_kernel, round 6: built, correct, measured level at 1e9 i64 keys and 8-12 % SLOWER on 5e7 f64 / two-key sorts — profiles/r06_sort_super_tiles_ab.jsonl — kept as the A/B: the second read of the keys costs what the shorter wait saves)
     int    opt_sort_super_force = 0;    // tests: this many tiles per ticket whatever the input's size (rdf_set_option("sort_super", 100 + K))
     int    opt_sort_pipe = 0;       // the digit passes of rdf_sort.hip: 0 = decoupled look-back between the tiles (os_scatter_kernel, default); 1 = a tile's digit counts are published one iteration before its offsets are asked for and scanner blocks turn counts into offsets (os_scatter3_kernel, round 6: built, correct, measured 4-16 % SLOWER — profiles/r06_sort_digit_pass_ab.jsonl — kept as the A/B)
@@ -3580,11 +3581,18 @@ byte_passes:
     return RDF_OK;
 }
 
+// A Utf8 sort criterion (rdf_capi_sort_utf8.inc): its chunk table on the device.
+struct Utf8SortCol { const Utf8Chunk* d_chunks; int64_t nchunks; bool nullable; };
+rdf_status utf8_sort_column(const Utf8SortCol& col, OsScratch& os, uint64_t* const keys[2], uint32_t* const idxb[2], uint8_t* nullflags,
+                            int64_t n, int descending, size_t pin_off, const uint32_t*& idx_cur);
+
 // The radix passes of DataFrame::sort over device-resident descriptor tables: d_chunks[k * nchunks + c] = chunk c of sort
 // column k (column 0 most significant), d_row_start = prefix of the batch lengths.  *idx_out = the sorted row order (u32,
-// arena memory, valid until the next arena_begin).  Shared by rdf_sort_to_indices and rdf_sort_frame.
+// arena memory, valid until the next arena_begin).  Shared by rdf_sort_to_indices and rdf_sort_frame; rdf_lexsort_to_indices
+// passes `utf8`, where utf8[k].d_chunks != nullptr makes column k a Utf8 criterion (its d_chunks entries are not read).
 rdf_status sort_core(const DevChunkCol* d_chunks, const int64_t* d_row_start, int64_t nchunks, int64_t n, int ncols, const int* dts,
-                     const bool* nullable, const rdf_sort_options* opts, size_t pin_off, const uint32_t** idx_out) {
+                     const bool* nullable, const rdf_sort_options* opts, size_t pin_off, const uint32_t** idx_out,
+                     const Utf8SortCol* utf8 = nullptr) {
     Ctx& ctx = g_ctx;
     const int64_t ntiles = (n + kSortTile - 1) / kSortTile;
     void *pk0, *pk1, *pi0, *pi1, *pnf, *ph0, *ph1;
@@ -3607,10 +3615,17 @@ rdf_status sort_core(const DevChunkCol* d_chunks, const int64_t* d_row_start, in
 
     OsScratch os;
     ctx.sort_used_local = false;
+    ctx.utf8_sort_rounds = 0;
     const bool gen2 = ctx.opt_sort_gen >= 2;   // rdf_sort.hip
-    if (gen2) RDF_TRY(os_scratch_alloc(n, os));
+    bool any_utf8 = false;
+    for (int k = 0; utf8 && k < ncols; ++k) any_utf8 |= utf8[k].d_chunks != nullptr;
+    if (gen2 || any_utf8) RDF_TRY(os_scratch_alloc(n, os));
     KernelTimer kt;
     for (int k = ncols - 1; k >= 0; --k) {  // LSD over the sort columns: least significant criterion first
+        if (utf8 && utf8[k].d_chunks) {
+            RDF_TRY(utf8_sort_column(utf8[k], os, keys, idxb, (uint8_t*)pnf, n, opts ? opts[k].descending : 0, pin_off, idx_cur));
+            continue;
+        }
         const int dt = dts[k];
         const bool has_nulls = nullable[k];
         SortKeyArgs ka;
@@ -3660,6 +3675,7 @@ rdf_status sort_core(const DevChunkCol* d_chunks, const int64_t* d_row_start, in
     }
     kt.stop();
     ctx.last_kernel = ctx.sort_used_local ? "os_scatter_kernel+os_local_kernel" : "sort_scatter_kernel";
+    if (any_utf8) ctx.last_kernel = "us_keys_kernel+os_scatter_kernel (Utf8 rounds: " + std::to_string(ctx.utf8_sort_rounds) + ")";
     *idx_out = idx_cur;
     return RDF_OK;
 }
@@ -4494,6 +4510,7 @@ rdf_status legacy_groupby_sum(const rdf_array* keys, const rdf_array* values, in
 #include "rdf_capi_stream.inc"
 #include "rdf_capi_comm.inc"
 #include "rdf_capi_utf8.inc"
+#include "rdf_capi_sort_utf8.inc"
 
 extern "C" {
 

@@ -10,6 +10,49 @@
 
 namespace {
 
+// lohi[2c], lohi[2c + 1] = the first and last value offset of chunk c, checked against its data array before a byte of it
+// is read (device-resident offsets are read by a kernel).  Uses the pinned staging buffer from offset 0.
+rdf_status utf8_value_ranges(const rdf_utf8_array* chunks, int64_t nchunks, int32_t mem, std::vector<int32_t>& lohi, const char* fn) {
+    Ctx& ctx = g_ctx;
+    lohi.assign((size_t)nchunks * 2, 0);
+    if (mem == RDF_MEM_HOST) {
+        for (int64_t i = 0; i < nchunks; ++i) {
+            const int32_t* off = (const int32_t*)chunks[i].offsets.values + chunks[i].offsets.offset;
+            lohi[2 * i] = off[0];
+            lohi[2 * i + 1] = off[chunks[i].offsets.length - 1];
+        }
+    } else if (nchunks > 0) {
+        std::vector<Utf8Chunk> hc((size_t)nchunks);
+        for (int64_t i = 0; i < nchunks; ++i) {
+            memset(&hc[i], 0, sizeof(Utf8Chunk));
+            hc[i].offs = (const int32_t*)chunks[i].offsets.values + chunks[i].offsets.offset;
+            hc[i].rows = chunks[i].offsets.length - 1;
+        }
+        const size_t tb = (size_t)nchunks * sizeof(Utf8Chunk), bb = (size_t)nchunks * 8;
+        void *dtab, *dbounds;
+        RDF_TRY(arena_alloc(tb, &dtab));
+        RDF_TRY(arena_alloc(bb, &dbounds));
+        RDF_TRY(pinned_reserve(tb + bb + 64));
+        memcpy(ctx.pinned, hc.data(), tb);
+        HIP_TRY(hipMemcpyAsync(dtab, ctx.pinned, tb, hipMemcpyHostToDevice, ctx.stream));
+        Utf8Args b;
+        memset(&b, 0, sizeof b);
+        b.chunks = (const Utf8Chunk*)dtab;
+        b.nchunks = nchunks;
+        b.bounds = (int32_t*)dbounds;
+        HIP_TRY(launch_utf8_bounds(b, ctx.stream));
+        char* pin_b = ctx.pinned + ((tb + 63) & ~(size_t)63);
+        HIP_TRY(hipMemcpyAsync(pin_b, dbounds, bb, hipMemcpyDeviceToHost, ctx.stream));
+        HIP_TRY(hipStreamSynchronize(ctx.stream));
+        memcpy(lohi.data(), pin_b, bb);
+    }
+    for (int64_t i = 0; i < nchunks; ++i)
+        if (lohi[2 * i] < 0 || lohi[2 * i + 1] < lohi[2 * i] || lohi[2 * i + 1] > chunks[i].data.length)
+            return fail(RDF_INVALID_ARGUMENT, "%s: chunk %lld: value offsets [%d, %d] outside the %lld data bytes", fn, (long long)i,
+                        lohi[2 * i], lohi[2 * i + 1], (long long)chunks[i].data.length);
+    return RDF_OK;
+}
+
 rdf_status utf8_run(int op, const rdf_utf8_array* chunks, int64_t nchunks, const rdf_array* mask, const rdf_array* indices,
                     int64_t pos, int64_t len, rdf_out* out_offsets, rdf_out* out_data, const char* fn) {
     const bool take = op == UTF8_TAKE, filter = op == UTF8_FILTER;
@@ -67,42 +110,8 @@ rdf_status utf8_run(int op, const rdf_utf8_array* chunks, int64_t nchunks, const
     arena_begin();
 
     // ---- the value-offset range of every chunk, checked against its data array before a byte of it is read
-    std::vector<int32_t> lohi((size_t)nchunks * 2);
-    if (mem == RDF_MEM_HOST) {
-        for (int64_t i = 0; i < nchunks; ++i) {
-            const int32_t* off = (const int32_t*)chunks[i].offsets.values + chunks[i].offsets.offset;
-            lohi[2 * i] = off[0];
-            lohi[2 * i + 1] = off[chunks[i].offsets.length - 1];
-        }
-    } else if (nchunks > 0) {
-        std::vector<Utf8Chunk> hc((size_t)nchunks);
-        for (int64_t i = 0; i < nchunks; ++i) {
-            memset(&hc[i], 0, sizeof(Utf8Chunk));
-            hc[i].offs = (const int32_t*)chunks[i].offsets.values + chunks[i].offsets.offset;
-            hc[i].rows = chunks[i].offsets.length - 1;
-        }
-        const size_t tb = (size_t)nchunks * sizeof(Utf8Chunk), bb = (size_t)nchunks * 8;
-        void *dtab, *dbounds;
-        RDF_TRY(arena_alloc(tb, &dtab));
-        RDF_TRY(arena_alloc(bb, &dbounds));
-        RDF_TRY(pinned_reserve(tb + bb + 64));
-        memcpy(ctx.pinned, hc.data(), tb);
-        HIP_TRY(hipMemcpyAsync(dtab, ctx.pinned, tb, hipMemcpyHostToDevice, ctx.stream));
-        Utf8Args b;
-        memset(&b, 0, sizeof b);
-        b.chunks = (const Utf8Chunk*)dtab;
-        b.nchunks = nchunks;
-        b.bounds = (int32_t*)dbounds;
-        HIP_TRY(launch_utf8_bounds(b, ctx.stream));
-        char* pin_b = ctx.pinned + ((tb + 63) & ~(size_t)63);
-        HIP_TRY(hipMemcpyAsync(pin_b, dbounds, bb, hipMemcpyDeviceToHost, ctx.stream));
-        HIP_TRY(hipStreamSynchronize(ctx.stream));
-        memcpy(lohi.data(), pin_b, bb);
-    }
-    for (int64_t i = 0; i < nchunks; ++i)
-        if (lohi[2 * i] < 0 || lohi[2 * i + 1] < lohi[2 * i] || lohi[2 * i + 1] > chunks[i].data.length)
-            return fail(RDF_INVALID_ARGUMENT, "%s: chunk %lld: value offsets [%d, %d] outside the %lld data bytes", fn, (long long)i,
-                        lohi[2 * i], lohi[2 * i + 1], (long long)chunks[i].data.length);
+    std::vector<int32_t> lohi;
+    RDF_TRY(utf8_value_ranges(chunks, nchunks, mem, lohi, fn));
 
     // ---- inputs on the device (host arrays staged, device arrays aliased)
     std::vector<rdf_array> views;

@@ -79,3 +79,49 @@ hipError_t launch_utf8_bounds(const Utf8Args& a, hipStream_t s);   // bounds[2c]
 hipError_t launch_utf8_span(const Utf8Args& a, hipStream_t s);     // keep / blen / src / flags, err
 hipError_t launch_utf8_totals(const Utf8Args& a, hipStream_t s);   // tot
 hipError_t launch_utf8_write(const Utf8Args& a, hipStream_t s);    // offsets, validity, null counts, the bytes
+
+// ---- sort by a Utf8 criterion (rdf_utf8_sort.hip; host side: rdf_capi_sort_utf8.inc)
+// One criterion refines the incoming row order `perm` in rounds.  A round takes m rows ("round rows", in permutation
+// order), each in a segment of rows that were equal so far; segment s compares its rows from byte sdepth[s] on.  Every row
+// gets a 64-bit word: its next 7 bytes big-endian, then an end code min(bytes left, 8) (a proper prefix sorts first;
+// 8 = the row goes on past the word), complemented when descending.  The rows are sorted stably by (segment, word),
+// written back into the slots they came from, and the rows that are still tied with a neighbour and not ended go on.
+constexpr int kUtf8SortWordBytes = 7;
+constexpr int32_t kUtf8SortNoLcp = 0x7fffffff;
+struct Utf8SortArgs {
+    const Utf8Chunk* chunks;
+    int64_t          nchunks;
+    int64_t          n, m;          // rows of the criterion, rows of this round
+    int32_t          round0, descending;
+    uint32_t*        perm;          // [n] position -> row: the criterion's order, refined in place
+    const uint32_t*  order_in;      // init: the incoming order (nullptr = identity)
+    const uint32_t*  upos;          // [m] position of round row j (round 0: j itself)
+    const uint32_t*  useg;          // [m] segment of round row j (round 0: all 0)
+    int32_t*         sdepth;        // [S] compare depth of each segment
+    int32_t*         slcp;          // [S] common prefix of the segment's rows beyond sdepth (min over rows, starts kUtf8SortNoLcp)
+    const uint32_t*  sfirst;        // [S] the segment's first round row
+    int64_t          nseg;
+    uint64_t*        word;          // [m] the rows' words (round order)
+    uint64_t*        keys;          // [m] sort keys out
+    uint8_t*         nullflags;     // [m] round 0: 1 = NULL (by round row)
+    uint64_t*        bit_stats;     // [2] min / max over the non-NULL words
+    const uint32_t*  order;         // [m] round rows in sorted order (nullptr = identity)
+    uint32_t*        trow;          // [m] in sorted order: the row,
+    uint64_t*        tword;         //      its word,
+    uint32_t*        tseg;          //      its segment,
+    uint8_t*         tnull;         //      NULL
+    int64_t*         fu;            // [m] 1 = the row is unresolved (goes on to the next round)
+    int64_t*         fh;            // [m] 1 = ... and heads a new segment
+    const int64_t*   su;            // exclusive scans of fu, fh
+    const int64_t*   sh;
+    uint32_t*        nupos;         // next round: upos, useg, sdepth, sfirst
+    uint32_t*        nuseg;
+    int32_t*         nsdepth;
+    uint32_t*        nsfirst;
+};
+hipError_t launch_utf8_sort_init(const Utf8SortArgs& a, hipStream_t s);   // perm = order_in
+hipError_t launch_utf8_sort_lcp(const Utf8SortArgs& a, hipStream_t s);    // slcp, then sdepth += slcp
+hipError_t launch_utf8_sort_keys(const Utf8SortArgs& a, hipStream_t s);   // word, keys, nullflags, bit_stats
+hipError_t launch_utf8_sort_seg_keys(const Utf8SortArgs& a, hipStream_t s);   // keys[t] = useg[order[t]]
+hipError_t launch_utf8_sort_mark(const Utf8SortArgs& a, hipStream_t s);   // trow .. tnull, perm written back, fu, fh
+hipError_t launch_utf8_sort_next(const Utf8SortArgs& a, hipStream_t s);   // nupos .. nsfirst, slcp reset

@@ -10,7 +10,14 @@ a fraction of the library's own rdf_probe_stream copy rate measured in the same 
 rdf_take of the same random u32 indices over a Float64 column is measured alongside (micro_take_random_u32).
 One JSON line per operator on stdout (and appended to --out).
 
+--sort measures rdf_lexsort_to_indices instead, on --sort-rows (1e7) device-resident rows: city-like rows (4-40 bytes,
+10 % NULL), the same rows behind a 1 KiB common prefix, rows of 1000 distinct values, and [utf8, f64].  Each is timed by
+HIP events around the whole call (rdf_kernel_timing_*: the rounds' host read-backs included), next to the floor — the
+numeric rdf_sort_to_indices of as many random u64 keys — and to pyarrow.compute.sort_indices of the same rows on the
+host.  The rounds each sort took come from rdf_last_kernel.
+
     python tools/bench_utf8.py [--rows 100000000] [--reps 5] [--out FILE]
+    python tools/bench_utf8.py --sort [--sort-rows 10000000] [--reps 3] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -61,6 +68,171 @@ def device_column(torch, strings, rows):
     return d, total
 
 
+def city_like(rng, n, null_frac=0.1, lo=4, hi=40):
+    """n rows of lo..hi ASCII bytes (a capital, then lower-case letters, spaces and commas), null_frac of them NULL
+    -> (int64 offsets, uint8 bytes, bool valid)."""
+    lens = rng.integers(lo, hi + 1, n)
+    valid = rng.random(n) >= null_frac
+    lens[~valid] = 0
+    offs = np.zeros(n + 1, dtype=np.int64)
+    offs[1:] = np.cumsum(lens)
+    alpha = np.frombuffer(b"abcdefghijklmnopqrstuvwxyz  ,", dtype=np.uint8)
+    data = alpha[rng.integers(0, len(alpha), int(offs[-1]))]
+    data[offs[:-1][lens > 0]] = rng.integers(65, 91, int((lens > 0).sum()))
+    return offs, data, valid
+
+
+def sort_bench(args, api, torch):
+    import time
+    import pyarrow as pa
+    import pyarrow.compute as pc
+    rng = np.random.default_rng(23)
+    n = args.sort_rows
+    lines = []
+
+    def dev_chunks(offs, data, valid, nch):
+        """device chunks of n / nch rows each (Int32 offsets per chunk) over one device copy of the bytes"""
+        dd = torch.from_numpy(data).cuda() if isinstance(data, np.ndarray) else data
+        per = (len(offs) - 1 + nch - 1) // nch
+        out = []
+        for c in range(nch):
+            r0, r1 = c * per, min((c + 1) * per, len(offs) - 1)
+            o = offs[r0:r1 + 1] - offs[r0]
+            assert o[-1] < 2**31
+            ot = torch.from_numpy(o.astype(np.int32)).cuda()
+            vt = None
+            if valid is not None:
+                bits = A.pack_bits(valid[r0:r1])
+                vt = torch.from_numpy(bits).cuda()
+            out.append(A.DeviceUtf8(ot.data_ptr(), dd.data_ptr() + int(offs[r0]), int(o[-1]), r1 - r0,
+                                    vt.data_ptr() if vt is not None else None, 0, 0, -1, keep=(ot, dd, vt)))
+        return out
+
+    def host_arrow(offs, data, valid):
+        assert offs[-1] < 2**31
+        return pa.StringArray.from_buffers(len(offs) - 1, pa.py_buffer(offs.astype(np.int32)), pa.py_buffer(data),
+                                           pa.py_buffer(A.pack_bits(valid)) if valid is not None else None)
+
+    def time_device(keys):
+        out_t = torch.empty(n + 64, dtype=torch.int32, device="cuda")
+        out = A.DeviceArray(out_t.data_ptr(), None, 0, n, A.U32, 0, keep=out_t)
+        for _ in range(args.warmup):
+            api.lexsort_to_indices(keys, out=out)
+        ms, wall = [], []
+        for _ in range(args.reps):
+            lib.kernel_timing_reset(True)
+            t0 = time.perf_counter()
+            api.lexsort_to_indices(keys, out=out)
+            wall.append((time.perf_counter() - t0) * 1e3)
+            ms.append(lib.kernel_timing_get()[0])
+        lib.kernel_timing_reset(False)
+        k = lib.last_kernel()
+        rounds = int(k.split("Utf8 rounds: ")[1].rstrip(")")) if "Utf8 rounds: " in k else 0
+        return min(ms), float(np.median(ms)), min(wall), rounds, out_t[:n].cpu().numpy().view(np.uint32)
+
+    def time_arrow(fn):
+        if fn is None:
+            return None
+        fn()
+        best = 1e30
+        for _ in range(max(1, min(args.reps, 3))):
+            t0 = time.perf_counter()
+            r = fn()
+            best = min(best, (time.perf_counter() - t0) * 1e3)
+        return best, r
+
+    def record(name, keys, arrow_fn, nbytes, note=None):
+        best, med, wall, rounds, got = time_device(keys)
+        ar = time_arrow(arrow_fn)
+        same = None
+        if ar is not None:
+            same = bool(np.array_equal(got.astype(np.int64), ar[1].to_numpy().astype(np.int64)))
+        rec = {"op": name, "rows": n, "bytes": int(nbytes), "rounds": rounds, "device_ms": round(best, 3), "device_ms_median": round(med, 3),
+               "call_wall_ms": round(wall, 3), "pyarrow_host_ms": round(ar[0], 1) if ar else None, "same_order_as_pyarrow": same,
+               "floor_u64_ms": round(floor_ms, 3)}
+        if note:
+            rec["note"] = note
+        print(json.dumps(rec), flush=True)
+        lines.append(rec)
+
+    # the floor: the numeric sort of n random u64 keys
+    kt = torch.randint(-2**62, 2**62, (n,), device="cuda", dtype=torch.int64)
+    K = A.DeviceArray(kt.data_ptr(), None, 0, n, A.U64, 0, keep=kt)
+    ft = torch.empty(n + 64, dtype=torch.int32, device="cuda")
+    F = A.DeviceArray(ft.data_ptr(), None, 0, n, A.U32, 0, keep=ft)
+    for _ in range(args.warmup):
+        api.sort_to_indices([[K]], [False], out=F)
+    fl = []
+    for _ in range(args.reps):
+        lib.kernel_timing_reset(True)
+        api.sort_to_indices([[K]], [False], out=F)
+        fl.append(lib.kernel_timing_get()[0])
+    lib.kernel_timing_reset(False)
+    floor_ms = min(fl)
+    kh = kt.cpu().numpy().view(np.uint64)
+    pa_floor = time_arrow(lambda: pc.sort_indices(pa.array(kh)))
+    rec = {"op": "sort_u64_floor", "rows": n, "device_ms": round(floor_ms, 3), "pyarrow_host_ms": round(pa_floor[0], 1)}
+    print(json.dumps(rec), flush=True)
+    lines.append(rec)
+    del kt, K, ft, F
+
+    # 1. city-like rows
+    offs, data, valid = city_like(rng, n)
+    col = dev_chunks(offs, data, valid, 1)
+    arr = host_arrow(offs, data, valid)
+    record("utf8_sort_city_like", [(col, False)], lambda: pc.sort_indices(arr), offs[-1])
+
+    # 2. the same rows behind a 1 KiB common prefix (built on the device: ~10 GB, 8 chunks)
+    P = 1024
+    lens = np.diff(offs)
+    offs2 = np.zeros(n + 1, dtype=np.int64)
+    offs2[1:] = np.cumsum(lens + P)
+    d2 = torch.full((int(offs2[-1]) + 64,), ord("p"), dtype=torch.uint8, device="cuda")
+    src = torch.from_numpy(data).cuda()
+    row_of = torch.repeat_interleave(torch.arange(n, device="cuda"), torch.from_numpy(lens).cuda())
+    o1 = torch.from_numpy(offs[:-1]).cuda()
+    o2 = torch.from_numpy(offs2[:-1]).cuda()
+    pos = torch.arange(int(offs[-1]), device="cuda", dtype=torch.int64)
+    d2[o2[row_of] + P + (pos - o1[row_of])] = src
+    del row_of, pos, o1, o2, src
+    col2 = dev_chunks(offs2, d2, valid, 8)
+    record("utf8_sort_city_like_1k_prefix", [(col2, False)], None, offs2[-1],
+           note="pyarrow not run: a host sort of 10 GB of strings sharing 1 KiB")
+    del col2, d2
+
+    # 3. rows of 1000 distinct values
+    woffs, wdata, _v = city_like(rng, 1000, null_frac=0.0)
+    pick = rng.integers(0, 1000, n)
+    wl = np.diff(woffs)
+    lens3 = wl[pick]
+    offs3 = np.zeros(n + 1, dtype=np.int64)
+    offs3[1:] = np.cumsum(lens3)
+    d3 = torch.empty(int(offs3[-1]) + 64, dtype=torch.uint8, device="cuda")
+    row_of = torch.repeat_interleave(torch.arange(n, device="cuda"), torch.from_numpy(lens3).cuda())
+    pos = torch.arange(int(offs3[-1]), device="cuda", dtype=torch.int64)
+    wsrc = torch.from_numpy(wdata).cuda()
+    pk = torch.from_numpy(pick).cuda()
+    d3[:int(offs3[-1])] = wsrc[torch.from_numpy(woffs[:-1]).cuda()[pk[row_of]] + (pos - torch.from_numpy(offs3[:-1]).cuda()[row_of])]
+    del row_of, pos
+    data3 = d3[:int(offs3[-1])].cpu().numpy()
+    col3 = dev_chunks(offs3, d3, None, 1)
+    arr3 = host_arrow(offs3, data3, None)
+    record("utf8_sort_1000_distinct", [(col3, False)], lambda: pc.sort_indices(arr3), offs3[-1])
+    del col3, d3
+
+    # 4. [utf8, f64]
+    fv = rng.random(n)
+    fa = torch.from_numpy(fv).cuda()
+    FA = A.DeviceArray(fa.data_ptr(), None, 0, n, A.F64, 0, keep=fa)
+    tab = pa.table({"s": arr, "f": pa.array(fv)})
+    record("utf8_sort_utf8_f64", [(col, False), ([FA], False)],
+           lambda: pc.sort_indices(tab, sort_keys=[("s", "ascending"), ("f", "ascending")]), offs[-1] + 8 * n)
+    if args.out:
+        with open(args.out, "a") as f:
+            for r in lines:
+                f.write(json.dumps(r) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=100_000_000)
@@ -68,11 +240,16 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--sort", action="store_true", help="measure rdf_lexsort_to_indices instead of the other operators")
+    ap.add_argument("--sort-rows", type=int, default=10_000_000)
     args = ap.parse_args()
     import torch
     api = lib.api()
     assert lib.device_count() >= 1, "needs a GPU"
     lib.set_device(0)
+    if args.sort:
+        sort_bench(args, api, torch)
+        return
     so = lib.load()
     for n in ("filter", "take", "trim", "lower"):
         getattr(so, "rdf_utf8_" + n).restype = C.c_int
