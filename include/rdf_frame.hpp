@@ -425,6 +425,39 @@ class ChunkedArray {
 };
 
 // ------------------------------------------------------------------------------------------------
+// Column::hist / Column::uniques results (src/table.rs:140-158, 244-341)
+
+// histo_fp::Histogram as the reference reads it back: buckets with start() / end() / count().  The buckets are
+// numpy.histogram's over [min, max] (rdf_hist); with `density` a bucket also carries count / counted rows.
+class Histogram {
+  public:
+    struct Bucket {
+        double start_ = 0, end_ = 0, density_ = 0;
+        uint64_t count_ = 0;
+        double start() const { return start_; }
+        double end() const { return end_; }
+        uint64_t count() const { return count_; }
+        double density() const { return density_; }
+    };
+    const std::vector<Bucket>& buckets() const { return buckets_; }
+    size_t num_buckets() const { return buckets_.size(); }
+    uint64_t num_samples() const { return samples_; }    // rows that landed in a bucket (NULL rows and NaN do not)
+    bool has_density() const { return density_; }
+    std::vector<Bucket> buckets_;
+    uint64_t samples_ = 0;
+    bool density_ = false;
+};
+
+// "Generic type that encapsulates vecs of primitive types" (src/table.rs:140-158): F / S / I
+struct GenericVector {
+    enum Kind { I, F, S } kind = I;
+    std::vector<int64_t> i;
+    std::vector<double> f;
+    std::vector<std::string> s;
+    size_t len() const { return kind == I ? i.size() : kind == F ? f.size() : s.size(); }
+};
+
+// ------------------------------------------------------------------------------------------------
 // Column (src/table.rs:134-344)
 
 class Column {
@@ -510,6 +543,97 @@ class Column {
         out->length = ov.length;
         out->null_count = ov.null_count;
         return Column(ChunkedArray::from_arrays({out}), field_);
+    }
+    // src/table.rs:244-290: Int64 / Float64 columns (the reference panics on the rest); NULL rows and NaN are not counted
+    // (the reference reads the value slot of a NULL row: not copied).  The counting runs on the device (rdf_hist); the
+    // density of a bucket is count / counted rows, computed here.
+    Histogram hist(uint64_t nbins, bool density) const {
+        if (data_type() != DataType::Int64 && data_type() != DataType::Float64)
+            throw DataFrameError(DataFrameError::ComputeError, "Unsupported type for histogram");
+        const auto cv = data_.views();
+        bool host = true;
+        for (auto& c : data_.chunks()) host &= c->host;
+        auto counts = Array::make_out(DataType::Int64, (int64_t)nbins, false, host);
+        auto edges = Array::make_out(DataType::Float64, (int64_t)nbins + 1, false, host);
+        rdf_out oc = counts->out_view((int64_t)nbins), oe = edges->out_view((int64_t)nbins + 1);
+        int64_t counted = 0;
+        check(rdf_hist(cv.data(), (int64_t)cv.size(), (int64_t)nbins, nullptr, &oc, &oe, &counted));
+        counts->length = oc.length;
+        edges->length = oe.length;
+        const std::vector<int64_t> c = counts->values_to_host<int64_t>();
+        const std::vector<double> e = edges->values_to_host<double>();
+        Histogram h;
+        h.samples_ = (uint64_t)counted;
+        h.density_ = density;
+        h.buckets_.resize((size_t)nbins);
+        for (size_t b = 0; b < (size_t)nbins; ++b) {
+            h.buckets_[b].start_ = e[b];
+            h.buckets_[b].end_ = e[b + 1];
+            h.buckets_[b].count_ = (uint64_t)c[b];
+            h.buckets_[b].density_ = density && counted > 0 ? (double)c[b] / (double)counted : 0.0;
+        }
+        return h;
+    }
+
+    // src/table.rs:293-341: the distinct values of the valid rows, in unspecified order (the reference's is HashSet order).
+    // Int64 -> I, Float64 -> F (-0.0 and +0.0 one value, all NaNs one value), Utf8 -> S; other types panic in the reference.
+    GenericVector uniques() const {
+        GenericVector g;
+        if (data_type() == DataType::Utf8) {
+            // text columns are carried on the host: every chunk goes as offsets + bytes built from the mirror's strings
+            struct Text { std::vector<int32_t> offs; std::string bytes; std::vector<uint8_t> valid; };
+            std::vector<std::unique_ptr<Text>> keep;
+            std::vector<rdf_utf8_array> txt;
+            int64_t rows = 0, bytes = 0;
+            for (auto& a : data_.chunks()) {
+                keep.push_back(std::make_unique<Text>());
+                Text& t = *keep.back();
+                t.offs.reserve((size_t)a->length + 1);
+                t.offs.push_back(0);
+                for (int64_t r = 0; r < a->length; ++r) {
+                    t.bytes += (*a->strings)[(size_t)(a->offset + r)];
+                    if (t.bytes.size() > (size_t)INT32_MAX) throw DataFrameError(DataFrameError::ComputeError, "uniques: a Utf8 chunk above 2^31-1 bytes");
+                    t.offs.push_back((int32_t)t.bytes.size());
+                }
+                if (a->validity) { t.valid = pack_bits(a->valid_to_host()); t.valid.resize(t.valid.size() + 8, 0); }
+                t.bytes.append(8, '\0');
+                rdf_utf8_array u;
+                u.offsets.values = t.offs.data();
+                u.offsets.validity = t.valid.empty() ? nullptr : t.valid.data();
+                u.offsets.offset = 0; u.offsets.length = a->length + 1; u.offsets.null_count = -1; u.offsets.dtype = RDF_I32; u.offsets.mem = RDF_MEM_HOST;
+                u.data.values = t.bytes.data();
+                u.data.validity = nullptr;
+                u.data.offset = 0; u.data.length = (int64_t)t.bytes.size() - 8; u.data.null_count = 0; u.data.dtype = RDF_U8; u.data.mem = RDF_MEM_HOST;
+                txt.push_back(u);
+                rows += a->length;
+                bytes += u.data.length;
+            }
+            // rows + 1 offsets and the input's bytes always suffice: one call
+            std::vector<int32_t> ooffs((size_t)rows + 1, 0);
+            std::vector<uint8_t> odata((size_t)bytes + 8, 0);
+            rdf_out oo{ooffs.data(), nullptr, rows + 1, 0, 0, RDF_I32, RDF_MEM_HOST};
+            rdf_out od{odata.data(), nullptr, bytes, 0, 0, RDF_U8, RDF_MEM_HOST};
+            int64_t count = 0;
+            check(rdf_utf8_uniques(txt.data(), (int64_t)txt.size(), &oo, &od, &count));
+            g.kind = GenericVector::S;
+            for (int64_t k = 0; k < count; ++k)
+                g.s.emplace_back((const char*)odata.data() + ooffs[(size_t)k], (size_t)(ooffs[(size_t)k + 1] - ooffs[(size_t)k]));
+            return g;
+        }
+        if (data_type() != DataType::Int64 && data_type() != DataType::Float64)
+            throw DataFrameError(DataFrameError::ComputeError, "Datatype not supported for uniques.");
+        const auto cv = data_.views();
+        bool host = true;
+        for (auto& c : data_.chunks()) host &= c->host;
+        int64_t count = 0;
+        check(rdf_uniques(cv.data(), (int64_t)cv.size(), nullptr, &count));
+        auto out = Array::make_out(data_type(), count, false, host);
+        rdf_out ov = out->out_view(count);
+        check(rdf_uniques(cv.data(), (int64_t)cv.size(), &ov, &count));
+        out->length = ov.length;
+        if (data_type() == DataType::Int64) { g.kind = GenericVector::I; g.i = out->values_to_host<int64_t>(); }
+        else { g.kind = GenericVector::F; g.f = out->values_to_host<double>(); }
+        return g;
     }
   private:
     ChunkedArray data_;

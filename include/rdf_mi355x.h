@@ -424,6 +424,48 @@ typedef struct {
 } rdf_sort_key;
 rdf_status rdf_lexsort_to_indices(const rdf_sort_key* keys, int32_t nkeys, int64_t nchunks, rdf_out* out_indices);
 
+/* ------------------------------------------------------------------ Column::hist / Column::uniques */
+
+/* Column::hist (src/table.rs:244-290): the histogram of an Int64 or Float64 column over `nbins` equal-width buckets.  The
+ * reference feeds every value `as f64` to the histo_fp crate, whose bucket boundaries it does not pin; the semantics here
+ * are numpy.histogram(x, bins = nbins, range = range), counts and edges alike:
+ *   - NULL rows and NaN are not counted; *out_counted = the rows that landed in a bucket;
+ *   - range == NULL: lo / hi = minimum / maximum of the counted values (rdf_min / rdf_max's rule: NaN never wins); an
+ *     infinite one is RDF_COMPUTE_ERROR ("range is not finite"); no counted value at all gives lo, hi = 0, 1.
+ *     range = {lo, hi}: both finite, lo <= hi, else RDF_INVALID_ARGUMENT; values outside [lo, hi] are not counted.
+ *     lo == hi becomes lo - 0.5, hi + 0.5 either way;
+ *   - step = (hi - lo) / nbins, edges[i] = lo + i * step (IEEE double, two roundings), edges[nbins] = hi exactly; x belongs
+ *     to bucket i with edges[i] <= x < edges[i + 1], the last bucket also takes x == hi.
+ * Other dtypes: RDF_INVALID_ARGUMENT (the reference panics "Unsupported type for histogram").  1 <= nbins <= 2^24.
+ * out_counts: ONE RDF_I64 array of nbins, out_edges: ONE RDF_F64 array of nbins + 1; a capacity below that is
+ * RDF_MEMORY_ERROR with the needed lengths set and nothing written.  Counts are exact: two runs, and host and device
+ * memory, give identical outputs.  With `range` given the call is additive over row ranges (shards can be summed). */
+rdf_status rdf_hist(const rdf_array* chunks, int64_t nchunks, int64_t nbins, const double* range, rdf_out* out_counts,
+                    rdf_out* out_edges, int64_t* out_counted);
+
+/* Column::uniques (src/table.rs:293-341) for Int64 / UInt64 / Float64 columns: the distinct values of the valid rows, each
+ * once, as ONE chunk of the input dtype in unspecified order (the reference's is HashSet iteration order).  NULL rows are
+ * skipped.  Float64 values compare numerically: -0.0 and +0.0 are one value, returned as +0.0; all NaNs are one value,
+ * returned once as the quiet NaN 0x7FF8000000000000; every other value comes back bit for bit.  *out_count is always set;
+ * out_values == NULL counts only; a capacity below the count is RDF_MEMORY_ERROR (out_values->length = the count, nothing
+ * written); a capacity of all rows always suffices.  Other dtypes: RDF_INVALID_ARGUMENT ("Datatype not supported for
+ * uniques").  The caller passes no cardinality: keys go into a hash set sized from the rows within a memory budget
+ * (rdf_set_option "uniques_table_bits"), and a column with more distinct values than the set was sized for is sorted
+ * instead (first row of every run of equal keys kept; "uniques_route" 1 forces this route). */
+rdf_status rdf_uniques(const rdf_array* chunks, int64_t nchunks, rdf_out* out_values, int64_t* out_count);
+
+/* Column::uniques for Utf8 columns (src/table.rs:311-324): the distinct byte strings of the valid rows, each once, as ONE
+ * Utf8 chunk (offsets from 0, no NULLs: no validity buffer needed) in unspecified order.  Equality is byte equality; the
+ * empty string is a value, 0x00 an ordinary byte, the bytes are not validated.  Sizing as for rdf_utf8_take: lengths
+ * reported in out_offsets->length / out_data->length, RDF_MEMORY_ERROR and nothing written when a capacity is short
+ * (out_data with values == NULL, capacity == 0 is the sizing call; out_offsets needs a buffer of at least one entry, and
+ * rows + 1 entries / the input's bytes always suffice).  *out_count is always set.  Rows are matched through a 64-bit hash
+ * of their bytes and every row is then compared with its hash's representative; two different strings with one hash (or
+ * more distinct values than the hash set was sized for, or "uniques_route" 1) send the call to the exact route: the order
+ * of rdf_lexsort_to_indices, neighbours compared. */
+rdf_status rdf_utf8_uniques(const rdf_utf8_array* chunks, int64_t nchunks, rdf_out* out_offsets, rdf_out* out_data,
+                            int64_t* out_count);
+
 /* ------------------------------------------------------------------ fused batch loop */
 
 typedef enum {
@@ -728,7 +770,11 @@ rdf_status rdf_fill_validity(uint8_t* dev_ptr, int64_t nbits, uint64_t seed, uin
  * in without far outliers / infinities / NaNs, as many bucket bits as the densest region needs —, default; 0 = [min, max], ~500 rows per bucket),
  * "stream_slab_bytes" (rdf_pipeline over host memory: bytes per slab of the streamed batch loop, 0 = 256 MiB, -1 = never stream),
  * "comm_max_bytes" (most bytes one ncclSend / peer copy of the group-by exchange moves, default 256 MiB: larger shares go in
- * several rounds; every rank of a communicator must use the same value). */
+ * several rounds; every rank of a communicator must use the same value),
+ * "uniques_route" (rdf_uniques / rdf_utf8_uniques: 0 = the hash route while its set holds the column's distinct values, the sort /
+ * exact route otherwise, default; 1 = always the sort / exact route),
+ * "uniques_table_bits" (log2 of the most slots that hash set may have, 10..32, default 24: it is filled to half, so up to 2^23
+ * distinct values stay on the hash route). */
 rdf_status rdf_set_option(const char* name, int64_t value);
 /* Number of program shapes with a specialised kernel. */
 int32_t    rdf_spec_catalog_size(void);

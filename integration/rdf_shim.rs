@@ -108,6 +108,11 @@ pub mod sys {
                                    out_indices: *mut rdf_out) -> i32;
         // DataFrame::sort whose criteria may be StringArray columns (byte order, NULLs last, stable)
         pub fn rdf_lexsort_to_indices(keys: *const rdf_sort_key, nkeys: i32, nchunks: i64, out_indices: *mut rdf_out) -> i32;
+        pub fn rdf_hist(chunks: *const rdf_array, nchunks: i64, nbins: i64, range: *const f64, out_counts: *mut rdf_out,
+                        out_edges: *mut rdf_out, out_counted: *mut i64) -> i32;
+        pub fn rdf_uniques(chunks: *const rdf_array, nchunks: i64, out_values: *mut rdf_out, out_count: *mut i64) -> i32;
+        pub fn rdf_utf8_uniques(chunks: *const rdf_utf8_array, nchunks: i64, out_offsets: *mut rdf_out, out_data: *mut rdf_out,
+                                out_count: *mut i64) -> i32;
         pub fn rdf_equijoin_indices(left_keys: *const rdf_array, left_nchunks: i64, right_keys: *const rdf_array, right_nchunks: i64,
                                     join_type: i32, out_left: *mut rdf_out, out_right: *mut rdf_out, out_rows: *mut i64) -> i32;
         pub fn rdf_equijoin_indices_multi(left_keys: *const rdf_array, left_nchunks: i64, right_keys: *const rdf_array,
@@ -217,7 +222,7 @@ pub mod sys {
 // (2) views over Arrow arrays, output buffers, error mapping
 
 use self::sys::*;
-use arrow::array::{Array, ArrayData, ArrayRef, BooleanArray, ListArray, PrimitiveArray, StringArray, UInt32Array};
+use arrow::array::{Array, ArrayData, ArrayRef, BooleanArray, Float64Array, Int64Array, ListArray, PrimitiveArray, StringArray, UInt32Array};
 use arrow::buffer::MutableBuffer;
 use arrow::datatypes::{ArrowNumericType, ArrowPrimitiveType, DataType};
 use arrow::error::ArrowError;
@@ -530,6 +535,39 @@ pub fn lexsort_to_indices(criteria: &[(Vec<&dyn Array>, bool)]) -> Result<ArrayR
     let mut buf = OutBuf::new(DataType::UInt32, rows, false);
     let mut out = buf.as_out();
     status(unsafe { rdf_lexsort_to_indices(keys.as_ptr(), keys.len() as i32, nchunks as i64, &mut out) })?;
+    Ok(buf.finish(&out))
+}
+
+/// Column::hist (src/table.rs:244-290) of an Int64 / Float64 column: (bucket start, bucket end, count[, count / counted])
+/// per bucket.  The buckets are numpy.histogram's over [min, max] (the reference's histo_fp buckets are not pinned by its
+/// test); NULL rows and NaN are not counted.
+pub fn column_hist(chunks: &[&dyn Array], nbins: usize, density: bool) -> Result<Vec<(f64, f64, u64, Option<f64>)>, ArrowError> {
+    let v: Vec<rdf_array> = chunks.iter().map(|a| view(*a)).collect();
+    let (mut cbuf, mut ebuf) = (OutBuf::new(DataType::Int64, nbins, false), OutBuf::new(DataType::Float64, nbins + 1, false));
+    let (mut oc, mut oe) = (cbuf.as_out(), ebuf.as_out());
+    let mut counted = 0i64;
+    status(unsafe { rdf_hist(v.as_ptr(), v.len() as i64, nbins as i64, std::ptr::null(), &mut oc, &mut oe, &mut counted) })?;
+    let (counts, edges) = (cbuf.finish(&oc), ebuf.finish(&oe));
+    let counts = counts.as_any().downcast_ref::<Int64Array>().unwrap();
+    let edges = edges.as_any().downcast_ref::<Float64Array>().unwrap();
+    Ok((0..nbins).map(|i| (edges.value(i), edges.value(i + 1), counts.value(i) as u64,
+                           if density && counted > 0 { Some(counts.value(i) as f64 / counted as f64) } else { None })).collect())
+}
+/// Column::uniques (src/table.rs:293-341): the distinct values of the valid rows as one array (Int64Array / Float64Array /
+/// StringArray -> GenericVector::I / F / S), in unspecified order.
+pub fn column_uniques(chunks: &[&dyn Array]) -> Result<ArrayRef, ArrowError> {
+    if let Some(DataType::Utf8) = chunks.first().map(|a| a.data_type()) {
+        let v: Vec<rdf_utf8_array> = chunks.iter().map(|a| utf8_view(a.as_any().downcast_ref::<StringArray>().unwrap())).collect();
+        let rows: usize = chunks.iter().map(|a| a.len()).sum();
+        let count = 0i64;   // written by the library; the row count of the result says the same
+        return Ok(utf8_call(&[rows], &[false], &|oo, od| unsafe { rdf_utf8_uniques(v.as_ptr(), v.len() as i64, oo, od, &count as *const i64 as *mut i64) })?.remove(0));
+    }
+    let v: Vec<rdf_array> = chunks.iter().map(|a| view(*a)).collect();
+    let mut count = 0i64;
+    status(unsafe { rdf_uniques(v.as_ptr(), v.len() as i64, std::ptr::null_mut(), &mut count) })?;
+    let mut buf = OutBuf::new(chunks[0].data_type().clone(), count as usize, false);
+    let mut out = buf.as_out();
+    status(unsafe { rdf_uniques(v.as_ptr(), v.len() as i64, &mut out, &mut count) })?;
     Ok(buf.finish(&out))
 }
 

@@ -1194,6 +1194,82 @@ class Api:
         return self._utf8_run(call, chunks, [c.length for c in chunks],
                               [c.validity is not None if isinstance(c, HostUtf8) else bool(c.validity_ptr) for c in chunks], as_arrow)
 
+    # ---- Column::hist / Column::uniques (bound lazily: only the product has them)
+    @staticmethod
+    def _stats_out(dtype: int, capacity: int, device: bool):
+        """One output array of `capacity` elements in host or device memory (device buffers padded to 64 elements)."""
+        if not device:
+            return HostArray.empty_out(dtype, capacity, False)
+        import torch
+        t = torch.zeros(((capacity + 63) // 64) * 64 + 64, dtype=torch.int64, device="cuda")
+        return DeviceArray(t.data_ptr(), None, 0, capacity, dtype, 0, keep=t, capacity=capacity)
+
+    @staticmethod
+    def stats_to_numpy(arr) -> np.ndarray:
+        """The logical values of an output of hist / uniques, whichever memory it lives in."""
+        if isinstance(arr, HostArray):
+            return arr.to_numpy().copy()
+        return arr.keep.cpu().numpy().view(NP_OF[arr.dtype])[:arr.length].copy()
+
+    def hist(self, chunks: Sequence, nbins: int, range=None, outs=None):
+        """Column::hist with numpy.histogram's buckets -> (counts, edges, counted): an Int64 array of nbins, a Float64 array of
+        nbins + 1 (HostArray / DeviceArray like the input; `outs` = caller-allocated (counts, edges)) and the rows counted."""
+        n = len(chunks)
+        device = any(isinstance(c, DeviceArray) for c in chunks) or (outs is not None and isinstance(outs[0], DeviceArray))
+        if outs is None:
+            outs = (self._stats_out(I64, nbins, device), self._stats_out(F64, nbins + 1, device))
+        cc, ce = (rdf_out * 1)(outs[0].out_struct()), (rdf_out * 1)(outs[1].out_struct())
+        rng = (C.c_double * 2)(float(range[0]), float(range[1])) if range is not None else None
+        counted = C.c_int64(-1)
+        fn = self._fn("hist")
+        fn.restype = C.c_int
+        self._check(fn(_flat([chunks], n), C.c_int64(n), C.c_int64(nbins), rng, cc, ce, C.byref(counted)))
+        self._finish([outs[0]], cc)
+        self._finish([outs[1]], ce)
+        return outs[0], outs[1], counted.value
+
+    def uniques(self, chunks: Sequence, out=None, count_only: bool = False):
+        """Column::uniques of an Int64 / UInt64 / Float64 column -> ONE array of the distinct values (unspecified order).
+        Without `out` the count-only call sizes the buffer; count_only=True returns just the count."""
+        n = len(chunks)
+        carr = _flat([chunks], n)
+        fn = self._fn("uniques")
+        fn.restype = C.c_int
+        count = C.c_int64(-1)
+        if out is None:
+            self._check(fn(carr, C.c_int64(n), None, C.byref(count)))
+            if count_only:
+                return count.value
+            device = any(isinstance(c, DeviceArray) for c in chunks)
+            out = self._stats_out(chunks[0].dtype if n else F64, count.value, device)
+        co = (rdf_out * 1)(out.out_struct())
+        self._check(fn(carr, C.c_int64(n), co, C.byref(count)))
+        return self._finish([out], co)[0]
+
+    def utf8_uniques(self, chunks: Sequence, as_arrow=False):
+        """Column::uniques of a Utf8 column -> ONE Utf8 chunk of the distinct strings (no NULLs, unspecified order).  The
+        output can never need more bytes than the input, so the buffers are sized from the input and one call is made."""
+        n = len(chunks)
+        carr = (rdf_utf8_array * max(1, n))(*[c.c_struct() for c in chunks])
+        fn = self._utf8_fn("utf8_uniques")
+        count = C.c_int64(-1)
+        rows = sum(c.length for c in chunks)
+        device = any(isinstance(c, DeviceUtf8) for c in chunks)
+        nbytes = sum(c.data_length if isinstance(c, DeviceUtf8) else len(c.data) - c.data_offset for c in chunks)
+        co, cd, keep = self._utf8_outs(chunks, [rows], [False], device, [max(1, nbytes)])
+        self._check(fn(carr, C.c_int64(n), co, cd, C.byref(count)))
+        got = co[0].length - 1
+        if device:
+            ot, dt, vt = keep[0]
+            r = DeviceUtf8(ot.data_ptr(), dt.data_ptr(), cd[0].length, got, None, 0, 0, 0, keep=(ot, dt, vt))
+        else:
+            ob, db, vb = keep[0]
+            r = HostUtf8(ob, db, None, 0, got, 0, 0)
+        if as_arrow:
+            h = r.to_host() if device else r
+            r = h.to_pylist() if as_arrow == "pylist" else h.to_arrow()
+        return r
+
     # ---- fused grouped aggregation over a small dense domain (TPC-H Q1 shape)
     def group_pipeline(self, expr: Expr, cols: Sequence[Sequence], value_roots: Sequence[int], group_root: int, ngroups: int,
                        filter_root: int = -1):

@@ -292,7 +292,10 @@ rdf_status utf8_run(int op, const rdf_utf8_array* chunks, int64_t nchunks, const
     HIP_TRY(hipStreamSynchronize(ctx.stream));
     std::vector<int64_t> nulls((size_t)nout);
     memcpy(nulls.data(), ctx.pinned + pin_n, (size_t)nout * 8);
-    if (mem == RDF_MEM_HOST) RDF_TRY(outr.download(0));
+    if (mem == RDF_MEM_HOST) {
+        RDF_TRY(pinned_reserve(outr.small_bytes));   // (inputs copied directly leave the staging buffer smaller than the packed outputs)
+        RDF_TRY(outr.download(0));
+    }
     for (int64_t o = 0; o < nout; ++o) {
         out_offsets[o].null_count = nulls[o];
         out_data[o].null_count = 0;

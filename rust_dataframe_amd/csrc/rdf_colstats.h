@@ -1,0 +1,87 @@
+// rdf_colstats.h — argument blocks and launchers of Column::hist / Column::uniques (kernels: rdf_colstats.hip, host side:
+// rdf_capi_colstats.inc), and the ONE definition of a histogram's bucket edges, shared by host and device.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "rdf_device.h"
+#include "rdf_utf8.h"
+
+// edges[i] of numpy.histogram(bins = nbins, range = (lo, hi)): lo + i * step with two roundings (the library is compiled
+// -ffp-contract=off, host and device alike), the last edge hi exactly.
+__host__ __device__ inline double cs_edge(double lo, double hi, double step, int64_t nbins, int64_t i) {
+    if (i >= nbins) return hi;
+    const double p = (double)i * step;
+    return lo + p;
+}
+
+constexpr int kCsThreads = 256;
+constexpr int kCsRowsPerLane = 8;
+constexpr int kCsTile = kCsThreads * kCsRowsPerLane;   // rows of one tile of a numeric column: 8 coalesced 8-byte loads per lane
+constexpr int kCsHistLdsBins = 4096;                   // up to here the counters of a block live in LDS (16 KiB of 32-bit words)
+constexpr int kCsHistWaveBins = 1024;                  // up to here every wave of the block has its own copy of them
+constexpr int kCsLdsSetSlots = 2048;                   // the block's LDS set of the numeric distinct pass (16 KiB), filled to half
+constexpr int kCsLongRow = 512;                        // Utf8 rows of this many bytes or more are hashed / compared by a whole wave
+constexpr uint64_t kCsEmpty = 0xFFF7A5A55A5A0001ull;   // free slot of the sets: a NaN payload no normalised Float64 key has
+
+// A chunked 8-byte column cut into tiles that never cross a chunk: tile t belongs to the chunk c with
+// tile_start[c] <= t < tile_start[c + 1].
+struct CsCol {
+    const rdfk::DevChunkCol* chunks;       // [nchunks]
+    const int64_t*           row_start;    // [nchunks + 1]
+    const int64_t*           tile_start;   // [nchunks + 1]
+    int64_t                  nchunks, ntiles, n;
+};
+
+struct CsHistArgs {
+    CsCol    col;
+    int32_t  is_int;       // Int64 values, converted `as f64`
+    int32_t  peels;        // rounds of "count the lanes that share the first lane's bucket" before single adds
+    double   lo, hi, step, scale;
+    int64_t  nbins;
+    unsigned long long* counts;    // [nbins], zeroed
+    unsigned long long* counted;   // [1], zeroed
+};
+
+// counters of the distinct passes (one zeroed block of 8 words)
+enum : int { CS_G_COUNT = 0, CS_G_OVERFLOW = 1, CS_G_SPECIAL = 2, CS_G_EMITTED = 3, CS_G_MISMATCH = 4 };
+
+struct CsSetArgs {
+    CsCol     col;
+    int32_t   is_f64;
+    uint64_t* table;       // [slots], kCsEmpty
+    uint32_t* rep;         // [slots] Utf8: the smallest row with the slot's hash (0xFFFFFFFF), else nullptr
+    uint64_t  mask;        // slots - 1
+    uint64_t  max_fill;    // keys the table may take before the pass gives up
+    unsigned long long* g;
+    uint64_t* out64;       // emit: the keys (numeric)
+    uint32_t* out32;       // emit: the representative rows (Utf8)
+};
+
+// the sort route: rows in sorted order, first of every run of equal values kept
+struct CsRunArgs {
+    CsCol           col;
+    int32_t         is_f64;
+    const uint32_t* perm;      // [n]
+    uint64_t*       out64;     // nullptr = count only
+    unsigned long long* g;
+};
+
+struct CsUtf8Args {
+    const Utf8Chunk* chunks;
+    int64_t          nchunks, n;
+    uint64_t*        hash;     // [n]
+    CsSetArgs        set;
+    const uint32_t*  perm;     // exact route: rows in sorted order
+    uint32_t*        out32;    // exact route: first row of every run (nullptr = count only)
+};
+
+int        cs_grid(int64_t items);
+hipError_t launch_cs_hist(const CsHistArgs& a, hipStream_t s);
+hipError_t launch_cs_fill64(uint64_t* p, int64_t n, uint64_t v, hipStream_t s);
+hipError_t launch_cs_distinct(const CsSetArgs& a, hipStream_t s);        // numeric keys -> LDS set -> table
+hipError_t launch_cs_emit(const CsSetArgs& a, hipStream_t s);            // table -> out64 / out32
+hipError_t launch_cs_runs(const CsRunArgs& a, hipStream_t s);
+hipError_t launch_cs_utf8_hash(const CsUtf8Args& a, hipStream_t s);      // hash[], table, rep
+hipError_t launch_cs_utf8_verify(const CsUtf8Args& a, hipStream_t s);    // every row against its hash's representative
+hipError_t launch_cs_utf8_runs(const CsUtf8Args& a, hipStream_t s);
