@@ -2189,20 +2189,30 @@ class DataFrame {
         idx->length = ov.length;
         return take(idx);
     }
-    // lexsort_to_indices when a criterion is a Utf8 column (rdf_lexsort_to_indices: byte order, NULLs last, stable).  A text
-    // column's chunks go as offsets + bytes built from the mirror's strings; they are copied to the device when the frame's
-    // numeric columns live there (one memory space per call, and the take that follows wants indices beside the columns).
-    ArrayRef lexsort_indices(const std::vector<SortCriteria>& criteria) const {
+    // The criteria of a sort or a window as rdf_sort_key entries.  A numeric column goes by its chunks' views; a text column's
+    // chunks go as offsets + bytes built from the mirror's strings, copied to the device when the frame's numeric columns
+    // live there (one memory space per call, and the take that follows wants indices beside the columns).
+    struct SortKeys {
+        struct Text { std::vector<int32_t> offs; std::string bytes; std::vector<uint8_t> valid; std::vector<std::shared_ptr<DeviceBuffer>> dev; };
+        std::vector<std::unique_ptr<Text>> keep;
+        std::vector<std::vector<rdf_array>> num;
+        std::vector<std::vector<rdf_utf8_array>> txt;
+        std::vector<rdf_sort_key> keys;
+    };
+    bool numeric_columns_on_host() const {
         bool host = true;
         for (auto& c : columns_)
             if (c.data_type() != DataType::Utf8)
                 for (auto& a : c.data().chunks()) host &= a->host;
+        return host;
+    }
+    SortKeys sort_keys(const std::vector<SortCriteria>& criteria, bool host) const {
         const int32_t mem = host ? RDF_MEM_HOST : RDF_MEM_DEVICE;
-        struct Text { std::vector<int32_t> offs; std::string bytes; std::vector<uint8_t> valid; std::vector<std::shared_ptr<DeviceBuffer>> dev; };
-        std::vector<std::unique_ptr<Text>> keep;
-        std::vector<std::vector<rdf_array>> num(criteria.size());
-        std::vector<std::vector<rdf_utf8_array>> txt(criteria.size());
-        std::vector<rdf_sort_key> keys(criteria.size());
+        using Text = SortKeys::Text;
+        SortKeys sk;
+        sk.num.resize(criteria.size());
+        sk.txt.resize(criteria.size());
+        sk.keys.resize(criteria.size());
         auto place = [&](Text& t, const void* src, int64_t bytes) -> const void* {   // host bytes, or a device copy of them
             if (host) return src;
             t.dev.push_back(std::make_shared<DeviceBuffer>(bytes));
@@ -2212,11 +2222,11 @@ class DataFrame {
         for (size_t k = 0; k < criteria.size(); ++k) {
             const Column& col = column_by_name(criteria[k].column);
             if (col.data_type() != DataType::Utf8) {
-                for (auto& a : col.data().chunks()) num[k].push_back(a->view());
+                for (auto& a : col.data().chunks()) sk.num[k].push_back(a->view());
             } else {
                 for (auto& a : col.data().chunks()) {
-                    keep.push_back(std::make_unique<Text>());
-                    Text& t = *keep.back();
+                    sk.keep.push_back(std::make_unique<Text>());
+                    Text& t = *sk.keep.back();
                     t.offs.reserve((size_t)a->length + 1);
                     t.offs.push_back(0);
                     for (int64_t r = 0; r < a->length; ++r) {
@@ -2232,16 +2242,22 @@ class DataFrame {
                     u.data.values = place(t, t.bytes.data(), (int64_t)t.bytes.size());
                     u.data.validity = nullptr;
                     u.data.offset = 0; u.data.length = (int64_t)t.bytes.size(); u.data.null_count = 0; u.data.dtype = RDF_U8; u.data.mem = mem;
-                    txt[k].push_back(u);
+                    sk.txt[k].push_back(u);
                 }
             }
-            keys[k].values = num[k].empty() ? nullptr : num[k].data();
-            keys[k].utf8 = txt[k].empty() ? nullptr : txt[k].data();
-            keys[k].options = rdf_sort_options{criteria[k].descending ? 1 : 0, 0};
+            sk.keys[k].values = sk.num[k].empty() ? nullptr : sk.num[k].data();
+            sk.keys[k].utf8 = sk.txt[k].empty() ? nullptr : sk.txt[k].data();
+            sk.keys[k].options = rdf_sort_options{criteria[k].descending ? 1 : 0, 0};
         }
+        return sk;
+    }
+    // lexsort_to_indices when a criterion is a Utf8 column (rdf_lexsort_to_indices: byte order, NULLs last, stable).
+    ArrayRef lexsort_indices(const std::vector<SortCriteria>& criteria) const {
+        const bool host = numeric_columns_on_host();
+        const SortKeys sk = sort_keys(criteria, host);
         auto idx = Array::make_out(DataType::UInt32, num_rows(), false, host);
         rdf_out ov = idx->out_view(num_rows());
-        check(rdf_lexsort_to_indices(keys.data(), (int32_t)keys.size(), (int64_t)num_chunks(), &ov));
+        check(rdf_lexsort_to_indices(sk.keys.data(), (int32_t)sk.keys.size(), (int64_t)num_chunks(), &ov));
         idx->length = ov.length;
         return idx;
     }
@@ -2252,10 +2268,65 @@ class DataFrame {
         return DataFrame(schema_, std::move(cols));
     }
 
+    // Window functions (the reference declares them with empty bodies: WindowSpec in src/window.rs, row_number .. lead in
+    // src/functions/window.rs, ntile in src/functions/scalar.rs:345; the semantics are SQL's, written down at rdf_window).
+    // partition_by: rows that agree on every listed column form a partition (NULL is a value); order_by: the order inside a
+    // partition, NULLs last, ties in row order.  rows_between / range_between frames are not covered.
+    enum class WindowFunction : int32_t {
+        RowNumber = RDF_WIN_ROW_NUMBER, Rank = RDF_WIN_RANK, DenseRank = RDF_WIN_DENSE_RANK, PercentRank = RDF_WIN_PERCENT_RANK,
+        CumeDist = RDF_WIN_CUME_DIST, Ntile = RDF_WIN_NTILE, Lag = RDF_WIN_LAG, Lead = RDF_WIN_LEAD
+    };
+    class WindowSpec {
+      public:
+        WindowSpec& partition_by(std::vector<std::string> cols) { partition_ = std::move(cols); return *this; }
+        WindowSpec& order_by(std::vector<SortCriteria> criteria) { order_ = std::move(criteria); return *this; }
+        const std::vector<std::string>& partition() const { return partition_; }
+        const std::vector<SortCriteria>& order() const { return order_; }
+      private:
+        std::vector<std::string> partition_;
+        std::vector<SortCriteria> order_;
+    };
+    // Appends fn over `spec` as column `name`, chunked like the frame: Int64 for RowNumber / Rank / DenseRank / Ntile(param
+    // buckets), Float64 for PercentRank / CumeDist; Lag / Lead(param rows) append `value_column` of the row param places
+    // before / after in the partition — any dtype, text included — NULL where the partition ends (rdf_window hands out row
+    // indices, Column::take gathers through them: a NULL index is a NULL row).
+    DataFrame with_window(const std::string& name, const WindowSpec& spec, WindowFunction fn, int64_t param = 0,
+                          const std::string& value_column = "") const {
+        const bool shifts = fn == WindowFunction::Lag || fn == WindowFunction::Lead;
+        if (shifts && value_column.empty()) throw DataFrameError(DataFrameError::ComputeError, "with_window: lag / lead need a value column");
+        const bool host = numeric_columns_on_host();
+        std::vector<SortCriteria> part;
+        for (auto& c : spec.partition()) part.push_back(SortCriteria{c, false, false});
+        const SortKeys pk = sort_keys(part, host), ok = sort_keys(spec.order(), host);
+        const DataType dt = shifts ? DataType::UInt32 : (fn == WindowFunction::PercentRank || fn == WindowFunction::CumeDist) ? DataType::Float64 : DataType::Int64;
+        auto out = Array::make_out(dt, num_rows(), shifts, host);
+        rdf_out ov = out->out_view(num_rows());
+        const rdf_window_call call{(int32_t)fn, 0, param};
+        const bool keyed = !pk.keys.empty() || !ok.keys.empty();
+        check(rdf_window(pk.keys.empty() ? nullptr : pk.keys.data(), (int32_t)pk.keys.size(), ok.keys.empty() ? nullptr : ok.keys.data(),
+                         (int32_t)ok.keys.size(), (int64_t)num_chunks(), keyed ? 0 : num_rows(), &call, 1, &ov));
+        out->length = ov.length;
+        out->null_count = ov.null_count;
+        ArrayRef whole = out;
+        Field field{name, dt, false};
+        if (shifts) {
+            const Column taken = column_by_name(value_column).take(out, 4096);
+            whole = taken.data().chunk(0);
+            field = Field{name, taken.data_type(), true};
+        }
+        std::vector<ArrayRef> chunks;                       // one array of all rows -> the frame's batches, zero-copy
+        int64_t at = 0;
+        for (int64_t len : columns_.at(0).data().chunk_counts()) { chunks.push_back(whole->slice(at, len)); at += len; }
+        return with_column(name, Column::from_arrays(std::move(chunks), field));
+    }
+
   private:
     Schema schema_;
     std::vector<Column> columns_;
 };
+
+using WindowSpec = DataFrame::WindowSpec;           // the reference's names (src/window.rs, src/functions/window.rs)
+using WindowFunction = DataFrame::WindowFunction;
 
 // ------------------------------------------------------------------------------------------------
 // GpuFrame: a DataFrame of numeric columns pinned in HBM behind a frame handle (rdf_frame_pin), and the reference's

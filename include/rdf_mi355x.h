@@ -466,6 +466,54 @@ rdf_status rdf_uniques(const rdf_array* chunks, int64_t nchunks, rdf_out* out_va
 rdf_status rdf_utf8_uniques(const rdf_utf8_array* chunks, int64_t nchunks, rdf_out* out_offsets, rdf_out* out_data,
                             int64_t* out_count);
 
+/* ------------------------------------------------------------------ window functions */
+
+/* SQL window functions over partitions: row_number / rank / dense_rank / percent_rank / cume_dist / ntile / lag / lead.
+ * The reference declares them (src/functions/window.rs, WindowSpec in src/window.rs, ntile in src/functions/scalar.rs) with
+ * empty bodies, so the semantics are SQL's / Spark's, written down here.  One call answers up to 8 functions from ONE sort.
+ *
+ * partition_by / order_by are rdf_sort_key lists (numeric or Utf8 chunks per key, rdf_lexsort_to_indices' conventions;
+ * 0 .. 4 keys each).  The `options` of a partition key are ignored; `descending` of an order key is honoured.  Rows are
+ * numbered over the concatenation of the chunks; outs[c] is ONE array of all rows for calls[c] in the ORIGINAL row order
+ * (row i's answer at position i).  Inputs and outputs all in host memory or all in device memory.
+ *   - Partitions: rows are in one partition iff they agree on every partition key.  NULL is a key value of its own.  No
+ *     partition keys: one partition of all rows.
+ *   - Order inside a partition: by the order keys, key 0 most significant, `descending` per key; NULLs last in both
+ *     directions (nulls_first is ignored); ties keep ascending row order.  No order keys: row order, and every row of a
+ *     partition is a peer of every other.
+ *   - Peers: rows of one partition that agree on every order key; NULL agrees with NULL.
+ *   - Float keys (partition and order alike) compare as rdf_uniques does: -0.0 == +0.0, every NaN equals every NaN, NaN
+ *     sorts after +inf (before it when descending).  rdf_sort_to_indices' IEEE total order is not changed by this.
+ *   - With k = 0-based position of the row in its ordered partition, n = rows of the partition, f / l = position of the
+ *     row's first / last peer, d = number of peer groups before the row's own:
+ *       ROW_NUMBER k + 1;  RANK f + 1;  DENSE_RANK d + 1;
+ *       PERCENT_RANK n == 1 ? 0.0 : (double)f / (double)(n - 1);  CUME_DIST (double)(l + 1) / (double)n  (one IEEE division
+ *       of exact integers each: bit-exact against any CPU);
+ *       NTILE(b): q = n / b, r = n % b; k < r(q+1) ? k/(q+1) + 1 : r + (k - r(q+1))/q + 1  (b > n gives k + 1);
+ *       LAG(o) / LEAD(o): the ROW INDEX (in the concatenation) of the row at position k - o / k + o of the same partition,
+ *       NULL when that position is outside it; offset 0 is the row itself.  Gather any column, numeric or Utf8, with
+ *       rdf_take / rdf_utf8_take: their "NULL index -> NULL row" rule gives SQL's default.
+ *   - Output dtypes: RDF_I64 for ROW_NUMBER / RANK / DENSE_RANK / NTILE, RDF_F64 for PERCENT_RANK / CUME_DIST, RDF_U32
+ *     with a validity bitmap for LAG / LEAD (validity required when the offset is > 0; written where given otherwise).
+ * param: NTILE buckets >= 1; LAG / LEAD offset >= 0; not read for the other functions.
+ * With no keys at all the row count is nrows_if_no_keys (nchunks is ignored); otherwise nchunks >= 1 and nrows_if_no_keys
+ * is 0 or the keys' rows.  Zero rows is a valid call that writes nothing.
+ * Errors, all before any device work: no calls, an unknown fn, param out of range, more than 4 keys of a kind or 8 calls,
+ * a key setting both pointers or neither, wrong dtypes, a missing validity for LAG / LEAD with offset > 0, mixed memory
+ * kinds, nrows_if_no_keys that contradicts the keys, an output with a capacity and no buffer: RDF_INVALID_ARGUMENT;
+ * chunk row counts that differ between keys: RDF_COMPUTE_ERROR; 2^32 rows or more: RDF_INVALID_ARGUMENT; an output
+ * capacity below the rows: RDF_MEMORY_ERROR with every
+ * outs[c].length set to the rows and nothing written. */
+typedef enum {
+    RDF_WIN_ROW_NUMBER = 0, RDF_WIN_RANK = 1, RDF_WIN_DENSE_RANK = 2, RDF_WIN_PERCENT_RANK = 3, RDF_WIN_CUME_DIST = 4,
+    RDF_WIN_NTILE = 5, RDF_WIN_LAG = 6, RDF_WIN_LEAD = 7
+} rdf_window_fn;
+typedef struct { int32_t fn; int32_t pad; int64_t param; } rdf_window_call;
+#define RDF_WINDOW_MAX_KEYS 4
+#define RDF_WINDOW_MAX_CALLS 8
+rdf_status rdf_window(const rdf_sort_key* partition_by, int32_t npartition, const rdf_sort_key* order_by, int32_t norder,
+                      int64_t nchunks, int64_t nrows_if_no_keys, const rdf_window_call* calls, int32_t ncalls, rdf_out* outs);
+
 /* ------------------------------------------------------------------ fused batch loop */
 
 typedef enum {

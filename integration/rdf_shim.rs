@@ -61,6 +61,11 @@ pub mod sys {
     // one criterion of rdf_lexsort_to_indices: exactly one of values / utf8 points at nchunks chunks
     #[repr(C)] #[derive(Clone, Copy)]
     pub struct rdf_sort_key { pub values: *const rdf_array, pub utf8: *const rdf_utf8_array, pub options: rdf_sort_options }
+    // one call of rdf_window: fn = RDF_WIN_*, param = ntile buckets / lag, lead offset
+    #[repr(C)] #[derive(Clone, Copy)] pub struct rdf_window_call { pub fn_: i32, pub pad: i32, pub param: i64 }
+    pub const RDF_WIN_ROW_NUMBER: i32 = 0; pub const RDF_WIN_RANK: i32 = 1; pub const RDF_WIN_DENSE_RANK: i32 = 2;
+    pub const RDF_WIN_PERCENT_RANK: i32 = 3; pub const RDF_WIN_CUME_DIST: i32 = 4; pub const RDF_WIN_NTILE: i32 = 5;
+    pub const RDF_WIN_LAG: i32 = 6; pub const RDF_WIN_LEAD: i32 = 7;
     #[repr(C)] pub struct rdf_frame { _opaque: [u8; 0] }
     #[repr(C)] pub struct rdf_comm { _opaque: [u8; 0] }
     #[repr(C)] #[derive(Clone, Copy, Default)]
@@ -113,6 +118,9 @@ pub mod sys {
         pub fn rdf_uniques(chunks: *const rdf_array, nchunks: i64, out_values: *mut rdf_out, out_count: *mut i64) -> i32;
         pub fn rdf_utf8_uniques(chunks: *const rdf_utf8_array, nchunks: i64, out_offsets: *mut rdf_out, out_data: *mut rdf_out,
                                 out_count: *mut i64) -> i32;
+        // WindowSpec / WindowFunctions (src/window.rs, src/functions/window.rs: declared, bodies empty) + ntile (scalar.rs:345)
+        pub fn rdf_window(partition_by: *const rdf_sort_key, npartition: i32, order_by: *const rdf_sort_key, norder: i32,
+                          nchunks: i64, nrows_if_no_keys: i64, calls: *const rdf_window_call, ncalls: i32, outs: *mut rdf_out) -> i32;
         pub fn rdf_equijoin_indices(left_keys: *const rdf_array, left_nchunks: i64, right_keys: *const rdf_array, right_nchunks: i64,
                                     join_type: i32, out_left: *mut rdf_out, out_right: *mut rdf_out, out_rows: *mut i64) -> i32;
         pub fn rdf_equijoin_indices_multi(left_keys: *const rdf_array, left_nchunks: i64, right_keys: *const rdf_array,
@@ -536,6 +544,42 @@ pub fn lexsort_to_indices(criteria: &[(Vec<&dyn Array>, bool)]) -> Result<ArrayR
     let mut out = buf.as_out();
     status(unsafe { rdf_lexsort_to_indices(keys.as_ptr(), keys.len() as i32, nchunks as i64, &mut out) })?;
     Ok(buf.finish(&out))
+}
+
+/// WindowSpec { partition_by, order_by } (src/window.rs) + one WindowFunctions entry (src/functions/window.rs; `ntile` of
+/// scalar.rs:345): the function's value for every row, in row order, as one array — Int64Array for row_number / rank /
+/// dense_rank / ntile, Float64Array for percent_rank / cume_dist, and for lag / lead a UInt32Array of ROW INDICES (NULL
+/// where the partition ends) to gather any column with `take` / `utf8_take`.  Keys as for `lexsort_to_indices`; the
+/// `bool` of a partition key is not read.  Several functions over one spec: pass them all, they share the sort.
+pub fn window(partition_by: &[(Vec<&dyn Array>, bool)], order_by: &[(Vec<&dyn Array>, bool)], rows: usize,
+              calls: &[(i32, i64)]) -> Result<Vec<ArrayRef>, ArrowError> {
+    let nchunks = partition_by.first().or(order_by.first()).map_or(0, |c| c.0.len());
+    let mut num: Vec<Vec<rdf_array>> = Vec::new();
+    let mut txt: Vec<Vec<rdf_utf8_array>> = Vec::new();
+    for (chunks, _) in partition_by.iter().chain(order_by.iter()) {
+        match chunks.first().map(|a| a.data_type()) {
+            Some(DataType::Utf8) => { txt.push(chunks.iter().map(|a| utf8_view(a.as_any().downcast_ref::<StringArray>().unwrap())).collect()); num.push(Vec::new()); }
+            _ => { num.push(chunks.iter().map(|a| view(*a)).collect()); txt.push(Vec::new()); }
+        }
+    }
+    let keys: Vec<rdf_sort_key> = partition_by.iter().chain(order_by.iter()).enumerate().map(|(k, (_, desc))| rdf_sort_key {
+        values: if num[k].is_empty() { std::ptr::null() } else { num[k].as_ptr() },
+        utf8: if txt[k].is_empty() { std::ptr::null() } else { txt[k].as_ptr() },
+        options: rdf_sort_options { descending: *desc as i32, nulls_first: 0 },
+    }).collect();
+    let (np, no) = (partition_by.len(), order_by.len());
+    let ccalls: Vec<rdf_window_call> = calls.iter().map(|(f, p)| rdf_window_call { fn_: *f, pad: 0, param: *p }).collect();
+    let mut bufs: Vec<OutBuf> = calls.iter().map(|(f, _)| match *f {
+        RDF_WIN_PERCENT_RANK | RDF_WIN_CUME_DIST => OutBuf::new(DataType::Float64, rows, false),
+        RDF_WIN_LAG | RDF_WIN_LEAD => OutBuf::new(DataType::UInt32, rows, true),
+        _ => OutBuf::new(DataType::Int64, rows, false),
+    }).collect();
+    let mut outs: Vec<rdf_out> = bufs.iter_mut().map(|b| b.as_out()).collect();
+    status(unsafe { rdf_window(if np > 0 { keys.as_ptr() } else { std::ptr::null() }, np as i32,
+                               if no > 0 { keys[np..].as_ptr() } else { std::ptr::null() }, no as i32,
+                               nchunks as i64, if np + no == 0 { rows as i64 } else { 0 },
+                               ccalls.as_ptr(), ccalls.len() as i32, outs.as_mut_ptr()) })?;
+    Ok(bufs.into_iter().zip(outs.iter()).map(|(b, o)| b.finish(o)).collect())
 }
 
 /// Column::hist (src/table.rs:244-290) of an Int64 / Float64 column: (bucket start, bucket end, count[, count / counted])

@@ -106,6 +106,21 @@ class rdf_sort_key(C.Structure):
     _fields_ = [("values", C.POINTER(rdf_array)), ("utf8", C.POINTER(rdf_utf8_array)), ("options", rdf_sort_options)]
 
 
+class rdf_window_call(C.Structure):
+    _fields_ = [("fn", C.c_int32), ("pad", C.c_int32), ("param", C.c_int64)]
+
+
+# rdf_window_fn
+WIN_ROW_NUMBER, WIN_RANK, WIN_DENSE_RANK, WIN_PERCENT_RANK, WIN_CUME_DIST, WIN_NTILE, WIN_LAG, WIN_LEAD = range(8)
+WINDOW_FNS = {"row_number": WIN_ROW_NUMBER, "rank": WIN_RANK, "dense_rank": WIN_DENSE_RANK, "percent_rank": WIN_PERCENT_RANK,
+              "cume_dist": WIN_CUME_DIST, "ntile": WIN_NTILE, "lag": WIN_LAG, "lead": WIN_LEAD}
+WINDOW_MAX_KEYS, WINDOW_MAX_CALLS = 4, 8
+
+
+def window_out_dtype(fn: int) -> int:
+    return F64 if fn in (WIN_PERCENT_RANK, WIN_CUME_DIST) else U32 if fn in (WIN_LAG, WIN_LEAD) else I64
+
+
 class rdf_exchange_stats(C.Structure):
     _fields_ = [("exchange", C.c_int32), ("rounds", C.c_int32), ("local_groups", C.c_int64), ("rows_sent", C.c_int64),
                 ("rows_sent_remote", C.c_int64), ("rows_received", C.c_int64), ("bytes_sent", C.c_int64),
@@ -1245,6 +1260,75 @@ class Api:
         co = (rdf_out * 1)(out.out_struct())
         self._check(fn(carr, C.c_int64(n), co, C.byref(count)))
         return self._finish([out], co)[0]
+
+    # ---- window functions (src/functions/window.rs, src/window.rs: declared by the reference, empty there)
+    @staticmethod
+    def _window_out(dtype: int, n: int, device: bool, with_validity: bool):
+        if not device:
+            return HostArray.empty_out(dtype, n, with_validity)
+        import torch
+        cap = ((n + 63) // 64) * 64 + 64
+        t = torch.zeros(cap, dtype=torch.int64, device="cuda")   # (8 bytes per element cover every output dtype)
+        v = torch.zeros(cap // 8, dtype=torch.uint8, device="cuda") if with_validity else None
+        return DeviceArray(t.data_ptr(), v.data_ptr() if with_validity else None, 0, n, dtype, 0, keep=(t, v), capacity=n)
+
+    @staticmethod
+    def _sort_keys(keys: Sequence):
+        """[(chunks, descending) | chunks] -> (rdf_sort_key array, objects to keep alive)"""
+        keys = [(k, False) if not isinstance(k, tuple) else k for k in keys]
+        ck = (rdf_sort_key * max(1, len(keys)))()
+        keep = []
+        for i, (chunks, desc) in enumerate(keys):
+            utf8 = len(chunks) > 0 and all(isinstance(c, (HostUtf8, DeviceUtf8)) for c in chunks)
+            if utf8:
+                arr = (rdf_utf8_array * max(1, len(chunks)))(*[c.c_struct() for c in chunks])
+                ck[i] = rdf_sort_key(None, C.cast(arr, C.POINTER(rdf_utf8_array)), rdf_sort_options(int(desc), 0))
+            else:
+                arr = (rdf_array * max(1, len(chunks)))(*[c.c_struct(getattr(c, "_unknown_nc", False)) for c in chunks])
+                ck[i] = rdf_sort_key(C.cast(arr, C.POINTER(rdf_array)), None, rdf_sort_options(int(desc), 0))
+            keep.append(arr)
+        return ck, keep
+
+    @staticmethod
+    def window_to_numpy(out):
+        """One output of window(raw=True) as numpy: an array, or for lag / lead the masked pair (row indices, valid)."""
+        if isinstance(out, HostArray):
+            vals = out.values[:out.length].copy()
+            valid = unpack_bits(out.validity, 0, out.length) if out.validity is not None else None
+        else:
+            t, v = out.keep
+            vals = t.cpu().numpy().view(NP_OF[out.dtype])[:out.length].copy()
+            valid = unpack_bits(v.cpu().numpy(), 0, out.length) if v is not None else None
+        if out.dtype != U32:
+            return vals
+        return vals, (valid if valid is not None else np.ones(out.length, dtype=bool))
+
+    def window(self, partition_by: Sequence, order_by: Sequence, calls: Sequence, mem: Optional[str] = None, nrows: int = 0,
+               outs=None, raw: bool = False):
+        """rdf_window: SQL window functions over partitions, every call answered from one sort.  partition_by = [chunks, ...],
+        order_by = [(chunks, descending) | chunks, ...] (chunks: HostArray / DeviceArray or HostUtf8 / DeviceUtf8 lists);
+        calls = [name | (name, param), ...] with the names of WINDOW_FNS (param: ntile buckets, lag / lead offset).  mem
+        ("host" / "device") is needed only when there are no keys, and nrows gives the rows then.  -> one numpy array per call
+        in the original row order, lag / lead as (row indices, valid); raw=True returns the output arrays as they are."""
+        pk, keep_p = self._sort_keys(partition_by)
+        ok, keep_o = self._sort_keys(order_by)
+        all_keys = [k[0] if isinstance(k, tuple) else k for k in list(partition_by) + list(order_by)]
+        nchunks = len(all_keys[0]) if all_keys else 0
+        n = sum(c.length for c in all_keys[0]) if all_keys else int(nrows)
+        device = mem == "device" if mem is not None else any(isinstance(c, (DeviceArray, DeviceUtf8)) for k in all_keys for c in k)
+        cc = (rdf_window_call * max(1, len(calls)))()
+        for i, c in enumerate(calls):
+            name, param = c if isinstance(c, tuple) else (c, 0)
+            cc[i] = rdf_window_call(WINDOW_FNS[name] if isinstance(name, str) else int(name), 0, int(param))
+        if outs is None:
+            outs = [self._window_out(window_out_dtype(cc[i].fn), n, device, cc[i].fn in (WIN_LAG, WIN_LEAD)) for i in range(len(calls))]
+        carr = (rdf_out * max(1, len(outs)))(*[o.out_struct() for o in outs])
+        fn = self._fn("window")
+        fn.restype = C.c_int
+        self._check(fn(pk if partition_by else None, C.c_int32(len(partition_by)), ok if order_by else None, C.c_int32(len(order_by)),
+                       C.c_int64(nchunks), C.c_int64(nrows), cc if calls else None, C.c_int32(len(calls)), carr))
+        self._finish(outs, carr)
+        return outs if raw else [self.window_to_numpy(o) for o in outs]
 
     def utf8_uniques(self, chunks: Sequence, as_arrow=False):
         """Column::uniques of a Utf8 column -> ONE Utf8 chunk of the distinct strings (no NULLs, unspecified order).  The

@@ -28,6 +28,7 @@
 #include "rdf_stage_copy.h"
 #include "rdf_utf8.h"
 #include "rdf_colstats.h"
+#include "rdf_window.h"
 
 using namespace rdfk;
 
@@ -3595,7 +3596,7 @@ rdf_status utf8_sort_column(const Utf8SortCol& col, OsScratch& os, uint64_t* con
 // passes `utf8`, where utf8[k].d_chunks != nullptr makes column k a Utf8 criterion (its d_chunks entries are not read).
 rdf_status sort_core(const DevChunkCol* d_chunks, const int64_t* d_row_start, int64_t nchunks, int64_t n, int ncols, const int* dts,
                      const bool* nullable, const rdf_sort_options* opts, size_t pin_off, const uint32_t** idx_out,
-                     const Utf8SortCol* utf8 = nullptr) {
+                     const Utf8SortCol* utf8 = nullptr, bool canon_float = false /* the window functions' float keys: SortKeyArgs::canon_float */) {
     Ctx& ctx = g_ctx;
     const int64_t ntiles = (n + kSortTile - 1) / kSortTile;
     void *pk0, *pk1, *pi0, *pi1, *pnf, *ph0, *ph1;
@@ -3642,6 +3643,7 @@ rdf_status sort_core(const DevChunkCol* d_chunks, const int64_t* d_row_start, in
         ka.nullflags = has_nulls ? (uint8_t*)pnf : nullptr;
         ka.dtype = dt;
         ka.descending = opts ? opts[k].descending : 0;
+        ka.canon_float = canon_float ? 1 : 0;
         ka.bit_stats = d_stats;
         RDF_TRY(sort_stats_reset(d_stats));
         HIP_TRY(launch_sort_keys(ka, ctx.stream));
@@ -4515,6 +4517,7 @@ rdf_status legacy_groupby_sum(const rdf_array* keys, const rdf_array* values, in
 #include "rdf_capi_utf8.inc"
 #include "rdf_capi_sort_utf8.inc"
 #include "rdf_capi_colstats.inc"
+#include "rdf_capi_window.inc"
 
 extern "C" {
 

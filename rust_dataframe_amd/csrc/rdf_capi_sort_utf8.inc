@@ -118,62 +118,23 @@ rdf_status utf8_sort_column(const Utf8SortCol& col, OsScratch& os, uint64_t* con
     return RDF_OK;
 }
 
-}  // namespace
-
-rdf_status rdf_lexsort_to_indices(const rdf_sort_key* keys, int32_t nkeys, int64_t nchunks, rdf_out* out_indices) {
-    if (nkeys < 1 || !keys) return fail(RDF_COMPUTE_ERROR, "Sort criteria cannot be empty");  // src/dataframe.rs:195-199
-    if (nchunks < 1 || !out_indices) return fail(RDF_INVALID_ARGUMENT, "lexsort: bad arguments");
-    if (nkeys > kMaxFrameCols) return fail(RDF_INVALID_ARGUMENT, "lexsort: at most %d sort criteria", kMaxFrameCols);
-    int32_t mem = -1;
-    bool any_utf8 = false;
-    for (int k = 0; k < nkeys; ++k) {
-        const rdf_sort_key& key = keys[k];
-        if ((key.values != nullptr) == (key.utf8 != nullptr)) return fail(RDF_INVALID_ARGUMENT, "lexsort: key %d must set exactly one of values / utf8", k);
-        if (key.values) {
-            RDF_TRY(check_mem(key.values, nchunks, &mem));
-            for (int64_t c = 0; c < nchunks; ++c)
-                if (!is_numeric(key.values[c].dtype) || key.values[c].dtype != key.values[0].dtype)
-                    return fail(RDF_INVALID_ARGUMENT, "lexsort: key %d: numeric chunks of one dtype", k);
-        } else {
-            any_utf8 = true;
-            for (int64_t c = 0; c < nchunks; ++c) {
-                const rdf_utf8_array& u = key.utf8[c];
-                if (u.offsets.dtype != RDF_I32 || u.offsets.length < 1)
-                    return fail(RDF_INVALID_ARGUMENT, "lexsort: key %d chunk %lld: offsets must be an Int32 array of rows + 1 entries", k, (long long)c);
-                if (u.data.dtype != RDF_U8) return fail(RDF_INVALID_ARGUMENT, "lexsort: key %d chunk %lld: data must be a UInt8 array", k, (long long)c);
-                RDF_TRY(check_mem(&u.offsets, 1, &mem));
-                RDF_TRY(check_mem(&u.data, 1, &mem));
-            }
-        }
-    }
-    RDF_TRY(check_out_mem(out_indices, 1, mem));
-    if (out_indices->dtype != RDF_U32) return fail(RDF_INVALID_ARGUMENT, "lexsort: indices are UInt32");
+// The criteria of a lexsort on the device (host arrays staged, device arrays aliased) and their descriptor tables: d_chunks
+// [k * nchunks + c] for the numeric criteria, Utf8Chunk [k * nchunks + c] for the Utf8 ones, the prefix of the batch lengths.
+// Shared by rdf_lexsort_to_indices and rdf_window.  pin_off: the first free byte of the pinned staging buffer afterwards.
+struct LexKeysOnDevice {
+    TableBuilder tb;
+    size_t o_ch = 0, o_rs = 0, o_u8 = 0;
+    int dts[kMaxFrameCols];
+    bool nullable[kMaxFrameCols];
+    Utf8SortCol ucols[kMaxFrameCols];
+};
+rdf_status lexsort_keys_to_device(const rdf_sort_key* keys, int nkeys, int64_t nchunks, int32_t mem, const std::vector<int64_t>& row_start,
+                                  const char* fn, size_t& pin_off, LexKeysOnDevice& d) {
     auto rows_of = [&](int k, int64_t c) { return keys[k].values ? keys[k].values[c].length : keys[k].utf8[c].offsets.length - 1; };
-    std::vector<int64_t> row_start((size_t)nchunks + 1, 0);
-    for (int64_t c = 0; c < nchunks; ++c) row_start[(size_t)c + 1] = row_start[(size_t)c] + rows_of(0, c);
-    for (int k = 1; k < nkeys; ++k)
-        for (int64_t c = 0; c < nchunks; ++c)
-            if (rows_of(k, c) != rows_of(0, c)) return fail(RDF_COMPUTE_ERROR, "lexsort: columns of a batch differ in length");
-    const int64_t n = row_start[(size_t)nchunks];
-    if (n >= (int64_t)1 << 32) return fail(RDF_INVALID_ARGUMENT, "lexsort: UInt32 indices cap a column at 2^32-1 rows (src/table.rs:218)");
-    if (out_indices->capacity < n) return fail(RDF_MEMORY_ERROR, "output capacity too small");
-    std::vector<rdf_sort_options> opts((size_t)nkeys);
-    for (int k = 0; k < nkeys; ++k) opts[k] = keys[k].options;
-    if (!any_utf8) {   // numeric criteria only: the numeric sort itself, bit for bit
-        std::vector<rdf_array> cols((size_t)nkeys * nchunks);
-        for (int k = 0; k < nkeys; ++k)
-            for (int64_t c = 0; c < nchunks; ++c) cols[(size_t)k * nchunks + c] = keys[k].values[c];
-        return rdf_sort_to_indices(cols.data(), nkeys, nchunks, opts.data(), out_indices);
-    }
-    if (n == 0) { out_indices->length = 0; out_indices->null_count = 0; return RDF_OK; }
-    RDF_TRY(ensure_ready());
-    Ctx& ctx = g_ctx;
-    arena_begin();
-
     // ---- every Utf8 chunk's value-offset range, checked against its data array before a byte of it is read
     std::vector<std::vector<int32_t>> lohi((size_t)nkeys);
     for (int k = 0; k < nkeys; ++k)
-        if (keys[k].utf8) RDF_TRY(utf8_value_ranges(keys[k].utf8, nchunks, mem, lohi[k], "lexsort"));
+        if (keys[k].utf8) RDF_TRY(utf8_value_ranges(keys[k].utf8, nchunks, mem, lohi[k], fn));
 
     // ---- inputs on the device (host arrays staged, device arrays aliased): numeric chunks, then per Utf8 chunk its
     // offsets, validity (a bitmap of `rows` bits) and the bytes of its value range
@@ -199,38 +160,36 @@ rdf_status rdf_lexsort_to_indices(const rdf_sort_key* keys, int32_t nkeys, int64
         }
     InputStager in;
     for (const rdf_array& v : views) in.add(&v);
-    size_t pin_off = 0, used = 0;
+    size_t used = 0;
+    pin_off = 0;
     RDF_TRY(in.finish(pin_off, &used));
     pin_off += (used + 255) & ~(size_t)255;
 
-    TableBuilder tb;
-    const size_t o_ch = tb.reserve(sizeof(DevChunkCol) * (size_t)nkeys * nchunks);
-    const size_t o_rs = tb.reserve(sizeof(int64_t) * row_start.size());
-    const size_t o_u8 = tb.reserve(sizeof(Utf8Chunk) * (size_t)nkeys * nchunks);
+    TableBuilder& tb = d.tb;
+    d.o_ch = tb.reserve(sizeof(DevChunkCol) * (size_t)nkeys * nchunks);
+    d.o_rs = tb.reserve(sizeof(int64_t) * row_start.size());
+    d.o_u8 = tb.reserve(sizeof(Utf8Chunk) * (size_t)nkeys * nchunks);
     RDF_TRY(tb.bind(pin_off));
-    DevChunkCol* hch = tb.at<DevChunkCol>(o_ch);
-    Utf8Chunk* hu8 = tb.at<Utf8Chunk>(o_u8);
+    DevChunkCol* hch = tb.at<DevChunkCol>(d.o_ch);
+    Utf8Chunk* hu8 = tb.at<Utf8Chunk>(d.o_u8);
     memset(hch, 0, sizeof(DevChunkCol) * (size_t)nkeys * nchunks);
     memset(hu8, 0, sizeof(Utf8Chunk) * (size_t)nkeys * nchunks);
-    memcpy(tb.at<char>(o_rs), row_start.data(), sizeof(int64_t) * row_start.size());
-    int dts[kMaxFrameCols];
-    bool nullable[kMaxFrameCols];
-    Utf8SortCol ucols[kMaxFrameCols];
+    memcpy(tb.at<char>(d.o_rs), row_start.data(), sizeof(int64_t) * row_start.size());
     for (int k = 0; k < nkeys; ++k) {
-        dts[k] = keys[k].values ? keys[k].values[0].dtype : RDF_U8;
-        nullable[k] = false;
-        ucols[k] = Utf8SortCol{nullptr, nchunks, false};
+        d.dts[k] = keys[k].values ? keys[k].values[0].dtype : RDF_U8;
+        d.nullable[k] = false;
+        d.ucols[k] = Utf8SortCol{nullptr, nchunks, false};
         for (int64_t c = 0; c < nchunks; ++c) {
             const size_t i = (size_t)k * nchunks + c, e = i * 3;
             if (keys[k].values) {
                 hch[i] = in.dev[vi[e]];
-                nullable[k] |= keys[k].values[c].validity != nullptr;
+                d.nullable[k] |= keys[k].values[c].validity != nullptr;
                 continue;
             }
             Utf8Chunk& u = hu8[i];
             const DevChunkCol& d_off = in.dev[vi[e]];
             u.offs = (const int32_t*)d_off.values + d_off.offset;
-            if (vi[e + 1] >= 0) { u.valid = (const uint8_t*)in.dev[vi[e + 1]].values; u.valid_off = in.dev[vi[e + 1]].offset; ucols[k].nullable = true; }
+            if (vi[e + 1] >= 0) { u.valid = (const uint8_t*)in.dev[vi[e + 1]].values; u.valid_off = in.dev[vi[e + 1]].offset; d.ucols[k].nullable = true; }
             const DevChunkCol& d_dat = in.dev[vi[e + 2]];
             u.lo = lohi[k][2 * c];
             u.hi = lohi[k][2 * c + 1];
@@ -242,8 +201,85 @@ rdf_status rdf_lexsort_to_indices(const rdf_sort_key* keys, int32_t nkeys, int64
     RDF_TRY(tb.alloc());
     RDF_TRY(tb.upload(pin_off));
     for (int k = 0; k < nkeys; ++k)
-        if (keys[k].utf8) ucols[k].d_chunks = tb.dev_at<Utf8Chunk>(o_u8) + (size_t)k * nchunks;
+        if (keys[k].utf8) d.ucols[k].d_chunks = tb.dev_at<Utf8Chunk>(d.o_u8) + (size_t)k * nchunks;
     pin_off += (tb.size + 255) & ~(size_t)255;
+    return RDF_OK;
+}
+
+// What a list of sort criteria must satisfy, for rdf_lexsort_to_indices and rdf_window alike (`fn` names the caller in the
+// message): exactly one of values / utf8 per key, numeric chunks of one dtype, Int32 offsets and UInt8 data, one memory space.
+rdf_status lexsort_check_keys(const rdf_sort_key* keys, int nkeys, int64_t nchunks, const char* fn, int32_t* mem, bool* any_utf8) {
+    for (int k = 0; k < nkeys; ++k) {
+        const rdf_sort_key& key = keys[k];
+        if ((key.values != nullptr) == (key.utf8 != nullptr)) return fail(RDF_INVALID_ARGUMENT, "%s: key %d must set exactly one of values / utf8", fn, k);
+        if (key.values) {
+            RDF_TRY(check_mem(key.values, nchunks, mem));
+            for (int64_t c = 0; c < nchunks; ++c)
+                if (!is_numeric(key.values[c].dtype) || key.values[c].dtype != key.values[0].dtype)
+                    return fail(RDF_INVALID_ARGUMENT, "%s: key %d: numeric chunks of one dtype", fn, k);
+        } else {
+            *any_utf8 = true;
+            for (int64_t c = 0; c < nchunks; ++c) {
+                const rdf_utf8_array& u = key.utf8[c];
+                if (u.offsets.dtype != RDF_I32 || u.offsets.length < 1)
+                    return fail(RDF_INVALID_ARGUMENT, "%s: key %d chunk %lld: offsets must be an Int32 array of rows + 1 entries", fn, k, (long long)c);
+                if (u.data.dtype != RDF_U8) return fail(RDF_INVALID_ARGUMENT, "%s: key %d chunk %lld: data must be a UInt8 array", fn, k, (long long)c);
+                RDF_TRY(check_mem(&u.offsets, 1, mem));
+                RDF_TRY(check_mem(&u.data, 1, mem));
+            }
+        }
+    }
+    return RDF_OK;
+}
+// The prefix of the batch lengths (nchunks + 1 entries) of checked keys: every key has the rows of key 0 in every chunk, and
+// UInt32 row numbers must reach every row.
+rdf_status lexsort_row_starts(const rdf_sort_key* keys, int nkeys, int64_t nchunks, const char* fn, std::vector<int64_t>& row_start) {
+    auto rows_of = [&](int k, int64_t c) { return keys[k].values ? keys[k].values[c].length : keys[k].utf8[c].offsets.length - 1; };
+    row_start.assign((size_t)nchunks + 1, 0);
+    for (int64_t c = 0; c < nchunks; ++c) row_start[(size_t)c + 1] = row_start[(size_t)c] + rows_of(0, c);
+    for (int k = 1; k < nkeys; ++k)
+        for (int64_t c = 0; c < nchunks; ++c)
+            if (rows_of(k, c) != rows_of(0, c)) return fail(RDF_COMPUTE_ERROR, "%s: columns of a batch differ in length", fn);
+    if (row_start[(size_t)nchunks] >= (int64_t)1 << 32) return fail(RDF_INVALID_ARGUMENT, "%s: UInt32 indices cap a column at 2^32-1 rows (src/table.rs:218)", fn);
+    return RDF_OK;
+}
+
+}  // namespace
+
+rdf_status rdf_lexsort_to_indices(const rdf_sort_key* keys, int32_t nkeys, int64_t nchunks, rdf_out* out_indices) {
+    if (nkeys < 1 || !keys) return fail(RDF_COMPUTE_ERROR, "Sort criteria cannot be empty");  // src/dataframe.rs:195-199
+    if (nchunks < 1 || !out_indices) return fail(RDF_INVALID_ARGUMENT, "lexsort: bad arguments");
+    if (nkeys > kMaxFrameCols) return fail(RDF_INVALID_ARGUMENT, "lexsort: at most %d sort criteria", kMaxFrameCols);
+    int32_t mem = -1;
+    bool any_utf8 = false;
+    RDF_TRY(lexsort_check_keys(keys, nkeys, nchunks, "lexsort", &mem, &any_utf8));
+    RDF_TRY(check_out_mem(out_indices, 1, mem));
+    if (out_indices->dtype != RDF_U32) return fail(RDF_INVALID_ARGUMENT, "lexsort: indices are UInt32");
+    std::vector<int64_t> row_start;
+    RDF_TRY(lexsort_row_starts(keys, nkeys, nchunks, "lexsort", row_start));
+    const int64_t n = row_start[(size_t)nchunks];
+    if (out_indices->capacity < n) return fail(RDF_MEMORY_ERROR, "output capacity too small");
+    std::vector<rdf_sort_options> opts((size_t)nkeys);
+    for (int k = 0; k < nkeys; ++k) opts[k] = keys[k].options;
+    if (!any_utf8) {   // numeric criteria only: the numeric sort itself, bit for bit
+        std::vector<rdf_array> cols((size_t)nkeys * nchunks);
+        for (int k = 0; k < nkeys; ++k)
+            for (int64_t c = 0; c < nchunks; ++c) cols[(size_t)k * nchunks + c] = keys[k].values[c];
+        return rdf_sort_to_indices(cols.data(), nkeys, nchunks, opts.data(), out_indices);
+    }
+    if (n == 0) { out_indices->length = 0; out_indices->null_count = 0; return RDF_OK; }
+    RDF_TRY(ensure_ready());
+    Ctx& ctx = g_ctx;
+    arena_begin();
+
+    size_t pin_off = 0;
+    LexKeysOnDevice d;
+    RDF_TRY(lexsort_keys_to_device(keys, nkeys, nchunks, mem, row_start, "lexsort", pin_off, d));
+    const TableBuilder& tb = d.tb;
+    const size_t o_ch = d.o_ch, o_rs = d.o_rs;
+    const int* dts = d.dts;
+    const bool* nullable = d.nullable;
+    const Utf8SortCol* ucols = d.ucols;
 
     const uint32_t* idx_cur = nullptr;
     RDF_TRY(sort_core(tb.dev_at<DevChunkCol>(o_ch), tb.dev_at<int64_t>(o_rs), nchunks, n, nkeys, dts, nullable, opts.data(), pin_off, &idx_cur, ucols));

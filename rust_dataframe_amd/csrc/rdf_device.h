@@ -268,7 +268,8 @@ struct SortKeyArgs {                                 // key[i] = order-preservin
     uint8_t*           nullflags;                    // out (per ORIGINAL row), nullptr when the column has no bitmap
     uint64_t*          bit_stats;                    // [2] in/out: min and max over the non-null keys written ([0] starts ~0, [1] starts 0)
     int32_t            dtype, descending;
-    int32_t            null_or, pad;                 // multi-column join keys: nullflags[row] |= isnull (the buffer starts zeroed)
+    int32_t            null_or;                      // multi-column join keys: nullflags[row] |= isnull (the buffer starts zeroed)
+    int32_t            canon_float;                  // window keys: -0.0 takes +0.0's key and every NaN the quiet NaN's (after +inf); 0 = IEEE total order
     uint64_t           hash_mul;                     // != 0 (the join's hash-ordered build side): keys[i] = key bits * hash_mul, bit_stats over THOSE,
     uint64_t*          raw_stats;                    //   and [min, max] of the key bits themselves here
 };

@@ -491,6 +491,20 @@ __device__ __forceinline__ uint64_t sort_key_bits(const DevChunkCol& cc, int dt,
     }
 }
 
+// The window functions' float keys (SortKeyArgs::canon_float): in key space -0.0 sits one below +0.0 and the NaNs lie
+// beyond the infinities at BOTH ends (sign bit set: below -inf).  -0.0 takes +0.0's key, every NaN the quiet NaN's.
+__device__ __forceinline__ uint64_t sort_key_canon(int dt, uint64_t k) {
+    if (dt == RDF_F64) {
+        if (k > 0xFFF0000000000000ull || k < 0x000FFFFFFFFFFFFFull) return 0xFFF8000000000000ull;
+        return k == 0x7FFFFFFFFFFFFFFFull ? 0x8000000000000000ull : k;
+    }
+    if (dt == RDF_F32) {
+        if (k > 0xFF800000ull || k < 0x007FFFFFull) return 0xFFC00000ull;
+        return k == 0x7FFFFFFFull ? 0x80000000ull : k;
+    }
+    return k;
+}
+
 __global__ __launch_bounds__(kBlock) void sort_keys_kernel(const SortKeyArgs a, uint64_t width_mask) {
     uint64_t kmin = ~0ull, kmax = 0, rmin = ~0ull, rmax = 0;
     const double inv = chunk_lookup_scale(a.chunk_row_start, a.nchunks);
@@ -506,6 +520,7 @@ __global__ __launch_bounds__(kBlock) void sort_keys_kernel(const SortKeyArgs a, 
         }
         const int64_t e = cc.offset + row - start;
         uint64_t k = sort_key_bits(cc, a.dtype, e);
+        if (a.canon_float) k = sort_key_canon(a.dtype, k);
         if (a.descending) k = ~k & width_mask;
         bool isnull = false;
         if (cc.validity) isnull = !((cc.validity[e >> 3] >> (e & 7)) & 1);
