@@ -72,12 +72,8 @@ struct Ctx {
     int    opt_filter_lookback = 3; // one-pass rdf_filter_frame, batches longer than a tile: 3 = a super-tile's first tile finds the rows in front of the super-tile for all 64, from the nearest super-tiles' tile counts and the older ones' totals (default); 2 = from totals only; 1 = every tile walks the totals (round 4; batches of at most 1024 tiles) — A/B
     int    opt_filter_tile = 0;     // 0: compaction tile chosen from the mean chunk length; 1024 / 4096 force one (A/B)
     int    opt_gb_debug = 0;        // ablations of the partitioned GROUP BY (tools/bench_kernels.py): 1 = aggregate without LDS work, 2 = scatter without stores
-    int    opt_sort_gen = 3;        // radix passes: 3 = one read + one write of the pairs per digit, decoupled look-back between 4096-pair tiles (rdf_sort.hip, default); 2 = count -> scan -> scatter over static tile ranges with the same wave-ranked tiles (A/B: slower, see rdf_sort.hip); 1 = first generation (rdf_kernels.hip)
     bool   sort_used_local = false; // the last sort finished at least one column with os_local_kernel
     int64_t utf8_sort_rounds = 0;   // the last sort: refinement rounds its Utf8 criteria took (round 0 included), summed
-    int    opt_sort_super = 1;      // the digit passes of rdf_sort.hip: 1 = a tile per ticket, decoupled look-back between tiles (os_scatter_kernel, default); K > 1 = a ticket is up to K consecutive tiles, counted together, ONE look-back, then ranked and written one by one (os_scatter4_kernel, round 6: built, correct, measured level at 1e9 i64 keys and 8-12 % SLOWER on 5e7 f64 / two-key sorts — profiles/r06_sort_super_tiles_ab.jsonl — kept as the A/B: the second read of the keys costs what the shorter wait saves)
-    int    opt_sort_super_force = 0;    // tests: this many tiles per ticket whatever the input's size (rdf_set_option("sort_super", 100 + K))
-    int    opt_sort_pipe = 0;       // the digit passes of rdf_sort.hip: 0 = decoupled look-back between the tiles (os_scatter_kernel, default); 1 = a tile's digit counts are published one iteration before its offsets are asked for and scanner blocks turn counts into offsets (os_scatter3_kernel, round 6: built, correct, measured 4-16 % SLOWER — profiles/r06_sort_digit_pass_ab.jsonl — kept as the A/B)
     int    opt_sort_msd = 1;        // sort keys that vary in more than 32 bits: passes over the top bits, then every bucket sorted in LDS (1, default); 0 = one pass per byte (A/B)
     int    opt_sort_sample = 1;     // doubles: value buckets planned from a sample of the keys (range without outliers, bucket bits from the densest region); 0 = [min, max] and ~500 rows per bucket (round 3, A/B)
     int    opt_join_table = 2;      // equi-join on one key column: probe a table of the distinct build keys — 2 (default, round 5): the build side sorted by hash, the table placed by a scan (no atomics); 1: sorted by key, slots claimed by compare-and-swap (round 3); 0 = the bucket index over the sorted build keys (A/B)
@@ -3316,33 +3312,19 @@ rdf_status sort_key_range(const uint64_t* d_stats, size_t pin_off, uint64_t* bia
 
 namespace {
 
-// The digit passes of one sort column over (keys, idx) ping-pong buffers, second generation (rdf_sort.hip): every digit's
+// The digit passes of one sort column over (keys, idx) ping-pong buffers (rdf_sort.hip): every digit's
 // histogram from ONE read of the keys, then one read + one write of the pairs per digit.  `need` low bytes of (key - bias) vary.
-constexpr size_t kOsClassTicketBytes = (size_t)16 * 64 * 128;
-struct OsScratch { unsigned long long* state = nullptr; unsigned long long* tickets = nullptr; unsigned int* ctick = nullptr; int64_t* hist = nullptr; int64_t ntiles = 0; int seq = 0;
-                   int64_t* bh0 = nullptr; int64_t* bh1 = nullptr; int64_t sgrid = 0; };
+struct OsScratch { unsigned long long* state = nullptr; unsigned long long* tickets = nullptr; int64_t* hist = nullptr; int64_t ntiles = 0; int seq = 0; };
 rdf_status os_scratch_alloc(int64_t n, OsScratch& o) {
     o.ntiles = (n + os_tile_items() - 1) / os_tile_items();
     void* p = nullptr;
-    if (g_ctx.opt_sort_gen == 2) {   // static ranges: per-block digit counts and their scan
-        o.sgrid = sr_grid(o.ntiles);
-        RDF_TRY(arena_alloc((size_t)(256 * o.sgrid + 1) * 8, &p));
-        o.bh0 = (int64_t*)p;
-        RDF_TRY(arena_alloc((size_t)(256 * o.sgrid + 1 + scan_scratch_words(256 * o.sgrid)) * 8, &p));
-        o.bh1 = (int64_t*)p;
-        return RDF_OK;
-    }
-    RDF_TRY(arena_alloc((size_t)(o.ntiles + kOsStatePadTiles) * 256 * 8 + 64, &p));
+    RDF_TRY(arena_alloc((size_t)o.ntiles * 256 * 8 + 64, &p));
     o.state = (unsigned long long*)p;
-    HIP_TRY(hipMemsetAsync(p, 0, (size_t)(o.ntiles + kOsStatePadTiles) * 256 * 8, g_ctx.stream));
+    HIP_TRY(hipMemsetAsync(p, 0, (size_t)o.ntiles * 256 * 8, g_ctx.stream));
     RDF_TRY(arena_alloc(16 * 8 + 9 * 256 * 8, &p));
     o.tickets = (unsigned long long*)p;
     o.hist = (int64_t*)((char*)p + 16 * 8);
     o.seq = 0;
-    // os_scatter3_kernel: 64 ticket counters per pass, 128 bytes apart, for the up to 16 passes of one column
-    RDF_TRY(arena_alloc(kOsClassTicketBytes, &p));
-    o.ctick = (unsigned int*)p;
-    HIP_TRY(hipMemsetAsync(p, 0, kOsClassTicketBytes, g_ctx.stream));
     return RDF_OK;
 }
 rdf_status os_column_passes(OsScratch& o, uint64_t* const keys[2], uint32_t* const idxb[2], const uint8_t* nullflags, int64_t n, uint64_t bias, int need,
@@ -3350,42 +3332,28 @@ rdf_status os_column_passes(OsScratch& o, uint64_t* const keys[2], uint32_t* con
                             int f64_keys = 0 /* 1: the keys are the bits of doubles (2: stored inverted, descending); -1: of 4-byte floats */) {
     Ctx& ctx = g_ctx;
     if (need == 0 && !null_pass) return RDF_OK;
-    if (ctx.opt_sort_gen == 2) {
-        for (int p = 0; p < need + (null_pass ? 1 : 0); ++p) {
-            const bool np = p == need;
-            OsPassArgs pa;
-            memset(&pa, 0, sizeof pa);
-            pa.keys_in = keys[kcur]; pa.idx_in = idx_cur; pa.keys_out = keys[kcur ^ 1]; pa.idx_out = idxb[icur ^ 1];
-            pa.nullflags = np ? nullflags : nullptr;
-            pa.n = n; pa.ntiles = o.ntiles; pa.bias = bias; pa.shift = 8 * p;
-            HIP_TRY(launch_sr_hist(pa, o.bh0, ctx.stream));
-            HIP_TRY(launch_scan(o.bh0, o.bh1, 256 * o.sgrid, o.bh1 + 256 * o.sgrid + 1, ctx.stream));
-            HIP_TRY(launch_sr_scatter(pa, o.bh1, ctx.stream));
-            kcur ^= 1; icur ^= 1; idx_cur = idxb[icur];
-        }
-        return RDF_OK;
-    }
     OsBucket fb;
     memset(&fb, 0, sizeof fb);
+    // one digit pass over the first `rows` rows: digit = ((key - bias) >> shift) & mask — of the value bucket when fb.bits —, or (np) the row's NULL flag
     auto one_pass = [&](int hist_row, int shift, int mask, bool np, int& launched, int64_t rows) -> rdf_status {
         if (o.seq >= 16000) { HIP_TRY(hipMemsetAsync(o.state, 0, (size_t)o.ntiles * 256 * 8, ctx.stream)); o.seq = 0; }
         OsPassArgs pa;
         memset(&pa, 0, sizeof pa);
         pa.keys_in = keys[kcur]; pa.idx_in = idx_cur; pa.keys_out = keys[kcur ^ 1]; pa.idx_out = idxb[icur ^ 1];
         pa.nullflags = np ? nullflags : nullptr;
-        pa.state = o.state; pa.ticket = o.tickets + launched; pa.class_tickets = ctx.opt_sort_pipe ? o.ctick + (size_t)launched * 64 * 32 : nullptr; pa.bases = o.hist + hist_row * 256;
+        pa.state = o.state; pa.ticket = o.tickets + launched; pa.bases = o.hist + hist_row * 256;
         pa.n = rows; pa.ntiles = (rows + os_tile_items() - 1) / os_tile_items(); pa.bias = bias; pa.shift = shift; pa.mask = mask; pa.seq = ++o.seq;
-        pa.super_tiles = ctx.opt_sort_pipe ? 1 : ctx.opt_sort_super_force ? ctx.opt_sort_super_force : os_super_tiles(pa.ntiles, ctx.opt_sort_super);
         if (!np) pa.fb = fb;
-        static const bool dbg3 = getenv("RDF_DEBUG_SORT") != nullptr;
-        if (dbg3) { pa.debug = o.tickets + 8; HIP_TRY(hipMemsetAsync(pa.debug, 0, 48, ctx.stream)); }
+        static const bool dbg = getenv("RDF_DEBUG_SORT") != nullptr;
+        if (dbg) { pa.debug = o.tickets + 8; HIP_TRY(hipMemsetAsync(pa.debug, 0, 48, ctx.stream)); }
         HIP_TRY(launch_os_scatter(pa, ctx.stream));
-        if (dbg3) {
+        if (dbg) {   // (the phase sums are filled by a build with -DRDF_SORT_TIMERS, rdf_sort.hip)
             unsigned long long h[6];
             HIP_TRY(hipMemcpyAsync(h, pa.debug, 48, hipMemcpyDeviceToHost, ctx.stream));
             HIP_TRY(hipStreamSynchronize(ctx.stream));
-            fprintf(stderr, "[rdf] digit pass (shift %d, %lld tiles): waiting for offsets %.2f us per tile of %.2f us; scanner rounds %llu, idle %llu, partial %llu\n", shift, (long long)pa.ntiles,
-                    h[5] ? h[0] * 0.01 / h[5] : 0.0, h[5] ? h[1] * 0.01 / h[5] : 0.0, h[2], h[3], h[4]);
+            const double t = (double)std::max<unsigned long long>(h[5], 1);
+            fprintf(stderr, "[rdf] os_scatter pass (shift %d, %lld tiles): per tile cycles (s_memtime, 100 MHz): ticket %.0f load+rank %.0f barrier %.0f look-back %.0f sort+write %.0f (%llu tiles)\n",
+                    shift, (long long)pa.ntiles, h[0] / t, h[1] / t, h[2] / t, h[3] / t, h[4] / t, h[5]);
         }
         ++launched;
         kcur ^= 1; icur ^= 1; idx_cur = idxb[icur];
@@ -3478,7 +3446,6 @@ rdf_status os_column_passes(OsScratch& o, uint64_t* const keys[2], uint32_t* con
         int64_t nv = n;                       // rows in front of the NULL keys
         int ks = -1, is = -1;                 // the buffers the NULL rows were left in
         HIP_TRY(hipMemsetAsync(o.tickets, 0, 16 * 8 + 9 * 256 * 8, ctx.stream));
-    HIP_TRY(hipMemsetAsync(o.ctick, 0, kOsClassTicketBytes, ctx.stream));
         OsHistArgs ha;
         memset(&ha, 0, sizeof ha);
         ha.bias = bias; ha.hist = o.hist; ha.generic = 1; ha.fb = fb;
@@ -3550,38 +3517,15 @@ rdf_status os_column_passes(OsScratch& o, uint64_t* const keys[2], uint32_t* con
         } else return RDF_OK;                 // every key is NULL: the NULLs-last pass was the whole sort
     }
 byte_passes:
-    fb.bits = 0;
+    memset(&fb, 0, sizeof fb);                // (a bucket map planned above is not used from here on: the passes take plain bytes)
     HIP_TRY(hipMemsetAsync(o.tickets, 0, 16 * 8 + 9 * 256 * 8, ctx.stream));
-    HIP_TRY(hipMemsetAsync(o.ctick, 0, kOsClassTicketBytes, ctx.stream));
     OsHistArgs ha;
     memset(&ha, 0, sizeof ha);
     ha.keys = keys[kcur]; ha.nullflags = null_pass ? nullflags : nullptr; ha.n = n; ha.bias = bias; ha.npass = need; ha.hist = o.hist;
     HIP_TRY(launch_os_hist(ha, ctx.stream));
     int launched = 0;
-    for (int p = 0; p < need + (null_pass ? 1 : 0); ++p) {
-        const bool np = p == need;
-        if (o.seq >= 16000) { HIP_TRY(hipMemsetAsync(o.state, 0, (size_t)o.ntiles * 256 * 8, ctx.stream)); o.seq = 0; }
-        OsPassArgs pa;
-        memset(&pa, 0, sizeof pa);
-        pa.keys_in = keys[kcur]; pa.idx_in = idx_cur; pa.keys_out = keys[kcur ^ 1]; pa.idx_out = idxb[icur ^ 1];
-        pa.nullflags = np ? nullflags : nullptr;
-        pa.state = o.state; pa.ticket = o.tickets + launched; pa.class_tickets = ctx.opt_sort_pipe ? o.ctick + (size_t)launched * 64 * 32 : nullptr; pa.bases = o.hist + (np ? 8 : p) * 256;
-        pa.n = n; pa.ntiles = o.ntiles; pa.bias = bias; pa.shift = 8 * p; pa.seq = ++o.seq;
-        pa.super_tiles = ctx.opt_sort_pipe ? 1 : ctx.opt_sort_super_force ? ctx.opt_sort_super_force : os_super_tiles(pa.ntiles, ctx.opt_sort_super);
-        static const bool dbg = getenv("RDF_DEBUG_SORT") != nullptr;
-        if (dbg) { pa.debug = o.tickets + 8; }
-        HIP_TRY(launch_os_scatter(pa, ctx.stream));
-        if (dbg) {
-            unsigned long long h[6];
-            HIP_TRY(hipMemcpyAsync(h, pa.debug, 48, hipMemcpyDeviceToHost, ctx.stream));
-            HIP_TRY(hipStreamSynchronize(ctx.stream));
-            HIP_TRY(hipMemsetAsync(pa.debug, 0, 48, ctx.stream));
-            const double t = (double)std::max<unsigned long long>(h[5], 1);
-            fprintf(stderr, "[rdf] os_scatter pass %d: per tile cycles (s_memtime, 100 MHz): ticket %.0f load+rank %.0f barrier %.0f look-back %.0f sort+write %.0f (%llu tiles)\n", p, h[0] / t, h[1] / t, h[2] / t, h[3] / t, h[4] / t, h[5]);
-        }
-        ++launched;
-        kcur ^= 1; icur ^= 1; idx_cur = idxb[icur];
-    }
+    for (int p = 0; p < need; ++p) RDF_TRY(one_pass(p, 8 * p, 255, false, launched, n));
+    if (null_pass) RDF_TRY(one_pass(8, 0, 255, true, launched, n));
     return RDF_OK;
 }
 
@@ -3598,16 +3542,12 @@ rdf_status sort_core(const DevChunkCol* d_chunks, const int64_t* d_row_start, in
                      const bool* nullable, const rdf_sort_options* opts, size_t pin_off, const uint32_t** idx_out,
                      const Utf8SortCol* utf8 = nullptr, bool canon_float = false /* the window functions' float keys: SortKeyArgs::canon_float */) {
     Ctx& ctx = g_ctx;
-    const int64_t ntiles = (n + kSortTile - 1) / kSortTile;
-    void *pk0, *pk1, *pi0, *pi1, *pnf, *ph0, *ph1;
+    void *pk0, *pk1, *pi0, *pi1, *pnf;
     RDF_TRY(arena_alloc((size_t)n * 8, &pk0));
     RDF_TRY(arena_alloc((size_t)n * 8, &pk1));
     RDF_TRY(arena_alloc((size_t)n * 4, &pi0));
     RDF_TRY(arena_alloc((size_t)n * 4, &pi1));
     RDF_TRY(arena_alloc((size_t)n, &pnf));
-    const int64_t sgrid = sort_grid(ntiles);
-    RDF_TRY(arena_alloc((size_t)(256 * sgrid + 1) * 8, &ph0));
-    RDF_TRY(arena_alloc((size_t)(256 * sgrid + 1 + scan_scratch_words(256 * sgrid)) * 8, &ph1));
     void* pstats;
     RDF_TRY(arena_alloc(64, &pstats));
     uint64_t* d_stats = (uint64_t*)pstats;
@@ -3620,10 +3560,9 @@ rdf_status sort_core(const DevChunkCol* d_chunks, const int64_t* d_row_start, in
     OsScratch os;
     ctx.sort_used_local = false;
     ctx.utf8_sort_rounds = 0;
-    const bool gen2 = ctx.opt_sort_gen >= 2;   // rdf_sort.hip
     bool any_utf8 = false;
     for (int k = 0; utf8 && k < ncols; ++k) any_utf8 |= utf8[k].d_chunks != nullptr;
-    if (gen2 || any_utf8) RDF_TRY(os_scratch_alloc(n, os));
+    RDF_TRY(os_scratch_alloc(n, os));
     KernelTimer kt;
     for (int k = ncols - 1; k >= 0; --k) {  // LSD over the sort columns: least significant criterion first
         if (utf8 && utf8[k].d_chunks) {
@@ -3653,30 +3592,7 @@ rdf_status sort_core(const DevChunkCol* d_chunks, const int64_t* d_row_start, in
         uint64_t kmax = 0;
         RDF_TRY(sort_key_range(d_stats, pin_off, &bias, &need, &kmax));
         if (k == 0 && idx_cur == nullptr && need == 0 && !has_nulls) need = 1;   // all keys equal: one pass still writes the identity order
-        if (gen2) { RDF_TRY(os_column_passes(os, keys, idxb, (const uint8_t*)pnf, n, bias, std::min(need, dtype_size(dt)), has_nulls, kcur, icur, idx_cur, kmax >= bias ? kmax - bias : ~0ull, dt == RDF_F64 ? (ka.descending ? 2 : 1) : dt == RDF_F32 ? -1 : 0)); continue; }
-        const int npass = dtype_size(dt) + (has_nulls ? 1 : 0);
-        for (int p = 0; p < npass; ++p) {
-            if (p < dtype_size(dt) && p >= need) continue;
-            SortPassArgs pa;
-            memset(&pa, 0, sizeof pa);
-            pa.bias = bias;
-            pa.keys_in = keys[kcur];
-            pa.idx_in = idx_cur;
-            pa.keys_out = keys[kcur ^ 1];
-            pa.idx_out = idxb[icur ^ 1];
-            pa.nullflags = p == dtype_size(dt) ? (const uint8_t*)pnf : nullptr;  // the nulls-last pass
-            pa.hist = (int64_t*)ph0;
-            pa.n = n;
-            pa.ntiles = ntiles;
-            pa.shift = 8 * p;
-            HIP_TRY(launch_sort_hist(pa, ctx.stream));
-            HIP_TRY(launch_scan((const int64_t*)ph0, (int64_t*)ph1, 256 * sgrid, (int64_t*)ph1 + 256 * sgrid + 1, ctx.stream));
-            pa.hist = (int64_t*)ph1;
-            HIP_TRY(launch_sort_scatter(pa, ctx.stream));
-            kcur ^= 1;
-            icur ^= 1;
-            idx_cur = idxb[icur];
-        }
+        RDF_TRY(os_column_passes(os, keys, idxb, (const uint8_t*)pnf, n, bias, std::min(need, dtype_size(dt)), has_nulls, kcur, icur, idx_cur, kmax >= bias ? kmax - bias : ~0ull, dt == RDF_F64 ? (ka.descending ? 2 : 1) : dt == RDF_F32 ? -1 : 0));
     }
     kt.stop();
     ctx.last_kernel = ctx.sort_used_local ? "os_scatter_kernel+os_local_kernel" : "sort_scatter_kernel";
@@ -3751,25 +3667,19 @@ rdf_status rdf_sort_to_indices(const rdf_array* cols, int32_t ncols, int64_t nch
 
 namespace {
 // Radix-sort (key bits, row) pairs already produced by sort_keys_kernel: `width` key bytes, then the nulls-last pass.
-struct SortBuffers { uint64_t* keys[2]; uint32_t* idx[2]; void* nullflags; void* hist0; void* hist1; int64_t sgrid, ntiles; };
+struct SortBuffers { uint64_t* keys[2]; uint32_t* idx[2]; void* nullflags; };
 rdf_status sort_buffers_alloc(int64_t n, SortBuffers& b) {
-    b.ntiles = (n + kSortTile - 1) / kSortTile;
-    b.sgrid = sort_grid(b.ntiles);
     void* p;
     for (int i = 0; i < 2; ++i) { RDF_TRY(arena_alloc((size_t)n * 8 + 8, &p)); b.keys[i] = (uint64_t*)p; }
     for (int i = 0; i < 2; ++i) { RDF_TRY(arena_alloc((size_t)n * 4 + 8, &p)); b.idx[i] = (uint32_t*)p; }
     RDF_TRY(arena_alloc((size_t)n + 8, &b.nullflags));
-    RDF_TRY(arena_alloc((size_t)(256 * b.sgrid + 1) * 8, &b.hist0));
-    RDF_TRY(arena_alloc((size_t)(256 * b.sgrid + 1 + scan_scratch_words(256 * b.sgrid)) * 8, &b.hist1));
     return RDF_OK;
 }
 // keys[0] holds the unsorted key bits (identity order).  On return keys[*kcur] / idx[*icur] are sorted.
 rdf_status radix_sort_rows(const SortBuffers& b, int64_t n, int width, bool has_nulls, int* kcur_out, int* icur_out, const uint64_t* d_stats, size_t pin_off,
                            uint64_t* kmin_out, uint64_t* kmax_out) {
-    Ctx& ctx = g_ctx;
     int kcur = 0, icur = 1;
     const uint32_t* idx_cur = nullptr;
-    const int npass = width + (has_nulls ? 1 : 0);
     uint64_t bias = 0;
     int need = 0;
     uint64_t kmax = 0;
@@ -3777,36 +3687,9 @@ rdf_status radix_sort_rows(const SortBuffers& b, int64_t n, int width, bool has_
     if (kmax_out) *kmax_out = kmax;
     *kmin_out = bias;
     if (need == 0 && !has_nulls) need = 1;   // all keys equal: one pass still writes the identity order
-    if (ctx.opt_sort_gen >= 2) {
-        OsScratch os;
-        RDF_TRY(os_scratch_alloc(n, os));
-        RDF_TRY(os_column_passes(os, b.keys, b.idx, (const uint8_t*)b.nullflags, n, bias, std::min(need, width), has_nulls, kcur, icur, idx_cur, kmax >= bias ? kmax - bias : ~0ull));
-        *kcur_out = kcur;
-        *icur_out = icur;
-        return RDF_OK;
-    }
-    for (int p = 0; p < npass; ++p) {
-        if (p < width && p >= need) continue;
-        SortPassArgs pa;
-        memset(&pa, 0, sizeof pa);
-        pa.bias = bias;
-        pa.keys_in = b.keys[kcur];
-        pa.idx_in = idx_cur;
-        pa.keys_out = b.keys[kcur ^ 1];
-        pa.idx_out = b.idx[icur ^ 1];
-        pa.nullflags = p == width ? (const uint8_t*)b.nullflags : nullptr;
-        pa.hist = (int64_t*)b.hist0;
-        pa.n = n;
-        pa.ntiles = b.ntiles;
-        pa.shift = 8 * p;
-        HIP_TRY(launch_sort_hist(pa, ctx.stream));
-        HIP_TRY(launch_scan((const int64_t*)b.hist0, (int64_t*)b.hist1, 256 * b.sgrid, (int64_t*)b.hist1 + 256 * b.sgrid + 1, ctx.stream));
-        pa.hist = (int64_t*)b.hist1;
-        HIP_TRY(launch_sort_scatter(pa, ctx.stream));
-        kcur ^= 1;
-        icur ^= 1;
-        idx_cur = b.idx[icur];
-    }
+    OsScratch os;
+    RDF_TRY(os_scratch_alloc(n, os));
+    RDF_TRY(os_column_passes(os, b.keys, b.idx, (const uint8_t*)b.nullflags, n, bias, std::min(need, width), has_nulls, kcur, icur, idx_cur, kmax >= bias ? kmax - bias : ~0ull));
     *kcur_out = kcur;
     *icur_out = icur;
     return RDF_OK;
@@ -4553,9 +4436,8 @@ rdf_status rdf_set_option(const char* name, int64_t value) {
     else if (strcmp(name, "filter_tile") == 0) g_ctx.opt_filter_tile = (int)value;
     else if (strcmp(name, "filter_one") == 0) g_ctx.opt_filter_one = value != 0;
     else if (strcmp(name, "take_rows") == 0) g_ctx.opt_take_rows = (int)value;
-    else if (strcmp(name, "sort_gen") == 0) g_ctx.opt_sort_gen = (int)value;
+    else if (strcmp(name, "sort_gen") == 0 || strcmp(name, "sort_pipe") == 0 || strcmp(name, "sort_super") == 0) {}   // retired forms of the digit pass (rdf_sort.hip): accepted and ignored, so that callers that still set them keep running
     else if (strcmp(name, "sort_msd") == 0) g_ctx.opt_sort_msd = (int)value;
-    else if (strcmp(name, "sort_pipe") == 0) g_ctx.opt_sort_pipe = value != 0;
     else if (strcmp(name, "sort_sample") == 0) g_ctx.opt_sort_sample = (int)value;
     else if (strcmp(name, "stream_table_kernel") == 0) g_ctx.opt_stream_table_kernel = value != 0;
     else if (strcmp(name, "join_table") == 0) g_ctx.opt_join_table = value < 0 || value > 2 ? 2 : (int)value;
@@ -4573,10 +4455,6 @@ rdf_status rdf_set_option(const char* name, int64_t value) {
     else if (strcmp(name, "filter_fused") == 0) g_ctx.opt_filter_fused = (int)value;
     else if (strcmp(name, "filter_block") == 0) g_ctx.opt_filter_block = value == 3 ? 3 : value != 0;      // (3: tests — the scanner wave stays idle, every wait must time out)
     else if (strcmp(name, "interp_lean") == 0) g_ctx.opt_interp_lean = value == 2 ? 2 : value != 0;   // (2: the lean kernel with one tile per trip of its step loop — the A/B of its two-tile form)
-    else if (strcmp(name, "sort_super") == 0) {
-        if (value > 100) g_ctx.opt_sort_super_force = value > 164 ? 64 : (int)value - 100;      // (tests: K tiles per ticket on inputs of any size)
-        else { g_ctx.opt_sort_super_force = 0; g_ctx.opt_sort_super = value < 1 ? 1 : value > 64 ? 64 : (int)value; }
-    }
     else if (strcmp(name, "filter_owned") == 0) g_ctx.opt_filter_owned = value == 2 ? 2 : value != 0;      // (2: tests — whatever the number and lengths of the batches)
     else if (strcmp(name, "filter_ends") == 0) g_ctx.opt_filter_ends = value != 0;
     else if (strcmp(name, "filter_mixed") == 0) g_ctx.opt_filter_mixed = value == 2 ? 2 : value != 0;

@@ -51,7 +51,7 @@ rdf_status utf8_sort_column(const Utf8SortCol& col, OsScratch& os, uint64_t* con
     HIP_TRY(launch_utf8_sort_init(a, s));   // the criterion's order starts as the incoming one
 
     static const bool dbg = getenv("RDF_DEBUG_SORT") != nullptr;
-    const int64_t tiles_full = os.ntiles, sgrid_full = os.sgrid;
+    const int64_t tiles_full = os.ntiles;
     RDF_TRY(pinned_reserve(pin_off + 64));
     int64_t m = n, nseg = 1;
     int cur = 0;
@@ -73,9 +73,8 @@ rdf_status utf8_sort_column(const Utf8SortCol& col, OsScratch& os, uint64_t* con
         int need = 0;
         RDF_TRY(sort_key_range(stats, pin_off, &bias, &need, &kmax));
         // the digit passes over the round's m rows (the scratch was sized for n; seq restarts well before it wraps)
-        if (os.state && os.seq > 15000) { HIP_TRY(hipMemsetAsync(os.state, 0, (size_t)(tiles_full + kOsStatePadTiles) * 256 * 8, s)); os.seq = 0; }
+        if (os.state && os.seq > 15000) { HIP_TRY(hipMemsetAsync(os.state, 0, (size_t)tiles_full * 256 * 8, s)); os.seq = 0; }
         os.ntiles = (m + os_tile_items() - 1) / os_tile_items();
-        if (ctx.opt_sort_gen == 2) os.sgrid = sr_grid(os.ntiles);
         int kc = 0, ic = 1;
         const uint32_t* ord = nullptr;
         rdf_status st = os_column_passes(os, keys, idxb, nullflags, m, bias, need, a.nullflags != nullptr, kc, ic, ord, kmax >= bias ? kmax - bias : ~0ull);
@@ -88,7 +87,6 @@ rdf_status utf8_sort_column(const Utf8SortCol& col, OsScratch& os, uint64_t* con
             if (st == RDF_OK) st = os_column_passes(os, keys, idxb, nullptr, m, 0, need2, false, kc, ic, ord, (uint64_t)(nseg - 1));
         }
         os.ntiles = tiles_full;
-        os.sgrid = sgrid_full;
         RDF_TRY(st);
         a.order = ord;
         HIP_TRY(launch_utf8_sort_mark(a, s));

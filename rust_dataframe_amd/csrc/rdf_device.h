@@ -286,7 +286,6 @@ struct SortPassArgs {
 
 // Second-generation radix passes (rdf_sort.hip): all digit histograms in one read, then one read + one write per digit with
 // decoupled look-back between tiles.
-constexpr int kOsStatePadTiles = 768;                // zeroed tile states behind the last tile: what os_scatter3_kernel's scanners may read past the end (two windows of 256 tiles and a run)
 constexpr int kOsItems = 16;                         // items per thread per tile: 4096-item tiles
 // f64 keys: the top bits of the key bits are sign and exponent — doubles of one magnitude crowd a few of their patterns —, so the
 // most-significant-first passes take their digits from the VALUE bucket floor((x - lo) * scale) instead (monotone in the key bits:
@@ -315,8 +314,6 @@ struct OsPassArgs {
     int32_t         mask, pad;                       // digit = ((key - bias) >> shift) & mask; 0 = 255
     OsBucket        fb;                              // ... or (value bucket >> shift) & mask
     unsigned long long* debug;                       // RDF_DEBUG: [6] cycle sums of the phases (ticket, load + rank, barrier, look-back, sort + write), tiles
-    unsigned int*   class_tickets;                   // os_scatter3_kernel (round 6): 64 ticket counters of this pass, 128 bytes apart (zeroed); nullptr = os_scatter_kernel
-    int32_t         nclass, super_tiles;             // nclass: counters in use (set by the launcher); super_tiles: K > 1 = os_scatter4_kernel (round 6): a ticket is K consecutive tiles, `state` holds one row of 256 words per super-tile
 };
 // Most-significant-digits-first finish (keys that vary in more than 32 bits): after stable passes over the TOP bits of the keys
 // the rows lie in buckets of <= kOsLocalMax rows that share those bits; every bucket is then sorted on the remaining `rbits`
@@ -339,10 +336,6 @@ hipError_t launch_os_sample(const uint64_t* keys, int64_t n, int nsamp, uint64_t
 hipError_t launch_os_hist(const OsHistArgs& a, hipStream_t s);
 hipError_t launch_os_scatter(const OsPassArgs& a, hipStream_t s);
 int os_tile_items();
-int os_super_tiles(int64_t ntiles, int max_k);
-int sr_grid(int64_t ntiles);
-hipError_t launch_sr_hist(const OsPassArgs& a, int64_t* hist, hipStream_t s);      // hist: [256 * sr_grid] digit-major per-block counts
-hipError_t launch_sr_scatter(const OsPassArgs& a, const int64_t* hist, hipStream_t s);   // hist: their exclusive scan
 
 // Equi-join indices (calc_equijoin_indices, src/functions/join.rs:19-137): sort the build side by key, binary-search
 // every probe row, count -> scan -> write.
@@ -762,8 +755,6 @@ hipError_t launch_compact(const FilterArgs& a, int tile_rows, hipStream_t s);
 hipError_t launch_take(const TakeArgs& a, hipStream_t s);
 int  sort_grid(int64_t ntiles);
 hipError_t launch_sort_keys(const SortKeyArgs& a, hipStream_t s);
-hipError_t launch_sort_hist(const SortPassArgs& a, hipStream_t s);
-hipError_t launch_sort_scatter(const SortPassArgs& a, hipStream_t s);
 hipError_t launch_join_buckets(const JoinBucketArgs& a, hipStream_t s);
 hipError_t launch_copy_small(const void* src_pinned, void* dst_dev, size_t bytes, hipStream_t s);   // src: page-locked, device-mapped host memory
 hipError_t launch_join_table(const JoinTableArgs& a, hipStream_t s);

@@ -470,11 +470,13 @@ __global__ __launch_bounds__(kBlock) void take_kernel(const TakeArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// sort to indices (DataFrame::sort -> arrow::compute::lexsort_to_indices, src/dataframe.rs:194-214): a
-// stable LSD radix sort of (key, row) pairs.  Per 8-bit pass: per-tile digit histograms (digit-major),
+// sort to indices (DataFrame::sort -> arrow::compute::lexsort_to_indices, src/dataframe.rs:194-214): the
+// order-preserving keys of a column are made here (sort_keys_kernel); the sort's digit passes are in rdf_sort.hip.
+// What remains here is the stable histogram -> scan -> scatter pass over (key, 64-bit payload) pairs that the GROUP BY's
+// radix partitioning runs.  Per 8-bit pass: per-block digit histograms (digit-major),
 // one exclusive scan, then a stable scatter whose in-tile ranks come from wave ballots (the lanes that
 // share my digit = AND over the 8 digit bits of the ballot or its complement) + an LDS prefix over the
-// (row-of-items, wave) groups.  Columns are applied last-to-first; nulls go last via one extra 1-bit pass.
+// (row-of-items, wave) groups.
 
 __device__ __forceinline__ uint64_t sort_key_bits(const DevChunkCol& cc, int dt, int64_t e) {
     switch (dt) {
@@ -573,12 +575,11 @@ __global__ __launch_bounds__(kBlock) void sort_hist_kernel(const SortPassArgs a)
     a.hist[(int64_t)threadIdx.x * gridDim.x + blockIdx.x] = h[threadIdx.x];
 }
 
-template <bool PAY64>
 __global__ __launch_bounds__(kBlock) void sort_scatter_kernel(const SortPassArgs a) {
     __shared__ unsigned short grp[kSortItems * (kBlock / 64)][256];  // count of each digit per (row-of-items, wave) group
     __shared__ unsigned short dbase[256];                            // tile-local exclusive prefix of the digit totals
     __shared__ uint64_t lkeys[kSortTile];                            // the tile, locally sorted by digit (stable)
-    __shared__ typename std::conditional<PAY64, uint64_t, uint32_t>::type lidx[kSortTile];
+    __shared__ uint64_t lidx[kSortTile];
     __shared__ int64_t gbase[256];                                   // running global offset of each digit for this block
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     gbase[threadIdx.x] = a.hist[(int64_t)threadIdx.x * gridDim.x + blockIdx.x];
@@ -591,15 +592,14 @@ __global__ __launch_bounds__(kBlock) void sort_scatter_kernel(const SortPassArgs
         const int count = (int)((a.n - base) < (int64_t)kSortTile ? (a.n - base) : (int64_t)kSortTile);
         int digit[kSortItems], rank[kSortItems];
         uint64_t key[kSortItems];
-        typename std::conditional<PAY64, uint64_t, uint32_t>::type idx[kSortItems];
+        uint64_t idx[kSortItems];
 #pragma unroll
         for (int j = 0; j < kSortItems; ++j) {
             const int64_t i = base + j * kBlock + threadIdx.x;
             const bool in = i < a.n;
             key[j] = in ? a.keys_in[i] : 0;
-            if (PAY64) idx[j] = in ? a.pay_in[i] : 0;
-            else idx[j] = in ? (a.idx_in ? a.idx_in[i] : (uint32_t)i) : 0;
-            const int d = in ? ((!PAY64 && a.nullflags) ? (int)a.nullflags[idx[j]] : (int)(((key[j] - a.bias) >> a.shift) & 255)) : 0;
+            idx[j] = in ? a.pay_in[i] : 0;
+            const int d = in ? (int)(((key[j] - a.bias) >> a.shift) & 255) : 0;
             digit[j] = d;
             uint64_t peers = __ballot(in);
 #pragma unroll
@@ -643,11 +643,10 @@ __global__ __launch_bounds__(kBlock) void sort_scatter_kernel(const SortPassArgs
         // coalesced write-out: consecutive threads hold consecutive members of a digit run
         for (int t = threadIdx.x; t < count; t += kBlock) {
             const uint64_t kk = lkeys[t];
-            const auto ii = lidx[t];
-            const int d = (!PAY64 && a.nullflags) ? (int)a.nullflags[ii] : (int)(((kk - a.bias) >> a.shift) & 255);
+            const int d = (int)(((kk - a.bias) >> a.shift) & 255);
             const int64_t dst = gbase[d] + (t - dbase[d]);
             a.keys_out[dst] = kk;
-            if (PAY64) a.pay_out[dst] = ii; else a.idx_out[dst] = (uint32_t)ii;
+            a.pay_out[dst] = lidx[t];
         }
         __syncthreads();
         gbase[threadIdx.x] += total_d;  // the next tile of this block continues each digit's run
@@ -1887,17 +1886,12 @@ int sort_grid(int64_t ntiles) {  // both sort kernels must agree on it: it fixes
     const int64_t g = ntiles < lim ? ntiles : lim;
     return g < 1 ? 1 : (int)g;
 }
-hipError_t launch_sort_hist(const SortPassArgs& a, hipStream_t s) {
+hipError_t launch_sort_hist64(const SortPassArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(sort_hist_kernel, dim3(sort_grid(a.ntiles)), dim3(kBlock), 0, s, a);
     return hipGetLastError();
 }
-hipError_t launch_sort_scatter(const SortPassArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL((sort_scatter_kernel<false>), dim3(sort_grid(a.ntiles)), dim3(kBlock), 0, s, a);
-    return hipGetLastError();
-}
-hipError_t launch_sort_hist64(const SortPassArgs& a, hipStream_t s) { return launch_sort_hist(a, s); }
 hipError_t launch_sort_scatter64(const SortPassArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL((sort_scatter_kernel<true>), dim3(sort_grid(a.ntiles)), dim3(kBlock), 0, s, a);
+    hipLaunchKernelGGL(sort_scatter_kernel, dim3(sort_grid(a.ntiles)), dim3(kBlock), 0, s, a);
     return hipGetLastError();
 }
 

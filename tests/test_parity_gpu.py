@@ -697,53 +697,44 @@ def test_sort_to_indices(gpu, ora, dtype):
 
 
 @pytest.mark.parametrize("dtype", [A.I64, A.F64, A.I32])
-def test_sort_digit_passes_with_scanner_blocks(gpu, ora, dtype):
-    """rdf_set_option("sort_pipe", 1): the digit passes publish a tile's counts one iteration before its offsets are asked for and
-    take the offsets from scanner blocks (os_scatter3_kernel, round 6; measured slower than the look-back kernel and not the default —
-    kept as the A/B partner, so it is held to the same oracle): several tiles per block, a ragged last tile, NULL keys (the
-    NULLs-last pass), ties, descending, two key columns."""
-    from rust_dataframe_amd import lib
+def test_sort_look_back_over_many_tiles(gpu, ora, dtype):
+    """The digit passes on inputs of 104 and 611 tiles of 4096 pairs, so that a tile's look-back crosses tiles other blocks are
+    still working on: several tiles per block, a ragged last tile, NULL keys (the NULLs-last pass), ties, descending, two key
+    columns, the value-bucket passes of doubles.  (These inputs were first written for a form of the passes that took its offsets
+    from scanner blocks; that form was measured slower and removed, the inputs stay.)"""
     rng = np.random.default_rng(1300 + dtype)
-    try:
-        lib.set_option("sort_pipe", 1)
-        for lens, nf in [([300_000, 1, 123_457], 0.05), ([2_500_000], 0.0)]:
-            kind = "special" if dtype == A.F64 else "extreme"
-            k1 = make_chunks(rng, dtype, lens, nf, 3, kind)
-            k2 = make_chunks(rng, A.I16, lens, 0.0, 0, "plain")
-            for ch in k2:
-                ch.values[:] = ch.values % 3
-            for cols, d in (([k1], [False]), ([k2, k1], [True, False])):
-                got = gpu.sort_to_indices(cols, d).to_numpy()
-                exp = ora.sort_to_indices(cols, d).to_numpy()
-                assert np.array_equal(got, exp), f"sort_pipe=1 dtype={dtype} lens={lens} desc={d}"
-    finally:
-        lib.set_option("sort_pipe", 0)
+    for lens, nf in [([300_000, 1, 123_457], 0.05), ([2_500_000], 0.0)]:
+        kind = "special" if dtype == A.F64 else "extreme"
+        k1 = make_chunks(rng, dtype, lens, nf, 3, kind)
+        k2 = make_chunks(rng, A.I16, lens, 0.0, 0, "plain")
+        for ch in k2:
+            ch.values[:] = ch.values % 3
+        for cols, d in (([k1], [False]), ([k2, k1], [True, False])):
+            got = gpu.sort_to_indices(cols, d).to_numpy()
+            exp = ora.sort_to_indices(cols, d).to_numpy()
+            assert np.array_equal(got, exp), f"dtype={dtype} lens={lens} desc={d}"
 
 
 @pytest.mark.parametrize("dtype", [A.I64, A.F64, A.I32, A.U8])
-def test_sort_digit_passes_on_super_tiles(gpu, ora, dtype):
-    """Round 6: a ticket of the digit passes is K consecutive tiles — counted together, ONE look-back, then ranked and written one
-    by one (os_scatter4_kernel; measured no faster than a tile per ticket and not the default — kept as its A/B partner, so it is
-    held to the same oracle).  `sort_super` 100 + K takes that form on inputs of any size: K = 2, 3, 8 over 104 and 611 tiles (a ragged last super-tile, a last tile of one row's worth), NULL keys (the NULLs-last
-    pass reads its digit through the row index), ties, descending, two key columns, value-bucket passes of doubles; and K = 1 by
-    option (the look-back kernel) gives the same indices."""
+def test_sort_look_back_over_many_tiles_and_one_byte_keys(gpu, ora, dtype):
+    """A second draw of the many-tile inputs above, and one-byte keys among them (a single digit pass): 104 and 611 tiles, a last
+    tile of one row's worth, NULL keys (the NULLs-last pass reads its digit through the row index), ties, descending, two key
+    columns, value-bucket passes of doubles.  (Written for a form of the passes that drew several tiles per ticket — measured no
+    faster and removed; the retired option names are still accepted.)"""
     from rust_dataframe_amd import lib
+    for name in ("sort_gen", "sort_pipe", "sort_super"):      # accepted and ignored (include/rdf_mi355x.h)
+        lib.set_option(name, 2)
     rng = np.random.default_rng(1400 + dtype)
-    try:
-        for lens, nf in [([300_000, 1, 123_457], 0.05), ([2_500_000], 0.0)]:
-            kind = "special" if dtype == A.F64 else "extreme"
-            k1 = make_chunks(rng, dtype, lens, nf, 3, kind)
-            k2 = make_chunks(rng, A.I16, lens, 0.0, 0, "plain")
-            for ch in k2:
-                ch.values[:] = ch.values % 3
-            for cols, d in (([k1], [False]), ([k2, k1], [True, False])):
-                exp = ora.sort_to_indices(cols, d).to_numpy()
-                for k in (102, 103, 108, 1):
-                    lib.set_option("sort_super", k)
-                    got = gpu.sort_to_indices(cols, d).to_numpy()
-                    assert np.array_equal(got, exp), f"sort_super={k} dtype={dtype} lens={lens} desc={d}"
-    finally:
-        lib.set_option("sort_super", 1)
+    for lens, nf in [([300_000, 1, 123_457], 0.05), ([2_500_000], 0.0)]:
+        kind = "special" if dtype == A.F64 else "extreme"
+        k1 = make_chunks(rng, dtype, lens, nf, 3, kind)
+        k2 = make_chunks(rng, A.I16, lens, 0.0, 0, "plain")
+        for ch in k2:
+            ch.values[:] = ch.values % 3
+        for cols, d in (([k1], [False]), ([k2, k1], [True, False])):
+            got = gpu.sort_to_indices(cols, d).to_numpy()
+            exp = ora.sort_to_indices(cols, d).to_numpy()
+            assert np.array_equal(got, exp), f"dtype={dtype} lens={lens} desc={d}"
 
 
 @pytest.mark.parametrize("ngroups,n", [(20_000, 150_000), (300_000, 700_000), (1_300_000, 2_000_000)])
