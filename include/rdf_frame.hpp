@@ -2271,7 +2271,8 @@ class DataFrame {
     // Window functions (the reference declares them with empty bodies: WindowSpec in src/window.rs, row_number .. lead in
     // src/functions/window.rs, ntile in src/functions/scalar.rs:345; the semantics are SQL's, written down at rdf_window).
     // partition_by: rows that agree on every listed column form a partition (NULL is a value); order_by: the order inside a
-    // partition, NULLs last, ties in row order.  rows_between / range_between frames are not covered.
+    // partition, NULLs last, ties in row order.  rows_between / range_between set the frame of with_window_agg; with_window
+    // ignores it (ranks have no frame in SQL).
     enum class WindowFunction : int32_t {
         RowNumber = RDF_WIN_ROW_NUMBER, Rank = RDF_WIN_RANK, DenseRank = RDF_WIN_DENSE_RANK, PercentRank = RDF_WIN_PERCENT_RANK,
         CumeDist = RDF_WIN_CUME_DIST, Ntile = RDF_WIN_NTILE, Lag = RDF_WIN_LAG, Lead = RDF_WIN_LEAD
@@ -2280,11 +2281,36 @@ class DataFrame {
       public:
         WindowSpec& partition_by(std::vector<std::string> cols) { partition_ = std::move(cols); return *this; }
         WindowSpec& order_by(std::vector<SortCriteria> criteria) { order_ = std::move(criteria); return *this; }
+        // The frame, in the reference's spelling (src/window.rs): unbounded_preceding / unbounded_following, 0 = current_row, a
+        // negative number = that many rows preceding, a positive one = following.  range_between takes no offsets.
+        static constexpr int64_t unbounded_preceding = INT64_MIN, current_row = 0, unbounded_following = INT64_MAX;
+        WindowSpec& rows_between(int64_t start, int64_t end) { frame_ = make_frame(RDF_FRAME_ROWS, start, end); return *this; }
+        WindowSpec& range_between(int64_t start, int64_t end) { frame_ = make_frame(RDF_FRAME_RANGE, start, end); return *this; }
         const std::vector<std::string>& partition() const { return partition_; }
         const std::vector<SortCriteria>& order() const { return order_; }
+        // no frame set: SQL's default, RANGE BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW
+        const rdf_window_frame& frame() const { return frame_; }
       private:
+        static rdf_window_frame make_frame(int32_t unit, int64_t start, int64_t end) {
+            auto bound = [](int64_t b, int32_t* kind, int64_t* off) {
+                *off = 0;
+                if (b == unbounded_preceding) *kind = RDF_BOUND_UNBOUNDED_PRECEDING;
+                else if (b == unbounded_following) *kind = RDF_BOUND_UNBOUNDED_FOLLOWING;
+                else if (b == 0) *kind = RDF_BOUND_CURRENT_ROW;
+                else { *kind = b < 0 ? RDF_BOUND_PRECEDING : RDF_BOUND_FOLLOWING; *off = b < 0 ? -b : b; }
+            };
+            rdf_window_frame f{unit, 0, 0, 0, 0, 0};
+            bound(start, &f.start_kind, &f.start);
+            bound(end, &f.end_kind, &f.end);
+            return f;
+        }
         std::vector<std::string> partition_;
         std::vector<SortCriteria> order_;
+        rdf_window_frame frame_{RDF_FRAME_RANGE, RDF_BOUND_UNBOUNDED_PRECEDING, RDF_BOUND_CURRENT_ROW, 0, 0, 0};
+    };
+    enum class WindowAggregate : int32_t {
+        Sum = RDF_WAGG_SUM, Min = RDF_WAGG_MIN, Max = RDF_WAGG_MAX, Count = RDF_WAGG_COUNT, Avg = RDF_WAGG_AVG,
+        FirstValue = RDF_WAGG_FIRST_VALUE, LastValue = RDF_WAGG_LAST_VALUE
     };
     // Appends fn over `spec` as column `name`, chunked like the frame: Int64 for RowNumber / Rank / DenseRank / Ntile(param
     // buckets), Float64 for PercentRank / CumeDist; Lag / Lead(param rows) append `value_column` of the row param places
@@ -2319,6 +2345,49 @@ class DataFrame {
         for (int64_t len : columns_.at(0).data().chunk_counts()) { chunks.push_back(whole->slice(at, len)); at += len; }
         return with_column(name, Column::from_arrays(std::move(chunks), field));
     }
+    // Appends fn of `value_column` over the frame of `spec` as column `name`, chunked like the frame (rdf_window_agg): Sum / Min /
+    // Max of an Int64 or Float64 column in its own type, Avg as Float64, Count as Int64 (an empty value_column counts the
+    // frame's rows); NULL where the frame holds no valid row, except Count.  FirstValue / LastValue append `value_column` — any
+    // dtype, text included — of the frame's first / last row, NULL where the frame is empty (row indices gathered by Column::take).
+    DataFrame with_window_agg(const std::string& name, const WindowSpec& spec, WindowAggregate fn, const std::string& value_column = "") const {
+        const bool picks = fn == WindowAggregate::FirstValue || fn == WindowAggregate::LastValue;
+        if (value_column.empty() && fn != WindowAggregate::Count) throw DataFrameError(DataFrameError::ComputeError, "with_window_agg: a value column is needed");
+        const bool host = numeric_columns_on_host();
+        std::vector<SortCriteria> part;
+        for (auto& c : spec.partition()) part.push_back(SortCriteria{c, false, false});
+        const SortKeys pk = sort_keys(part, host), ok = sort_keys(spec.order(), host);
+        const bool reads = !picks && !value_column.empty();
+        std::vector<rdf_array> vchunks;
+        DataType vdt = DataType::Int64;
+        if (reads) {
+            const Column& vc = column_by_name(value_column);
+            vdt = vc.data_type();
+            if (vdt != DataType::Int64 && vdt != DataType::Float64) throw DataFrameError(DataFrameError::ComputeError, "with_window_agg: Int64 or Float64 value columns");
+            for (auto& a : vc.data().chunks()) vchunks.push_back(a->view());
+        }
+        const rdf_array* vptr = vchunks.data();
+        const DataType dt = picks ? DataType::UInt32 : fn == WindowAggregate::Count ? DataType::Int64 : fn == WindowAggregate::Avg ? DataType::Float64 : vdt;
+        const bool nullable = fn != WindowAggregate::Count;
+        auto out = Array::make_out(dt, num_rows(), nullable, host);
+        rdf_out ov = out->out_view(num_rows());
+        const rdf_window_agg_call call{(int32_t)fn, reads ? 0 : -1, spec.frame()};
+        const bool keyed = !pk.keys.empty() || !ok.keys.empty() || reads;
+        check(rdf_window_agg(pk.keys.empty() ? nullptr : pk.keys.data(), (int32_t)pk.keys.size(), ok.keys.empty() ? nullptr : ok.keys.data(),
+                             (int32_t)ok.keys.size(), reads ? &vptr : nullptr, reads ? 1 : 0, (int64_t)num_chunks(), keyed ? 0 : num_rows(), &call, 1, &ov));
+        out->length = ov.length;
+        out->null_count = ov.null_count;
+        ArrayRef whole = out;
+        Field field{name, dt, nullable};
+        if (picks) {
+            const Column taken = column_by_name(value_column).take(out, 4096);
+            whole = taken.data().chunk(0);
+            field = Field{name, taken.data_type(), true};
+        }
+        std::vector<ArrayRef> chunks;                       // one array of all rows -> the frame's batches, zero-copy
+        int64_t at = 0;
+        for (int64_t len : columns_.at(0).data().chunk_counts()) { chunks.push_back(whole->slice(at, len)); at += len; }
+        return with_column(name, Column::from_arrays(std::move(chunks), field));
+    }
 
   private:
     Schema schema_;
@@ -2327,6 +2396,7 @@ class DataFrame {
 
 using WindowSpec = DataFrame::WindowSpec;           // the reference's names (src/window.rs, src/functions/window.rs)
 using WindowFunction = DataFrame::WindowFunction;
+using WindowAggregate = DataFrame::WindowAggregate;
 
 // ------------------------------------------------------------------------------------------------
 // GpuFrame: a DataFrame of numeric columns pinned in HBM behind a frame handle (rdf_frame_pin), and the reference's

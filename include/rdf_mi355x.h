@@ -514,6 +514,65 @@ typedef struct { int32_t fn; int32_t pad; int64_t param; } rdf_window_call;
 rdf_status rdf_window(const rdf_sort_key* partition_by, int32_t npartition, const rdf_sort_key* order_by, int32_t norder,
                       int64_t nchunks, int64_t nrows_if_no_keys, const rdf_window_call* calls, int32_t ncalls, rdf_out* outs);
 
+/* Window FRAMES: sum / min / max / count / avg / first_value / last_value over WindowSpec::rows_between / range_between
+ * (src/window.rs; the aggregates are AggregateFunctions' of src/functions/aggregate.rs).  Up to 8 calls, each with its own
+ * frame and one of up to 4 value columns, all answered from ONE sort.  Partitions, order, peers, float key
+ * canonicalisation, chunk conventions, memory kinds, the 2^32-row cap and "outs[c] is one array in the original row
+ * order" are rdf_window's rules above, unchanged; so are zero rows, short capacities and the error codes.
+ *
+ * values[v]: nchunks chunks of one dtype, Int64 or Float64 (other dtypes RDF_INVALID_ARGUMENT, as rdf_hist), with the keys'
+ * rows per chunk.  With no keys at all the value chunks give the rows (no value columns either: nrows_if_no_keys, nchunks
+ * ignored); nrows_if_no_keys is 0 or agrees.  calls[c].value indexes `values`; -1 is allowed for COUNT (count the frame's
+ * rows) and FIRST_VALUE / LAST_VALUE (they read no values).
+ *
+ * The frame of a row at position k of n in its ordered partition, with first / last peer f / l, is the closed range [a, b]:
+ *   ROWS   UNBOUNDED_PRECEDING 0;  PRECEDING s  k - s;  CURRENT_ROW k;  FOLLOWING s  k + s;  UNBOUNDED_FOLLOWING n - 1
+ *   RANGE  the two unbounded kinds as above; CURRENT_ROW is f as a start and l as an end (SQL's default frame, RANGE
+ *          BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW, is [0, l]).  RANGE with an offset: RDF_INVALID_ARGUMENT ("range
+ *          offsets are not built").
+ * then a = max(a, 0), b = min(b, n - 1); the frame is empty when a > b.
+ *
+ * Results, with c = the valid (non-NULL) value rows of the frame — NULL rows are skipped:
+ *   COUNT        RDF_I64, never NULL: c, or b - a + 1 with value == -1; an empty frame gives 0.
+ *   SUM          the value dtype, with validity.  NULL when c == 0: SQL's rule, deliberately NOT rdf_sum's 0.  Int64: the
+ *                wrapping sum, bit-exact.  Float64: the partition's running sum is carried as a double-double (Knuth's
+ *                TwoSum on both words, relative error <= 3u^2 + 13u^3 per addition, u = 2^-53); the frame's value is the
+ *                double-double difference of two prefixes rounded ONCE, a zero comes back as +0.0.  Non-finite values are
+ *                counted, not summed: any NaN or both infinities in the frame give NaN, one kind of infinity that
+ *                infinity; a frame after them is finite again.  With F = the exact sum of the frame, m = the partition's
+ *                rows up to the frame's end and T = the sum of |x| over them: |result - F| <= ulp(F) + 8 (m + 1) 2^-106 T;
+ *                integer-valued doubles whose partial sums stay below 2^53 give F bit for bit.  (A partition whose running
+ *                sum of |x| itself overflows Float64 returns what IEEE arithmetic gives.)
+ *   AVG          RDF_F64, with validity: NULL when c == 0, else the Float64 SUM / (double)c, one IEEE division; Int64
+ *                values enter `as f64` and take the Float64 path.
+ *   MIN / MAX    the value dtype, with validity: NULL when c == 0.  Float64 follows rdf_min / rdf_max: NaNs are ignored
+ *                unless every valid value of the frame is NaN (then the quiet NaN 0x7FF8000000000000); other values
+ *                compare in IEEE total order (-0.0 < +0.0), so the result is one of the inputs bit for bit.
+ *   FIRST_VALUE / LAST_VALUE   RDF_U32 ROW INDICES with validity, the LAG / LEAD convention: the row at position a / b,
+ *                for rdf_take / rdf_utf8_take (any column type; NULL values are not skipped); an empty frame gives NULL.
+ * null_count is set on every output.  A validity bitmap is required for every function but COUNT (written all-valid where
+ * given).
+ * Refused before any device work with RDF_INVALID_ARGUMENT: a start of UNBOUNDED_FOLLOWING, an end of
+ * UNBOUNDED_PRECEDING, a start that lies after the end for every row (start kind > end kind; both PRECEDING with
+ * start < end; both FOLLOWING with start > end), a negative offset, an unknown unit, kind or fn, a value index out of
+ * range or -1 for SUM / MIN / MAX / AVG, more than 4 value columns or 8 calls, a wrong output dtype, a missing validity
+ * bitmap.  Scratch that does not fit device memory is RDF_MEMORY_ERROR, never a partial answer. */
+typedef enum { RDF_FRAME_ROWS = 0, RDF_FRAME_RANGE = 1 } rdf_frame_unit;
+typedef enum {
+    RDF_BOUND_UNBOUNDED_PRECEDING = 0, RDF_BOUND_PRECEDING = 1, RDF_BOUND_CURRENT_ROW = 2, RDF_BOUND_FOLLOWING = 3,
+    RDF_BOUND_UNBOUNDED_FOLLOWING = 4
+} rdf_frame_bound;
+typedef struct { int32_t unit, start_kind, end_kind, pad; int64_t start, end; } rdf_window_frame;
+typedef enum {
+    RDF_WAGG_SUM = 0, RDF_WAGG_MIN = 1, RDF_WAGG_MAX = 2, RDF_WAGG_COUNT = 3, RDF_WAGG_AVG = 4, RDF_WAGG_FIRST_VALUE = 5,
+    RDF_WAGG_LAST_VALUE = 6
+} rdf_window_agg_fn;
+typedef struct { int32_t fn; int32_t value; rdf_window_frame frame; } rdf_window_agg_call;
+#define RDF_WINDOW_MAX_VALUES 4
+rdf_status rdf_window_agg(const rdf_sort_key* partition_by, int32_t npartition, const rdf_sort_key* order_by, int32_t norder,
+                          const rdf_array* const* values, int32_t nvalues, int64_t nchunks, int64_t nrows_if_no_keys,
+                          const rdf_window_agg_call* calls, int32_t ncalls, rdf_out* outs);
+
 /* ------------------------------------------------------------------ fused batch loop */
 
 typedef enum {

@@ -66,6 +66,15 @@ pub mod sys {
     pub const RDF_WIN_ROW_NUMBER: i32 = 0; pub const RDF_WIN_RANK: i32 = 1; pub const RDF_WIN_DENSE_RANK: i32 = 2;
     pub const RDF_WIN_PERCENT_RANK: i32 = 3; pub const RDF_WIN_CUME_DIST: i32 = 4; pub const RDF_WIN_NTILE: i32 = 5;
     pub const RDF_WIN_LAG: i32 = 6; pub const RDF_WIN_LEAD: i32 = 7;
+    // one call of rdf_window_agg: fn = RDF_WAGG_*, value = index into `values` (-1: COUNT of rows, FIRST / LAST_VALUE), its frame
+    #[repr(C)] #[derive(Clone, Copy)]
+    pub struct rdf_window_frame { pub unit: i32, pub start_kind: i32, pub end_kind: i32, pub pad: i32, pub start: i64, pub end: i64 }
+    #[repr(C)] #[derive(Clone, Copy)] pub struct rdf_window_agg_call { pub fn_: i32, pub value: i32, pub frame: rdf_window_frame }
+    pub const RDF_FRAME_ROWS: i32 = 0; pub const RDF_FRAME_RANGE: i32 = 1;
+    pub const RDF_BOUND_UNBOUNDED_PRECEDING: i32 = 0; pub const RDF_BOUND_PRECEDING: i32 = 1; pub const RDF_BOUND_CURRENT_ROW: i32 = 2;
+    pub const RDF_BOUND_FOLLOWING: i32 = 3; pub const RDF_BOUND_UNBOUNDED_FOLLOWING: i32 = 4;
+    pub const RDF_WAGG_SUM: i32 = 0; pub const RDF_WAGG_MIN: i32 = 1; pub const RDF_WAGG_MAX: i32 = 2; pub const RDF_WAGG_COUNT: i32 = 3;
+    pub const RDF_WAGG_AVG: i32 = 4; pub const RDF_WAGG_FIRST_VALUE: i32 = 5; pub const RDF_WAGG_LAST_VALUE: i32 = 6;
     #[repr(C)] pub struct rdf_frame { _opaque: [u8; 0] }
     #[repr(C)] pub struct rdf_comm { _opaque: [u8; 0] }
     #[repr(C)] #[derive(Clone, Copy, Default)]
@@ -121,6 +130,10 @@ pub mod sys {
         // WindowSpec / WindowFunctions (src/window.rs, src/functions/window.rs: declared, bodies empty) + ntile (scalar.rs:345)
         pub fn rdf_window(partition_by: *const rdf_sort_key, npartition: i32, order_by: *const rdf_sort_key, norder: i32,
                           nchunks: i64, nrows_if_no_keys: i64, calls: *const rdf_window_call, ncalls: i32, outs: *mut rdf_out) -> i32;
+        // WindowSpec::rows_between / range_between (src/window.rs) + AggregateFunctions over the frame
+        pub fn rdf_window_agg(partition_by: *const rdf_sort_key, npartition: i32, order_by: *const rdf_sort_key, norder: i32,
+                              values: *const *const rdf_array, nvalues: i32, nchunks: i64, nrows_if_no_keys: i64,
+                              calls: *const rdf_window_agg_call, ncalls: i32, outs: *mut rdf_out) -> i32;
         pub fn rdf_equijoin_indices(left_keys: *const rdf_array, left_nchunks: i64, right_keys: *const rdf_array, right_nchunks: i64,
                                     join_type: i32, out_left: *mut rdf_out, out_right: *mut rdf_out, out_rows: *mut i64) -> i32;
         pub fn rdf_equijoin_indices_multi(left_keys: *const rdf_array, left_nchunks: i64, right_keys: *const rdf_array,
@@ -579,6 +592,47 @@ pub fn window(partition_by: &[(Vec<&dyn Array>, bool)], order_by: &[(Vec<&dyn Ar
                                if no > 0 { keys[np..].as_ptr() } else { std::ptr::null() }, no as i32,
                                nchunks as i64, if np + no == 0 { rows as i64 } else { 0 },
                                ccalls.as_ptr(), ccalls.len() as i32, outs.as_mut_ptr()) })?;
+    Ok(bufs.into_iter().zip(outs.iter()).map(|(b, o)| b.finish(o)).collect())
+}
+
+/// WindowSpec { partition_by, order_by, rows_between | range_between } + one AggregateFunctions entry over the frame: `calls`
+/// are (RDF_WAGG_*, value column index or -1, frame).  SUM / MIN / MAX come back in the value column's type (Int64Array /
+/// Float64Array), AVG as Float64Array, COUNT as Int64Array (never NULL), FIRST_VALUE / LAST_VALUE as a UInt32Array of ROW
+/// INDICES for `take` / `utf8_take`; everything but COUNT is NULL where the frame holds no valid row.  `values`: Int64 /
+/// Float64 columns, chunked like the keys.  Several calls over one spec share the sort.
+pub fn window_agg(partition_by: &[(Vec<&dyn Array>, bool)], order_by: &[(Vec<&dyn Array>, bool)], values: &[Vec<&dyn Array>], rows: usize,
+                  calls: &[(i32, i32, rdf_window_frame)]) -> Result<Vec<ArrayRef>, ArrowError> {
+    let nchunks = partition_by.first().or(order_by.first()).map(|c| c.0.len()).or(values.first().map(|v| v.len())).unwrap_or(0);
+    let mut num: Vec<Vec<rdf_array>> = Vec::new();
+    let mut txt: Vec<Vec<rdf_utf8_array>> = Vec::new();
+    for (chunks, _) in partition_by.iter().chain(order_by.iter()) {
+        match chunks.first().map(|a| a.data_type()) {
+            Some(DataType::Utf8) => { txt.push(chunks.iter().map(|a| utf8_view(a.as_any().downcast_ref::<StringArray>().unwrap())).collect()); num.push(Vec::new()); }
+            _ => { num.push(chunks.iter().map(|a| view(*a)).collect()); txt.push(Vec::new()); }
+        }
+    }
+    let keys: Vec<rdf_sort_key> = partition_by.iter().chain(order_by.iter()).enumerate().map(|(k, (_, desc))| rdf_sort_key {
+        values: if num[k].is_empty() { std::ptr::null() } else { num[k].as_ptr() },
+        utf8: if txt[k].is_empty() { std::ptr::null() } else { txt[k].as_ptr() },
+        options: rdf_sort_options { descending: *desc as i32, nulls_first: 0 },
+    }).collect();
+    let vviews: Vec<Vec<rdf_array>> = values.iter().map(|v| v.iter().map(|a| view(*a)).collect()).collect();
+    let vptrs: Vec<*const rdf_array> = vviews.iter().map(|v| v.as_ptr()).collect();
+    let vtype = |i: i32| if i >= 0 { values[i as usize][0].data_type().clone() } else { DataType::Int64 };
+    let (np, no) = (partition_by.len(), order_by.len());
+    let ccalls: Vec<rdf_window_agg_call> = calls.iter().map(|(f, v, fr)| rdf_window_agg_call { fn_: *f, value: *v, frame: *fr }).collect();
+    let mut bufs: Vec<OutBuf> = calls.iter().map(|(f, v, _)| match *f {
+        RDF_WAGG_COUNT => OutBuf::new(DataType::Int64, rows, false),
+        RDF_WAGG_AVG => OutBuf::new(DataType::Float64, rows, true),
+        RDF_WAGG_FIRST_VALUE | RDF_WAGG_LAST_VALUE => OutBuf::new(DataType::UInt32, rows, true),
+        _ => OutBuf::new(vtype(*v), rows, true),
+    }).collect();
+    let mut outs: Vec<rdf_out> = bufs.iter_mut().map(|b| b.as_out()).collect();
+    status(unsafe { rdf_window_agg(if np > 0 { keys.as_ptr() } else { std::ptr::null() }, np as i32,
+                                   if no > 0 { keys[np..].as_ptr() } else { std::ptr::null() }, no as i32,
+                                   if vptrs.is_empty() { std::ptr::null() } else { vptrs.as_ptr() }, vptrs.len() as i32,
+                                   nchunks as i64, if np + no + values.len() == 0 { rows as i64 } else { 0 },
+                                   ccalls.as_ptr(), ccalls.len() as i32, outs.as_mut_ptr()) })?;
     Ok(bufs.into_iter().zip(outs.iter()).map(|(b, o)| b.finish(o)).collect())
 }
 

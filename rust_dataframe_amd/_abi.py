@@ -121,6 +121,41 @@ def window_out_dtype(fn: int) -> int:
     return F64 if fn in (WIN_PERCENT_RANK, WIN_CUME_DIST) else U32 if fn in (WIN_LAG, WIN_LEAD) else I64
 
 
+class rdf_window_frame(C.Structure):
+    _fields_ = [("unit", C.c_int32), ("start_kind", C.c_int32), ("end_kind", C.c_int32), ("pad", C.c_int32), ("start", C.c_int64), ("end", C.c_int64)]
+
+
+class rdf_window_agg_call(C.Structure):
+    _fields_ = [("fn", C.c_int32), ("value", C.c_int32), ("frame", rdf_window_frame)]
+
+
+FRAME_ROWS, FRAME_RANGE = 0, 1
+BOUND_UNBOUNDED_PRECEDING, BOUND_PRECEDING, BOUND_CURRENT_ROW, BOUND_FOLLOWING, BOUND_UNBOUNDED_FOLLOWING = range(5)
+WAGG_SUM, WAGG_MIN, WAGG_MAX, WAGG_COUNT, WAGG_AVG, WAGG_FIRST_VALUE, WAGG_LAST_VALUE = range(7)
+WINDOW_AGG_FNS = {"sum": WAGG_SUM, "min": WAGG_MIN, "max": WAGG_MAX, "count": WAGG_COUNT, "avg": WAGG_AVG,
+                  "first_value": WAGG_FIRST_VALUE, "last_value": WAGG_LAST_VALUE}
+WINDOW_MAX_VALUES = 4
+UNBOUNDED_PRECEDING, CURRENT_ROW, UNBOUNDED_FOLLOWING = "unbounded_preceding", 0, "unbounded_following"
+
+
+def window_agg_out_dtype(fn: int, value_dtype: int = I64) -> int:
+    return I64 if fn == WAGG_COUNT else F64 if fn == WAGG_AVG else U32 if fn in (WAGG_FIRST_VALUE, WAGG_LAST_VALUE) else value_dtype
+
+
+def window_frame(unit, start, end) -> rdf_window_frame:
+    """("rows" | "range", start, end) in WindowSpec's spelling: UNBOUNDED_PRECEDING / UNBOUNDED_FOLLOWING, 0 = the current row, a
+    negative number = that many rows preceding, a positive one = following."""
+    def bound(b):
+        if b == UNBOUNDED_PRECEDING:
+            return BOUND_UNBOUNDED_PRECEDING, 0
+        if b == UNBOUNDED_FOLLOWING:
+            return BOUND_UNBOUNDED_FOLLOWING, 0
+        b = int(b)
+        return (BOUND_CURRENT_ROW, 0) if b == 0 else (BOUND_PRECEDING, -b) if b < 0 else (BOUND_FOLLOWING, b)
+    (sk, so), (ek, eo) = bound(start), bound(end)
+    return rdf_window_frame({"rows": FRAME_ROWS, "range": FRAME_RANGE}[unit], sk, ek, 0, so, eo)
+
+
 class rdf_exchange_stats(C.Structure):
     _fields_ = [("exchange", C.c_int32), ("rounds", C.c_int32), ("local_groups", C.c_int64), ("rows_sent", C.c_int64),
                 ("rows_sent_remote", C.c_int64), ("rows_received", C.c_int64), ("bytes_sent", C.c_int64),
@@ -1329,6 +1364,50 @@ class Api:
                        C.c_int64(nchunks), C.c_int64(nrows), cc if calls else None, C.c_int32(len(calls)), carr))
         self._finish(outs, carr)
         return outs if raw else [self.window_to_numpy(o) for o in outs]
+
+    def window_agg(self, partition_by: Sequence, order_by: Sequence, values: Sequence, calls: Sequence, mem: Optional[str] = None,
+                   nrows: int = 0, outs=None, raw: bool = False):
+        """rdf_window_agg: sum / min / max / count / avg / first_value / last_value over window frames, every call answered
+        from one sort.  partition_by / order_by as for window(); values = [chunks, ...] (Int64 or Float64 columns);
+        calls = [(name, value index, frame), ...] with the names of WINDOW_AGG_FNS, frame = ("rows" | "range", start, end) in
+        window_frame's spelling or an rdf_window_frame.  -> per call (values, valid) as numpy in the original row order
+        (count: valid all True); raw=True returns the output arrays as they are."""
+        pk, keep_p = self._sort_keys(partition_by)
+        ok, keep_o = self._sort_keys(order_by)
+        cols = [k[0] if isinstance(k, tuple) else k for k in list(partition_by) + list(order_by)] + list(values)
+        nchunks = len(cols[0]) if cols else 0
+        n = sum(c.length for c in cols[0]) if cols else int(nrows)
+        device = mem == "device" if mem is not None else any(isinstance(c, (DeviceArray, DeviceUtf8)) for k in cols for c in k)
+        varrs = [(rdf_array * max(1, len(v)))(*[c.c_struct(getattr(c, "_unknown_nc", False)) for c in v]) for v in values]
+        vptr = (C.POINTER(rdf_array) * max(1, len(values)))(*[C.cast(a, C.POINTER(rdf_array)) for a in varrs])
+        cc = (rdf_window_agg_call * max(1, len(calls)))()
+        for i, (name, value, frame) in enumerate(calls):
+            fr = frame if isinstance(frame, rdf_window_frame) else window_frame(*frame)
+            cc[i] = rdf_window_agg_call(WINDOW_AGG_FNS[name] if isinstance(name, str) else int(name), int(value), fr)
+        if outs is None:
+            vdt = [v[0].dtype if len(v) else I64 for v in values]
+            outs = [self._window_out(window_agg_out_dtype(cc[i].fn, vdt[cc[i].value] if 0 <= cc[i].value < len(vdt) else I64), n, device,
+                                     cc[i].fn != WAGG_COUNT) for i in range(len(calls))]
+        carr = (rdf_out * max(1, len(outs)))(*[o.out_struct() for o in outs])
+        fn = self._fn("window_agg")
+        fn.restype = C.c_int
+        self._check(fn(pk if partition_by else None, C.c_int32(len(partition_by)), ok if order_by else None, C.c_int32(len(order_by)),
+                       vptr if values else None, C.c_int32(len(values)), C.c_int64(nchunks), C.c_int64(nrows),
+                       cc if calls else None, C.c_int32(len(calls)), carr))
+        self._finish(outs, carr)
+        return outs if raw else [self.window_agg_to_numpy(o) for o in outs]
+
+    @staticmethod
+    def window_agg_to_numpy(out):
+        """One output of window_agg(raw=True) as (values, valid)."""
+        if isinstance(out, HostArray):
+            vals = out.values[:out.length].copy()
+            valid = unpack_bits(out.validity, 0, out.length) if out.validity is not None else None
+        else:
+            t, v = out.keep
+            vals = t.cpu().numpy().view(NP_OF[out.dtype])[:out.length].copy()
+            valid = unpack_bits(v.cpu().numpy(), 0, out.length) if v is not None else None
+        return vals, (valid if valid is not None else np.ones(out.length, dtype=bool))
 
     def utf8_uniques(self, chunks: Sequence, as_arrow=False):
         """Column::uniques of a Utf8 column -> ONE Utf8 chunk of the distinct strings (no NULLs, unspecified order).  The

@@ -29,6 +29,7 @@
 #include "rdf_utf8.h"
 #include "rdf_colstats.h"
 #include "rdf_window.h"
+#include "rdf_window_agg.h"
 
 using namespace rdfk;
 
@@ -4401,6 +4402,7 @@ rdf_status legacy_groupby_sum(const rdf_array* keys, const rdf_array* values, in
 #include "rdf_capi_sort_utf8.inc"
 #include "rdf_capi_colstats.inc"
 #include "rdf_capi_window.inc"
+#include "rdf_capi_window_agg.inc"
 
 extern "C" {
 
