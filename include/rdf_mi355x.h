@@ -830,9 +830,12 @@ rdf_status rdf_fill_validity(uint8_t* dev_ptr, int64_t nbits, uint64_t seed, uin
  * when the program shape is in the catalogs, default; 0 = always the general evaluator), "fast_filter",
  * "vec_bitmap" (accepted and ignored since round 5: the specialised kernels read bitmap words on the scalar unit only), "gb_partition" (hash GROUP BY: 3 = second
  * generation, default: LDS-table stream <= 2048 groups, line-aligned scatter + LDS tables <= 1.3 M, else one table in HBM;
- * 4 = its scatter path whatever max_groups says; 1 = first-generation histogram + scatter; 2 = radix-sort partitioning;
- * 0 = one table in HBM),
- * "gb_debug" (1 / 2: ablations of the aggregate / scatter pass, results invalid; 3: force the skew variant),
+ * 4 = its scatter path whatever max_groups says; 1 = rdf_groupby_sum runs on the first-generation histogram + scatter + aggregate
+ * path — otherwise the fallback for heavily skewed sums / counts of one key column — where that path's range holds
+ * (1024 < max_groups <= 1 331 200, at least one row), elsewhere as 3; 2 = accepted, behaves as 3 (it named the retired radix-sort
+ * partitioning); 0 = one table in HBM),
+ * "gb_debug" (3 = tests: rdf_groupby_sum takes that first-generation path, inside the same range, with its combining scatter
+ * forced; every other value is accepted and ignored: no value changes a result),
  * "jit" (a program shape no catalog holds: 1 = the specialised kernel template is compiled for it at run time — `hipcc` as a child
  * process on a helper thread, about half a second; THIS call and the ones until it is ready are answered by the general evaluator,
  * a code object found in the cache directory is loaded at once —, default; 2 = the call waits for the compiler; 0 = always the

@@ -72,7 +72,7 @@ struct Ctx {
     int    opt_filter_fused = 1;    // rdf_filter_frame: `col CMP literal [AND|OR col CMP literal]` predicates evaluated inside the compaction kernel, one pass (1, default); 0 = predicate -> mask, count, compact (A/B)
     int    opt_filter_lookback = 3; // one-pass rdf_filter_frame, batches longer than a tile: 3 = a super-tile's first tile finds the rows in front of the super-tile for all 64, from the nearest super-tiles' tile counts and the older ones' totals (default); 2 = from totals only; 1 = every tile walks the totals (round 4; batches of at most 1024 tiles) — A/B
     int    opt_filter_tile = 0;     // 0: compaction tile chosen from the mean chunk length; 1024 / 4096 force one (A/B)
-    int    opt_gb_debug = 0;        // ablations of the partitioned GROUP BY (tools/bench_kernels.py): 1 = aggregate without LDS work, 2 = scatter without stores
+    int    opt_gb_debug = 0;        // 3 = rdf_groupby_sum takes the first-generation fallback (where its range holds) with the combining scatter forced (tests); nothing else is stored
     bool   sort_used_local = false; // the last sort finished at least one column with os_local_kernel
     int64_t utf8_sort_rounds = 0;   // the last sort: refinement rounds its Utf8 criteria took (round 0 included), summed
     int    opt_sort_msd = 1;        // sort keys that vary in more than 32 bits: passes over the top bits, then every bucket sorted in LDS (1, default); 0 = one pass per byte (A/B)
@@ -92,7 +92,7 @@ struct Ctx {
     int    opt_gb_bucket = 0;       // partition tables of the aggregate pass: 4 = four keys per 32-byte bucket, 1 = one key per probe, 0 = by the sampled key range (default: one key per probe for keys packed into <= 4 x max_groups values, buckets otherwise)
     int    opt_uniques_route = 0;     // rdf_uniques / rdf_utf8_uniques: 0 = the hash route while its table holds the keys, else the sort route (default); 1 = always the sort (exact) route (tests, A/B)
     int    opt_uniques_table_bits = 24;   // ... log2 of the most slots the hash route's table may have (8 bytes each, + 4 for Utf8); it is filled to half, so 2^23 distinct values fit by default
-    int    opt_gb_partition = 3;    // hash GROUP BY: 3 = second generation (rdf_groupby.hip: stream / line-aligned scatter / table by max_groups, default), 4 = its partition path whatever max_groups says, 1 = first-generation histogram + scatter, 2 = first-generation radix sort, 0 = one table in HBM
+    int    opt_gb_partition = 3;    // hash GROUP BY: 3 = second generation (rdf_groupby.hip: stream / line-aligned scatter / table by max_groups, default), 4 = its partition path whatever max_groups says, 1 = rdf_groupby_sum on the first-generation histogram + scatter fallback where its range holds (A/B), 0 = one table in HBM
     // kernel timing (bench.py roofline leg)
     bool   timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
@@ -3280,7 +3280,7 @@ rdf_status rdf_list_sort(const rdf_list_array* list, rdf_out* out_values) {
     }
     out_values->length = total;
     out_values->null_count = 0;
-    ctx.last_kernel = "list_row_ids_kernel + sort_scatter_kernel + take_kernel";
+    ctx.last_kernel = "list_row_ids_kernel + os_scatter_kernel + take_kernel";
     return RDF_OK;
 }
 
@@ -3596,7 +3596,7 @@ rdf_status sort_core(const DevChunkCol* d_chunks, const int64_t* d_row_start, in
         RDF_TRY(os_column_passes(os, keys, idxb, (const uint8_t*)pnf, n, bias, std::min(need, dtype_size(dt)), has_nulls, kcur, icur, idx_cur, kmax >= bias ? kmax - bias : ~0ull, dt == RDF_F64 ? (ka.descending ? 2 : 1) : dt == RDF_F32 ? -1 : 0));
     }
     kt.stop();
-    ctx.last_kernel = ctx.sort_used_local ? "os_scatter_kernel+os_local_kernel" : "sort_scatter_kernel";
+    ctx.last_kernel = ctx.sort_used_local ? "os_scatter_kernel+os_local_kernel" : "os_scatter_kernel";
     if (any_utf8) ctx.last_kernel = "us_keys_kernel+os_scatter_kernel (Utf8 rounds: " + std::to_string(ctx.utf8_sort_rounds) + ")";
     *idx_out = idx_cur;
     return RDF_OK;
@@ -4018,74 +4018,18 @@ rdf_status rdf_equijoin_indices_multi(const rdf_array* left_keys, int64_t left_n
 
 // ---------------------------------------------------------------- group-by
 
-// Tail of both partitioned GROUP BY paths: read back {special sums, counts, flags, cursor}, append the two special
-// groups (the key whose hash is the LDS free marker; the NULL key) and copy the dense results to the caller.
-static rdf_status groupby_finish_partitioned(void* pspec, void* d_keys, void* d_sums, void* d_counts, int kdt, int64_t max_groups, int32_t mem,
-                                             rdf_out* out_keys, rdf_out* out_sums, rdf_out* out_counts, size_t pin_off, bool single_pass) {
-    Ctx& ctx = g_ctx;
-    struct { void* out_keys; void* out_sums; void* out_counts; } ga = {d_keys, d_sums, d_counts};
-        // specials + cursor + flags
-        RDF_TRY(pinned_reserve(pin_off + 256));
-        HIP_TRY(hipMemcpyAsync(ctx.pinned + pin_off, pspec, 128, hipMemcpyDeviceToHost, ctx.stream));
-        HIP_TRY(hipStreamSynchronize(ctx.stream));
-        unsigned long long hs[4];
-        unsigned int hf[8];
-        memcpy(hs, ctx.pinned + pin_off, 32);
-        memcpy(hf, ctx.pinned + pin_off + 32, 32);
-        const int64_t ng_main = hf[2];
-        if ((hf[4] & 4u) || ng_main > max_groups) return fail(RDF_MEMORY_ERROR, "groupby: more than max_groups (%lld) distinct keys", (long long)max_groups);
-        // append the two special groups on the host side of the copy
-        const size_t kes2 = (size_t)dtype_size(kdt);
-        int64_t ng = ng_main;
-        int64_t null_idx = -1;
-        auto put = [&](uint64_t key, unsigned long long sum, unsigned long long cnt) -> rdf_status {
-            HIP_TRY(hipMemcpyAsync((char*)ga.out_keys + (size_t)ng * kes2, &key, kes2, hipMemcpyHostToDevice, ctx.stream));
-            HIP_TRY(hipMemcpyAsync((char*)ga.out_sums + (size_t)ng * 8, &sum, 8, hipMemcpyHostToDevice, ctx.stream));
-            HIP_TRY(hipMemcpyAsync((char*)ga.out_counts + (size_t)ng * 8, &cnt, 8, hipMemcpyHostToDevice, ctx.stream));
-            HIP_TRY(hipStreamSynchronize(ctx.stream));
-            ++ng;
-            return RDF_OK;
-        };
-        if (hf[0]) {  // the key whose hash equals the LDS free marker: unmix on the host
-            uint64_t z = ~0ull;
-            if (single_pass) { z ^= z >> 32; z *= 0xF1DE83E19937733Dull; z ^= z >> 32; }   // inverse of gb_hash
-            else { z ^= z >> 31; z ^= z >> 62; z *= 0x319642b2d24d8ec3ull; z ^= z >> 27; z ^= z >> 54; z *= 0x96de1b173f119089ull; z ^= z >> 30; z ^= z >> 60; }   // inverse of mix64
-            RDF_TRY(put(z, hs[0], hs[2]));
-        }
-        if (hf[1]) { null_idx = ng; RDF_TRY(put(0, hs[1], hs[3])); }
-        if (ng > out_keys->capacity || ng > out_sums->capacity || ng > out_counts->capacity)
-            return fail(RDF_MEMORY_ERROR, "groupby: more than max_groups (%lld) distinct keys", (long long)max_groups);
-        const hipMemcpyKind kind = mem == RDF_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-        if (ng > 0) {
-            HIP_TRY(hipMemcpyAsync(out_keys->values, ga.out_keys, (size_t)ng * kes2, kind, ctx.stream));
-            HIP_TRY(hipMemcpyAsync(out_sums->values, ga.out_sums, (size_t)ng * 8, kind, ctx.stream));
-            HIP_TRY(hipMemcpyAsync(out_counts->values, ga.out_counts, (size_t)ng * 8, kind, ctx.stream));
-        }
-        rdf_out* outs3[3] = {out_keys, out_sums, out_counts};
-        for (rdf_out* o : outs3)
-            if (o->validity && ng > 0) {
-                if (mem == RDF_MEM_HOST) memset(o->validity, 0xFF, (size_t)((ng + 7) / 8));
-                else HIP_TRY(hipMemsetAsync(o->validity, 0xFF, (size_t)((ng + 7) / 8), ctx.stream));
-            }
-        if (null_idx >= 0) {
-            const uint8_t byte = (uint8_t)~(1u << (null_idx & 7));
-            if (mem == RDF_MEM_HOST) out_keys->validity[null_idx >> 3] &= byte;
-            else HIP_TRY(hipMemcpyAsync(out_keys->validity + (null_idx >> 3), &byte, 1, hipMemcpyHostToDevice, ctx.stream));
-        }
-        HIP_TRY(hipStreamSynchronize(ctx.stream));
-        out_keys->length = out_sums->length = out_counts->length = ng;
-        out_keys->null_count = null_idx >= 0 ? 1 : 0;
-        out_sums->null_count = out_counts->null_count = 0;
-    return RDF_OK;
-}
-
 }  // extern "C"
 namespace {
-// The first-generation hash GROUP BY (sum / count of one key column): histogram -> scatter (with the combining variant for
-// skewed keys) -> aggregate, the radix-sort variant and the single HBM table.  Since round 2 the default is rdf_groupby_agg
-// (rdf_capi_groupby.inc); this stays as its fallback for heavily skewed keys and as the A/B baseline (gb_partition = 1 / 2).
-rdf_status legacy_groupby_sum(const rdf_array* keys, const rdf_array* values, int64_t nchunks, int64_t max_groups,
-                              rdf_out* out_keys, rdf_out* out_sums, rdf_out* out_counts) {
+// What is left of the first-generation hash GROUP BY: histogram -> scatter -> aggregate on 9 hash bits, for sums / counts of ONE
+// integer key column.  When the histogram shows skew the scatter combines equal keys inside each super-tile, which is what this path
+// is kept for: rdf_groupby_agg (rdf_capi_groupby.inc) hands it the inputs whose heavily skewed keys overflowed a scatter region of
+// the second generation, and rdf_groupby_sum routes here under gb_partition = 1 / gb_debug = 3.  Its LDS tables hold
+// 1024 < max_groups <= kGbMaxGroups and there is no empty-input form: callers ask gb_fallback_in_range first.
+static_assert(kG2MaxGroups <= kGbMaxGroups, "whatever max_groups the second generation's partition path gives up on, the fallback's tables hold");
+bool gb_fallback_in_range(int64_t max_groups, int64_t nrows) { return max_groups > 1024 && max_groups <= kGbMaxGroups && nrows > 0; }
+
+rdf_status groupby_sum_fallback(const rdf_array* keys, const rdf_array* values, int64_t nchunks, int64_t max_groups,
+                                rdf_out* out_keys, rdf_out* out_sums, rdf_out* out_counts) {
     if (nchunks < 1 || !keys) return fail(RDF_INVALID_ARGUMENT, "groupby: a column has at least one chunk");
     if (!out_keys || !out_sums || !out_counts) return fail(RDF_INVALID_ARGUMENT, "groupby: null output");
     if (max_groups < 1) return fail(RDF_INVALID_ARGUMENT, "groupby: max_groups must be positive");
@@ -4112,9 +4056,9 @@ rdf_status legacy_groupby_sum(const rdf_array* keys, const rdf_array* values, in
         tile_start[(size_t)c + 1] = tile_start[(size_t)c] + (keys[c].length + kEvalTile - 1) / kEvalTile;
     }
     if (null_keys && !out_keys->validity) return fail(RDF_INVALID_ARGUMENT, "output validity buffer required");
-    int64_t nrows_total = 0;
-    for (int64_t c = 0; c < nchunks; ++c) nrows_total += keys[c].length;
-    const int64_t cap_needed = std::min<int64_t>(max_groups + 2, nrows_total + 2);    // the contract rdf_groupby_agg states
+    int64_t nrows = 0;
+    for (int64_t c = 0; c < nchunks; ++c) nrows += keys[c].length;
+    const int64_t cap_needed = std::min<int64_t>(max_groups + 2, nrows + 2);    // the contract rdf_groupby_agg states
     if (out_keys->capacity < cap_needed || out_sums->capacity < cap_needed || out_counts->capacity < cap_needed)
         return fail(RDF_MEMORY_ERROR, "output capacity too small (need max_groups + 2)");
     RDF_TRY(ensure_ready());
@@ -4131,265 +4075,139 @@ rdf_status legacy_groupby_sum(const rdf_array* keys, const rdf_array* values, in
     const size_t o_v = tb.reserve(sizeof(DevChunkCol) * (size_t)nchunks);
     const size_t o_ts = tb.reserve(sizeof(int64_t) * tile_start.size());
     const size_t o_len = tb.reserve(sizeof(int64_t) * clen.size());
-    std::vector<int64_t> row_start((size_t)nchunks + 1, 0);
-    for (int64_t c = 0; c < nchunks; ++c) row_start[(size_t)c + 1] = row_start[(size_t)c] + clen[(size_t)c];
-    const size_t o_rs = tb.reserve(sizeof(int64_t) * row_start.size());
     RDF_TRY(tb.bind(pin_off));
     memcpy(tb.at<char>(o_k), in.dev.data(), sizeof(DevChunkCol) * (size_t)nchunks);
     if (values) memcpy(tb.at<char>(o_v), in.dev.data() + nchunks, sizeof(DevChunkCol) * (size_t)nchunks);
     memcpy(tb.at<char>(o_ts), tile_start.data(), sizeof(int64_t) * tile_start.size());
     memcpy(tb.at<char>(o_len), clen.data(), sizeof(int64_t) * clen.size());
-    memcpy(tb.at<char>(o_rs), row_start.data(), sizeof(int64_t) * row_start.size());
     RDF_TRY(tb.alloc());
     RDF_TRY(tb.upload(pin_off));
     pin_off += (tb.size + 255) & ~(size_t)255;
 
-    // High cardinality: radix-partition on the hashed key, aggregate each partition in LDS (no HBM atomics per row).
-    bool value_nulls = false;
-    if (values) for (int64_t c = 0; c < nchunks; ++c) value_nulls |= values[c].validity != nullptr;
-    const int64_t nrows = row_start[(size_t)nchunks];
-    if (ctx.opt_gb_partition && max_groups > 1024 && max_groups <= kGbMaxGroups && nrows > 0 && ctx.opt_gb_partition != 2) {
-        // single scatter pass on 9 hash bits, then one LDS table per partition
-        constexpr int P = 1 << kGbPartBits;
-        const int64_t ntiles = tile_start[(size_t)nchunks];
-        const int64_t nsuper = (ntiles + kGbSuper / kEvalTile - 1) / (kGbSuper / kEvalTile);
-        int nb = (int)std::min<int64_t>(nsuper, (int64_t)eval_grid_limit() / 4);   // 2 resident blocks of 512 threads per CU
-        if (nb < 1) nb = 1;
-        void *precs, *hist0, *hist1, *ptmp, *pspec;
-        RDF_TRY(arena_alloc((size_t)nrows * 16 + 64, &precs));
-        RDF_TRY(arena_alloc((size_t)((int64_t)P * nb + 1) * 8, &hist0));
-        RDF_TRY(arena_alloc((size_t)((int64_t)P * nb + 1 + scan_scratch_words((int64_t)P * nb)) * 8, &hist1));
-        const int64_t cap_out = max_groups + 2;
-        RDF_TRY(arena_alloc((size_t)cap_out * 24 + 64, &ptmp));
-        RDF_TRY(arena_alloc(128, &pspec));
-        HIP_TRY(hipMemsetAsync(pspec, 0, 128, ctx.stream));
-        unsigned long long* sp_sums = (unsigned long long*)pspec;         // [2]
-        unsigned long long* sp_counts = sp_sums + 2;                      // [2]
-        unsigned int* sp_flag = (unsigned int*)(sp_counts + 2);           // [2]
-        unsigned int* d_cursor = sp_flag + 2;
-        uint32_t* d_flags2 = (uint32_t*)(sp_flag + 4);
-        GbPartArgs pa;
-        memset(&pa, 0, sizeof pa);
-        pa.keys = tb.dev_at<DevChunkCol>(o_k);
-        pa.values = tb.dev_at<DevChunkCol>(o_v);
-        pa.chunk_tile_start = tb.dev_at<int64_t>(o_ts);
-        pa.chunk_len = tb.dev_at<int64_t>(o_len);
-        pa.nchunks = nchunks;
-        pa.ntiles = ntiles;
-        if (nchunks == 1) { pa.key0 = in.dev[0]; if (values) pa.val0 = in.dev[1]; pa.len0 = clen[0]; }
-        pa.ablate_stores = (ctx.opt_gb_debug == 2 || ctx.opt_gb_debug == 7 || ctx.opt_gb_debug == 8) ? ctx.opt_gb_debug : 0;
-        pa.key_dtype = kdt;
-        pa.value_dtype = vdt;
-        pa.hist = (int64_t*)hist0;
-        pa.recs = (uint64_t*)precs;
-        pa.special_sums = sp_sums;
-        pa.special_counts = sp_counts;
-        pa.special = sp_flag;
-        KernelTimer kt;
-        HIP_TRY(launch_gb_hist(pa, nb, ctx.stream));
-        HIP_TRY(launch_scan((const int64_t*)hist0, (int64_t*)hist1, (int64_t)P * nb, (int64_t*)hist1 + (int64_t)P * nb + 1, ctx.stream));
-        pa.hist = (int64_t*)hist1;
-        // skewed key distribution (one partition far above the average)?  Then equal keys are combined inside each
-        // super-tile before they are scattered, so a hot key does not serialise one block's LDS atomics.
-        unsigned int* d_skew = d_cursor + 1;
-        HIP_TRY(launch_gb_skew((const int64_t*)hist1, nb, d_skew, ctx.stream));
-        RDF_TRY(pinned_reserve(pin_off + 64));
-        HIP_TRY(hipMemcpyAsync(ctx.pinned + pin_off, d_skew, 4, hipMemcpyDeviceToHost, ctx.stream));
-        HIP_TRY(hipStreamSynchronize(ctx.stream));
-        unsigned int skew = 0;
-        memcpy(&skew, ctx.pinned + pin_off, 4);
-        if (ctx.opt_gb_debug == 3) skew = 1;   // tests: force the combining variant
-        void* pemit = nullptr;
-        if (skew) { RDF_TRY(arena_alloc((size_t)((int64_t)P * nb + 1) * 8, &pemit)); pa.emitted = (int64_t*)pemit; }
-        HIP_TRY(launch_gb_scatter(pa, nb, skew != 0, ctx.stream));
-        GbAggArgs ga;
-        memset(&ga, 0, sizeof ga);
-        ga.recs = (const uint64_t*)precs;
-        ga.scan = (const int64_t*)hist1;
-        ga.nblocks = nb;
-        ga.emitted = (const int64_t*)pemit;
-        ga.is_f64 = sdt == RDF_F64;
-        ga.has_values = values != nullptr;
-        ga.key_dtype = kdt;
-        char* tmp = (char*)ptmp;
-        ga.out_keys = tmp;
-        ga.out_sums = tmp + (size_t)cap_out * 8;
-        ga.out_counts = (int64_t*)(tmp + (size_t)cap_out * 16);
-        ga.cursor = d_cursor;
-        ga.flags = d_flags2;
-        ga.max_out = max_groups;
-        ga.ablate_lds = (ctx.opt_gb_debug == 1 || (ctx.opt_gb_debug >= 4 && ctx.opt_gb_debug <= 6)) ? ctx.opt_gb_debug : 0;
-        HIP_TRY(launch_gb_aggregate(ga, ctx.stream));
-        kt.stop();
-        ctx.last_kernel = skew ? "gb_aggregate_kernel(combined)" : "gb_aggregate_kernel";
-        RDF_TRY(groupby_finish_partitioned(pspec, ga.out_keys, ga.out_sums, ga.out_counts, kdt, max_groups, mem, out_keys, out_sums, out_counts, pin_off, true));
-        return RDF_OK;
-    }
-    if (ctx.opt_gb_partition && max_groups > 1024 && !value_nulls && nrows > 0) {
-        const int npass = max_groups > 131072 ? 2 : 1;
-        const int64_t stiles = (nrows + kSortTile - 1) / kSortTile;
-        const int64_t sgrid = sort_grid(stiles);
-        void *ph[4], *hist0, *hist1, *ptmp, *pspec;
-        for (int i = 0; i < 4; ++i) RDF_TRY(arena_alloc((size_t)nrows * 8, &ph[i]));
-        RDF_TRY(arena_alloc((size_t)(256 * sgrid + 1) * 8, &hist0));
-        RDF_TRY(arena_alloc((size_t)(256 * sgrid + 1 + scan_scratch_words(256 * sgrid)) * 8, &hist1));
-        const int64_t cap_out = max_groups + 2;
-        RDF_TRY(arena_alloc((size_t)cap_out * 24 + 64, &ptmp));
-        RDF_TRY(arena_alloc(128, &pspec));
-        HIP_TRY(hipMemsetAsync(pspec, 0, 128, ctx.stream));
-        unsigned long long* sp_sums = (unsigned long long*)pspec;         // [2]
-        unsigned long long* sp_counts = sp_sums + 2;                      // [2]
-        unsigned int* sp_flag = (unsigned int*)(sp_counts + 2);           // [2]
-        unsigned int* d_cursor = sp_flag + 2;
-        uint32_t* d_flags2 = (uint32_t*)(sp_flag + 4);
-        GroupPrepArgs pa;
-        memset(&pa, 0, sizeof pa);
-        pa.keys = tb.dev_at<DevChunkCol>(o_k);
-        pa.values = tb.dev_at<DevChunkCol>(o_v);
-        pa.chunk_tile_start = tb.dev_at<int64_t>(o_ts);
-        pa.chunk_len = tb.dev_at<int64_t>(o_len);
-        pa.chunk_row_start = tb.dev_at<int64_t>(o_rs);
-        pa.nchunks = nchunks;
-        pa.ntiles = tile_start[(size_t)nchunks];
-        pa.key_dtype = kdt;
-        pa.value_dtype = vdt;
-        pa.hkeys = (uint64_t*)ph[0];
-        pa.vals = (uint64_t*)ph[1];
-        pa.special_sums = sp_sums;
-        pa.special_counts = sp_counts;
-        pa.special = sp_flag;
-        KernelTimer kt;
-        HIP_TRY(launch_groupby_prepare(pa, ctx.stream));
-        int cur = 0;  // (ph[cur], ph[cur + 1]) hold the current streams
-        for (int p = 0; p < npass; ++p) {
-            SortPassArgs sa;
-            memset(&sa, 0, sizeof sa);
-            sa.keys_in = (const uint64_t*)ph[cur];
-            sa.pay_in = (const uint64_t*)ph[cur + 1];
-            sa.keys_out = (uint64_t*)ph[cur ^ 2];
-            sa.pay_out = (uint64_t*)ph[(cur ^ 2) + 1];
-            sa.hist = (int64_t*)hist0;
-            sa.n = nrows;
-            sa.ntiles = stiles;
-            sa.shift = 64 - 8 * npass + 8 * p;
-            HIP_TRY(launch_sort_hist64(sa, ctx.stream));
-            HIP_TRY(launch_scan((const int64_t*)hist0, (int64_t*)hist1, 256 * sgrid, (int64_t*)hist1 + 256 * sgrid + 1, ctx.stream));
-            sa.hist = (int64_t*)hist1;
-            HIP_TRY(launch_sort_scatter64(sa, ctx.stream));
-            cur ^= 2;
-        }
-        GroupAggArgs ga;
-        memset(&ga, 0, sizeof ga);
-        ga.hkeys = (const uint64_t*)ph[cur];
-        ga.vals = (const uint64_t*)ph[cur + 1];
-        ga.n = nrows;
-        ga.part_bits = 8 * npass;
-        ga.is_f64 = sdt == RDF_F64;
-        ga.has_values = values != nullptr;
-        ga.key_dtype = kdt;
-        char* tmp = (char*)ptmp;
-        ga.out_keys = tmp;
-        ga.out_sums = tmp + (size_t)cap_out * 8;
-        ga.out_counts = (int64_t*)(tmp + (size_t)cap_out * 16);
-        ga.cursor = d_cursor;
-        ga.flags = d_flags2;
-        ga.max_out = max_groups;
-        HIP_TRY(launch_groupby_partitions(ga, ctx.stream));
-        kt.stop();
-        ctx.last_kernel = "groupby_partitions_kernel";
-        RDF_TRY(groupby_finish_partitioned(pspec, ga.out_keys, ga.out_sums, ga.out_counts, kdt, max_groups, mem, out_keys, out_sums, out_counts, pin_off, false));
-        return RDF_OK;
-    }
-
-    int64_t capacity = 1024;
-    while (capacity < 2 * max_groups) capacity <<= 1;
-    void* p = nullptr;
-    const size_t tab_bytes = sizeof(uint64_t) * (size_t)(3 * capacity + 4) + 64;
-    RDF_TRY(arena_alloc(tab_bytes, &p));
-    GroupTable t;
-    t.keys = (unsigned long long*)p;
-    t.sums = t.keys + capacity;
-    t.counts = t.sums + capacity + 2;
-    t.special = (unsigned int*)(t.counts + capacity + 2);
-    t.ngroups = t.special + 2;
-    t.flags = (uint32_t*)(t.special + 4);
-    unsigned int* cursor = t.special + 6;
-    t.capacity = capacity;
-    // keys <- i64::MIN pattern (0x80 00 .. per 8 bytes): fill via a 64-bit pattern memset
-    // every slot key <- i64::MIN (the free marker): the fill kernel with a span of 1 writes the constant
-    HIP_TRY(launch_fill_i64((int64_t*)t.keys, capacity, 0, 0, 0, INT64_MIN, INT64_MIN + 1, ctx.stream));
-    HIP_TRY(hipMemsetAsync(t.sums, 0, sizeof(uint64_t) * (size_t)(2 * capacity + 4) + 64, ctx.stream));
-
-    GroupByArgs ga;
-    memset(&ga, 0, sizeof ga);
-    ga.keys = tb.dev_at<DevChunkCol>(o_k);
-    ga.values = tb.dev_at<DevChunkCol>(o_v);
-    ga.chunk_tile_start = tb.dev_at<int64_t>(o_ts);
-    ga.chunk_len = tb.dev_at<int64_t>(o_len);
-    ga.nchunks = nchunks;
-    ga.ntiles = tile_start[(size_t)nchunks];
-    ga.key_dtype = kdt;
-    ga.value_dtype = vdt;
-    ga.t = t;
-    ga.max_groups = max_groups;
-    {
-        KernelTimer kt;
-        HIP_TRY(launch_groupby_build(ga, ctx.stream));
-        kt.stop();
-    }
-    // group count + flags
+    // single scatter pass on 9 hash bits, then one LDS table per partition
+    constexpr int P = 1 << kGbPartBits;
+    const int64_t ntiles = tile_start[(size_t)nchunks];
+    const int64_t nsuper = (ntiles + kGbSuper / kEvalTile - 1) / (kGbSuper / kEvalTile);
+    int nb = (int)std::min<int64_t>(nsuper, (int64_t)eval_grid_limit() / 4);   // 2 resident blocks of 512 threads per CU
+    if (nb < 1) nb = 1;
+    void *precs, *hist0, *hist1, *ptmp, *pspec;
+    RDF_TRY(arena_alloc((size_t)nrows * 16 + 64, &precs));
+    RDF_TRY(arena_alloc((size_t)((int64_t)P * nb + 1) * 8, &hist0));
+    RDF_TRY(arena_alloc((size_t)((int64_t)P * nb + 1 + scan_scratch_words((int64_t)P * nb)) * 8, &hist1));
+    const int64_t cap_out = max_groups + 2;
+    RDF_TRY(arena_alloc((size_t)cap_out * 24 + 64, &ptmp));
+    RDF_TRY(arena_alloc(128, &pspec));
+    HIP_TRY(hipMemsetAsync(pspec, 0, 128, ctx.stream));
+    unsigned long long* sp_sums = (unsigned long long*)pspec;         // [2]
+    unsigned long long* sp_counts = sp_sums + 2;                      // [2]
+    unsigned int* sp_flag = (unsigned int*)(sp_counts + 2);           // [2]
+    unsigned int* d_cursor = sp_flag + 2;
+    uint32_t* d_flags2 = (uint32_t*)(sp_flag + 4);
+    GbPartArgs pa;
+    memset(&pa, 0, sizeof pa);
+    pa.keys = tb.dev_at<DevChunkCol>(o_k);
+    pa.values = tb.dev_at<DevChunkCol>(o_v);
+    pa.chunk_tile_start = tb.dev_at<int64_t>(o_ts);
+    pa.chunk_len = tb.dev_at<int64_t>(o_len);
+    pa.nchunks = nchunks;
+    pa.ntiles = ntiles;
+    if (nchunks == 1) { pa.key0 = in.dev[0]; if (values) pa.val0 = in.dev[1]; pa.len0 = clen[0]; }
+    pa.key_dtype = kdt;
+    pa.value_dtype = vdt;
+    pa.hist = (int64_t*)hist0;
+    pa.recs = (uint64_t*)precs;
+    pa.special_sums = sp_sums;
+    pa.special_counts = sp_counts;
+    pa.special = sp_flag;
+    KernelTimer kt;
+    HIP_TRY(launch_gb_hist(pa, nb, ctx.stream));
+    HIP_TRY(launch_scan((const int64_t*)hist0, (int64_t*)hist1, (int64_t)P * nb, (int64_t*)hist1 + (int64_t)P * nb + 1, ctx.stream));
+    pa.hist = (int64_t*)hist1;
+    // skewed key distribution (one partition far above the average)?  Then equal keys are combined inside each
+    // super-tile before they are scattered, so a hot key does not serialise one block's LDS atomics.
+    unsigned int* d_skew = d_cursor + 1;
+    HIP_TRY(launch_gb_skew((const int64_t*)hist1, nb, d_skew, ctx.stream));
     RDF_TRY(pinned_reserve(pin_off + 64));
-    unsigned int pin[8];  // copied out: a later pinned_reserve may move the staging buffer
-    HIP_TRY(hipMemcpyAsync(ctx.pinned + pin_off, t.special, 32, hipMemcpyDeviceToHost, ctx.stream));
+    HIP_TRY(hipMemcpyAsync(ctx.pinned + pin_off, d_skew, 4, hipMemcpyDeviceToHost, ctx.stream));
     HIP_TRY(hipStreamSynchronize(ctx.stream));
-    memcpy(pin, ctx.pinned + pin_off, 32);
-    const int64_t ngroups = (int64_t)pin[2] + (pin[0] ? 1 : 0) + (pin[1] ? 1 : 0);
-    if ((pin[4] & 4u) || (int64_t)pin[2] > max_groups) return fail(RDF_MEMORY_ERROR, "groupby: more than max_groups (%lld) distinct keys", (long long)max_groups);
-    pin_off += 256;
+    unsigned int skew = 0;
+    memcpy(&skew, ctx.pinned + pin_off, 4);
+    if (ctx.opt_gb_debug == 3) skew = 1;   // tests: force the combining variant
+    void* pemit = nullptr;
+    if (skew) { RDF_TRY(arena_alloc((size_t)((int64_t)P * nb + 1) * 8, &pemit)); pa.emitted = (int64_t*)pemit; }
+    HIP_TRY(launch_gb_scatter(pa, nb, skew != 0, ctx.stream));
+    GbAggArgs ga;
+    memset(&ga, 0, sizeof ga);
+    ga.recs = (const uint64_t*)precs;
+    ga.scan = (const int64_t*)hist1;
+    ga.nblocks = nb;
+    ga.emitted = (const int64_t*)pemit;
+    ga.is_f64 = sdt == RDF_F64;
+    ga.has_values = values != nullptr;
+    ga.key_dtype = kdt;
+    char* tmp = (char*)ptmp;
+    ga.out_keys = tmp;
+    ga.out_sums = tmp + (size_t)cap_out * 8;
+    ga.out_counts = (int64_t*)(tmp + (size_t)cap_out * 16);
+    ga.cursor = d_cursor;
+    ga.flags = d_flags2;
+    ga.max_out = max_groups;
+    HIP_TRY(launch_gb_aggregate(ga, ctx.stream));
+    kt.stop();
+    ctx.last_kernel = skew ? "gb_aggregate_kernel(combined)" : "gb_aggregate_kernel";
 
-    // outputs
+    // read back {special sums, counts, flags, cursor}, append the two special groups (the key whose hash is the LDS free marker;
+    // the NULL key) and copy the dense results to the caller
+    RDF_TRY(pinned_reserve(pin_off + 256));
+    HIP_TRY(hipMemcpyAsync(ctx.pinned + pin_off, pspec, 128, hipMemcpyDeviceToHost, ctx.stream));
+    HIP_TRY(hipStreamSynchronize(ctx.stream));
+    unsigned long long hs[4];
+    unsigned int hf[8];
+    memcpy(hs, ctx.pinned + pin_off, 32);
+    memcpy(hf, ctx.pinned + pin_off + 32, 32);
+    const int64_t ng_main = hf[2];
+    if ((hf[4] & 4u) || ng_main > max_groups) return fail(RDF_MEMORY_ERROR, "groupby: more than max_groups (%lld) distinct keys", (long long)max_groups);
+    // append the two special groups on the host side of the copy
     const size_t kes = (size_t)dtype_size(kdt);
-    Region outr;
-    int ik = -1, ikv = -1, is = -1, ic = -1;
-    GroupEmitArgs ea;
-    memset(&ea, 0, sizeof ea);
-    ea.t = t;
-    ea.cursor = cursor;
-    ea.key_dtype = kdt;
-    if (mem == RDF_MEM_HOST) {
-        ik = outr.add(out_keys->values, (size_t)ngroups * kes);
-        if (out_keys->validity) ikv = outr.add(out_keys->validity, (size_t)((ngroups + 7) / 8));
-        is = outr.add(out_sums->values, (size_t)ngroups * 8);
-        ic = outr.add(out_counts->values, (size_t)ngroups * 8);
-        RDF_TRY(outr.layout());
-        ea.out_keys = outr.ptr(ik);
-        ea.out_keys_validity = ikv >= 0 ? (uint8_t*)outr.ptr(ikv) : nullptr;
-        ea.out_sums = outr.ptr(is);
-        ea.out_counts = (int64_t*)outr.ptr(ic);
-    } else {
-        ea.out_keys = out_keys->values;
-        ea.out_keys_validity = out_keys->validity;
-        ea.out_sums = out_sums->values;
-        ea.out_counts = (int64_t*)out_counts->values;
+    int64_t ng = ng_main;
+    int64_t null_idx = -1;
+    auto put = [&](uint64_t key, unsigned long long sum, unsigned long long cnt) -> rdf_status {
+        HIP_TRY(hipMemcpyAsync((char*)ga.out_keys + (size_t)ng * kes, &key, kes, hipMemcpyHostToDevice, ctx.stream));
+        HIP_TRY(hipMemcpyAsync((char*)ga.out_sums + (size_t)ng * 8, &sum, 8, hipMemcpyHostToDevice, ctx.stream));
+        HIP_TRY(hipMemcpyAsync((char*)ga.out_counts + (size_t)ng * 8, &cnt, 8, hipMemcpyHostToDevice, ctx.stream));
+        HIP_TRY(hipStreamSynchronize(ctx.stream));
+        ++ng;
+        return RDF_OK;
+    };
+    if (hf[0]) {  // the key whose hash equals the LDS free marker: unmix on the host
+        uint64_t z = ~0ull;
+        z ^= z >> 32; z *= 0xF1DE83E19937733Dull; z ^= z >> 32;   // inverse of gb_hash
+        RDF_TRY(put(z, hs[0], hs[2]));
     }
-    if (ea.out_keys_validity) HIP_TRY(hipMemsetAsync(ea.out_keys_validity, 0, (size_t)((ngroups + 63) / 64 * 8), ctx.stream));
-    if (ngroups > 0) HIP_TRY(launch_groupby_emit(ea, ctx.stream));
-    if (mem == RDF_MEM_HOST) {
-        RDF_TRY(pinned_reserve(pin_off + outr.small_bytes + 256));
-        RDF_TRY(outr.download(pin_off));
-    } else HIP_TRY(hipStreamSynchronize(ctx.stream));
-    out_keys->length = out_sums->length = out_counts->length = ngroups;
-    out_keys->null_count = pin[1] ? 1 : 0;
+    if (hf[1]) { null_idx = ng; RDF_TRY(put(0, hs[1], hs[3])); }
+    if (ng > out_keys->capacity || ng > out_sums->capacity || ng > out_counts->capacity)
+        return fail(RDF_MEMORY_ERROR, "groupby: more than max_groups (%lld) distinct keys", (long long)max_groups);
+    const hipMemcpyKind kind = mem == RDF_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (ng > 0) {
+        HIP_TRY(hipMemcpyAsync(out_keys->values, ga.out_keys, (size_t)ng * kes, kind, ctx.stream));
+        HIP_TRY(hipMemcpyAsync(out_sums->values, ga.out_sums, (size_t)ng * 8, kind, ctx.stream));
+        HIP_TRY(hipMemcpyAsync(out_counts->values, ga.out_counts, (size_t)ng * 8, kind, ctx.stream));
+    }
+    rdf_out* outs3[3] = {out_keys, out_sums, out_counts};
+    for (rdf_out* o : outs3)
+        if (o->validity && ng > 0) {
+            if (mem == RDF_MEM_HOST) memset(o->validity, 0xFF, (size_t)((ng + 7) / 8));
+            else HIP_TRY(hipMemsetAsync(o->validity, 0xFF, (size_t)((ng + 7) / 8), ctx.stream));
+        }
+    if (null_idx >= 0) {
+        const uint8_t byte = (uint8_t)~(1u << (null_idx & 7));
+        if (mem == RDF_MEM_HOST) out_keys->validity[null_idx >> 3] &= byte;
+        else HIP_TRY(hipMemcpyAsync(out_keys->validity + (null_idx >> 3), &byte, 1, hipMemcpyHostToDevice, ctx.stream));
+    }
+    HIP_TRY(hipStreamSynchronize(ctx.stream));
+    out_keys->length = out_sums->length = out_counts->length = ng;
+    out_keys->null_count = null_idx >= 0 ? 1 : 0;
     out_sums->null_count = out_counts->null_count = 0;
-    if (out_sums->validity && ngroups > 0) {
-        if (mem == RDF_MEM_HOST) memset(out_sums->validity, 0xFF, (size_t)((ngroups + 7) / 8));
-        else HIP_TRY(hipMemsetAsync(out_sums->validity, 0xFF, (size_t)((ngroups + 7) / 8), ctx.stream));
-    }
-    if (out_counts->validity && ngroups > 0) {
-        if (mem == RDF_MEM_HOST) memset(out_counts->validity, 0xFF, (size_t)((ngroups + 7) / 8));
-        else HIP_TRY(hipMemsetAsync(out_counts->validity, 0xFF, (size_t)((ngroups + 7) / 8), ctx.stream));
-    }
-    if (mem == RDF_MEM_DEVICE) HIP_TRY(hipStreamSynchronize(ctx.stream));
     return RDF_OK;
 }
 }  // namespace
@@ -4433,8 +4251,8 @@ rdf_status rdf_set_option(const char* name, int64_t value) {
     if (strcmp(name, "spec") == 0) g_ctx.opt_spec = value != 0;
     else if (strcmp(name, "fast_filter") == 0) g_ctx.opt_fast_filter = value != 0;
     else if (strcmp(name, "vec_bitmap") == 0) g_ctx.opt_vec_bitmap = value != 0;
-    else if (strcmp(name, "gb_partition") == 0) g_ctx.opt_gb_partition = (int)value;
-    else if (strcmp(name, "gb_debug") == 0) g_ctx.opt_gb_debug = (int)value;
+    else if (strcmp(name, "gb_partition") == 0) g_ctx.opt_gb_partition = value == 2 ? 3 : (int)value;   // (2 named the retired radix-sort partitioning: accepted, the planner decides as under 3)
+    else if (strcmp(name, "gb_debug") == 0) g_ctx.opt_gb_debug = value == 3 ? 3 : 0;   // (every other value named a retired ablation of the kernels: accepted and ignored)
     else if (strcmp(name, "filter_tile") == 0) g_ctx.opt_filter_tile = (int)value;
     else if (strcmp(name, "filter_one") == 0) g_ctx.opt_filter_one = value != 0;
     else if (strcmp(name, "take_rows") == 0) g_ctx.opt_take_rows = (int)value;

@@ -235,9 +235,8 @@ rdf_status gb_engine(const GbInput& in, int op, int64_t max_groups, int force_pa
     a.special_counts = sc.counts();
     a.special = sc.special();
     a.flags = sc.flags();
-    a.ablate = ctx.opt_gb_debug >= 20 ? ctx.opt_gb_debug : 0;
     {   // the fast loader: 8-byte integer keys and 8-byte (or no) values, no bitmap, every chunk 16-byte aligned
-        bool fast = (in.kdt == RDF_I64 || in.kdt == RDF_U64) && (in.vdt < 0 || in.vdt == RDF_F64 || in.vdt == RDF_I64 || in.vdt == RDF_U64) && ctx.opt_gb_debug != 19;
+        bool fast = (in.kdt == RDF_I64 || in.kdt == RDF_U64) && (in.vdt < 0 || in.vdt == RDF_F64 || in.vdt == RDF_I64 || in.vdt == RDF_U64);
         if (framed) fast = fast && in.f_fast;
         for (int64_t c = 0; c < nchunks && fast && !framed; ++c) {
             if (in.clen[(size_t)c] == 0) continue;
@@ -617,8 +616,10 @@ rdf_status gb_engine(const GbInput& in, int op, int64_t max_groups, int force_pa
     return gb_finish_values(sc, d, op, vcls, pin_off);
 }
 
-rdf_status legacy_groupby_sum(const rdf_array* keys, const rdf_array* values, int64_t nchunks, int64_t max_groups,
-                              rdf_out* out_keys, rdf_out* out_sums, rdf_out* out_counts);
+// the first-generation histogram / combining scatter / aggregate path (rdf_capi.cpp): sums and counts of one integer key column
+bool gb_fallback_in_range(int64_t max_groups, int64_t nrows);
+rdf_status groupby_sum_fallback(const rdf_array* keys, const rdf_array* values, int64_t nchunks, int64_t max_groups,
+                                rdf_out* out_keys, rdf_out* out_sums, rdf_out* out_counts);
 
 }  // namespace
 
@@ -833,8 +834,9 @@ rdf_status rdf_groupby_agg(const rdf_array* keys, int32_t nkeys, const rdf_array
         if (skewed && lds_full) continue;                   // too many groups landed in one partition: the HBM table takes any distribution
         if (skewed) {
             // heavily skewed keys overflowed a scatter region: sums of a single key column take the first-generation
-            // histogram + combining path (built for exactly this), everything else the HBM table
-            if (op == AGG_SUM && nkeys == 1 && ctx.opt_gb_partition != 4) return legacy_groupby_sum(keys, values, nchunks, max_groups, out_keys, out_values, out_counts);
+            // histogram + combining path (built for exactly this) where its tables hold max_groups, everything else the HBM table
+            if (op == AGG_SUM && nkeys == 1 && ctx.opt_gb_partition != 4 && gb_fallback_in_range(max_groups, nrows))
+                return groupby_sum_fallback(keys, values, nchunks, max_groups, out_keys, out_values, out_counts);
             continue;
         }
         const int64_t ng = d.ng;
@@ -898,8 +900,11 @@ rdf_status rdf_groupby_agg(const rdf_array* keys, int32_t nkeys, const rdf_array
 
 rdf_status rdf_groupby_sum(const rdf_array* keys, const rdf_array* values, int64_t nchunks, int64_t max_groups,
                            rdf_out* out_keys, rdf_out* out_sums, rdf_out* out_counts) {
-    if (g_ctx.opt_gb_partition == 1 || g_ctx.opt_gb_partition == 2 || (g_ctx.opt_gb_debug && g_ctx.opt_gb_debug < 20))   // A/B: the first-generation paths
-        return legacy_groupby_sum(keys, values, nchunks, max_groups, out_keys, out_sums, out_counts);
+    if ((g_ctx.opt_gb_partition == 1 || g_ctx.opt_gb_debug == 3) && keys && nchunks >= 1) {   // A/B, tests: the first-generation fallback where its range holds
+        int64_t nrows = 0;
+        for (int64_t c = 0; c < nchunks; ++c) nrows += keys[c].length;
+        if (gb_fallback_in_range(max_groups, nrows)) return groupby_sum_fallback(keys, values, nchunks, max_groups, out_keys, out_sums, out_counts);
+    }
     return rdf_groupby_agg(keys, 1, values, nchunks, values ? RDF_AGG_SUM : RDF_AGG_COUNT, max_groups, out_keys, out_sums, out_counts);
 }
 

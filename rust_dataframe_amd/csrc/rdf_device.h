@@ -256,9 +256,7 @@ hipError_t launch_fcount(const FilterWArgs& a, int tile_rows, int64_t* tile_coun
 hipError_t launch_fcompact(const FilterWArgs& a, int tile_rows, hipStream_t s);
 hipError_t launch_mask_count_one(const DevChunkCol& mask, int64_t clen, int64_t ntiles, int64_t* tile_counts, hipStream_t s);
 
-// Stable LSD radix sort of (key, row index) pairs, 8 bits per pass (DataFrame::sort -> lexsort_to_indices).
-constexpr int kSortItems = 8;                       // items per thread per tile
-constexpr int kSortTile = kBlock * kSortItems;      // 2048 items per tile
+// Order-preserving 64-bit keys of a sort column (DataFrame::sort -> lexsort_to_indices); the radix passes are rdf_sort.hip's.
 struct SortKeyArgs {                                 // key[i] = order-preserving transform of column[idx[i]]
     const DevChunkCol* chunks;                       // [nchunks]
     const int64_t*     chunk_row_start;              // [nchunks + 1]
@@ -272,16 +270,6 @@ struct SortKeyArgs {                                 // key[i] = order-preservin
     int32_t            canon_float;                  // window keys: -0.0 takes +0.0's key and every NaN the quiet NaN's (after +inf); 0 = IEEE total order
     uint64_t           hash_mul;                     // != 0 (the join's hash-ordered build side): keys[i] = key bits * hash_mul, bit_stats over THOSE,
     uint64_t*          raw_stats;                    //   and [min, max] of the key bits themselves here
-};
-struct SortPassArgs {
-    const uint64_t* keys_in;  const uint32_t* idx_in;   // idx_in nullptr = identity (first pass)
-    uint64_t*       keys_out; uint32_t*       idx_out;
-    const uint64_t* pay_in;   uint64_t*       pay_out;  // 64-bit payload variant (group-by partitioning); idx_* unused then
-    const uint8_t*  nullflags;                       // digit source of the nulls-last pass (indexed by row), else nullptr
-    int64_t*        hist;                            // [256 * sort_grid] digit-major per-block counts, then their exclusive scan
-    int64_t         n, ntiles;
-    int32_t         shift;                           // bit offset of this pass's digit in (key - bias)
-    uint64_t        bias;                            // smallest key of the column: digits are taken from key - bias, so a narrow key RANGE needs few passes
 };
 
 // Second-generation radix passes (rdf_sort.hip): all digit histograms in one read, then one read + one write per digit with
@@ -390,36 +378,9 @@ struct JoinAppendArgs {        // FULL: build rows nobody matched (and NULL-key 
     int32_t         count_only;
 };
 
-// Partitioned GROUP BY (high cardinality): keys are replaced by an invertible 64-bit mix, the (hashed key, value)
-// pairs are radix-partitioned on the top hash bits with the sort kernels, and every partition is aggregated
-// in an LDS table and emitted directly.
-struct GroupPrepArgs {
-    const DevChunkCol* keys;             // [nchunks]
-    const DevChunkCol* values;           // [nchunks]
-    const int64_t*     chunk_tile_start; // [nchunks + 1], tiles of kEvalTile rows
-    const int64_t*     chunk_len;
-    const int64_t*     chunk_row_start;  // [nchunks + 1]
-    int64_t            nchunks, ntiles;
-    int32_t            key_dtype, value_dtype;
-    uint64_t*          hkeys;            // [n] out: mix64(key)
-    uint64_t*          vals;             // [n] out: value bits (f64 bits / wrapping i64), 0 when there is no value column
-    unsigned long long* special_sums;    // [2]: rows whose hashed key equals the LDS free marker / rows with a NULL key
-    unsigned long long* special_counts;  // [2]
-    unsigned int*      special;          // [2] group exists
-};
-struct GroupAggArgs {
-    const uint64_t* hkeys; const uint64_t* vals;
-    int64_t         n;
-    int32_t         part_bits;           // partitions = 2^part_bits, partition id = hkey >> (64 - part_bits)
-    int32_t         is_f64, has_values, key_dtype;
-    void*           out_keys; void* out_sums; int64_t* out_counts;
-    unsigned int*   cursor;              // output cursor
-    uint32_t*       flags;               // bit 2: an LDS table overflowed (max_groups was too small for the data)
-    int64_t         max_out;
-};
-
-// Single-pass partitioned GROUP BY (the default for 1024 < max_groups <= kGbMaxGroups): rows are scattered ONCE on the
-// top kGbPartBits bits of mix64(key) as 16-byte (hashed key, value bits) records — per-block LDS staging turns the
+// First-generation partitioned GROUP BY, kept as the fallback of rdf_groupby.hip's engine for heavily skewed sums / counts of one
+// integer key column (1024 < max_groups <= kGbMaxGroups; groupby_sum_fallback, rdf_capi.cpp): rows are scattered ONCE on the
+// top kGbPartBits bits of the hashed key as 16-byte (hashed key, value bits) records — per-block LDS staging turns the
 // scatter into runs of consecutive records — and every partition is aggregated in an LDS table.
 // HBM traffic: 8 (histogram) + 16 + 16 (scatter) + 16 (aggregate) = 56 B/row.
 constexpr int kGbBlock = 512;                       // threads per block of the three kernels
@@ -437,7 +398,6 @@ struct GbPartArgs {
     DevChunkCol        key0, val0;       // nchunks == 1: the chunk's descriptors inline (kernel arguments = scalar registers)
     int64_t            len0;
     int32_t            key_dtype, value_dtype;
-    int32_t            ablate_stores, pad;   // bench ablation (rdf_set_option("gb_debug", 2)): run the scatter without its global stores
     int64_t*           hist;             // histogram kernel: out counts [digit * gridDim.x + block]; scatter: their exclusive scan
     uint64_t*          recs;             // scatter out: [2 * rows] records, see rdf_kernels.hip
     int64_t*           emitted;          // combining scatter variant out: [digit * gridDim.x + block] records really written
@@ -451,7 +411,6 @@ struct GbAggArgs {
     const int64_t*  emitted;             // combined (skewed) inputs: real record count of every (partition, block) range, else nullptr
     int64_t         nblocks;             // blocks of the histogram / scatter kernels
     int32_t         is_f64, has_values, key_dtype;
-    int32_t         ablate_lds;          // bench ablation (rdf_set_option("gb_debug", 1)): stream the records without the LDS table work
     void*           out_keys; void* out_sums; int64_t* out_counts;
     unsigned int*   cursor;
     uint32_t*       flags;               // bit 2: an LDS table overflowed / more than max_out groups
@@ -469,16 +428,6 @@ struct GroupTable {
     int64_t             capacity;  // power of two
 };
 constexpr unsigned long long kGroupEmpty = 0x8000000000000000ull;  // i64::MIN doubles as the free marker
-struct GroupByArgs {
-    const DevChunkCol* keys;             // [nchunks]
-    const DevChunkCol* values;           // [nchunks] (values pointer null = count rows only)
-    const int64_t*     chunk_tile_start; // [nchunks + 1], tiles of kEvalTile rows
-    const int64_t*     chunk_len;
-    int64_t            nchunks, ntiles;
-    int32_t            key_dtype, value_dtype;  // value_dtype < 0: no values
-    GroupTable         t;
-    int64_t            max_groups;
-};
 struct GroupEmitArgs {
     GroupTable t;
     void*      out_keys;  uint8_t* out_keys_validity;
@@ -530,8 +479,7 @@ struct Gb2Args {
     // stream kernel: the global table the block tables are merged into
     GroupTable         t;
     int32_t            replicas, sub_slots;   // LDS table = replicas sub-tables of sub_slots slots (lane % replicas picks one)
-    int32_t            table_slots, pad2;     // slots of the block's LDS table (20 B each)
-    int32_t            ablate, fast;          // fast: 8-byte keys / values, no bitmaps, 16-byte aligned chunks (host-checked); bench ablations of the scatter (rdf_set_option("gb_debug", 21..24)): results invalid
+    int32_t            table_slots, fast;     // slots of the block's LDS table (20 B each); fast: 8-byte keys / values, no bitmaps, 16-byte aligned chunks (host-checked)
     // skewed keys (capacity plan from the skew probe's histogram): partition p's regions start at line part_off[p] and hold
     // part_cap[p] lines each (region (p, b) = part_off[p] + b * part_cap[p]); nullptr: every region holds cap_lines lines
     const uint32_t*    part_off;
@@ -688,7 +636,6 @@ hipError_t launch_idx_locality(const DevChunkCol& indices, int64_t n, bool idx64
 hipError_t launch_frame_totals(const int64_t* tile_scan, const int64_t* chunk_tile_start, int64_t nchunks, int64_t* out_len, int64_t* padded, hipStream_t s);
 hipError_t launch_frame_tables(const FrameTabArgs& a, hipStream_t s);
 hipError_t launch_frame_mask_tables(const int64_t* pos, int64_t nchunks, uint8_t* values, uint8_t* validity, DevOutChunk* outs, DevChunkCol* cols, hipStream_t s);
-hipError_t launch_frame_pad(const int64_t* len, int64_t n, int64_t* padded, hipStream_t s);
 hipError_t launch_frame_mask_count(const uint64_t* mask, const int64_t* pos, const int64_t* chunk_tile_start, const int64_t* chunk_len, int64_t nchunks,
                                    int64_t ntiles, int tile_rows, uint64_t tile_inv, int64_t* counts, hipStream_t s);
 hipError_t launch_take_cols(const TakeColsArgs& a, hipStream_t s);
@@ -753,7 +700,6 @@ hipError_t launch_scan(const int64_t* counts, int64_t* scan, int64_t n, int64_t*
 int64_t scan_scratch_words(int64_t n);
 hipError_t launch_compact(const FilterArgs& a, int tile_rows, hipStream_t s);
 hipError_t launch_take(const TakeArgs& a, hipStream_t s);
-int  sort_grid(int64_t ntiles);
 hipError_t launch_sort_keys(const SortKeyArgs& a, hipStream_t s);
 hipError_t launch_join_buckets(const JoinBucketArgs& a, hipStream_t s);
 hipError_t launch_copy_small(const void* src_pinned, void* dst_dev, size_t bytes, hipStream_t s);   // src: page-locked, device-mapped host memory
@@ -766,16 +712,10 @@ hipError_t launch_join_count(const JoinProbeArgs& a, hipStream_t s);
 hipError_t launch_join_write(const JoinProbeArgs& a, hipStream_t s);
 hipError_t launch_join_append(const JoinAppendArgs& a, hipStream_t s);
 hipError_t launch_count_bytes(const uint8_t* p, int64_t n, unsigned long long* out, hipStream_t s);
-hipError_t launch_sort_hist64(const SortPassArgs& a, hipStream_t s);
-hipError_t launch_sort_scatter64(const SortPassArgs& a, hipStream_t s);
 hipError_t launch_gb_hist(const GbPartArgs& a, int grid, hipStream_t s);
 hipError_t launch_gb_skew(const int64_t* scan, int64_t nblocks, unsigned int* flag, hipStream_t s);
 hipError_t launch_gb_scatter(const GbPartArgs& a, int grid, bool dedup, hipStream_t s);
 hipError_t launch_gb_aggregate(const GbAggArgs& a, hipStream_t s);
-hipError_t launch_groupby_prepare(const GroupPrepArgs& a, hipStream_t s);
-hipError_t launch_groupby_partitions(const GroupAggArgs& a, hipStream_t s);
-hipError_t launch_groupby_build(const GroupByArgs& a, hipStream_t s);
-hipError_t launch_groupby_emit(const GroupEmitArgs& a, hipStream_t s);
 hipError_t launch_fill_f64(double* p, int64_t n, uint64_t seed, uint64_t col, int64_t first_row, double lo, double hi, hipStream_t s);
 hipError_t launch_fill_i64(int64_t* p, int64_t n, uint64_t seed, uint64_t col, int64_t first_row, int64_t lo, int64_t hi, hipStream_t s);
 hipError_t launch_fill_validity(uint8_t* p, int64_t nbits, uint64_t seed, uint64_t col, int64_t first_row, double null_fraction, hipStream_t s);

@@ -82,11 +82,6 @@ hipError_t launch_frame_mask_count(const uint64_t* mask, const int64_t* pos, con
     return hipGetLastError();
 }
 
-// padded[c] = round_up(len[c], 64)
-__global__ __launch_bounds__(kBlock) void frame_pad_kernel(const int64_t* __restrict__ len, int64_t n, int64_t* __restrict__ padded) {
-    for (int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x; c < n; c += (int64_t)gridDim.x * kBlock) padded[c] = (len[c] + 63) & ~(int64_t)63;
-}
-
 // ------------------------------------------------------------------------------------------------
 // take over every column of a frame at once.  A wave owns kTakeU x 64 consecutive output rows per iteration: their indices
 // come in with kTakeU coalesced loads, each lane resolves its kTakeU rows to (chunk, element) ONCE, and then the
@@ -399,12 +394,6 @@ hipError_t launch_frame_mask_tables(const int64_t* pos, int64_t nchunks, uint8_t
     if (nchunks <= 0) return hipSuccess;
     const int64_t grid = std::min<int64_t>((nchunks + kBlock - 1) / kBlock, eval_grid_limit());
     hipLaunchKernelGGL(frame_mask_tables_kernel, dim3((unsigned)grid), dim3(kBlock), 0, s, pos, nchunks, values, validity, outs, cols);
-    return hipGetLastError();
-}
-hipError_t launch_frame_pad(const int64_t* len, int64_t n, int64_t* padded, hipStream_t s) {
-    if (n <= 0) return hipSuccess;
-    const int64_t grid = std::min<int64_t>((n + kBlock - 1) / kBlock, eval_grid_limit());
-    hipLaunchKernelGGL(frame_pad_kernel, dim3((unsigned)grid), dim3(kBlock), 0, s, len, n, padded);
     return hipGetLastError();
 }
 template <int U>

@@ -709,7 +709,6 @@ __global__ __launch_bounds__(kG2Block, 2 * kG2BlocksPerCU) void gb2_scatter_kern
     for (; st < a.ntiles; st += stride) {
         const bool more = st + stride < a.ntiles;
         if (more) g2_load<kG2Rows, kG2Block, FAST>(a, st + stride, tid, raw);   // the next tile's loads fly during the LDS phases
-        if (a.ablate == 24) { uint64_t x = 0; for (int j = 0; j < kG2Rows; ++j) x ^= rows.hk[j] ^ rows.val[j]; if (x == 0x1234567) a.special[0] = 1; if (more) g2_prepare<kG2Rows, FAST, COMPACT>(a, raw, rows, LdsSpecial{nullptr, nullptr, nullptr}, hot_lds); continue; }   // loads + hash only
         if (COMPACT && rows.bad) { err |= 64u; atomicOr(a.flags, 64u); }   // a key outside the 32-bit window: every block stops at its next tile
         // (B) rank inside the partition
         uint32_t rank[kG2Rows];
@@ -760,7 +759,7 @@ __global__ __launch_bounds__(kG2Block, 2 * kG2BlocksPerCU) void gb2_scatter_kern
         // (D) stage the tile's records grouped by partition
 #pragma unroll
         for (int j = 0; j < kG2Rows; ++j)
-            if (((rows.live >> j) & 1) && a.ablate != 23) {
+            if ((rows.live >> j) & 1) {
                 const uint32_t d = (uint32_t)(rows.hk[j] >> (64 - kG2PartBits));
                 const uint32_t at = lstart[d] + rank[j], ci = at & 0x7FFFFFFFu;
                 const bool to_carry = at >> 31;
@@ -784,7 +783,7 @@ __global__ __launch_bounds__(kG2Block, 2 * kG2BlocksPerCU) void gb2_scatter_kern
         // new one), so the compact layout — half as many lines per pass of the block — takes two lines per lane group and
         // iteration, every LDS read of both before the first store.  (The 16-byte layout spills registers when it does that:
         // measured 10.1 against 9.6 ms per 1e9 rows.)
-        const uint32_t nl = (a.ablate == 22 || a.ablate == 23) ? 0u : ltot;
+        const uint32_t nl = ltot;
         struct Line { uint64_t v, nv; uint32_t kw, nkw, dst, slot; u64x2 rec, nrec; bool live, carry_w; };
         const uint32_t l8 = (uint32_t)tid & (L - 1);
         auto line_load = [&](uint32_t i, Line& ln) {
@@ -810,13 +809,10 @@ __global__ __launch_bounds__(kG2Block, 2 * kG2BlocksPerCU) void gb2_scatter_kern
         auto line_store = [&](const Line& ln) {
             if (!ln.live) return;
             if constexpr (COMPACT) {
-                if (ln.dst != 0xFFFFFFFFu) {
-                    if (a.ablate != 21) { recs_k[(uint64_t)ln.dst * L + l8] = ln.kw; if (has_values) recs_v[(uint64_t)ln.dst * L + l8] = ln.v; }
-                    else if (ln.kw == 0x1234567u && ln.v == 1) a.special[0] = 1;
-                }
+                if (ln.dst != 0xFFFFFFFFu) { recs_k[(uint64_t)ln.dst * L + l8] = ln.kw; if (has_values) recs_v[(uint64_t)ln.dst * L + l8] = ln.v; }
                 if (ln.carry_w) { carry_k[ln.slot] = ln.nkw; if (has_values) carry_v[ln.slot] = ln.nv; }
             } else {
-                if (ln.dst != 0xFFFFFFFFu) { if (a.ablate != 21) recs[(uint64_t)ln.dst * kG2Line + l8] = ln.rec; else if (ln.rec[0] == 0x1234567) a.special[0] = 1; }
+                if (ln.dst != 0xFFFFFFFFu) recs[(uint64_t)ln.dst * kG2Line + l8] = ln.rec;
                 if (ln.carry_w) carry[ln.slot] = ln.nrec;
             }
         };

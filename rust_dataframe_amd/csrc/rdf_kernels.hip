@@ -472,11 +472,6 @@ __global__ __launch_bounds__(kBlock) void take_kernel(const TakeArgs a) {
 // ------------------------------------------------------------------------------------------------
 // sort to indices (DataFrame::sort -> arrow::compute::lexsort_to_indices, src/dataframe.rs:194-214): the
 // order-preserving keys of a column are made here (sort_keys_kernel); the sort's digit passes are in rdf_sort.hip.
-// What remains here is the stable histogram -> scan -> scatter pass over (key, 64-bit payload) pairs that the GROUP BY's
-// radix partitioning runs.  Per 8-bit pass: per-block digit histograms (digit-major),
-// one exclusive scan, then a stable scatter whose in-tile ranks come from wave ballots (the lanes that
-// share my digit = AND over the 8 digit bits of the ballot or its complement) + an LDS prefix over the
-// (row-of-items, wave) groups.
 
 __device__ __forceinline__ uint64_t sort_key_bits(const DevChunkCol& cc, int dt, int64_t e) {
     switch (dt) {
@@ -547,110 +542,6 @@ __global__ __launch_bounds__(kBlock) void sort_keys_kernel(const SortKeyArgs a, 
             rmin = x < rmin ? x : rmin; rmax = y > rmax ? y : rmax;
         }
         if ((threadIdx.x & 63) == 0 && rmin <= rmax) { atomicMin((unsigned long long*)&a.raw_stats[0], (unsigned long long)rmin); atomicMax((unsigned long long*)&a.raw_stats[1], (unsigned long long)rmax); }
-    }
-}
-
-__device__ __forceinline__ int sort_digit(const SortPassArgs& a, int64_t i) {
-    if (a.nullflags) return a.nullflags[a.idx_in ? (int64_t)a.idx_in[i] : i];
-    return (int)(((a.keys_in[i] - a.bias) >> a.shift) & 255);
-}
-
-// Block b owns the contiguous tiles [b*tpb, (b+1)*tpb): one histogram row per BLOCK (256 x gridDim entries
-// to scan, a few MB), and the scatter walks its tiles in order carrying the running digit offsets in LDS.
-__global__ __launch_bounds__(kBlock) void sort_hist_kernel(const SortPassArgs a) {
-    __shared__ unsigned int h[256];
-    h[threadIdx.x] = 0;
-    __syncthreads();
-    const int64_t tpb = (a.ntiles + gridDim.x - 1) / gridDim.x;
-    const int64_t t0 = (int64_t)blockIdx.x * tpb, t1 = t0 + tpb < a.ntiles ? t0 + tpb : a.ntiles;
-    for (int64_t tile = t0; tile < t1; ++tile) {
-        const int64_t base = tile * kSortTile;
-#pragma unroll
-        for (int j = 0; j < kSortItems; ++j) {
-            const int64_t i = base + j * kBlock + threadIdx.x;
-            if (i < a.n) atomicAdd(&h[sort_digit(a, i)], 1u);
-        }
-    }
-    __syncthreads();
-    a.hist[(int64_t)threadIdx.x * gridDim.x + blockIdx.x] = h[threadIdx.x];
-}
-
-__global__ __launch_bounds__(kBlock) void sort_scatter_kernel(const SortPassArgs a) {
-    __shared__ unsigned short grp[kSortItems * (kBlock / 64)][256];  // count of each digit per (row-of-items, wave) group
-    __shared__ unsigned short dbase[256];                            // tile-local exclusive prefix of the digit totals
-    __shared__ uint64_t lkeys[kSortTile];                            // the tile, locally sorted by digit (stable)
-    __shared__ uint64_t lidx[kSortTile];
-    __shared__ int64_t gbase[256];                                   // running global offset of each digit for this block
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    gbase[threadIdx.x] = a.hist[(int64_t)threadIdx.x * gridDim.x + blockIdx.x];
-    const int64_t tpb = (a.ntiles + gridDim.x - 1) / gridDim.x;
-    const int64_t t0 = (int64_t)blockIdx.x * tpb, t1 = t0 + tpb < a.ntiles ? t0 + tpb : a.ntiles;
-    for (int64_t tile = t0; tile < t1; ++tile) {
-        for (int i = threadIdx.x; i < kSortItems * (kBlock / 64) * 256; i += kBlock) (&grp[0][0])[i] = 0;
-        __syncthreads();
-        const int64_t base = tile * kSortTile;
-        const int count = (int)((a.n - base) < (int64_t)kSortTile ? (a.n - base) : (int64_t)kSortTile);
-        int digit[kSortItems], rank[kSortItems];
-        uint64_t key[kSortItems];
-        uint64_t idx[kSortItems];
-#pragma unroll
-        for (int j = 0; j < kSortItems; ++j) {
-            const int64_t i = base + j * kBlock + threadIdx.x;
-            const bool in = i < a.n;
-            key[j] = in ? a.keys_in[i] : 0;
-            idx[j] = in ? a.pay_in[i] : 0;
-            const int d = in ? (int)(((key[j] - a.bias) >> a.shift) & 255) : 0;
-            digit[j] = d;
-            uint64_t peers = __ballot(in);
-#pragma unroll
-            for (int b = 0; b < 8; ++b) {
-                const uint64_t m = __ballot((d >> b) & 1);
-                peers &= ((d >> b) & 1) ? m : ~m;
-            }
-            rank[j] = __popcll(peers & ((1ull << lane) - 1));
-            if (in && rank[j] == 0) grp[j * (kBlock / 64) + wave][d] = (unsigned short)__popcll(peers);  // the group's first holder of d
-        }
-        __syncthreads();
-        unsigned int total_d;
-        {   // thread d: exclusive prefix of digit d's counts over the groups, in item order
-            unsigned int run = 0;
-#pragma unroll
-            for (int g = 0; g < kSortItems * (kBlock / 64); ++g) { const unsigned int c = grp[g][threadIdx.x]; grp[g][threadIdx.x] = (unsigned short)run; run += c; }
-            total_d = run;
-        }
-        // exclusive scan of the 256 digit totals (wave scan + 4 wave sums)
-        unsigned int inc = total_d;
-#pragma unroll
-        for (int dd = 1; dd < 64; dd <<= 1) { const unsigned int o = __shfl_up(inc, dd); if (lane >= dd) inc += o; }
-        __shared__ unsigned int wsum[kBlock / 64];
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        unsigned int wb = 0;
-        for (int w = 0; w < wave; ++w) wb += wsum[w];
-        dbase[threadIdx.x] = (unsigned short)(wb + inc - total_d);
-        __syncthreads();
-        // local stable sort by digit into LDS
-#pragma unroll
-        for (int j = 0; j < kSortItems; ++j) {
-            const int64_t i = base + j * kBlock + threadIdx.x;
-            if (i < a.n) {
-                const int pos = dbase[digit[j]] + grp[j * (kBlock / 64) + wave][digit[j]] + rank[j];
-                lkeys[pos] = key[j];
-                lidx[pos] = idx[j];
-            }
-        }
-        __syncthreads();
-        // coalesced write-out: consecutive threads hold consecutive members of a digit run
-        for (int t = threadIdx.x; t < count; t += kBlock) {
-            const uint64_t kk = lkeys[t];
-            const int d = (int)(((kk - a.bias) >> a.shift) & 255);
-            const int64_t dst = gbase[d] + (t - dbase[d]);
-            a.keys_out[dst] = kk;
-            a.pay_out[dst] = lidx[t];
-        }
-        __syncthreads();
-        gbase[threadIdx.x] += total_d;  // the next tile of this block continues each digit's run
-        __syncthreads();
     }
 }
 
@@ -940,169 +831,8 @@ __global__ __launch_bounds__(kBlock) void count_bytes_kernel(const uint8_t* p, i
 // ------------------------------------------------------------------------------------------------
 // hash GROUP BY (Transformation::GroupAggregate, planned by Dataset::try_aggregate src/expression.rs:114-221,
 // never executed by the reference: src/evaluation.rs:73 panics).  SQL semantics: NULL keys form one
-// group, NULL values are skipped.  One global open-addressing table in HBM (it lives in L2/Infinity
-// Cache for the 1e6-group configuration), 64-bit CAS to claim a slot, hardware f64 / u64 atomic adds.
-
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-__device__ __forceinline__ int64_t load_key(const DevChunkCol& k, int dt, int64_t row) {
-    const int64_t e = k.offset + row;
-    switch (dt) {
-        case RDF_I32: return as_global<int32_t>(k.values)[e];
-        case RDF_U32: return (int64_t)as_global<uint32_t>(k.values)[e];
-        case RDF_I16: return as_global<int16_t>(k.values)[e];
-        case RDF_U16: return (int64_t)as_global<uint16_t>(k.values)[e];
-        case RDF_I8: return as_global<int8_t>(k.values)[e];
-        case RDF_U8: return (int64_t)as_global<uint8_t>(k.values)[e];
-        default: return as_global<int64_t>(k.values)[e];
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void groupby_build_kernel(const GroupByArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int wave = wave_id();
-    const uint64_t mask = (uint64_t)a.t.capacity - 1;
-    uint32_t err = 0;
-    for (int64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
-        const int64_t c = a.nchunks == 1 ? 0 : find_chunk_tile(a.chunk_tile_start, a.nchunks, tile);
-        const int64_t r0 = (tile - a.chunk_tile_start[c]) * kEvalTile;
-        const int64_t clen = a.chunk_len[c];
-        const DevChunkCol kc = a.keys[c];
-        const DevChunkCol vc = a.value_dtype >= 0 ? a.values[c] : DevChunkCol{nullptr, nullptr, 0};
-        const int64_t rw = r0 + (int64_t)wave * (kVPT * 64);
-        uint64_t kvw[kVPT], vvw[kVPT];
-        if (kc.validity) load_windows<kVPT>(kc.validity, kc.offset + rw, clen - rw, kvw);
-        if (vc.validity) load_windows<kVPT>(vc.validity, vc.offset + rw, clen - rw, vvw);
-#pragma unroll
-        for (int j = 0; j < kVPT; ++j) {
-            const int64_t row = rw + j * 64 + lane;
-            if (row >= clen) continue;
-            const bool kvalid = !kc.validity || ((kvw[j] >> lane) & 1);
-            const bool vvalid = a.value_dtype < 0 || !vc.validity || ((vvw[j] >> lane) & 1);
-            const uint64_t key = (uint64_t)load_key(kc, a.key_dtype, row);
-            int64_t slot;
-            if (!kvalid) { slot = a.t.capacity + 1; a.t.special[1] = 1; }
-            else if (key == kGroupEmpty) { slot = a.t.capacity; a.t.special[0] = 1; }
-            else {
-                uint64_t s = mix64(key) & mask;
-                int64_t probes = 0;
-                for (;;) {
-                    const unsigned long long old = atomicCAS(&a.t.keys[s], kGroupEmpty, (unsigned long long)key);
-                    if (old == kGroupEmpty) { atomicAdd(a.t.ngroups, 1u); break; }
-                    if (old == key) break;
-                    s = (s + 1) & mask;
-                    if (++probes > a.t.capacity) { err |= 4u; break; }
-                }
-                slot = (int64_t)s;
-            }
-            if (err) break;
-            if (vvalid) {
-                if (a.value_dtype == RDF_F64) unsafeAtomicAdd((double*)&a.t.sums[slot], ((const double*)vc.values)[vc.offset + row]);
-                else if (a.value_dtype == RDF_F32) unsafeAtomicAdd((double*)&a.t.sums[slot], (double)as_global<float>(vc.values)[vc.offset + row]);
-                else if (a.value_dtype >= 0) atomicAdd(&a.t.sums[slot], (unsigned long long)load_key(vc, a.value_dtype, row));
-                atomicAdd(&a.t.counts[slot], 1ull);
-            }
-        }
-    }
-    if (err) atomicOr(a.t.flags, err);
-}
-
-// Insert-or-find `key` in the global table and add (v, cnt) to its slot.  Returns false on overflow.
-__device__ __forceinline__ bool global_upsert(const GroupTable& t, uint64_t mask, uint64_t key, bool is_f64, uint64_t v, uint64_t cnt) {
-    uint64_t s = mix64(key) & mask;
-    int64_t probes = 0;
-    for (;;) {
-        const unsigned long long old = atomicCAS(&t.keys[s], kGroupEmpty, (unsigned long long)key);
-        if (old == kGroupEmpty) { atomicAdd(t.ngroups, 1u); break; }
-        if (old == key) break;
-        s = (s + 1) & mask;
-        if (++probes > t.capacity) return false;
-    }
-    if (cnt) {
-        if (is_f64) unsafeAtomicAdd((double*)&t.sums[s], u2d(v)); else atomicAdd(&t.sums[s], (unsigned long long)v);
-        atomicAdd(&t.counts[s], (unsigned long long)cnt);
-    }
-    return true;
-}
-
-// Low-cardinality variant (max_groups <= kLdsGroups/2, e.g. TPC-H Q1's 4 groups): every block
-// pre-aggregates into an LDS-resident table (ds_cmpst / ds_add, no HBM atomics per row) and merges its
-// <= kLdsGroups partial groups into the global table once at the end.
-constexpr int kLdsGroups = 2048;
-__global__ __launch_bounds__(kBlock) void groupby_build_lds_kernel(const GroupByArgs a) {
-    __shared__ unsigned long long lkeys[kLdsGroups];
-    __shared__ unsigned long long lsums[kLdsGroups + 2];
-    __shared__ unsigned long long lcnts[kLdsGroups + 2];
-    __shared__ unsigned int lspecial[2];
-    const int lane = threadIdx.x & 63;
-    const int wave = wave_id();
-    const uint64_t gmask = (uint64_t)a.t.capacity - 1;
-    const bool is_f64 = a.value_dtype == RDF_F64 || a.value_dtype == RDF_F32;
-    for (int i = threadIdx.x; i < kLdsGroups + 2; i += kBlock) {
-        if (i < kLdsGroups) lkeys[i] = kGroupEmpty;
-        lsums[i] = 0; lcnts[i] = 0;
-    }
-    if (threadIdx.x < 2) lspecial[threadIdx.x] = 0;
-    __syncthreads();
-    uint32_t err = 0;
-    for (int64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
-        const int64_t c = a.nchunks == 1 ? 0 : find_chunk_tile(a.chunk_tile_start, a.nchunks, tile);
-        const int64_t r0 = (tile - a.chunk_tile_start[c]) * kEvalTile;
-        const int64_t clen = a.chunk_len[c];
-        const DevChunkCol kc = a.keys[c];
-        const DevChunkCol vc = a.value_dtype >= 0 ? a.values[c] : DevChunkCol{nullptr, nullptr, 0};
-        const int64_t rw = r0 + (int64_t)wave * (kVPT * 64);
-        uint64_t kvw[kVPT], vvw[kVPT];
-        if (kc.validity) load_windows<kVPT>(kc.validity, kc.offset + rw, clen - rw, kvw);
-        if (vc.validity) load_windows<kVPT>(vc.validity, vc.offset + rw, clen - rw, vvw);
-#pragma unroll
-        for (int j = 0; j < kVPT; ++j) {
-            const int64_t row = rw + j * 64 + lane;
-            if (row >= clen) continue;
-            const bool kvalid = !kc.validity || ((kvw[j] >> lane) & 1);
-            const bool vvalid = a.value_dtype < 0 || !vc.validity || ((vvw[j] >> lane) & 1);
-            const uint64_t key = (uint64_t)load_key(kc, a.key_dtype, row);
-            uint64_t v = 0;
-            if (a.value_dtype == RDF_F64) v = as_global<uint64_t>(vc.values)[vc.offset + row];
-            else if (a.value_dtype == RDF_F32) v = d2u((double)as_global<float>(vc.values)[vc.offset + row]);
-            else if (a.value_dtype >= 0) v = (uint64_t)load_key(vc, a.value_dtype, row);
-            int slot = -1;
-            if (!kvalid) { slot = kLdsGroups + 1; lspecial[1] = 1; }
-            else if (key == kGroupEmpty) { slot = kLdsGroups; lspecial[0] = 1; }
-            else {
-                uint32_t s = (uint32_t)mix64(key) & (kLdsGroups - 1);
-                for (int probes = 0; probes < 64; ++probes) {
-                    const unsigned long long old = atomicCAS(&lkeys[s], kGroupEmpty, (unsigned long long)key);
-                    if (old == kGroupEmpty || old == key) { slot = (int)s; break; }
-                    s = (s + 1) & (kLdsGroups - 1);
-                }
-            }
-            if (slot >= 0) {
-                if (vvalid) {
-                    if (is_f64) unsafeAtomicAdd((double*)&lsums[slot], u2d(v)); else atomicAdd(&lsums[slot], (unsigned long long)v);
-                    atomicAdd(&lcnts[slot], 1ull);
-                }
-            } else if (!global_upsert(a.t, gmask, key, is_f64, v, vvalid ? 1 : 0)) err |= 4u;  // LDS table full: straight to HBM
-        }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < kLdsGroups + 2; i += kBlock) {
-        if (i < kLdsGroups) {
-            if (lkeys[i] != kGroupEmpty && !global_upsert(a.t, gmask, lkeys[i], is_f64, lsums[i], lcnts[i])) err |= 4u;
-        } else if (lspecial[i - kLdsGroups]) {
-            const int64_t gs = a.t.capacity + (i - kLdsGroups);
-            a.t.special[i - kLdsGroups] = 1;
-            if (lcnts[i]) {
-                if (is_f64) unsafeAtomicAdd((double*)&a.t.sums[gs], u2d(lsums[i])); else atomicAdd(&a.t.sums[gs], lsums[i]);
-                atomicAdd(&a.t.counts[gs], lcnts[i]);
-            }
-        }
-    }
-    if (err) atomicOr(a.t.flags, err);
-}
+// group, NULL values are skipped.  The engine the planner picks is rdf_groupby.hip; what lives here is the combining
+// histogram -> scatter -> aggregate fallback it hands heavily skewed sums / counts of one key column to.
 
 __device__ __forceinline__ void store_key(void* out, int dt, unsigned idx, uint64_t key) {
     switch (dt) {
@@ -1113,119 +843,8 @@ __device__ __forceinline__ void store_key(void* out, int dt, unsigned idx, uint6
     }
 }
 
-// ---- partitioned GROUP BY (high cardinality) ----
-__device__ __forceinline__ uint64_t unmix64(uint64_t z) {  // inverse of mix64 (it is a bijection on 64 bits)
-    z ^= z >> 31; z ^= z >> 62;
-    z *= 0x319642b2d24d8ec3ull;
-    z ^= z >> 27; z ^= z >> 54;
-    z *= 0x96de1b173f119089ull;
-    z ^= z >> 30; z ^= z >> 60;
-    return z;
-}
-constexpr unsigned long long kHashFree = ~0ull;  // LDS free marker in hashed-key space
-
-// (key, value) columns -> dense (mix64(key), value bits) streams; NULL keys and the one key whose hash is the
-// free marker go to two dedicated accumulators.
-__global__ __launch_bounds__(kBlock) void groupby_prepare_kernel(const GroupPrepArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int wave = wave_id();
-    for (int64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
-        const int64_t c = a.nchunks == 1 ? 0 : find_chunk_tile(a.chunk_tile_start, a.nchunks, tile);
-        const int64_t r0 = (tile - a.chunk_tile_start[c]) * kEvalTile;
-        const int64_t clen = a.chunk_len[c];
-        const int64_t g0 = a.chunk_row_start[c];
-        const DevChunkCol kc = a.keys[c];
-        const DevChunkCol vc = a.value_dtype >= 0 ? a.values[c] : DevChunkCol{nullptr, nullptr, 0};
-        const int64_t rw = r0 + (int64_t)wave * (kVPT * 64);
-        uint64_t kvw[kVPT];
-        if (kc.validity) load_windows<kVPT>(kc.validity, kc.offset + rw, clen - rw, kvw);
-#pragma unroll
-        for (int j = 0; j < kVPT; ++j) {
-            const int64_t row = rw + j * 64 + lane;
-            if (row >= clen) continue;
-            const bool kvalid = !kc.validity || ((kvw[j] >> lane) & 1);
-            uint64_t v = 0;
-            if (a.value_dtype == RDF_F64) v = as_global<uint64_t>(vc.values)[vc.offset + row];
-            else if (a.value_dtype == RDF_F32) v = d2u((double)as_global<float>(vc.values)[vc.offset + row]);
-            else if (a.value_dtype >= 0) v = (uint64_t)load_key(vc, a.value_dtype, row);
-            uint64_t hk = mix64((uint64_t)load_key(kc, a.key_dtype, row));
-            const bool is_f = a.value_dtype == RDF_F64 || a.value_dtype == RDF_F32;
-            if (!kvalid || hk == kHashFree) {
-                const int s = kvalid ? 0 : 1;
-                a.special[s] = 1;
-                if (is_f) unsafeAtomicAdd((double*)&a.special_sums[s], u2d(v)); else atomicAdd(&a.special_sums[s], (unsigned long long)v);
-                atomicAdd(&a.special_counts[s], 1ull);
-                // park the row in a partition where it is harmless: hashed key 0 with value 0 would create a bogus group,
-                // so give it the hash of its own neighbour-free marker and let the aggregation skip it
-                hk = kHashFree;
-                v = 0;
-            }
-            a.hkeys[g0 + row] = hk;
-            a.vals[g0 + row] = v;
-        }
-    }
-}
-
-// One block per partition (grid-stride): the partition's rows are a contiguous range of the sorted stream, found
-// by binary search on the top hash bits; its groups live in an LDS table and are written out directly.
-__global__ __launch_bounds__(kBlock) void groupby_partitions_kernel(const GroupAggArgs a) {
-    __shared__ unsigned long long lkeys[kLdsGroups];
-    __shared__ unsigned long long lsums[kLdsGroups];
-    __shared__ unsigned long long lcnts[kLdsGroups];
-    __shared__ unsigned int ngroups_s, obase_s;
-    const int64_t nparts = (int64_t)1 << a.part_bits;
-    const int shift = 64 - a.part_bits;
-    uint32_t err = 0;
-    for (int64_t p = blockIdx.x; p < nparts; p += gridDim.x) {
-        // [lo, hi) = rows whose top bits equal p: lower bounds of p and p+1
-        auto lower_bound = [&](uint64_t part) -> int64_t {
-            if (part >= (uint64_t)nparts) return a.n;
-            int64_t lo = 0, hi = a.n;
-            while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if ((a.hkeys[mid] >> shift) < part) lo = mid + 1; else hi = mid; }
-            return lo;
-        };
-        const int64_t lo = lower_bound((uint64_t)p), hi = lower_bound((uint64_t)p + 1);
-        if (hi <= lo) continue;
-        for (int i = threadIdx.x; i < kLdsGroups; i += kBlock) { lkeys[i] = kHashFree; lsums[i] = 0; lcnts[i] = 0; }
-        if (threadIdx.x == 0) ngroups_s = 0;
-        __syncthreads();
-        for (int64_t i = lo + threadIdx.x; i < hi; i += kBlock) {
-            const uint64_t hk = a.hkeys[i];
-            if (hk == kHashFree) continue;  // parked special rows
-            const uint64_t v = a.vals[i];
-            uint32_t s = (uint32_t)(hk >> 7) & (kLdsGroups - 1);  // bits below the partition bits are still well mixed
-            int slot = -1;
-            for (int probes = 0; probes < kLdsGroups; ++probes) {
-                const unsigned long long old = atomicCAS(&lkeys[s], kHashFree, (unsigned long long)hk);
-                if (old == kHashFree) { atomicAdd(&ngroups_s, 1u); slot = (int)s; break; }
-                if (old == hk) { slot = (int)s; break; }
-                s = (s + 1) & (kLdsGroups - 1);
-            }
-            if (slot < 0) { err |= 4u; continue; }
-            if (a.has_values) {
-                if (a.is_f64) unsafeAtomicAdd((double*)&lsums[slot], u2d(v)); else atomicAdd(&lsums[slot], (unsigned long long)v);
-            }
-            atomicAdd(&lcnts[slot], 1ull);
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) obase_s = atomicAdd(a.cursor, ngroups_s);
-        __syncthreads();
-        if (threadIdx.x == 0) ngroups_s = 0;  // reused as the local emit cursor
-        __syncthreads();
-        for (int i = threadIdx.x; i < kLdsGroups; i += kBlock) {
-            if (lkeys[i] == kHashFree) continue;
-            const unsigned idx = obase_s + atomicAdd(&ngroups_s, 1u);
-            if ((int64_t)idx >= a.max_out) { err |= 4u; continue; }
-            store_key(a.out_keys, a.key_dtype, idx, unmix64(lkeys[i]));
-            ((uint64_t*)a.out_sums)[idx] = lsums[i];
-            a.out_counts[idx] = (int64_t)lcnts[i];
-        }
-        __syncthreads();
-    }
-    if (err) atomicOr(a.flags, err);
-}
-
 // ---- single-pass partitioned GROUP BY ----
+constexpr unsigned long long kHashFree = ~0ull;  // LDS free marker in hashed-key space
 // A block iteration covers one super-tile: 4 tiles of kEvalTile rows (each inside one chunk), thread t takes the rows
 // q = j * kGbBlock + t.  All loads of the iteration are issued before anything depends on them (one row at a time
 // would leave a single 8-byte load in flight per lane: latency-bound at a quarter of the bandwidth).
@@ -1448,7 +1067,6 @@ __global__ __launch_bounds__(kGbBlock) void gb_scatter_kernel(const GbPartArgs a
         }
         // rank inside the partition (LDS atomics: 512 counters, random digits -> little contention).  A combined record
         // whose cnt does not fit the 9-bit field is continued by (0-valued) records carrying the rest of the count.
-        if (a.ablate_stores == 8) { uint64_t x = 0; for (int j = 0; j < kGbRows; ++j) x ^= b.key[j] ^ b.val[j]; if (x == 0x1234567) a.special[0] = 1; continue; }   // ablation: loads + hash only
 #pragma unroll
         for (int j = 0; j < kGbRows; ++j)
             if ((live >> j) & 1) {
@@ -1471,7 +1089,7 @@ __global__ __launch_bounds__(kGbBlock) void gb_scatter_kernel(const GbPartArgs a
         // (C) stage the records grouped by partition
 #pragma unroll
         for (int j = 0; j < kGbRows; ++j)
-            if (rank[j] != ~0u && a.ablate_stores != 7) {
+            if (rank[j] != ~0u) {
                 unsigned int pos = lstart[(unsigned)(b.key[j] >> (64 - kGbPartBits))] + rank[j];
                 unsigned int left = cnt[j];
                 skey[pos] = b.key[j];
@@ -1488,13 +1106,13 @@ __global__ __launch_bounds__(kGbBlock) void gb_scatter_kernel(const GbPartArgs a
         __syncthreads();
         // (D) write them out: consecutive staging slots of one partition are consecutive output records; the partition bits
         // of the key make room for cnt
-        for (unsigned int i = tid; i < total && a.ablate_stores != 7; i += kGbBlock) {
+        for (unsigned int i = tid; i < total; i += kGbBlock) {
             const uint64_t k = skey[i];
             const unsigned int d = (unsigned int)(k >> (64 - kGbPartBits));
             u64x2 rec;
             rec[0] = ((uint64_t)scnt[i] << (64 - kGbPartBits)) | (k & kGbKeyMask);
             rec[1] = sval[i];
-            if (a.ablate_stores != 2) ((u64x2*)a.recs)[gbase[d] + (int64_t)(i - lstart[d])] = rec;   // (nontemporal stores measured slower: 13.6 vs 10.7 ms)
+            ((u64x2*)a.recs)[gbase[d] + (int64_t)(i - lstart[d])] = rec;   // (nontemporal stores measured slower: 13.6 vs 10.7 ms)
         }
         __syncthreads();
         // (E) advance the block's output positions
@@ -1523,19 +1141,16 @@ __global__ __launch_bounds__(kGbBlock) void gb_aggregate_kernel(const GbAggArgs 
         for (int i = threadIdx.x; i < kGbSlots; i += kGbBlock) { lkeys[i] = kHashFree; lsums[i] = 0; lcnts[i] = 0; }
         if (threadIdx.x == 0) misc[0] = 0;
         __syncthreads();
-        uint64_t dbg_acc = 0;
         const uint64_t ptop = (uint64_t)p << (64 - kGbPartBits);
         auto upsert = [&](const u64x2 rec) {
             if (rec[0] == kGbDead) return;
             const unsigned int cnt = (unsigned int)(rec[0] >> (64 - kGbPartBits));
             const uint64_t hk = (rec[0] & kGbKeyMask) | ptop;
-            if (a.ablate_lds == 1) { dbg_acc ^= hk ^ rec[1]; return; }
             // slot from the 32 bits right below the partition bits (the best-mixed bits of a multiplicative hash); multiply-shift range reduction
             uint32_t s = (uint32_t)(((uint64_t)(uint32_t)(hk >> (32 - kGbPartBits)) * (uint64_t)kGbSlots) >> 32);
             const uint32_t step = 1u + (uint32_t)(((uint64_t)(uint32_t)(hk >> 3) * (uint64_t)(kGbSlots - 1)) >> 32);
             int slot = -1;
-            if (a.ablate_lds == 6) slot = (int)s;   // ablation: no key table
-            else for (int probes = 0; probes < kGbSlots; ++probes) {
+            for (int probes = 0; probes < kGbSlots; ++probes) {
                 unsigned long long old = lkeys[s];
                 if (old != hk) {
                     if (old == kHashFree) {
@@ -1549,10 +1164,10 @@ __global__ __launch_bounds__(kGbBlock) void gb_aggregate_kernel(const GbAggArgs 
             }
             if (slot < 0) { err |= 4u; return; }
             if (cnt == 0) return;   // a NULL value: the group exists, nothing to add
-            if (a.has_values && a.ablate_lds != 5) {
+            if (a.has_values) {
                 if (a.is_f64) unsafeAtomicAdd((double*)&lsums[slot], u2d(rec[1])); else atomicAdd(&lsums[slot], (unsigned long long)rec[1]);
             }
-            if (a.ablate_lds != 4) atomicAdd(&lcnts[slot], cnt);
+            atomicAdd(&lcnts[slot], cnt);
         };
         // The key probe, not the atomics, is what the table costs (ablation: without the sum or the count atomic the pass
         // takes the same 7.6 ms, without the key table 2.85 ms): every probe is a dependent LDS round trip, and a wave
@@ -1560,11 +1175,6 @@ __global__ __launch_bounds__(kGbBlock) void gb_aggregate_kernel(const GbAggArgs 
         // interleaved — one round trip serves up to 4 pending records per lane — and (2) collisions step by a second hash
         // (the table size is prime), which cuts the long clusters linear probing builds at a load of 0.5.
         auto upsert_batch = [&](const u64x2 (&rec)[kGbBatch]) {
-            if (a.ablate_lds) {
-#pragma unroll
-                for (int u = 0; u < kGbBatch; ++u) upsert(rec[u]);
-                return;
-            }
             uint64_t hk[kGbBatch];
             uint32_t s[kGbBatch], step[kGbBatch];
             uint32_t pending = 0;
@@ -1644,7 +1254,6 @@ __global__ __launch_bounds__(kGbBlock) void gb_aggregate_kernel(const GbAggArgs 
             have = nhave;
         }
         for (; i < hi; i += kGbBlock) upsert(__builtin_nontemporal_load(recs + i));
-        if (a.ablate_lds == 1 && dbg_acc == 0x1234567) err |= 8u;   // keeps the loads alive
         __syncthreads();
         if (threadIdx.x == 0) { misc[1] = atomicAdd(a.cursor, misc[0]); misc[0] = 0; }
         __syncthreads();
@@ -1659,25 +1268,6 @@ __global__ __launch_bounds__(kGbBlock) void gb_aggregate_kernel(const GbAggArgs 
         __syncthreads();
     }
     if (err) atomicOr(a.flags, err);
-}
-
-// Occupied slots -> dense outputs (order = claim order of the output cursor, i.e. unspecified).
-__global__ __launch_bounds__(kBlock) void groupby_emit_kernel(const GroupEmitArgs a) {
-    const int64_t n = a.t.capacity + 2;
-    for (int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x; s < n; s += (int64_t)gridDim.x * kBlock) {
-        bool occ; uint64_t key = 0; bool knull = false;
-        if (s < a.t.capacity) { key = a.t.keys[s]; occ = key != kGroupEmpty; }
-        else if (s == a.t.capacity) { key = kGroupEmpty; occ = a.t.special[0] != 0; }
-        else { knull = true; occ = a.t.special[1] != 0; }
-        if (!occ) continue;
-        const unsigned idx = atomicAdd(a.cursor, 1u);
-        store_key(a.out_keys, a.key_dtype, idx, key);
-        if (a.out_keys_validity) {
-            if (!knull) atomicOr((unsigned int*)a.out_keys_validity + (idx >> 5), 1u << (idx & 31));
-        }
-        ((uint64_t*)a.out_sums)[idx] = a.t.sums[s];
-        a.out_counts[idx] = (int64_t)a.t.counts[s];
-    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1881,27 +1471,6 @@ hipError_t launch_sort_keys(const SortKeyArgs& a, hipStream_t s) {
     if (grid > 0) hipLaunchKernelGGL(sort_keys_kernel, dim3((unsigned)grid), dim3(kBlock), 0, s, a, mask);
     return hipGetLastError();
 }
-int sort_grid(int64_t ntiles) {  // both sort kernels must agree on it: it fixes the tile -> block ownership
-    const int64_t lim = (int64_t)eval_grid_limit() / 2;  // 24.5 KiB of LDS per block: 4 blocks per CU
-    const int64_t g = ntiles < lim ? ntiles : lim;
-    return g < 1 ? 1 : (int)g;
-}
-hipError_t launch_sort_hist64(const SortPassArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(sort_hist_kernel, dim3(sort_grid(a.ntiles)), dim3(kBlock), 0, s, a);
-    return hipGetLastError();
-}
-hipError_t launch_sort_scatter64(const SortPassArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(sort_scatter_kernel, dim3(sort_grid(a.ntiles)), dim3(kBlock), 0, s, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_groupby_build(const GroupByArgs& a, hipStream_t s) {
-    int64_t grid = a.ntiles < (int64_t)eval_grid_limit() ? a.ntiles : (int64_t)eval_grid_limit();
-    if (grid <= 0) return hipSuccess;
-    if (a.max_groups <= kLdsGroups / 2) hipLaunchKernelGGL(groupby_build_lds_kernel, dim3((unsigned)grid), dim3(kBlock), 0, s, a);
-    else hipLaunchKernelGGL(groupby_build_kernel, dim3((unsigned)grid), dim3(kBlock), 0, s, a);
-    return hipGetLastError();
-}
 static int rows_grid(int64_t n) {
     int64_t g = (n + kBlock - 1) / kBlock;
     if (g > eval_grid_limit()) g = eval_grid_limit();
@@ -2010,24 +1579,6 @@ hipError_t launch_gb_aggregate(const GbAggArgs& a, hipStream_t s) {
     const size_t lds = (size_t)kGbSlots * 20 + 16;
     (void)hipFuncSetAttribute((const void*)gb_aggregate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);   // > 64 KB
     hipLaunchKernelGGL(gb_aggregate_kernel, dim3(1 << kGbPartBits), dim3(kGbBlock), lds, s, a);
-    return hipGetLastError();
-}
-hipError_t launch_groupby_prepare(const GroupPrepArgs& a, hipStream_t s) {
-    int64_t grid = a.ntiles < (int64_t)eval_grid_limit() ? a.ntiles : (int64_t)eval_grid_limit();
-    if (grid > 0) hipLaunchKernelGGL(groupby_prepare_kernel, dim3((unsigned)grid), dim3(kBlock), 0, s, a);
-    return hipGetLastError();
-}
-hipError_t launch_groupby_partitions(const GroupAggArgs& a, hipStream_t s) {
-    int64_t grid = (int64_t)1 << a.part_bits;
-    const int64_t lim = 3 * (int64_t)eval_grid_limit() / 8;  // 48 KiB of LDS per block: 3 blocks per CU
-    if (grid > lim) grid = lim;
-    hipLaunchKernelGGL(groupby_partitions_kernel, dim3((unsigned)grid), dim3(kBlock), 0, s, a);
-    return hipGetLastError();
-}
-hipError_t launch_groupby_emit(const GroupEmitArgs& a, hipStream_t s) {
-    int64_t grid = (a.t.capacity + 2 + kBlock - 1) / kBlock;
-    if (grid > eval_grid_limit()) grid = eval_grid_limit();
-    hipLaunchKernelGGL(groupby_emit_kernel, dim3((unsigned)grid), dim3(kBlock), 0, s, a);
     return hipGetLastError();
 }
 

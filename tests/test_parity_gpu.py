@@ -739,9 +739,10 @@ def test_sort_look_back_over_many_tiles_and_one_byte_keys(gpu, ora, dtype):
 
 @pytest.mark.parametrize("ngroups,n", [(20_000, 150_000), (300_000, 700_000), (1_300_000, 2_000_000)])
 def test_groupby_partitioned_high_cardinality(gpu, ora, ngroups, n):
-    """More than 1024 groups: records are scattered once on 9 hash bits (default) — or radix-sorted in 1-2 passes (the
-    earlier variant, kept for very large domains) — and aggregated per partition in LDS; the HBM-atomics table is the third path.
-    NULL keys, the free-marker keys of both tables, multi-chunk input with offsets; both value classes."""
+    """More than 1024 groups: the second generation's line-aligned scatter (by the planner, and forced), the first generation's
+    single scatter on 9 hash bits with one LDS table per partition (the skew fallback, run here on uniform keys through
+    gb_partition 1) and the HBM-atomics table.  NULL keys, the free-marker keys of the hashes and of the HBM table, multi-chunk
+    input with offsets; both value classes."""
     from rust_dataframe_amd import lib
     rng = np.random.default_rng(ngroups)
     lens = [n // 3, 0, n - n // 3]
@@ -751,17 +752,17 @@ def test_groupby_partitioned_high_cardinality(gpu, ora, ngroups, n):
             kv = rng.integers(-ngroups // 2, ngroups // 2, ln).astype(np.int64)
             if ln > 4:
                 kv[0], kv[1] = np.iinfo(np.int64).min, np.iinfo(np.int64).max
-                kv[2] = np.int64(-3487469807577879104)  # mix64(key) == 2^64 - 1, the LDS free marker of the partition tables
-                kv[3] = np.int64(7406324358081711299)   # the same for the single-pass path's hash (gb_hash)
+                kv[2] = np.int64(-3487469807577879104)  # SplitMix64 finaliser(key) == 2^64 - 1: an ordinary key to every path here
+                kv[3] = np.int64(7406324358081711299)   # gb_hash(key) == 2^64 - 1, the LDS free marker of both generations' partition tables
             keys.append(A.HostArray.from_numpy(kv, valid=rng.uniform(size=ln) >= 0.01, offset=5, rng=rng))
             if val_dtype is not None:
                 vals.append(A.HostArray.from_numpy(rng.uniform(-1, 1, ln) if val_dtype == A.F64 else rng.integers(-10 ** 9, 10 ** 9, ln), offset=2, dtype=val_dtype, rng=rng))
         exp = _sorted_groups(*ora.groupby_sum(keys, vals, ngroups + 8))
-        for part in (3, 4, 1, 2, 0):  # second generation (auto / scatter path forced), first-generation single-pass and radix-sort partitioning, the HBM table
+        for part in (3, 4, 1, 0):  # second generation (auto / scatter path forced), the first-generation single-pass fallback, the HBM table
             lib.set_option("gb_partition", part)
             got = _sorted_groups(*gpu.groupby_sum(keys, vals, ngroups + 8))
-            if part in (1, 2):
-                assert lib.last_kernel().startswith("gb_aggregate_kernel" if part == 1 else "groupby_partitions_kernel")
+            if part == 1:
+                assert lib.last_kernel().startswith("gb_aggregate_kernel")
             elif part:
                 assert lib.last_kernel().startswith("gb2_"), lib.last_kernel()
             assert np.array_equal(got[1], exp[1]) and np.array_equal(got[0][exp[1]], exp[0][exp[1]]), f"keys part={part}"

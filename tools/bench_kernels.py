@@ -376,9 +376,10 @@ def main():
         oc2_ = out_like(A.I64, ng + 2)
         report(f"groupby_sum_{ng}_groups", 16.0 * n, lambda: api.groupby_sum([KK], [X], ng, (ok_, os_, oc_)))
         report(f"groupby_max_{ng}_groups", 16.0 * n, lambda: api.groupby_agg([[KK]], [X], "max", ng, ([ok_], os_, oc_)))
-        lib.set_option("gb_partition", 1)
-        report(f"groupby_sum_{ng}_groups_first_generation", 16.0 * n, lambda: api.groupby_sum([KK], [X], ng, (ok_, os_, oc_)))
-        lib.set_option("gb_partition", 3)
+        if ng > 1024:      # the first-generation histogram + scatter path (the skew fallback) takes 1024 < max_groups <= 1 331 200
+            lib.set_option("gb_partition", 1)
+            report(f"groupby_sum_{ng}_groups_first_generation", 16.0 * n, lambda: api.groupby_sum([KK], [X], ng, (ok_, os_, oc_)))
+            lib.set_option("gb_partition", 3)
         if ng > 2048:
             # skewed keys (SURVEY.md §8d C4 variant): Zipf-like s = 1.1 (inverse-CDF of the continuous power law, clamped) and one hot key
             u = torch.rand(n, device="cuda", dtype=torch.float64).clamp_(min=1e-12)
@@ -400,21 +401,12 @@ def main():
             del ks
             report(f"groupby_sum_{ng}_groups_null_values", 16.125 * n, lambda: api.groupby_sum([KK], [XV], ng, (ok_, os_, oc_)))
             del u, kz, kh
-            for dbg in ((1, 2, 4, 5, 6, 7, 8) if "ablate" in args.only else ()):   # ablations of the FIRST-generation passes
-                lib.set_option("gb_debug", dbg)
-                try:
-                    report(f"groupby_sum_{ng}_groups_ablate{dbg}", 16.0 * n, lambda: api.groupby_sum([KK], [X], ng, (ok_, os_, oc_)))
-                except Exception as ex:   # the ablations produce wrong results by construction
-                    print("ablation", dbg, ex)
-            lib.set_option("gb_debug", 0)
             report(f"groupby_count_{ng}_groups", 8.0 * n, lambda: api.groupby_sum([KK], None, ng, (ok_, oc2_, oc_)))
             lib.set_option("gb_compact", 0)      # A/B: 16-byte records for COUNT too
             report(f"groupby_count_{ng}_groups_16_byte_records", 8.0 * n, lambda: api.groupby_sum([KK], None, ng, (ok_, oc2_, oc_)))
             lib.set_option("gb_compact", 2)      # A/B: 12-byte records (key word + value) for SUM
             report(f"groupby_sum_{ng}_groups_12_byte_records", 16.0 * n, lambda: api.groupby_sum([KK], [X], ng, (ok_, os_, oc_)))
             lib.set_option("gb_compact", 1)
-            lib.set_option("gb_partition", 2)
-            report(f"groupby_sum_{ng}_groups_radix_sort", 16.0 * n, lambda: api.groupby_sum([KK], [X], ng, (ok_, os_, oc_)))
             lib.set_option("gb_partition", 0)
             report(f"groupby_sum_{ng}_groups_hbm_atomics", 16.0 * n, lambda: api.groupby_sum([KK], [X], ng, (ok_, os_, oc_)))
             lib.set_option("gb_partition", 3)
