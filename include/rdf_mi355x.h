@@ -843,8 +843,7 @@ rdf_status rdf_fill_validity(uint8_t* dev_ptr, int64_t nbits, uint64_t seed, uin
  * "gb_compact" (scatter path, keys inside a window of 2^39: 1 = 4-byte records when only rows are counted, default; 2 = also
  * 12-byte records for sum / min / max; 0 = 16-byte records always), "gb_skew_plan" (1 = per-partition capacity plan when the probe finds a few heavy
  * partitions, default; 0 = the first-generation combining path instead; 2 = always),
- * "filter_tile" (0: compaction tile from the mean chunk length; 1024 / 4096 force one), "filter_one" (one-chunk
- * compaction kernel with kernel-argument descriptors, default on), "take_rows" (rdf_take_frame / rdf_sort_frame: 1 = gather
+ * "take_rows" (rdf_take_frame / rdf_sort_frame: 1 = gather
  * interleaved row records when the index list is long and the frame wide, default; 0 = always column by column; 2 = always records),
  * "gb_hot" (skewed keys on the scatter path: 1 = the few dozen hash classes that hold the heavy hitters get a pass of their own — folded in
  * LDS per block — and the scatter takes the other rows, default; 0 = capacity plan / first-generation combining path),
@@ -856,10 +855,6 @@ rdf_status rdf_fill_validity(uint8_t* dev_ptr, int64_t nbits, uint64_t seed, uin
  * "filter_block" (rdf_filter_frame's one-pass form and rdf_filter / rdf_filter_columns over device-resident chunks, on frames of equally wide 4- / 8-byte columns in LONG batches: 1 = block tiles held in registers, every tile's row count
  * published one iteration before its offset is asked for, offsets from one scanner wave, default; 0 = the wave-tile kernels),
  * "filter_block_rows" (the mean batch length from which that kernel is taken, default 8192),
- * "filter_mixed" (rdf_filter_frame's one-pass form over frames of 8- AND 4-byte columns: the block kernel twice — the columns of the predicate's
- * width first, which also writes the kept rows into the frame's own mask, then the other width's columns by that mask; measured behind the
- * wave-tile kernel, which takes any widths: 0 = never, default; 1 = where that kernel's 1024-row tiles come out partial; 2 = wherever the
- * block kernel's forms apply),
  * "filter_ends" (the wave-tile one-pass kernel on frames whose batch lengths are not multiples of its 1024-row tile: 1 = the tiles at the end
  * of a batch take the LDS-DMA path too, default; 0 = they load row by row),
  * "filter_short" (the same operators on frames whose batches are no longer than one block tile — the readers' 1024-row RecordBatches,
@@ -869,8 +864,9 @@ rdf_status rdf_fill_validity(uint8_t* dev_ptr, int64_t nbits, uint64_t seed, uin
  * comparison, f64 / 64-bit integer arithmetic, a Boolean connective, an integer -> f64 cast or the filter, aggregated or stored: 1 = the
  * interpreter's branch-free kernel with host-assigned step handlers (eval_lean_kernel, 1.4-2.2 x the general kernel on aggregates), default;
  * 2 = the same with one tile per trip of its step loop (the A/B of its two-tile form); 0 = eval_kernel),
- * "filter_lookback" (the wave-tile kernel on batches longer than a tile: 3 = one tile per 64 finds the rows in front of them all, from tile
- * counts and older totals, default; 2 = from totals only; 1 = every tile walks the totals and batches beyond 1 048 576 rows take the three passes),
+ * "filter_gen", "filter_one", "filter_tile", "filter_mixed", "filter_lookback" (accepted and ignored: they selected forms of the compaction
+ * kernels that were measured slower and removed — the table-driven block tiles, the two-launch form for frames of 8- and 4-byte columns, the
+ * older look-back walks of the wave-tile kernel),
  * "join_table" (equi-join on one key column: 2 = the build side sorted by hash, the table of its distinct keys laid out by a scan,
  * default; 1 = sorted by key, table slots claimed by compare-and-swap; 0 = a bucket index over the sorted build keys),
  * "sort_msd" (keys that vary in 25 bits or more: 1 = passes over the top bits, buckets finished in LDS, default; 0 = one pass per byte),

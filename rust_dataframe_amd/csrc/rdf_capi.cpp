@@ -60,18 +60,13 @@ struct Ctx {
     bool   opt_spec = true;        // specialised straight-line kernels (rdf_spec.hip)
     bool   opt_fast_filter = true; // filter_agg_f64_kernel (handles 8-byte-misaligned columns)
     bool   opt_vec_bitmap = false; // validity words of the specialised kernels: scalar loads (default since the wave-granular tiles: 1.30 vs 1.355 ms on the 1e9-row filter->sum with nulls) or one vector load by lanes 0..NW + readlane (A/B; it was the faster one with block-wide tiles)
-    bool   opt_filter_one = true;   // one-chunk compaction kernel with its descriptors in the kernel arguments (A/B)
-    int    opt_filter_gen = 2;      // compaction kernels: 2 = wave-granular tiles (rdf_filter.hip, default), 1 = first-generation block tiles (A/B)
     int    opt_filter_block = 1;    // one-pass compaction of LONG batches on block tiles held in registers, prefixes from a scanner wave (rdf_bfilter.hip, round 6; default); 0 = the wave-tile kernels only (A/B)
     int    opt_interp_lean = 1;             // interpreted aggregate programs whose every step has a lean handler run on eval_lean_kernel (rdf_eval_lean.hip); 0: always eval_kernel (the A/B)
     int    opt_filter_owned = 1;    // long batches, many of them, none a large share of the frame: a block draws whole batches and adds up its own offsets (round 6; default); 0 = tiles by ticket, offsets from the scanner wave (A/B)
     int    opt_filter_ends = 1;     // the wave-tile one-pass kernel: tiles at the END of a batch take the LDS-DMA path too (clamped addresses; frames whose batch lengths are not multiples of 1024 rows; round 6, default); 0 = they load row by row (A/B)
-    int    opt_filter_mixed = 0;    // rdf_filter_frame over frames of 8- AND 4-byte columns: the block kernel twice (the predicate's width first, writing the kept rows into the frame's mask; the other width by that mask; round 6: built, parity-tested, measured 2 - 20 % BEHIND the wave-tile kernel on multiples of 1024 rows and — once that kernel's end-of-batch tiles took the DMA path, filter_ends — behind it on ragged lengths too: not the default) — 0 = never (default); 1 = for short batches whose rows mostly lie in partial 1024-row tiles; 2 = wherever the block kernel's forms apply (tests, A/B)
     int    opt_filter_short = 1;    // batches / chunks no longer than a block tile on the block kernel's short-batch mode (round 6; default); 0 = the wave-tile kernels (A/B)
     int    opt_filter_block_rows = 8192;    // ... for frames whose mean batch length is at least this many rows (one block tile of a single 8-byte column; measured ahead of the wave-tile kernel from 8192-row batches up: profiles/r06_filter_frame_batch_length_sweep.jsonl)
     int    opt_filter_fused = 1;    // rdf_filter_frame: `col CMP literal [AND|OR col CMP literal]` predicates evaluated inside the compaction kernel, one pass (1, default); 0 = predicate -> mask, count, compact (A/B)
-    int    opt_filter_lookback = 3; // one-pass rdf_filter_frame, batches longer than a tile: 3 = a super-tile's first tile finds the rows in front of the super-tile for all 64, from the nearest super-tiles' tile counts and the older ones' totals (default); 2 = from totals only; 1 = every tile walks the totals (round 4; batches of at most 1024 tiles) — A/B
-    int    opt_filter_tile = 0;     // 0: compaction tile chosen from the mean chunk length; 1024 / 4096 force one (A/B)
     int    opt_gb_debug = 0;        // 3 = rdf_groupby_sum takes the first-generation fallback (where its range holds) with the combining scatter forced (tests); nothing else is stored
     bool   sort_used_local = false; // the last sort finished at least one column with os_local_kernel
     int64_t utf8_sort_rounds = 0;   // the last sort: refinement rounds its Utf8 criteria took (round 0 included), summed
@@ -2390,7 +2385,7 @@ struct FilterPrep {
     InputStager in;         // mask chunks first, then the columns
     TableBuilder tb;
     MaskTables mt;
-    int tile_rows = kFilterTile;   // kFilterTile or kFilterTileSmall, picked from the mean chunk length
+    int tile_rows = kFilterTile;   // kFilterTile (block tiles) or one of the wave-tile sizes
     std::vector<int64_t> clen, tile_start;
     int64_t ntiles = 0;
     int64_t* d_counts = nullptr;  // [ntiles]
@@ -2428,7 +2423,6 @@ rdf_status filter_tiles(FilterPrep& fp, int tile_rows, int64_t nchunks, std::vec
     if (fp.wave) {
         memset(&fp.wa, 0, sizeof fp.wa);
         fp.wa.t = fp.mt;
-        fp.wa.prefetch = ctx.opt_filter_gen != 3;   // (3: A/B without the look-ahead)
         {   // chunk lengths that are not multiples of the DMA tile: the instantiation whose end-of-chunk tiles take the DMA path too
             int64_t rows = 0;
             for (int64_t c = 0; c < nchunks; ++c) rows += fp.clen[(size_t)c];
@@ -2438,8 +2432,7 @@ rdf_status filter_tiles(FilterPrep& fp, int tile_rows, int64_t nchunks, std::vec
         if (nchunks > 1 && fp.tile_start[(size_t)nchunks - 1] > 0 && nchunks - 1 < ((int64_t)1 << 31))
             fp.wa.tile_inv = (uint64_t)(((unsigned __int128)(uint64_t)(nchunks - 1) << 32) / (unsigned __int128)(uint64_t)fp.tile_start[(size_t)nchunks - 1]);
         HIP_TRY(launch_fcount(fp.wa, fp.tile_rows, fp.d_counts, ctx.stream));
-    } else if (nchunks == 1 && fp.tile_rows == kFilterTile && ctx.opt_filter_one) HIP_TRY(launch_mask_count_one(fp.in.dev[0], fp.clen[0], fp.ntiles, fp.d_counts, ctx.stream));
-    else HIP_TRY(launch_mask_count(fp.mt, fp.tile_rows, fp.d_counts, ctx.stream));
+    } else HIP_TRY(launch_mask_count_one(fp.in.dev[0], fp.clen[0], fp.ntiles, fp.d_counts, ctx.stream));   // (one chunk, block tiles)
     HIP_TRY(launch_scan(fp.d_counts, fp.d_scan, fp.ntiles, fp.d_scan + fp.ntiles + 1, ctx.stream));
     kt_count.stop();
 
@@ -2465,7 +2458,6 @@ rdf_status filter_tiles(FilterPrep& fp, int tile_rows, int64_t nchunks, std::vec
 // Stage mask (+ columns), build the descriptor tables, pick the compaction kernels and their tile size, count + scan.
 rdf_status filter_prepare(FilterPrep& fp, const rdf_array* cols, int ncols, const rdf_array* mask, int64_t nchunks,
                           std::vector<int64_t>& totals, bool count = true) {
-    Ctx& ctx = g_ctx;
     for (int64_t c = 0; c < nchunks; ++c) fp.in.add(&mask[c]);
     for (int64_t i = 0; i < (int64_t)ncols * nchunks; ++i) fp.in.add(&cols[i]);
     size_t used = 0;
@@ -2476,20 +2468,15 @@ rdf_status filter_prepare(FilterPrep& fp, const rdf_array* cols, int ncols, cons
     int64_t rows_total = 0;
     for (int64_t c = 0; c < nchunks; ++c) { fp.clen[(size_t)c] = mask[c].length; rows_total += mask[c].length; }
     const int64_t mean_len = nchunks > 0 ? rows_total / nchunks : 0;
-    // first generation (block tiles, one barrier per tile): 1024-row tiles for frames in the reader's batches, 4096 otherwise
-    int tile_rows = nchunks > 0 && mean_len <= 2048 ? kFilterTileSmall : kFilterTile;
-    if (ctx.opt_filter_tile == kFilterTileSmall || ctx.opt_filter_tile == kFilterTile) tile_rows = ctx.opt_filter_tile;
-    // wave-granular kernels (rdf_filter.hip) — the default, with one exception: ONE column of ONE long chunk is still
-    // faster on the first-generation block tiles when the LDS-DMA kernel cannot take it (measured per 1e9 rows: 2.34 ms
-    // against 2.8 ms for the register-staged wave tiles)
+    // wave-granular kernels (rdf_filter.hip), with one exception: ONE column of ONE chunk is faster on the block tiles
+    // of compact_one_kernel (one barrier per 4096-row tile) when the LDS-DMA kernel cannot take it (measured per 1e9 rows:
+    // 2.34 ms against 2.8 ms for the register-staged wave tiles)
+    int tile_rows = kFilterTile;
     bool all_wide = ncols > 0;
     for (int k = 0; k < ncols; ++k) { const int es = dtype_size(cols[(int64_t)k * nchunks].dtype); all_wide &= es == 8 || es == 4; }
-    fp.dma_ok = all_wide && rows_total >= nchunks * (int64_t)(kWDmaTile * 3 / 4) && ctx.opt_filter_gen == 2;   // most tiles full (the reader's last batch is short)
-    fp.wave = ctx.opt_filter_gen >= 2 && !(ctx.opt_filter_gen == 2 && nchunks == 1 && ncols == 1 && !fp.dma_ok);
-    if (fp.wave) {
-        tile_rows = fp.dma_ok ? kWDmaTile : nchunks > 0 && mean_len <= 256 ? kWTileSmall : kWTile;
-        if (!fp.dma_ok && (ctx.opt_filter_tile == kWTileSmall || ctx.opt_filter_tile == kWTile)) tile_rows = ctx.opt_filter_tile;
-    }
+    fp.dma_ok = all_wide && rows_total >= nchunks * (int64_t)(kWDmaTile * 3 / 4);   // most tiles full (the reader's last batch is short)
+    fp.wave = !(nchunks == 1 && ncols == 1 && !fp.dma_ok);
+    if (fp.wave) tile_rows = fp.dma_ok ? kWDmaTile : nchunks > 0 && mean_len <= 256 ? kWTileSmall : kWTile;
 
     const size_t o_mask = fp.tb.reserve(sizeof(DevChunkCol) * (size_t)nchunks);
     const size_t o_len = fp.tb.reserve(sizeof(int64_t) * fp.clen.size());
@@ -2635,7 +2622,6 @@ rdf_status filter_columns_block(FilterPrep& fp, const rdf_array* cols, int ncols
                 // the readers' batches: a chunk is ONE wave tile, its kept rows start its output — the wave-tile LDS-DMA kernel without
                 // the count and scan passes in front of it (it writes the lengths itself)
                 wa.out_len = d_len;
-                wa.prefetch = 1;
                 if (!kt) kt.reset(new KernelTimer());
                 HIP_TRY(launch_fcompact(wa, kWDmaTile, ctx.stream));
                 continue;
@@ -2724,7 +2710,7 @@ rdf_status rdf_filter_columns(const rdf_array* cols, int32_t ncols, const rdf_ar
         // chunk on 1 / 2 / 4 / 8 waves of a block, no prefix between blocks (round 6) — unless most slots would sit half empty
         int64_t max_len = 0;
         for (int64_t c = 0; c < nchunks; ++c) max_len = std::max<int64_t>(max_len, mask[c].length);
-        if (roomy && ctx.opt_filter_gen == 2) {
+        if (roomy) {
             // (every column group of a call must fit: the groups of eight columns have the shortest tiles)
             // The same choice as rdf_filter_frame's (filter_frame_fused): slots filled to 0.9 -> the short form; chunks that average
             // half a tile and fill their tiles to 0.5 (one column) / 0.65 -> the long forms; slots half full -> the short form.
@@ -2741,7 +2727,7 @@ rdf_status rdf_filter_columns(const rdf_array* cols, int32_t ncols, const rdf_ar
             if (sh >= 0 && short_fill >= 0.5) return filter_columns_block(fp, cols, ncols, mask, nchunks, outs, es0, 2, max_len);
         }
         // ... and before that kernel had its short-batch mode: no chunk longer than one wave tile of 1024 rows, most of them full
-        if (roomy && max_len <= kWDmaTile && rows_total >= nchunks * (int64_t)(kWDmaTile * 3 / 4) && ctx.opt_filter_gen == 2)
+        if (roomy && max_len <= kWDmaTile && rows_total >= nchunks * (int64_t)(kWDmaTile * 3 / 4))
             return filter_columns_block(fp, cols, ncols, mask, nchunks, outs, es0, 1);
     }
     RDF_TRY(filter_prepare(fp, cols, ncols, mask, nchunks, totals));
@@ -2789,48 +2775,30 @@ rdf_status rdf_filter_columns(const rdf_array* cols, int32_t ncols, const rdf_ar
 
     {
         KernelTimer kt;
-        for (int g = 0; g < ncols; g += kMaxFilterCols) {  // ranks are recomputed per group of columns (1 bit/row)
-            if (fp.wave) {
-                FilterWArgs& wa = fp.wa;
-                wa.cols = fp.tb.dev_at<DevChunkCol>(fp.o_cols) + (size_t)g * (size_t)nchunks;
-                wa.outs = fp.tb.dev_at<DevOutChunk>(fp.o_outs) + (size_t)g * (size_t)nchunks;
-                wa.out_null_counts = d_nullc + (size_t)g * (size_t)nchunks;
-                wa.tile_scan = fp.d_scan;
-                wa.ncols = ncols - g < kMaxFilterCols ? ncols - g : kMaxFilterCols;
-                for (int k = 0; k < wa.ncols; ++k) {
-                    wa.esize[k] = dtype_size(cols[(int64_t)(g + k) * nchunks].dtype);
-                    if (nchunks == 1) { wa.cols0[k] = fp.in.dev[(size_t)(1 + g + k)]; wa.outs0[k] = dev_outs[(size_t)(g + k)]; }
-                }
-                HIP_TRY(launch_fcompact(wa, fp.tile_rows, ctx.stream));
-                continue;
+        if (!fp.wave) {   // one column of one chunk on block tiles (filter_prepare): descriptors in the kernel arguments
+            FilterOneArgs oa;
+            memset(&oa, 0, sizeof oa);
+            oa.mask = fp.in.dev[0];
+            oa.clen = fp.clen[0];
+            oa.ntiles = fp.ntiles;
+            oa.tile_scan = fp.d_scan;
+            oa.out_null_count = d_nullc;
+            oa.esize = dtype_size(cols[0].dtype);
+            oa.col = fp.in.dev[1];
+            oa.out = dev_outs[0];
+            HIP_TRY(launch_compact_one(oa, ctx.stream));
+        } else for (int g = 0; g < ncols; g += kMaxFilterCols) {  // ranks are recomputed per group of columns (1 bit/row)
+            FilterWArgs& wa = fp.wa;
+            wa.cols = fp.tb.dev_at<DevChunkCol>(fp.o_cols) + (size_t)g * (size_t)nchunks;
+            wa.outs = fp.tb.dev_at<DevOutChunk>(fp.o_outs) + (size_t)g * (size_t)nchunks;
+            wa.out_null_counts = d_nullc + (size_t)g * (size_t)nchunks;
+            wa.tile_scan = fp.d_scan;
+            wa.ncols = ncols - g < kMaxFilterCols ? ncols - g : kMaxFilterCols;
+            for (int k = 0; k < wa.ncols; ++k) {
+                wa.esize[k] = dtype_size(cols[(int64_t)(g + k) * nchunks].dtype);
+                if (nchunks == 1) { wa.cols0[k] = fp.in.dev[(size_t)(1 + g + k)]; wa.outs0[k] = dev_outs[(size_t)(g + k)]; }
             }
-            if (nchunks == 1 && fp.tile_rows == kFilterTile && ctx.opt_filter_one) {   // one long chunk: descriptors in the kernel arguments
-                FilterOneArgs oa;
-                memset(&oa, 0, sizeof oa);
-                oa.mask = fp.in.dev[0];
-                oa.clen = fp.clen[0];
-                oa.ntiles = fp.ntiles;
-                oa.tile_scan = fp.d_scan;
-                oa.out_null_counts = d_nullc + (size_t)g;
-                oa.ncols = ncols - g < kMaxFilterCols ? ncols - g : kMaxFilterCols;
-                for (int k = 0; k < oa.ncols; ++k) {
-                    oa.esize[k] = dtype_size(cols[g + k].dtype);
-                    oa.cols[k] = fp.in.dev[(size_t)(1 + g + k)];
-                    oa.outs[k] = dev_outs[(size_t)(g + k)];
-                }
-                HIP_TRY(launch_compact_one(oa, ctx.stream));
-                continue;
-            }
-            FilterArgs fa;
-            memset(&fa, 0, sizeof fa);
-            fa.t = fp.mt;
-            fa.cols = fp.tb.dev_at<DevChunkCol>(fp.o_cols) + (size_t)g * (size_t)nchunks;
-            fa.outs = fp.tb.dev_at<DevOutChunk>(fp.o_outs) + (size_t)g * (size_t)nchunks;
-            fa.out_null_counts = d_nullc + (size_t)g * (size_t)nchunks;
-            fa.tile_scan = fp.d_scan;
-            fa.ncols = ncols - g < kMaxFilterCols ? ncols - g : kMaxFilterCols;
-            for (int k = 0; k < fa.ncols; ++k) fa.esize[k] = dtype_size(cols[(int64_t)(g + k) * nchunks].dtype);
-            HIP_TRY(launch_compact(fa, fp.tile_rows, ctx.stream));
+            HIP_TRY(launch_fcompact(wa, fp.tile_rows, ctx.stream));
         }
         kt.stop();
     }
@@ -4253,8 +4221,6 @@ rdf_status rdf_set_option(const char* name, int64_t value) {
     else if (strcmp(name, "vec_bitmap") == 0) g_ctx.opt_vec_bitmap = value != 0;
     else if (strcmp(name, "gb_partition") == 0) g_ctx.opt_gb_partition = value == 2 ? 3 : (int)value;   // (2 named the retired radix-sort partitioning: accepted, the planner decides as under 3)
     else if (strcmp(name, "gb_debug") == 0) g_ctx.opt_gb_debug = value == 3 ? 3 : 0;   // (every other value named a retired ablation of the kernels: accepted and ignored)
-    else if (strcmp(name, "filter_tile") == 0) g_ctx.opt_filter_tile = (int)value;
-    else if (strcmp(name, "filter_one") == 0) g_ctx.opt_filter_one = value != 0;
     else if (strcmp(name, "take_rows") == 0) g_ctx.opt_take_rows = (int)value;
     else if (strcmp(name, "sort_gen") == 0 || strcmp(name, "sort_pipe") == 0 || strcmp(name, "sort_super") == 0) {}   // retired forms of the digit pass (rdf_sort.hip): accepted and ignored, so that callers that still set them keep running
     else if (strcmp(name, "sort_msd") == 0) g_ctx.opt_sort_msd = (int)value;
@@ -4271,16 +4237,14 @@ rdf_status rdf_set_option(const char* name, int64_t value) {
     else if (strcmp(name, "spec_xcd_swz") == 0) g_ctx.opt_spec_xcd_swz = value < 0 ? -1 : value != 0;
     else if (strcmp(name, "spec_grid_adj") == 0) g_ctx.opt_spec_grid_adj = (int)value;
     else if (strcmp(name, "gspec_blocks_per_cu") == 0) g_ctx.opt_gspec_blocks = (int)value;
-    else if (strcmp(name, "filter_gen") == 0) g_ctx.opt_filter_gen = (int)value;
+    else if (strcmp(name, "filter_gen") == 0 || strcmp(name, "filter_one") == 0 || strcmp(name, "filter_tile") == 0 || strcmp(name, "filter_mixed") == 0 || strcmp(name, "filter_lookback") == 0) {}   // retired forms of the compaction kernels (the table-driven block tiles, the two-launch form for frames of two column widths, the older look-back walks): accepted and ignored
     else if (strcmp(name, "filter_fused") == 0) g_ctx.opt_filter_fused = (int)value;
     else if (strcmp(name, "filter_block") == 0) g_ctx.opt_filter_block = value == 3 ? 3 : value != 0;      // (3: tests — the scanner wave stays idle, every wait must time out)
     else if (strcmp(name, "interp_lean") == 0) g_ctx.opt_interp_lean = value == 2 ? 2 : value != 0;   // (2: the lean kernel with one tile per trip of its step loop — the A/B of its two-tile form)
     else if (strcmp(name, "filter_owned") == 0) g_ctx.opt_filter_owned = value == 2 ? 2 : value != 0;      // (2: tests — whatever the number and lengths of the batches)
     else if (strcmp(name, "filter_ends") == 0) g_ctx.opt_filter_ends = value != 0;
-    else if (strcmp(name, "filter_mixed") == 0) g_ctx.opt_filter_mixed = value == 2 ? 2 : value != 0;
     else if (strcmp(name, "filter_short") == 0) g_ctx.opt_filter_short = value != 0;
     else if (strcmp(name, "filter_block_rows") == 0) g_ctx.opt_filter_block_rows = value < 1 ? 1 : (int)value;
-    else if (strcmp(name, "filter_lookback") == 0) g_ctx.opt_filter_lookback = value == 1 ? 1 : value == 2 ? 2 : 3;
     else if (strcmp(name, "comm_max_bytes") == 0) g_ctx.opt_comm_max_bytes = value;
     else if (strcmp(name, "stream_slab_bytes") == 0) g_ctx.opt_stream_slab = value;
     else if (strcmp(name, "uniques_route") == 0) g_ctx.opt_uniques_route = value == 1 ? 1 : 0;

@@ -258,7 +258,7 @@ BfTerm bf_term(const FusedTerm& t) {
 rdf_status filter_frame_fused(rdf_frame& f, const rdf_expr_node* nodes, int32_t nnodes, int32_t root, rdf_frame** out, bool* handled) {
     *handled = false;
     Ctx& ctx = g_ctx;
-    if (!ctx.opt_filter_fused || ctx.opt_filter_gen < 2 || f.ncols > kMaxFilterCols || f.total_rows <= 0) return RDF_OK;
+    if (!ctx.opt_filter_fused || f.ncols > kMaxFilterCols || f.total_rows <= 0) return RDF_OK;
     for (int k = 0; k < f.ncols; ++k) { const int es = dtype_size(f.col_dtype[k]); if (es != 8 && es != 4) return RDF_OK; }
     if (f.total_rows < f.nchunks * (int64_t)(kWDmaTile * 3 / 4)) return RDF_OK;      // short batches: mostly partial tiles
     // A batch of up to 64 tiles finds its offsets with ONE 64-wide read of its predecessors' counts (65 536-row batches: 2.78 ms
@@ -274,13 +274,12 @@ rdf_status filter_frame_fused(rdf_frame& f, const rdf_expr_node* nodes, int32_t 
     // Round 5: what a tile of a long batch waits for is a chain of memory round trips (its neighbours' counts -> the super-tile's
     // total -> the walk over the totals), and a wave holds one tile at a time, so every hop of that chain is time the wave moves no
     // data.  Now the walk is done once per super-tile, by its first tile, which leaves the rows in front of the super-tile in a word
-    // of its own (ffilter_dma_kernel, lookback >= 2); the other 63 tiles read that word with lane 63 of the same 64-wide read that
+    // of its own (ffilter_dma_kernel); the other 63 tiles read that word with lane 63 of the same 64-wide read that
     // brings their neighbours' counts; and the first tile adds up the nearest 8 super-tiles from their tiles' counts instead of
-    // waiting for their totals (lookback == 3, the default).  1e9 rows, kernels, one pass against three: 262 144-row batches 3.57
+    // waiting for their totals.  1e9 rows, kernels, one pass against three: 262 144-row batches 3.57
     // against 4.07 ms (four columns 9.06 / 10.17), 1 048 576 rows 3.82 / 4.06 (9.30 / 10.3), 16 M rows 3.99 / 3.98 (9.64 / 10.1),
-    // ONE batch of 1e9 rows 3.78 / 4.09 (9.60 / 10.2) — the one pass is taken for batches of any length;
-    // rdf_set_option("filter_lookback", 1) brings the every-tile walk (and its 1024-tile cap) back for A/B, 2 the walk over totals only.
-    if (ctx.opt_filter_fused < 2 && ctx.opt_filter_lookback == 1 && f.max_clen > (int64_t)1024 * kWDmaTile) return RDF_OK;
+    // ONE batch of 1e9 rows 3.78 / 4.09 (9.60 / 10.2) — the one pass is taken for batches of any length.  (The two older walks, by
+    // every tile and over totals only, are measured in profiles/r05_filter_frame_lookback_ab_box8.jsonl / _box9.jsonl.)
     FusedFilterArgs fa;
     memset(&fa, 0, sizeof fa);
     const rdf_expr_node& rn = nodes[root];
@@ -299,38 +298,13 @@ rdf_status filter_frame_fused(rdf_frame& f, const rdf_expr_node* nodes, int32_t 
     rdf_frame& o = *nf.f;
     // Long batches of equally wide columns: block tiles in registers, counts published ahead of their prefixes, one scanner wave
     // (rdf_bfilter.hip).  The wave-tile kernel below keeps the readers' short batches, where a batch is a tile.
+    // Frames of TWO column widths (8- and 4-byte columns side by side: a lineitem-shaped frame) stay on the wave-tile kernel too.  The
+    // block kernel twice — the predicate's width first, writing the kept rows into the frame's mask, then the other width by that mask —
+    // was built, measured 5 - 20 % behind it and removed: profiles/r06_filter_frame_mixed_widths.jsonl.
     int es0 = dtype_size(f.col_dtype[0]);
     for (int k = 1; k < f.ncols; ++k) if (dtype_size(f.col_dtype[k]) != es0) es0 = 0;
-    BFilterArgs block_args, block_args2;
+    BFilterArgs block_args;
     memset(&block_args, 0, sizeof block_args);
-    memset(&block_args2, 0, sizeof block_args2);
-    // Frames of TWO column widths (8- and 4-byte columns side by side: a lineitem-shaped frame): the block kernel ties a lane's rows to
-    // the element size, so such a frame takes it twice over the same tiles — first the columns of the predicate's width, predicate
-    // form, which ALSO writes the kept rows, in row order, into the frame's own mask (1 bit per row); then the other width's columns
-    // by that mask.  Both launches use the several-column geometry (512 rows per wave, 4096 per tile whatever the width), so their
-    // tiles, forms and slots coincide.  Measured (profiles/r06_filter_frame_mixed_widths.jsonl): the second launch moves half the
-    // bytes per slot of the first, so at batch lengths the wave-tile kernel likes (multiples of 1024 rows) the pair is 5 - 20 % BEHIND
-    // it (f64 + i32, 1024-row batches: 4.1 against 3.5 ms per 1e9 rows) — and 1.2 - 1.65 x ahead where that kernel's tiles come out
-    // partial (1000-row batches 5.1 against 8.4, four columns 9.1 against 14.5; 1500 rows 5.8 / 6.9) — until that kernel's tiles at
-    // the end of a batch took its DMA path as well (FusedFilterArgs::ends: 1000-row batches 8.4 -> 4.4, four columns 14.2 -> 6.9), which
-    // puts it ahead there too.  So the pair is NOT the default: rdf_set_option("filter_mixed", 2) takes it wherever its forms apply
-    // (tests, A/B), 1 for short batches of which less than 3/4 of the rows lie in whole 1024-row tiles, 0 (default) never.
-    std::vector<int> grp_a, grp_b;           // frame columns of the predicate's width / of the other width
-    int es_a = 0, es_b = 0;
-    bool mixed = false;
-    if (es0 == 0 && ctx.opt_filter_block && ctx.opt_filter_mixed) {
-        const int64_t mean0 = (f.total_rows + f.nchunks - 1) / f.nchunks;
-        const bool partial_tiles = f.max_clen < 2 * kWDmaTile && (mean0 < kWDmaTile || (double)kWDmaTile / (double)mean0 < 0.75);
-        es_a = dtype_size(f.col_dtype[fa.term[0].col]);
-        bool ok = fa.nterms == 1 || dtype_size(f.col_dtype[fa.term[1].col]) == es_a;
-        for (int k = 0; k < f.ncols && ok; ++k) {
-            const int w = dtype_size(f.col_dtype[k]);
-            if (w != 4 && w != 8) ok = false;
-            else (w == es_a ? grp_a : grp_b).push_back(k);
-        }
-        mixed = ok && !grp_a.empty() && !grp_b.empty() && (ctx.opt_filter_mixed == 2 || partial_tiles);
-        es_b = 12 - es_a;
-    }
     // Which form (round 6, measured by batch length: profiles/r06_filter_frame_ragged_batches.jsonl).  The block kernel's time goes with the
     // SLOTS it walks, not with the rows in them: short batches that fill their slots (>= 0.9: the readers' 1024-row batches, batches
     // of 1000 rows) take the short form; batches that average at least half a tile and fill their tiles to 0.5 (one column) / 0.65
@@ -358,18 +332,13 @@ rdf_status filter_frame_fused(rdf_frame& f, const rdf_expr_node* nodes, int32_t 
         if (fm.long_tiles) RDF_TRY(frame_tiles(f, (int)fm.tile_rows, &fm.tiles));
         return RDF_OK;
     };
-    Form form, form_a, form_b;               // the frame's (columns of one width) / the two groups' (each picks its own: the second launch reads
-                                             // the first one's mask in row order, so their tiles need not coincide)
-    if (mixed) {
-        RDF_TRY(pick_form(es_a, (int)grp_a.size(), form_a));
-        RDF_TRY(pick_form(es_b, (int)grp_b.size(), form_b));
-        if (!form_a.block() || !form_b.block()) mixed = false;
-    } else RDF_TRY(pick_form(es0, f.ncols, form));
-    const bool block_tiles = mixed ? form_a.long_tiles : form.long_tiles;       // (mixed: the first launch's form; only the wait check below asks)
+    Form form;
+    RDF_TRY(pick_form(es0, f.ncols, form));
+    const bool block_tiles = form.long_tiles;
     const int short_shift = form.short_shift;
-    const bool block_short = !mixed && short_shift >= 0;
+    const bool block_short = short_shift >= 0;
     const rdf_frame::Tiles* tiles = form.tiles;
-    if (!mixed && !form.block()) RDF_TRY(frame_tiles(f, kWDmaTile, &tiles));
+    if (!form.block()) RDF_TRY(frame_tiles(f, kWDmaTile, &tiles));
     RDF_TRY(frame_new_buffers(nf, f.mask_padded_rows + 64, true));
     void* pouts = nullptr;
     RDF_TRY(arena_alloc(sizeof(DevOutChunk) * (size_t)f.ncols * (size_t)f.nchunks + 64, &pouts));
@@ -386,11 +355,11 @@ rdf_status filter_frame_fused(rdf_frame& f, const rdf_expr_node* nodes, int32_t 
     ta.cols = o.d_cols;
     HIP_TRY(launch_frame_tables(ta, ctx.stream));
     FilterWArgs& wa = fa.w;
-    wa.t.chunk_tile_start = block_short || mixed ? nullptr : tiles->d_start;
+    wa.t.chunk_tile_start = block_short ? nullptr : tiles->d_start;
     wa.t.chunk_len = f.d_clen;
     wa.t.nchunks = f.nchunks;
-    wa.t.ntiles = mixed ? 0 : block_short ? (f.nchunks + (8 >> short_shift) - 1) / (8 >> short_shift) : tiles->ntiles;
-    wa.tile_inv = block_short || mixed ? 0 : tiles->tile_inv;
+    wa.t.ntiles = block_short ? (f.nchunks + (8 >> short_shift) - 1) / (8 >> short_shift) : tiles->ntiles;
+    wa.tile_inv = block_short ? 0 : tiles->tile_inv;
     wa.cols = f.d_cols;
     wa.outs = (DevOutChunk*)pouts;
     wa.out_null_counts = (int64_t*)pnc;
@@ -401,56 +370,7 @@ rdf_status filter_frame_fused(rdf_frame& f, const rdf_expr_node* nodes, int32_t 
         if (f.nchunks == 1) { wa.cols0[k] = f.dev[(size_t)k]; wa.outs0[k] = DevOutChunk{nf.values[k], nf.validity[k]}; }
     }
     fa.out_len = o.d_clen;
-    if (mixed) {
-        // the two groups' descriptor tables: their columns' rows of the frame-order tables, side by side
-        auto gather = [&](const std::vector<int>& g, const DevChunkCol** cols, const DevOutChunk** outs) -> rdf_status {
-            void *pc = nullptr, *po = nullptr;
-            RDF_TRY(arena_alloc(sizeof(DevChunkCol) * g.size() * (size_t)f.nchunks + 64, &pc));
-            RDF_TRY(arena_alloc(sizeof(DevOutChunk) * g.size() * (size_t)f.nchunks + 64, &po));
-            for (size_t i = 0; i < g.size(); ++i) {
-                HIP_TRY(hipMemcpyAsync((DevChunkCol*)pc + i * (size_t)f.nchunks, f.d_cols + (size_t)g[i] * (size_t)f.nchunks, sizeof(DevChunkCol) * (size_t)f.nchunks, hipMemcpyDeviceToDevice, ctx.stream));
-                HIP_TRY(hipMemcpyAsync((DevOutChunk*)po + i * (size_t)f.nchunks, (DevOutChunk*)pouts + (size_t)g[i] * (size_t)f.nchunks, sizeof(DevOutChunk) * (size_t)f.nchunks, hipMemcpyDeviceToDevice, ctx.stream));
-            }
-            *cols = (const DevChunkCol*)pc; *outs = (const DevOutChunk*)po;
-            return RDF_OK;
-        };
-        auto group_args = [&](BFilterArgs& ba, const std::vector<int>& g, int es, int64_t nc_row0, const Form& fm, bool* nulls) -> rdf_status {
-            memset(&ba, 0, sizeof ba);
-            ba.w = wa;
-            if (fm.long_tiles) { ba.w.t.chunk_tile_start = fm.tiles->d_start; ba.w.t.ntiles = fm.tiles->ntiles; ba.w.tile_inv = fm.tiles->tile_inv; }
-            else ba.w.t.ntiles = (f.nchunks + (8 >> fm.short_shift) - 1) / (8 >> fm.short_shift);
-            if (f.nchunks > 1) RDF_TRY(gather(g, &ba.w.cols, &ba.w.outs));
-            ba.w.ncols = (int32_t)g.size();
-            ba.w.out_null_counts = (int64_t*)pnc + nc_row0 * f.nchunks;
-            ba.w.t.mask = f.d_mask_cols;
-            if (f.nchunks == 1) ba.w.mask0 = DevChunkCol{f.mask_values, nullptr, 0};
-            *nulls = false;
-            for (size_t i = 0; i < g.size(); ++i) {
-                ba.w.esize[i] = es;
-                *nulls |= f.col_nullable[g[i]];
-                if (f.nchunks == 1) { ba.w.cols0[i] = f.dev[(size_t)g[i]]; ba.w.outs0[i] = DevOutChunk{nf.values[g[i]], nf.validity[g[i]]}; }
-            }
-            if (!fm.long_tiles) { ba.short_mode = 1; ba.short_shift = fm.short_shift; }
-            else if (bfilter_owned_ok(f.nchunks, f.max_clen, f.total_rows)) ba.short_mode = 2;
-            ba.out_len = o.d_clen;
-            RDF_TRY(bfilter_scratch(ba));
-            return RDF_OK;
-        };
-        BFilterArgs ba, bb;
-        bool nulls_a = false, nulls_b = false;
-        RDF_TRY(group_args(ba, grp_a, es_a, 0, form_a, &nulls_a));
-        for (int i = 0; i < fa.nterms; ++i) {
-            ba.bterm[i] = bf_term(fa.term[i]);
-            ba.bterm[i].col = (int32_t)(std::find(grp_a.begin(), grp_a.end(), fa.term[i].col) - grp_a.begin());
-        }
-        ba.nterms = fa.nterms; ba.combine = fa.combine;
-        ba.keep_out = 1;
-        HIP_TRY(launch_bfilter(ba, es_a, nulls_a, ctx.stream));
-        RDF_TRY(group_args(bb, grp_b, es_b, (int64_t)grp_a.size(), form_b, &nulls_b));
-        bb.nterms = 0;                           // the kept rows are the mask the first launch has just written
-        HIP_TRY(launch_bfilter(bb, es_b, nulls_b, ctx.stream));
-        block_args = ba; block_args2 = bb;
-    } else if (block_tiles || block_short) {
+    if (block_tiles || block_short) {
         BFilterArgs ba;
         memset(&ba, 0, sizeof ba);
         ba.w = wa;
@@ -465,22 +385,22 @@ rdf_status filter_frame_fused(rdf_frame& f, const rdf_expr_node* nodes, int32_t 
         HIP_TRY(launch_bfilter(ba, es0, nulls, ctx.stream));
         block_args = ba;
     } else {
-    fa.lookback = f.max_clen > kWDmaTile ? ctx.opt_filter_lookback : 0;
-    // tiles at the end of their batch through the DMA path as well, when there is more than the odd one of them (more than 1 % of the
-    // tiles' rows do not exist): 1000-row batches of an f64 + i32 frame 8.4 -> 4.3 ms per 1e9 rows; frames of full tiles keep the
-    // instantiation without that code (it costs them 15 - 20 % when compiled in)
-    fa.ends = ctx.opt_filter_ends && (double)f.total_rows < 0.99 * (double)tiles->ntiles * (double)kWDmaTile ? 1 : 0;
-    if (fa.lookback) {
-        void* ps = nullptr;
-        // [ntiles] tile states, 8 spare words, [ntiles] super-tile states (at the index of a super-tile's first tile), 8 spare words,
-        // [ntiles] rows in front of a super-tile (same index), then the 64 ticket counters, 128 bytes apart
-        const size_t words = 3 * (size_t)tiles->ntiles + 32 + 64 * 16;
-        RDF_TRY(arena_alloc(sizeof(unsigned long long) * words, &ps));
-        HIP_TRY(hipMemsetAsync(ps, 0, sizeof(unsigned long long) * words, ctx.stream));
-        fa.tile_state = (unsigned long long*)ps;
-        fa.ticket = (unsigned int*)((unsigned long long*)ps + 3 * (size_t)tiles->ntiles + 32);
-    }
-    HIP_TRY(launch_ffilter(fa, ctx.stream));
+        fa.lookback = f.max_clen > kWDmaTile;
+        // tiles at the end of their batch through the DMA path as well, when there is more than the odd one of them (more than 1 % of the
+        // tiles' rows do not exist): 1000-row batches of an f64 + i32 frame 8.4 -> 4.3 ms per 1e9 rows; frames of full tiles keep the
+        // instantiation without that code (it costs them 15 - 20 % when compiled in)
+        fa.ends = ctx.opt_filter_ends && (double)f.total_rows < 0.99 * (double)tiles->ntiles * (double)kWDmaTile ? 1 : 0;
+        if (fa.lookback) {
+            void* ps = nullptr;
+            // [ntiles] tile states, 8 spare words, [ntiles] super-tile states (at the index of a super-tile's first tile), 8 spare words,
+            // [ntiles] rows in front of a super-tile (same index), then the 64 ticket counters, 128 bytes apart
+            const size_t words = 3 * (size_t)tiles->ntiles + 32 + 64 * 16;
+            RDF_TRY(arena_alloc(sizeof(unsigned long long) * words, &ps));
+            HIP_TRY(hipMemsetAsync(ps, 0, sizeof(unsigned long long) * words, ctx.stream));
+            fa.tile_state = (unsigned long long*)ps;
+            fa.ticket = (unsigned int*)((unsigned long long*)ps + 3 * (size_t)tiles->ntiles + 32);
+        }
+        HIP_TRY(launch_ffilter(fa, ctx.stream));
     }
     // rows of the new frame: the sum of its batch lengths
     void* psum = nullptr;
@@ -493,10 +413,6 @@ rdf_status filter_frame_fused(rdf_frame& f, const rdf_expr_node* nodes, int32_t 
     int64_t kept = 0;
     memcpy(&kept, ctx.pinned, 8);
     if (block_tiles) RDF_TRY(bfilter_check(block_args));
-    if (mixed && form_b.long_tiles) RDF_TRY(bfilter_check(block_args2));
-    if (mixed)
-        ctx.last_kernel = block_args.short_mode == 1 ? "bfilter_kernel x 2 (two column widths, short batches)" : block_args.short_mode == 2 ? "bfilter_kernel x 2 (two column widths, a block per batch)" : "bfilter_kernel x 2 (two column widths)";
-    else
     ctx.last_kernel = block_tiles ? (block_args.short_mode == 2 ? "bfilter_kernel (a block per batch)" : "bfilter_kernel") : block_short ? "bfilter_kernel (short batches)" : "ffilter_dma_kernel";
     o.total_rows = kept;
     *out = nf.f.release();
@@ -733,7 +649,7 @@ rdf_status rdf_filter_frame(rdf_frame* frame, const rdf_expr_node* nodes, int32_
     bool all_wide = true;
     for (int k = 0; k < f.ncols; ++k) { const int es = dtype_size(f.col_dtype[k]); all_wide &= es == 8 || es == 4; }
     const int64_t mean_len = f.total_rows / f.nchunks;
-    const bool dma_ok = all_wide && f.total_rows >= f.nchunks * (int64_t)(kWDmaTile * 3 / 4) && ctx.opt_filter_gen >= 2;
+    const bool dma_ok = all_wide && f.total_rows >= f.nchunks * (int64_t)(kWDmaTile * 3 / 4);
     int tile_rows = dma_ok ? kWDmaTile : mean_len <= 256 ? kWTileSmall : kWTile;
     FilterWArgs wa;
     int64_t* d_scan = nullptr;
@@ -747,7 +663,6 @@ rdf_status rdf_filter_frame(rdf_frame* frame, const rdf_expr_node* nodes, int32_
         wa.t.nchunks = f.nchunks;
         wa.t.ntiles = tiles->ntiles;
         wa.tile_inv = tiles->tile_inv;
-        wa.prefetch = ctx.opt_filter_gen != 3;
         if (f.nchunks == 1) { wa.mask0 = DevChunkCol{f.mask_values, nullptr, 0}; wa.len0 = f.clen[0]; }
         void* p = nullptr;
         RDF_TRY(arena_alloc(sizeof(int64_t) * (2 * (size_t)tiles->ntiles + 2 + (size_t)scan_scratch_words(tiles->ntiles)), &p));

@@ -13,8 +13,7 @@ namespace rdfk {
 constexpr int kBlock = 256;          // 4 wavefronts of 64
 constexpr int kVPT = 4;              // rows per thread per tile in the fused evaluator
 constexpr int kEvalTile = kBlock * kVPT;   // 1024 rows: one reference RecordBatch (src/dataframe.rs:352)
-constexpr int kFilterTile = 4096;    // rows per compaction tile (64 mask words, 16 per wave): measured best of 2048 / 4096 / 8192
-constexpr int kFilterTileSmall = 1024;   // the tile for frames in small RecordBatches (mean chunk length <= 2048 rows)
+constexpr int kFilterTile = 4096;    // rows per block tile of mask_count_one_kernel / compact_one_kernel (64 mask words, 16 per wave): measured best of 2048 / 4096 / 8192
 constexpr int kMaxCode = 56;         // accumulator-machine instructions per program
 constexpr int kMaxCols = 8;          // columns referenced by one program
 constexpr int kMaxFrameCols = 64;    // columns of a pinned frame (programs run over frames of <= kMaxCols columns)
@@ -160,31 +159,21 @@ struct SpecArgs {
 
 struct MaskTables {
     const DevChunkCol* mask;             // [nchunks]; values = bit-packed booleans
-    const int64_t*     chunk_tile_start; // [nchunks + 1], tiles of kFilterTile rows
+    const int64_t*     chunk_tile_start; // [nchunks + 1], in tiles of the launch's tile size
     const int64_t*     chunk_len;        // [nchunks]
     int64_t            nchunks, ntiles;
 };
-struct FilterArgs {
-    MaskTables         t;
-    const DevChunkCol* cols;             // [ncols * nchunks]
-    DevOutChunk*       outs;             // [ncols * nchunks]
-    int64_t*           out_null_counts;  // [ncols * nchunks]
-    const int64_t*     tile_scan;        // [ntiles + 1] exclusive scan of per-tile keep counts
-    int32_t            ncols;
-    int32_t            esize[kMaxFilterCols];
-};
 
-// Compaction of a frame held in ONE chunk (the long-column case): every descriptor travels in the kernel arguments, so no
-// table is read between the data loads of a tile.
+// Compaction of ONE column held in ONE chunk, on block tiles of kFilterTile rows (the layout the wave-granular kernels below do not
+// take, see filter_prepare): every descriptor travels in the kernel arguments, so no table is read between the data loads of a tile.
 struct FilterOneArgs {
     DevChunkCol        mask;
     int64_t            clen, ntiles;
-    const int64_t*     tile_scan;        // [ntiles + 1]
-    int64_t*           out_null_counts;  // [ncols]
-    int32_t            ncols;
-    int32_t            esize[kMaxFilterCols];
-    DevChunkCol        cols[kMaxFilterCols];
-    DevOutChunk        outs[kMaxFilterCols];
+    const int64_t*     tile_scan;        // [ntiles + 1] exclusive scan of the per-tile keep counts
+    int64_t*           out_null_count;   // kept rows whose value is null (pre-zeroed)
+    DevChunkCol        col;
+    DevOutChunk        out;
+    int32_t            esize, pad_;      // element size of the column: 8 / 4 / 2 / 1
 };
 hipError_t launch_compact_one(const FilterOneArgs& a, hipStream_t s);   // kFilterTile-row tiles
 
@@ -201,8 +190,7 @@ struct FilterWArgs {
     int64_t*           out_null_counts;  // [ncols * nchunks]
     const int64_t*     tile_scan;        // [ntiles + 1] exclusive scan of the per-tile keep counts
     uint64_t           tile_inv;         // see find_chunk_tile_inv
-    int32_t            ncols, prefetch;  // prefetch: look the next tile up under the current tile's loads (chunked frames)
-    int32_t            ends, pad_;       // ends (fcompact_dma_kernel): 1 = tiles at the END of a chunk take the LDS-DMA path too (chunk lengths that are not multiples of the tile)
+    int32_t            ncols, ends;      // ends (fcompact_dma_kernel): 1 = tiles at the END of a chunk take the LDS-DMA path too (chunk lengths that are not multiples of the tile)
     int32_t            esize[kMaxFilterCols];
     DevChunkCol        cols0[kMaxFilterCols];   // nchunks == 1
     DevOutChunk        outs0[kMaxFilterCols];
@@ -219,7 +207,7 @@ struct FusedFilterArgs {
     FilterWArgs         w;            // tile tables, column / output descriptors, null counters (mask / tile_scan unused)
     FusedTerm           term[2];
     int32_t             nterms, combine;     // combine: RDF_OP_AND / RDF_OP_OR of the two terms
-    int32_t             lookback, ends;      // lookback: some batch spans several tiles: tiles are taken by ticket, prefixes by look-back; ends: 1 = the instantiation whose tiles at the END of a batch take the LDS-DMA path too (batch lengths that are not multiples of the tile)
+    int32_t             lookback, ends;      // lookback: 1 = some batch spans several tiles: tiles are taken by ticket, prefixes by look-back (0: a batch is a tile); ends: 1 = the instantiation whose tiles at the END of a batch take the LDS-DMA path too (batch lengths that are not multiples of the tile)
     int64_t*            out_len;             // [nchunks] kept rows per batch (pre-zeroed)
     unsigned long long* tile_state;          // (lookback; pre-zeroed) [ntiles] tile states, status << 62 | rows; 8 spare words; [ntiles] super-tile states
     unsigned int*       ticket;              // (lookback; pre-zeroed) 64 counters, 128 bytes apart
@@ -244,7 +232,6 @@ struct BFilterArgs {
     unsigned long long* tile_state;          // (pre-zeroed) [ntiles]: 0 -> count -> prefix
     unsigned int*       ticket;              // (pre-zeroed) 64 counters, 128 bytes apart
     int32_t             stall_test, pad;     // tests: 1 = the scanner does nothing (every wait must give up and the call must fail, not hang)
-    int32_t             keep_out, force_multi;   // keep_out 1 (predicate form): the kept rows are ALSO written, in row order, into the mask chunks w.t.mask / w.mask0 describe (bit offsets 0, 8-byte aligned: the frame's own mask) — a frame of two column widths is compacted by two launches, the second one by that mask; force_multi 1: the several-column instantiation (its tile geometry) whatever ncols
     int32_t             short_mode, short_shift;   // short_mode 1: no batch is longer than a tile — a batch takes 1 << short_shift waves of one block, w.t.ntiles counts tiles of 8 >> short_shift BATCHES (chunk_tile_start / tile_inv / tile_state unused), block 0 works like the others; 2: the long form's tiles and tables, but a block draws whole batches (ticket = batch) and adds up the rows in front of a tile itself (tile_state unused, no scanner block)
     unsigned int*       abort_flag;          // (pre-zeroed) set by a wait that saw no progress for kBfWaitSeconds: every waiter then leaves, the host reports a device error — a stuck prefix must cost a call, not the GPU
 };
@@ -695,10 +682,8 @@ hipError_t jit_launch_grouped(const JitKernel& k, const GSpecArgs& a, int grid, 
 int jit_compiled_count();
 void jit_shutdown();                                 // kills compilers in flight and joins every helper thread (atexit / library unload; idempotent)
 hipError_t launch_filter_agg_f64(const FilterAggF64Args& a, int cmp_op, int grid, hipStream_t s);
-hipError_t launch_mask_count(const MaskTables& t, int tile_rows, int64_t* tile_counts, hipStream_t s);   // tile_rows: kFilterTile or kFilterTileSmall
 hipError_t launch_scan(const int64_t* counts, int64_t* scan, int64_t n, int64_t* scratch, hipStream_t s);
 int64_t scan_scratch_words(int64_t n);
-hipError_t launch_compact(const FilterArgs& a, int tile_rows, hipStream_t s);
 hipError_t launch_take(const TakeArgs& a, hipStream_t s);
 hipError_t launch_sort_keys(const SortKeyArgs& a, hipStream_t s);
 hipError_t launch_join_buckets(const JoinBucketArgs& a, hipStream_t s);

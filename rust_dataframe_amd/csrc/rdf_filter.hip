@@ -682,14 +682,14 @@ __global__ __launch_bounds__(kBlock, 4) void ffilter_dma_kernel(const FusedFilte
             long long local = 0, before = 0;
             const bool closes = (j & 63) == 63 || last;    // the super-tile's last tile
             int64_t q = (j >> 6) - 1;                       // super-tiles of this batch before mine
-            // Round 5 (lookback == 2): the walk over the super-tiles' totals — one word per super-tile, a cache line apart: up to 64
+            // The walk over the super-tiles' totals — one word per super-tile, a cache line apart: up to 64
             // line fetches per step — is done by ONE tile per super-tile, its first, which leaves what it found (the rows of the batch
             // in front of the super-tile) in a word of its own; the other 63 tiles read that one word — with lane 63 of the SAME
             // 64-wide read that brings their neighbours' counts (a tile has at most 63 neighbours before it), so a tile of a batch of
             // any length pays one memory round trip for its position, as a tile of a 64-tile batch does.  Every wait is for a tile
             // with an earlier ticket, as before.
             unsigned long long* super_excl = super_state + a.t.ntiles + 8;
-            const bool follower = fa.lookback >= 2 && q >= 0 && (j & 63) != 0;
+            const bool follower = q >= 0 && (j & 63) != 0;
             bool need_local = nb > 0, need_before = follower;
             if (!need_local && closes) st(super_state + sfirst, kFfAggregate | (unsigned long long)cnt);
             while (need_local || need_before) {
@@ -713,13 +713,13 @@ __global__ __launch_bounds__(kBlock, 4) void ffilter_dma_kernel(const FusedFilte
                 if (!progress) __builtin_amdgcn_s_sleep(2);
             }
             if (follower) q = -1;
-            const bool leads = fa.lookback >= 2 && q >= 0;
-            // lookback == 3: the leader adds up the nearest super-tiles from their tiles' OWN counts (one 64-wide read each, all in
+            const bool leads = q >= 0;
+            // The leader adds up the nearest super-tiles from their tiles' OWN counts (one 64-wide read each, all in
             // flight together with the walk over the older totals) instead of waiting for each of them to be added up by its last
             // tile first — a total is one more memory round trip away than the counts it is made of, and every tile of the leader's
             // super-tile waits that long.  Super-tiles further back than kRawSupers have their totals out by the time anybody asks.
             constexpr int kRawSupers = 8;
-            const int nraw = leads && fa.lookback == 3 ? (int)(q + 1 < kRawSupers ? q + 1 : kRawSupers) : 0;
+            const int nraw = leads ? (int)(q + 1 < kRawSupers ? q + 1 : kRawSupers) : 0;
             bool need_raw = nraw > 0;
             q -= nraw;
             while (q >= 0 || need_raw) {
@@ -825,7 +825,7 @@ hipError_t launch_fcompact(const FilterWArgs& a, int tile_rows, hipStream_t s) {
     int es = a.esize[0];
     for (int k = 1; k < a.ncols; ++k) if (a.esize[k] != es) es = 0;
     const int grid = wgrid(a.t.ntiles, tile_rows == kWTileSmall ? 8 : 4);   // 19 KB of LDS per block at WW = 8
-    const bool pf = a.t.nchunks > 1 && a.prefetch;   // one chunk: nothing to look up
+    const bool pf = a.t.nchunks > 1;   // look the next tile up under the current tile's loads; one chunk: nothing to look up
 #define RDF_FCOMPACT_LAUNCH(WW, PF)                                                                                    \
     switch (es) {                                                                                                      \
         case 8: hipLaunchKernelGGL((fcompact_kernel<8, WW, PF>), dim3(grid), dim3(kBlock), 0, s, a); break;            \

@@ -142,19 +142,11 @@ __global__ __launch_bounds__(kBlock) void filter_agg_f64_kernel(const FilterAggF
 }
 
 // ------------------------------------------------------------------------------------------------
-// stream compaction (Column::filter).  A tile never spans two chunks, and wave w of the block owns WW consecutive mask
-// words of it: WW = 16 (tiles of kFilterTile = 4096 rows, 1024 per wave: the best of 2048 / 4096 / 8192 on long chunks) or
-// WW = 4 (tiles of kFilterTileSmall = 1024 rows) for frames held in the reader's 1024-row RecordBatches, where a
-// 4096-row tile would leave three of the four waves without rows.  The host picks per call (filter_prepare).
+// stream compaction (Column::filter) of ONE column held in ONE chunk, on block tiles: wave w of the block owns WW = 16
+// consecutive mask words of a tile (tiles of kFilterTile = 4096 rows, 1024 per wave: the best of 2048 / 4096 / 8192 on long
+// chunks).  Every other layout runs on the wave-granular kernels of rdf_filter.hip (filter_prepare picks).
 template <int WW> constexpr int filter_tile_rows() { return WW * 64 * (kBlock / 64); }
-static_assert(filter_tile_rows<16>() == kFilterTile && filter_tile_rows<4>() == kFilterTileSmall, "tile sizes of the two instantiations");
-
-template <int WW>
-__device__ __forceinline__ void locate_tile(const MaskTables& t, int64_t tile, int64_t& c, int64_t& r0, int64_t& clen) {
-    c = t.nchunks == 1 ? 0 : find_chunk_tile(t.chunk_tile_start, t.nchunks, tile);
-    r0 = (tile - t.chunk_tile_start[c]) * filter_tile_rows<WW>();
-    clen = t.chunk_len[c];
-}
+static_assert(filter_tile_rows<16>() == kFilterTile, "tile size of the block-tile kernels");
 
 // keep-words of this wave's WW * 64 rows: mask value bits AND mask validity bits, rows past the chunk end cleared
 template <int kWW>
@@ -168,27 +160,8 @@ __device__ __forceinline__ void keep_words(const DevChunkCol& m, int64_t rw, int
     }
 }
 
-// One wave per tile-quarter: counts the kept rows of its WW words (s_bcnt1); reads 1 bit/row.
-template <int kWW>
-__global__ __launch_bounds__(kBlock) void mask_count_kernel(const MaskTables t, int64_t* tile_counts) {
-    __shared__ int wave_cnt[kBlock / 64];
-    const int wave = wave_id();
-    for (int64_t tile = blockIdx.x; tile < t.ntiles; tile += gridDim.x) {
-        int64_t c, r0, clen;
-        locate_tile<kWW>(t, tile, c, r0, clen);
-        uint64_t kw[kWW];
-        keep_words<kWW>(t.mask[c], r0 + (int64_t)wave * (kWW * 64), clen, kw);
-        int cnt = 0;
-#pragma unroll
-        for (int i = 0; i < kWW; ++i) cnt += __popcll(kw[i]);
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0) wave_cnt[wave] = cnt;
-        __syncthreads();
-        if (threadIdx.x == 0) tile_counts[tile] = (int64_t)wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
-    }
-}
-
-// The same for a mask held in one chunk: its descriptor and length travel in the kernel arguments.
+// One wave per tile-quarter: counts the kept rows of its WW words (s_bcnt1); reads 1 bit/row.  The mask's descriptor and
+// length travel in the kernel arguments.
 __global__ __launch_bounds__(kBlock) void mask_count_one_kernel(const DevChunkCol mask, int64_t clen, int64_t ntiles, int64_t* tile_counts) {
     constexpr int kWW = 16;
     __shared__ int wave_cnt[kBlock / 64];
@@ -264,9 +237,9 @@ __global__ __launch_bounds__(kScanThreads) void scan_add_kernel(int64_t* scan, i
     for (int j = 0; j < kScanPer; ++j) if (base + j < n) scan[base + j] += off;
 }
 
-// Compaction of one column of one wave's 512 rows.  Ranks come from popcounts of the wave's keep words
+// Compaction of one column of one wave's kWW * 64 rows (1024).  Ranks come from popcounts of the wave's keep words
 // (scalar prefix + lane prefix): no shuffles, no atomics for the values.  Kept values are staged in the
-// wave's PRIVATE 4 KiB LDS region at their rank and written out as one contiguous, coalesced run at
+// wave's PRIVATE 8 KiB LDS region at their rank and written out as one contiguous, coalesced run at
 // the wave's output offset — waves never wait for each other inside a column.
 template <typename T, int kWW>
 __device__ __forceinline__ void compact_wave(const DevChunkCol col, const DevOutChunk oc, int64_t rw, int64_t clen,
@@ -314,83 +287,20 @@ __device__ __forceinline__ void compact_wave(const DevChunkCol col, const DevOut
     __builtin_amdgcn_wave_barrier();
 }
 
-constexpr int kCompactCols = 8;  // columns per launch (the host loops over wider frames)
-
-// ES = common element size of all columns of the launch (8/4/2/1) or 0 for mixed sizes.
-template <int ES, int kWW>
-__global__ __launch_bounds__(kBlock) void compact_kernel(const FilterArgs a) {
-    __shared__ __attribute__((aligned(16))) unsigned char stage[kBlock / 64][kWW * 64 * 8];  // 8 KiB (WW = 16) or 2 KiB per wave
-    __shared__ uint8_t vstage[kBlock / 64][kWW * 64];
-    __shared__ int wave_cnt[2][kBlock / 64];
-    const int lane = threadIdx.x & 63;
-    const int wave = wave_id();
-    // per-wave null counters per column (in LDS: the kernel has no registers to spare), flushed once per
-    // (column, chunk) — not once per tile
-    __shared__ uint32_t nullacc[kBlock / 64][kCompactCols];
-    if (lane < kCompactCols) nullacc[wave][lane] = 0;
-    __builtin_amdgcn_wave_barrier();
-    int64_t cur_chunk = -1;
-    int parity = 0;
-    for (int64_t tile = blockIdx.x; tile < a.t.ntiles; tile += gridDim.x, parity ^= 1) {
-        int64_t c, r0, clen;
-        locate_tile<kWW>(a.t, tile, c, r0, clen);
-        // where this tile's kept rows start in the chunk's output: asked for before the mask words are waited on
-        const int64_t out_base = a.tile_scan[tile] - a.tile_scan[a.t.chunk_tile_start[c]];
-        if (c != cur_chunk) {
-            if (cur_chunk >= 0 && lane < a.ncols && nullacc[wave][lane]) {
-                atomicAdd((unsigned long long*)&a.out_null_counts[(int64_t)lane * a.t.nchunks + cur_chunk], (unsigned long long)nullacc[wave][lane]);
-                nullacc[wave][lane] = 0;
-            }
-            __builtin_amdgcn_wave_barrier();
-            cur_chunk = c;
-        }
-        const int64_t rw = r0 + (int64_t)wave * (kWW * 64);
-        uint64_t kw[kWW];
-        keep_words<kWW>(a.t.mask[c], rw, clen, kw);
-        int cnt = 0;
-#pragma unroll
-        for (int i = 0; i < kWW; ++i) cnt += __popcll(kw[i]);
-        if (lane == 0) wave_cnt[parity][wave] = cnt;
-        __syncthreads();  // the only block barrier per tile (wave_cnt is double-buffered by tile parity)
-        int wave_base = 0;
-#pragma unroll
-        for (int w = 0; w < kBlock / 64; ++w) if (w < wave) wave_base += wave_cnt[parity][w];
-        if (cnt > 0) {
-            const int64_t wave_out = out_base + wave_base;
-#pragma unroll 1
-            for (int k = 0; k < a.ncols; ++k) {
-                const DevChunkCol col = a.cols[(int64_t)k * a.t.nchunks + c];
-                const DevOutChunk oc = a.outs[(int64_t)k * a.t.nchunks + c];
-                uint32_t nn = 0;
-                const int es = ES ? ES : a.esize[k];
-                if (es == 8) compact_wave<uint64_t, kWW>(col, oc, rw, clen, wave_out, kw, cnt, stage[wave], vstage[wave], nn);
-                else if (es == 4) compact_wave<uint32_t, kWW>(col, oc, rw, clen, wave_out, kw, cnt, stage[wave], vstage[wave], nn);
-                else if (es == 2) compact_wave<uint16_t, kWW>(col, oc, rw, clen, wave_out, kw, cnt, stage[wave], vstage[wave], nn);
-                else compact_wave<uint8_t, kWW>(col, oc, rw, clen, wave_out, kw, cnt, stage[wave], vstage[wave], nn);
-                if (lane == 0 && nn) nullacc[wave][k] += nn;
-            }
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (cur_chunk >= 0 && lane < a.ncols && nullacc[wave][lane])
-        atomicAdd((unsigned long long*)&a.out_null_counts[(int64_t)lane * a.t.nchunks + cur_chunk], (unsigned long long)nullacc[wave][lane]);
-}
-
-// The same for a frame in one chunk, descriptors in the kernel arguments (FilterOneArgs): the per-tile chain is
-// mask words -> barrier -> values -> store, without the chunk lookup and the two descriptor-table reads in between.
-template <int ES>
+// One column of one chunk, descriptors in the kernel arguments (FilterOneArgs): the per-tile chain is mask words -> barrier ->
+// values -> store, with no chunk lookup and no descriptor-table read in between.
+template <typename T>
 __global__ __launch_bounds__(kBlock) void compact_one_kernel(const FilterOneArgs a) {
     constexpr int kWW = 16;
-    __shared__ __attribute__((aligned(16))) unsigned char stage[kBlock / 64][kWW * 64 * 8];
+    __shared__ __attribute__((aligned(16))) unsigned char stage[kBlock / 64][kWW * 64 * 8];  // 8 KiB per wave
     __shared__ uint8_t vstage[kBlock / 64][kWW * 64];
     __shared__ int wave_cnt[2][kBlock / 64];
-    __shared__ uint32_t nullacc[kBlock / 64][kCompactCols];
     const int lane = threadIdx.x & 63;
     const int wave = wave_id();
-    if (lane < kCompactCols) nullacc[wave][lane] = 0;
-    __builtin_amdgcn_wave_barrier();
+    uint32_t nulls = 0;       // (lane 0) kept rows of this wave whose value is null
     int parity = 0;
     for (int64_t tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x, parity ^= 1) {
+        // where this tile's kept rows start in the output: asked for before the mask words are waited on
         const int64_t out_base = a.tile_scan[tile];
         const int64_t rw = tile * filter_tile_rows<kWW>() + (int64_t)wave * (kWW * 64);
         uint64_t kw[kWW];
@@ -399,26 +309,13 @@ __global__ __launch_bounds__(kBlock) void compact_one_kernel(const FilterOneArgs
 #pragma unroll
         for (int i = 0; i < kWW; ++i) cnt += __popcll(kw[i]);
         if (lane == 0) wave_cnt[parity][wave] = cnt;
-        __syncthreads();
+        __syncthreads();  // the only block barrier per tile (wave_cnt is double-buffered by tile parity)
         int wave_base = 0;
 #pragma unroll
         for (int w = 0; w < kBlock / 64; ++w) if (w < wave) wave_base += wave_cnt[parity][w];
-        if (cnt > 0) {
-            const int64_t wave_out = out_base + wave_base;
-#pragma unroll 1
-            for (int k = 0; k < a.ncols; ++k) {
-                uint32_t nn = 0;
-                const int es = ES ? ES : a.esize[k];
-                if (es == 8) compact_wave<uint64_t, kWW>(a.cols[k], a.outs[k], rw, a.clen, wave_out, kw, cnt, stage[wave], vstage[wave], nn);
-                else if (es == 4) compact_wave<uint32_t, kWW>(a.cols[k], a.outs[k], rw, a.clen, wave_out, kw, cnt, stage[wave], vstage[wave], nn);
-                else if (es == 2) compact_wave<uint16_t, kWW>(a.cols[k], a.outs[k], rw, a.clen, wave_out, kw, cnt, stage[wave], vstage[wave], nn);
-                else compact_wave<uint8_t, kWW>(a.cols[k], a.outs[k], rw, a.clen, wave_out, kw, cnt, stage[wave], vstage[wave], nn);
-                if (lane == 0 && nn) nullacc[wave][k] += nn;
-            }
-        }
+        if (cnt > 0) compact_wave<T, kWW>(a.col, a.out, rw, a.clen, out_base + wave_base, kw, cnt, stage[wave], vstage[wave], nulls);
     }
-    __builtin_amdgcn_wave_barrier();
-    if (lane < a.ncols && nullacc[wave][lane]) atomicAdd((unsigned long long*)&a.out_null_counts[lane], (unsigned long long)nullacc[wave][lane]);
+    if (lane == 0 && nulls) atomicAdd((unsigned long long*)a.out_null_count, (unsigned long long)nulls);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1392,14 +1289,6 @@ hipError_t launch_mask_count_one(const DevChunkCol& mask, int64_t clen, int64_t 
     if (grid > 0) hipLaunchKernelGGL(mask_count_one_kernel, dim3((unsigned)grid), dim3(kBlock), 0, s, mask, clen, ntiles, tile_counts);
     return hipGetLastError();
 }
-hipError_t launch_mask_count(const MaskTables& t, int tile_rows, int64_t* tile_counts, hipStream_t s) {
-    int64_t grid = t.ntiles < (int64_t)eval_grid_limit() ? t.ntiles : (int64_t)eval_grid_limit();
-    if (grid > 0) {
-        if (tile_rows == kFilterTileSmall) hipLaunchKernelGGL(mask_count_kernel<4>, dim3((unsigned)grid), dim3(kBlock), 0, s, t, tile_counts);
-        else hipLaunchKernelGGL(mask_count_kernel<16>, dim3((unsigned)grid), dim3(kBlock), 0, s, t, tile_counts);
-    }
-    return hipGetLastError();
-}
 // `scratch` holds ceil(n / 4096) + 1 int64 words.
 hipError_t launch_scan(const int64_t* counts, int64_t* scan, int64_t n, int64_t* scratch, hipStream_t s) {
     const int64_t nseg = (n + kScanSeg - 1) / kScanSeg;
@@ -1409,35 +1298,14 @@ hipError_t launch_scan(const int64_t* counts, int64_t* scan, int64_t n, int64_t*
     return hipGetLastError();
 }
 int64_t scan_scratch_words(int64_t n) { return (n + kScanSeg - 1) / kScanSeg + 2; }
-hipError_t launch_compact(const FilterArgs& a, int tile_rows, hipStream_t s) {
-    int64_t grid = a.t.ntiles < (int64_t)eval_grid_limit() ? a.t.ntiles : (int64_t)eval_grid_limit();
-    if (grid <= 0) return hipSuccess;
-    int es = a.esize[0];
-    for (int k = 1; k < a.ncols; ++k) if (a.esize[k] != es) es = 0;
-#define RDF_COMPACT_LAUNCH(WW)                                                                                          \
-    switch (es) {                                                                                                       \
-        case 8: hipLaunchKernelGGL((compact_kernel<8, WW>), dim3((unsigned)grid), dim3(kBlock), 0, s, a); break;        \
-        case 4: hipLaunchKernelGGL((compact_kernel<4, WW>), dim3((unsigned)grid), dim3(kBlock), 0, s, a); break;        \
-        case 2: hipLaunchKernelGGL((compact_kernel<2, WW>), dim3((unsigned)grid), dim3(kBlock), 0, s, a); break;        \
-        case 1: hipLaunchKernelGGL((compact_kernel<1, WW>), dim3((unsigned)grid), dim3(kBlock), 0, s, a); break;        \
-        default: hipLaunchKernelGGL((compact_kernel<0, WW>), dim3((unsigned)grid), dim3(kBlock), 0, s, a); break;       \
-    }
-    if (tile_rows == kFilterTileSmall) { RDF_COMPACT_LAUNCH(4) } else { RDF_COMPACT_LAUNCH(16) }
-#undef RDF_COMPACT_LAUNCH
-    return hipGetLastError();
-}
-
 hipError_t launch_compact_one(const FilterOneArgs& a, hipStream_t s) {
     int64_t grid = a.ntiles < (int64_t)eval_grid_limit() ? a.ntiles : (int64_t)eval_grid_limit();
     if (grid <= 0) return hipSuccess;
-    int es = a.esize[0];
-    for (int k = 1; k < a.ncols; ++k) if (a.esize[k] != es) es = 0;
-    switch (es) {
-        case 8: hipLaunchKernelGGL((compact_one_kernel<8>), dim3((unsigned)grid), dim3(kBlock), 0, s, a); break;
-        case 4: hipLaunchKernelGGL((compact_one_kernel<4>), dim3((unsigned)grid), dim3(kBlock), 0, s, a); break;
-        case 2: hipLaunchKernelGGL((compact_one_kernel<2>), dim3((unsigned)grid), dim3(kBlock), 0, s, a); break;
-        case 1: hipLaunchKernelGGL((compact_one_kernel<1>), dim3((unsigned)grid), dim3(kBlock), 0, s, a); break;
-        default: hipLaunchKernelGGL((compact_one_kernel<0>), dim3((unsigned)grid), dim3(kBlock), 0, s, a); break;
+    switch (a.esize) {
+        case 8: hipLaunchKernelGGL((compact_one_kernel<uint64_t>), dim3((unsigned)grid), dim3(kBlock), 0, s, a); break;
+        case 4: hipLaunchKernelGGL((compact_one_kernel<uint32_t>), dim3((unsigned)grid), dim3(kBlock), 0, s, a); break;
+        case 2: hipLaunchKernelGGL((compact_one_kernel<uint16_t>), dim3((unsigned)grid), dim3(kBlock), 0, s, a); break;
+        default: hipLaunchKernelGGL((compact_one_kernel<uint8_t>), dim3((unsigned)grid), dim3(kBlock), 0, s, a); break;
     }
     return hipGetLastError();
 }

@@ -395,28 +395,20 @@ def test_filter_frame_one_pass_predicates(gpu, ora, lens, off, nf):
         "or over two nullable columns": e.op("or", e.op("gt", e.col(2), e.scalar(0.9)), e.op("lt", e.col(1), e.scalar(-900, A.I64))),
         "eq keeps almost nothing": e.op("eq", e.col(4), e.scalar(7, A.I32)),
     }
-    seen_kernels = set()
     with A.PinnedFrame(gpu, dev) as frame:
         for name, root in preds.items():
             exp = ora.filter_columns(host, ora.predicate(e, root, host))
             try:
-                # fused 2: the one-pass kernels whatever the batch lengths; 1: the default choice; 0: three passes.  mixed 1 (round 6): a frame
-                # of 8- and 4-byte columns takes the block kernel twice over the same tiles when the predicate's columns are of one width
-                # and the batches fill its slots / tiles — the second launch by the mask the first one wrote (2: wherever those forms
-                # apply; 1, the default: only where the wave-tile kernel's 1024-row tiles come out partial); 0: the wave-tile kernel
-                for fused, mixed in ((2, 2), (2, 0), (1, 2), (1, 1), (0, 2)):
+                # fused 2: the one-pass kernel whatever the batch lengths; 1: the default choice; 0: three passes.  A frame of 8- and
+                # 4-byte columns takes the wave-tile kernel
+                for fused in (2, 1, 0):
                     lib.set_option("filter_fused", fused)
-                    lib.set_option("filter_mixed", mixed)
                     out = gpu.filter_frame(frame, e, root)
                     kern = lib.last_kernel()
-                    one_pass = kern == "ffilter_dma_kernel" or kern.startswith("bfilter_kernel x 2")
-                    if not mixed:
-                        assert kern == "ffilter_dma_kernel", (name, kern)
-                    elif fused != 1:
-                        assert one_pass == bool(fused), (name, kern)
-                    elif max(lens) <= 65536:
-                        assert one_pass, (name, kern)
-                    seen_kernels.add(kern)
+                    if fused != 0:
+                        assert kern == "ffilter_dma_kernel", (name, fused, kern)
+                    else:       # the three passes, not a one-pass kernel against itself
+                        assert kern != "ffilter_dma_kernel" and not kern.startswith("bfilter_kernel"), (name, fused, kern)
                     nc, nch, rows = out.info()
                     assert (nc, nch) == (len(dts), len(lens)) and rows == sum(x.length for x in exp[0]), (name, fused)
                     got = frame_columns(out)
@@ -432,17 +424,14 @@ def test_filter_frame_one_pass_predicates(gpu, ora, lens, off, nf):
                     out.release()
             finally:
                 lib.set_option("filter_fused", 1)
-                lib.set_option("filter_mixed", 1)
-    if sum(lens) >= len(lens) * 768:                 # (layouts the one-pass paths take at all) the two-launch form ran for some predicate
-        assert any(k.startswith("bfilter_kernel x 2") for k in seen_kernels), seen_kernels
 
 
 @pytest.mark.parametrize("lens,nf", [([3_000_000, 1024, 200_000], 0.0), ([1_500_000, 700_001], 0.1)])
 def test_filter_frame_one_pass_on_long_batches(gpu, ora, lens, nf):
-    """Batches far longer than a super-tile of 64 tiles: the offsets inside a batch come from the two-level look-back — round 5: the
-    rows in front of a super-tile are found once per super-tile by its first tile (`filter_lookback` 3, the default: from the nearest
-    super-tiles' tile counts and the older ones' totals; 2: from totals only; any batch length), round 4: by every tile (1).  All
-    against the oracle and the three-pass path, bit for bit."""
+    """Batches far longer than a super-tile of 64 tiles: the offsets inside a batch come from the two-level look-back — the rows in
+    front of a super-tile are found once per super-tile by its first tile, from the nearest super-tiles' tile counts and the older
+    ones' totals.  The block-tile kernel, the wave-tile kernel (default choice and forced) and the three-pass path, all against the
+    oracle, bit for bit."""
     from rust_dataframe_amd import lib
     rng = np.random.default_rng(77)
     dts = [A.F64, A.I64]
@@ -455,21 +444,19 @@ def test_filter_frame_one_pass_on_long_batches(gpu, ora, lens, nf):
         try:
             for name, root in preds.items():
                 exp = ora.filter_columns(host, ora.predicate(e, root, host))
-                for fused, lookback, block in ((1, 3, 1), (1, 3, 0), (1, 2, 0), (2, 1, 0), (0, 3, 1)):
+                for fused, block in ((1, 1), (1, 0), (2, 0), (0, 1)):
                     lib.set_option("filter_fused", fused)
-                    lib.set_option("filter_lookback", lookback)
                     lib.set_option("filter_block", block)      # round 6: block tiles + scanner wave (the default for batches this long)
                     out = gpu.filter_frame(frame, e, root)
                     want_kernel = "bfilter_kernel" if fused and block else "ffilter_dma_kernel" if fused else None
-                    assert want_kernel is None or lib.last_kernel() == want_kernel, (name, fused, lookback, block, lib.last_kernel())
+                    assert want_kernel is None or lib.last_kernel() == want_kernel, (name, fused, block, lib.last_kernel())
                     assert fused or lib.last_kernel() not in ("bfilter_kernel", "ffilter_dma_kernel")
                     got = frame_columns(out)
                     for k in range(len(dts)):
-                        match_unknown_nulls(got[k], exp[k], f"{name} fused={fused} lookback={lookback} block={block} column {k}")
+                        match_unknown_nulls(got[k], exp[k], f"{name} fused={fused} block={block} column {k}")
                     out.release()
         finally:
             lib.set_option("filter_fused", 1)
-            lib.set_option("filter_lookback", 3)
             lib.set_option("filter_block", 1)
 
 

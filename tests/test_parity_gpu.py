@@ -301,8 +301,8 @@ def test_filter_columns_one_pass(gpu, ora):
 
 @pytest.mark.parametrize("lens", [[9000], [5000, 4097], [1024] * 9 + [100]])
 def test_filter_wide_frames_every_kernel_variant(gpu, ora, lens):
-    """11 columns (two launches of <= 8 columns) of mixed and of equal element sizes through the three compaction paths:
-    one long chunk (descriptors in the kernel arguments), long chunks (4096-row tiles), reader batches (1024-row tiles)."""
+    """11 columns (two launches of <= 8 columns) of mixed and of equal element sizes through the wave-tile compaction kernels:
+    one long chunk (descriptors in the kernel arguments), long chunks, reader batches."""
     rng = np.random.default_rng(4000 + len(lens))
     for dts in ([A.F64, A.I64, A.I32, A.U8, A.F32, A.I16, A.U64, A.F64, A.I8, A.U16, A.I64], [A.F64] * 6 + [A.I64] * 5):
         cols = [make_chunks(rng, dt, lens, 0.2 if k % 3 == 0 else 0.0, k % 4) for k, dt in enumerate(dts)]
@@ -312,37 +312,38 @@ def test_filter_wide_frames_every_kernel_variant(gpu, ora, lens):
         got, exp = gpu.filter_columns(cols, mask), ora.filter_columns(cols, mask)
         for k in range(len(cols)):
             assert_chunks_match(got[k], exp[k], exact=True, what=f"lens={lens} column {k} dtype={dts[k]}")
-        from rust_dataframe_amd import lib
-        lib.set_option("filter_one", 0)   # the table-driven kernels on the same input
-        try:
-            got = gpu.filter_columns(cols, mask)
-        finally:
-            lib.set_option("filter_one", 1)
-        for k in range(len(cols)):
-            assert_chunks_match(got[k], exp[k], exact=True, what=f"table-driven, lens={lens} column {k}")
 
 
 @pytest.mark.parametrize("dtype", [A.F64, A.I64, A.F32, A.I32, A.I16, A.U8])
-def test_filter_wave_granular_and_first_generation(gpu, ora, dtype):
-    """Both compaction generations (rdf_set_option("filter_gen", 2 | 1)) on the shapes that separate their code paths:
-    dense tiles (vector loads + 16-byte stores), sparse tiles (kept rows only), tiles that start at odd output positions,
-    chunk slices whose values are not 16-byte aligned, the reader's 1024-row batches (two wave tiles per chunk), chunks
-    shorter than a tile, empty chunks, all-kept / none-kept masks, NULLs in mask and column."""
+def test_filter_wave_granular_and_one_chunk_block_tiles(gpu, ora, dtype):
+    """Column::filter at the default options on the shapes that separate the compaction kernels' code paths: dense tiles (vector
+    loads + 16-byte stores), sparse tiles (kept rows only), tiles that start at odd output positions, chunk slices whose values
+    are not 16-byte aligned, the reader's 1024-row batches (two wave tiles per chunk), chunks shorter than a tile, empty chunks,
+    all-kept / none-kept masks, NULLs in mask and column.
+    The planner's split (filter_prepare) is pinned by the kernel's name: ONE column in ONE chunk runs on the block tiles of
+    compact_one_kernel (label "compact_kernel") unless the LDS-DMA kernel can take it, i.e. unless the column is 8 or 4 bytes wide
+    AND the chunk has at least 768 rows; everything else runs on the wave-tile kernels (fcompact*).  The single-chunk layouts sit
+    below and across the 768-row DMA threshold, 2048 rows (where a smaller block tile was once chosen) and one 4096-row tile, so
+    every dtype reaches compact_one_kernel: the wide ones at 1 and 700 rows, the narrow ones at every length."""
     from rust_dataframe_amd import lib
+    for name, value in (("filter_gen", 1), ("filter_one", 0), ("filter_tile", 1024), ("filter_mixed", 2), ("filter_lookback", 1)):
+        lib.set_option(name, value)      # retired forms: accepted and ignored (include/rdf_mi355x.h) — the kernel names below hold all the same
     rng = np.random.default_rng(700 + dtype)
-    try:
-        for lens, nf, off in [([5000], 0.0, 0), ([1024] * 7 + [333], 0.15, 0), ([4096, 0, 777, 2048], 0.1, 1), ([100, 300, 50, 1, 0, 600], 0.2, 5), ([20000], 0.05, 3)]:
-            col = make_chunks(rng, dtype, lens, nf, off, "extreme" if dtype <= A.U64 else "special")
-            for sel in (0.9, 0.5, 0.05, 1.0, 0.0):
-                mask = [A.HostArray.from_numpy(rng.uniform(size=n) < sel, valid=(rng.uniform(size=n) > 0.1) if nf else None,
-                                               offset=(off * 3) % 11, dtype=A.BOOL, rng=rng) for n in lens]
-                exp = ora.filter(col, mask)
-                for gen in (2, 3, 1):   # default (LDS-DMA tiles where eligible), register-staged wave tiles, first generation
-                    lib.set_option("filter_gen", gen)
-                    assert gpu.filter_count(mask) == ora.filter_count(mask), f"count gen={gen}"
-                    assert_chunks_match(gpu.filter(col, mask), exp, exact=True, what=f"filter gen={gen} {dtype} {lens} sel={sel}")
-    finally:
-        lib.set_option("filter_gen", 2)
+    wide = A.NP_OF[dtype]().itemsize in (8, 4)
+    one_chunk = [([n], nf, off) for n, nf, off in ((1, 0.0, 0), (700, 0.1, 1), (2048, 0.0, 0), (2049, 0.2, 5), (4097, 0.1, 3))]
+    for lens, nf, off in [([5000], 0.0, 0), ([1024] * 7 + [333], 0.15, 0), ([4096, 0, 777, 2048], 0.1, 1), ([100, 300, 50, 1, 0, 600], 0.2, 5), ([20000], 0.05, 3)] + one_chunk:
+        col = make_chunks(rng, dtype, lens, nf, off, "extreme" if dtype <= A.U64 else "special")
+        for sel in (0.9, 0.5, 0.05, 1.0, 0.0):
+            mask = [A.HostArray.from_numpy(rng.uniform(size=n) < sel, valid=(rng.uniform(size=n) > 0.1) if nf else None,
+                                           offset=(off * 3) % 11, dtype=A.BOOL, rng=rng) for n in lens]
+            exp = ora.filter(col, mask)
+            assert gpu.filter_count(mask) == ora.filter_count(mask), f"count {dtype} {lens} sel={sel}"
+            assert_chunks_match(gpu.filter(col, mask), exp, exact=True, what=f"filter {dtype} {lens} sel={sel}")
+            kern = lib.last_kernel()
+            if len(lens) == 1 and not (wide and lens[0] >= 768):
+                assert kern == "compact_kernel", (dtype, lens, sel, kern)
+            else:
+                assert kern.startswith("fcompact"), (dtype, lens, sel, kern)
 
 
 @pytest.mark.parametrize("dtype", NUMERIC)

@@ -74,7 +74,6 @@ def main():
     ap.add_argument("--sort-rows", type=int, default=100_000_000)
     ap.add_argument("--only", type=str, default="")
     ap.add_argument("--fused", type=int, default=1, help="rdf_set_option(\"filter_fused\") of the filter_frame_* entries: 2 forces the one-pass kernel on batches of any length")
-    ap.add_argument("--lookback", type=int, default=3, help="rdf_set_option(\"filter_lookback\"): 3 = a super-tile's first tile finds the rows in front of it from tile counts + older totals (default), 2 = from totals only, 1 = every tile walks the totals (round 4)")
     ap.add_argument("--block", type=int, default=1, help="rdf_set_option(\"filter_block\"): 1 = long batches on block tiles with a scanner wave (rdf_bfilter.hip, round 6, default), 0 = wave tiles + look-back (round 5)")
     ap.add_argument("--block-rows", type=int, default=0, help="rdf_set_option(\"filter_block_rows\"): the mean batch length from which the block kernel is taken (0: the library's default)")
     ap.add_argument("--short", type=int, default=1, help="rdf_set_option(\"filter_short\"): 1 = batches no longer than a block tile on the block kernel's short-batch mode (round 6, default), 0 = the wave-tile kernel")
@@ -84,7 +83,6 @@ def main():
     only = set(filter(None, args.only.split(",")))
     lib.set_device(0)
     api = lib.api()
-    lib.set_option("filter_lookback", args.lookback)
     lib.set_option("filter_block", args.block)
     lib.set_option("filter_short", args.short)
     lib.set_option("filter_owned", args.owned)
@@ -136,8 +134,8 @@ def main():
             lib.set_option("filter_fused", 0)
             report(f"filter_frame_{m}col_three_pass", n, (8 + 8 * sel) * m * n, run, selectivity=sel, path="predicate -> mask, count, compact (round 3)")
             lib.set_option("filter_fused", 1)
-    # ---- the same over frames of TWO column widths (f64 predicate column + 4-byte columns beside it: a lineitem-shaped frame; round 6:
-    #      the block kernel twice over the same tiles, the second launch by the mask the first one wrote) against the wave-tile kernel
+    # ---- the same over frames of TWO column widths (f64 predicate column + 4-byte columns beside it: a lineitem-shaped frame): the
+    #      wave-tile kernel (the entries keep the names they have in profiles/r06_filter_frame_mixed_widths.jsonl)
     q = (k & 0x7FFFFFFF).to(torch.int32)
     r32 = x.to(torch.float32)
     lib.synchronize()
@@ -152,11 +150,7 @@ def main():
                 out = api.filter_frame(fr, e, gt)
                 out.release()
             lib.set_option("filter_fused", args.fused)
-            for mixed in (2, 0):
-                lib.set_option("filter_mixed", mixed)
-                report(f"filter_frame_{name}" + ("" if mixed else "_wave_tiles"), n, (1 + sel) * row_bytes * n + (0.25 * n if mixed else 0), run, selectivity=sel,
-                       path="block kernel x 2 (predicate's width, then the other width by the mask)" if mixed else "wave-tile kernel (any widths)")
-            lib.set_option("filter_mixed", 1)
+            report(f"filter_frame_{name}_wave_tiles", n, (1 + sel) * row_bytes * n, run, selectivity=sel, path="wave-tile kernel (any widths)")
             lib.set_option("filter_fused", 1)
     # ---- frames of 4-byte columns only (f32 predicate column)
     q2 = (q >> 3).contiguous()

@@ -166,13 +166,6 @@ def main():
     report("filter_count", n / 8.0, lambda: api.filter_count([m]))
     report("filter_1col", (8 + 8 * sel + 0.25) * n, lambda: api.filter([X], [m], [of]))
     report("filter_2col", (16 + 16 * sel + 0.25) * n, lambda: api.filter_columns([[X], [K]], [m], [[of], [ok2]]))
-    lib.set_option("filter_block", 0)     # (the A/B of the count -> scan -> compact kernels: round 6's one-pass block kernel would take all three otherwise)
-    for gen in (1, 3, 2):   # A/B: first-generation block tiles (one barrier per tile), register-staged wave tiles, default (LDS-DMA wave tiles)
-        lib.set_option("filter_gen", gen)
-        report(f"filter_1col_gen{gen}", (8 + 8 * sel + 0.25) * n, lambda: api.filter([X], [m], [of]))
-        report(f"filter_2col_gen{gen}", (16 + 16 * sel + 0.25) * n, lambda: api.filter_columns([[X], [K]], [m], [[of], [ok2]]))
-    lib.set_option("filter_gen", 2)
-    lib.set_option("filter_block", 1)
     # selective filters: 1 row in 16 kept (sparse tiles fetch only the sectors that hold a kept row)
     m16 = out_like(A.BOOL, n)
     api.predicate(e, e.op("gt", cx, e.scalar(0.875)), [[X]], [m16])
@@ -188,12 +181,6 @@ def main():
     lib.set_option("filter_short", 0)
     report("filter_1col_1024_row_chunks_wave_tiles", (8 + 8 * sel + 0.25) * nfc, lambda: api.filter(XF, MF, OF))     # round 6, earlier: one pass on the wave-tile LDS-DMA kernel
     lib.set_option("filter_short", 1)
-    lib.set_option("filter_block", 0)
-    for gen in (1, 2, 3):   # 3 = wave-granular without the next-tile look-ahead
-        lib.set_option("filter_gen", gen)
-        report(f"filter_1col_1024_row_chunks_gen{gen}", (8 + 8 * sel + 0.25) * nfc, lambda: api.filter(XF, MF, OF))
-    lib.set_option("filter_gen", 2)
-    lib.set_option("filter_block", 1)
     # the same with output chunks sized by rdf_filter_count and packed back to back (what a two-phase caller allocates):
     # the slots above leave every other 4 KB of the output buffer untouched
     import itertools
@@ -202,7 +189,6 @@ def main():
     OFP = [A.DeviceArray(ofb.data_ptr() + o * 8, None, 0, c, A.F64, 0, keep=ofb, capacity=(c + 7) // 8 * 8) for o, c in zip(offs, cnts)]
     report("filter_1col_1024_row_chunks_packed_outputs", (8 + 8 * sel + 0.25) * nfc, lambda: api.filter(XF, MF, OFP))
     del OFP
-    lib.set_option("filter_gen", 2)
     del XF, MF, OF
     for cr in (4096, 65536):   # the per-chunk cost: the same filter on longer batches
         XF = A.PreparedCol([A.DeviceArray(x.data_ptr() + i * 8, None, 0, min(cr, nfc - i), A.F64, 0, keep=x) for i in range(0, nfc, cr)])
