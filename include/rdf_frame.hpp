@@ -580,34 +580,9 @@ class Column {
     GenericVector uniques() const {
         GenericVector g;
         if (data_type() == DataType::Utf8) {
-            // text columns are carried on the host: every chunk goes as offsets + bytes built from the mirror's strings
-            struct Text { std::vector<int32_t> offs; std::string bytes; std::vector<uint8_t> valid; };
-            std::vector<std::unique_ptr<Text>> keep;
-            std::vector<rdf_utf8_array> txt;
-            int64_t rows = 0, bytes = 0;
-            for (auto& a : data_.chunks()) {
-                keep.push_back(std::make_unique<Text>());
-                Text& t = *keep.back();
-                t.offs.reserve((size_t)a->length + 1);
-                t.offs.push_back(0);
-                for (int64_t r = 0; r < a->length; ++r) {
-                    t.bytes += (*a->strings)[(size_t)(a->offset + r)];
-                    if (t.bytes.size() > (size_t)INT32_MAX) throw DataFrameError(DataFrameError::ComputeError, "uniques: a Utf8 chunk above 2^31-1 bytes");
-                    t.offs.push_back((int32_t)t.bytes.size());
-                }
-                if (a->validity) { t.valid = pack_bits(a->valid_to_host()); t.valid.resize(t.valid.size() + 8, 0); }
-                t.bytes.append(8, '\0');
-                rdf_utf8_array u;
-                u.offsets.values = t.offs.data();
-                u.offsets.validity = t.valid.empty() ? nullptr : t.valid.data();
-                u.offsets.offset = 0; u.offsets.length = a->length + 1; u.offsets.null_count = -1; u.offsets.dtype = RDF_I32; u.offsets.mem = RDF_MEM_HOST;
-                u.data.values = t.bytes.data();
-                u.data.validity = nullptr;
-                u.data.offset = 0; u.data.length = (int64_t)t.bytes.size() - 8; u.data.null_count = 0; u.data.dtype = RDF_U8; u.data.mem = RDF_MEM_HOST;
-                txt.push_back(u);
-                rows += a->length;
-                bytes += u.data.length;
-            }
+            const TextChunks tc = text_chunks("uniques");
+            const std::vector<rdf_utf8_array>& txt = tc.txt;
+            const int64_t rows = tc.rows, bytes = tc.bytes;
             // rows + 1 offsets and the input's bytes always suffice: one call
             std::vector<int32_t> ooffs((size_t)rows + 1, 0);
             std::vector<uint8_t> odata((size_t)bytes + 8, 0);
@@ -635,7 +610,69 @@ class Column {
         else { g.kind = GenericVector::F; g.f = out->values_to_host<double>(); }
         return g;
     }
+
+    // {UInt32 codes with the input's chunking, Utf8 dictionary}: rdf_utf8_dictionary_encode.  A code is the rank of its value's
+    // first occurrence over the whole column (pandas.factorize), a NULL row gives a NULL code, the dictionary holds every
+    // distinct value once in that order; take() of the dictionary by a chunk of codes gives the chunk back.
+    std::pair<Column, Column> dictionary_encode() const {
+        if (data_type() != DataType::Utf8) throw DataFrameError(DataFrameError::ComputeError, "dictionary_encode: Utf8 columns only");
+        const TextChunks tc = text_chunks("dictionary_encode");
+        std::vector<std::shared_ptr<Array>> codes;
+        std::vector<rdf_out> oc;
+        for (auto& a : data_.chunks()) {
+            codes.push_back(Array::make_out(DataType::UInt32, a->length, a->validity != nullptr, true));
+            oc.push_back(codes.back()->out_view(a->length));
+        }
+        std::vector<int32_t> ooffs((size_t)tc.rows + 1, 0);
+        std::vector<uint8_t> odata((size_t)tc.bytes + 8, 0);
+        rdf_out oo{ooffs.data(), nullptr, tc.rows + 1, 0, 0, RDF_I32, RDF_MEM_HOST};
+        rdf_out od{odata.data(), nullptr, tc.bytes, 0, 0, RDF_U8, RDF_MEM_HOST};
+        int64_t count = 0;
+        check(rdf_utf8_dictionary_encode(tc.txt.data(), (int64_t)tc.txt.size(), oc.data(), &oo, &od, &count));
+        std::vector<ArrayRef> cc;
+        for (size_t i = 0; i < codes.size(); ++i) { codes[i]->length = oc[i].length; codes[i]->null_count = oc[i].null_count; cc.push_back(codes[i]); }
+        std::vector<std::string> dict;
+        for (int64_t k = 0; k < count; ++k)
+            dict.emplace_back((const char*)odata.data() + ooffs[(size_t)k], (size_t)(ooffs[(size_t)k + 1] - ooffs[(size_t)k]));
+        return {Column::from_arrays(cc, Field{field_.name, DataType::UInt32, true}),
+                Column::from_arrays({Array::from_strings(std::move(dict))}, Field{field_.name, DataType::Utf8, false})};
+    }
   private:
+    // text columns are carried on the host: every chunk as offsets + bytes built from the mirror's strings, in host memory
+    struct TextChunks {
+        struct Text { std::vector<int32_t> offs; std::string bytes; std::vector<uint8_t> valid; };
+        std::vector<std::unique_ptr<Text>> keep;
+        std::vector<rdf_utf8_array> txt;
+        int64_t rows = 0, bytes = 0;
+    };
+    TextChunks text_chunks(const char* what) const {
+        using Text = TextChunks::Text;
+        TextChunks tc;
+        for (auto& a : data_.chunks()) {
+            tc.keep.push_back(std::make_unique<Text>());
+            Text& t = *tc.keep.back();
+            t.offs.reserve((size_t)a->length + 1);
+            t.offs.push_back(0);
+            for (int64_t r = 0; r < a->length; ++r) {
+                t.bytes += (*a->strings)[(size_t)(a->offset + r)];
+                if (t.bytes.size() > (size_t)INT32_MAX) throw DataFrameError(DataFrameError::ComputeError, std::string(what) + ": a Utf8 chunk above 2^31-1 bytes");
+                t.offs.push_back((int32_t)t.bytes.size());
+            }
+            if (a->validity) { t.valid = pack_bits(a->valid_to_host()); t.valid.resize(t.valid.size() + 8, 0); }
+            t.bytes.append(8, '\0');
+            rdf_utf8_array u;
+            u.offsets.values = t.offs.data();
+            u.offsets.validity = t.valid.empty() ? nullptr : t.valid.data();
+            u.offsets.offset = 0; u.offsets.length = a->length + 1; u.offsets.null_count = -1; u.offsets.dtype = RDF_I32; u.offsets.mem = RDF_MEM_HOST;
+            u.data.values = t.bytes.data();
+            u.data.validity = nullptr;
+            u.data.offset = 0; u.data.length = (int64_t)t.bytes.size() - 8; u.data.null_count = 0; u.data.dtype = RDF_U8; u.data.mem = RDF_MEM_HOST;
+            tc.txt.push_back(u);
+            tc.rows += a->length;
+            tc.bytes += u.data.length;
+        }
+        return tc;
+    }
     ChunkedArray data_;
     Field field_;
 };
@@ -2153,12 +2190,34 @@ class DataFrame {
         // key pair k: this[criteria[k].first] against other[criteria[k].second], laid out [k * nchunks + chunk]
         std::vector<rdf_array> lk, rk;
         for (auto& c : jc.criteria) {
+            if (column_by_name(c.first).data_type() == DataType::Utf8 || other.column_by_name(c.second).data_type() == DataType::Utf8) continue;
             for (auto& v : column_by_name(c.first).data().views()) lk.push_back(v);
             for (auto& v : other.column_by_name(c.second).data().views()) rk.push_back(v);
         }
         const int32_t nk = (int32_t)jc.criteria.size();
         const int64_t lnc = (int64_t)num_chunks(), rnc = (int64_t)other.num_chunks();
         int64_t rows = 0;
+        bool any_text = false;
+        for (auto& c : jc.criteria) any_text |= column_by_name(c.first).data_type() == DataType::Utf8 || other.column_by_name(c.second).data_type() == DataType::Utf8;
+        if (any_text) {   // a text pair is dictionary-encoded against one dictionary of both sides (rdf_equijoin_indices_keys)
+            for (auto& c : jc.criteria)
+                if ((column_by_name(c.first).data_type() == DataType::Utf8) != (other.column_by_name(c.second).data_type() == DataType::Utf8))
+                    throw DataFrameError(DataFrameError::ComputeError, "Join columns must have compatible types");
+            const bool host = numeric_columns_on_host() && other.numeric_columns_on_host();
+            std::vector<SortCriteria> lc, rc;
+            for (auto& c : jc.criteria) { lc.push_back(SortCriteria{c.first, false, false}); rc.push_back(SortCriteria{c.second, false, false}); }
+            const SortKeys lsk = sort_keys(lc, host), rsk = other.sort_keys(rc, host);
+            check(rdf_equijoin_indices_keys(lsk.keys.data(), lnc, rsk.keys.data(), rnc, nk, (int32_t)jc.join_type, nullptr, nullptr, &rows));
+            auto li = Array::make_out(DataType::UInt32, rows, true, host), ri = Array::make_out(DataType::UInt32, rows, true, host);
+            rdf_out lo = li->out_view(rows), ro = ri->out_view(rows);
+            check(rdf_equijoin_indices_keys(lsk.keys.data(), lnc, rsk.keys.data(), rnc, nk, (int32_t)jc.join_type, &lo, &ro, &rows));
+            li->length = ri->length = rows;
+            li->null_count = lo.null_count; ri->null_count = ro.null_count;
+            std::vector<Column> cols;
+            for (auto& c : columns_) cols.push_back(c.take(li, 4096));
+            for (auto& c : other.columns_) cols.push_back(c.take(ri, 4096));
+            return DataFrame::from_columns(cols);
+        }
         check(rdf_equijoin_indices_multi(lk.data(), lnc, rk.data(), rnc, nk, (int32_t)jc.join_type, nullptr, nullptr, &rows));
         auto li = Array::make_out(DataType::UInt32, rows, true), ri = Array::make_out(DataType::UInt32, rows, true);
         rdf_out lo = li->out_view(rows), ro = ri->out_view(rows);
@@ -2888,6 +2947,25 @@ class Evaluate {
         ev.step_calculate(calc);
         return ev.flush();
     }
+    // GROUP BY, eager, over 1..4 grouping columns of which each is an integer or a Utf8 column: the grouping columns, then one
+    // column per (aggregation, input column), named and typed as Dataset::try_aggregate plans them; rows ordered by the
+    // grouping columns, text in byte order, the NULL group last.  Integer columns only: the GroupAggregate step of a plan,
+    // unchanged.  With a text column the keys are dictionary-encoded on the device (rdf_groupby_agg_keys).  The lazy plan's
+    // GroupAggregate step itself keeps refusing text columns, as the reference's evaluation does.
+    static DataFrame group_aggregate(const DataFrame& frame, const std::vector<std::string>& groups, const std::vector<plan::Aggregation>& aggregations) {
+        plan::Transformation t;
+        t.kind = plan::Transformation::GroupAggregate;
+        t.names = groups;
+        t.aggregations = aggregations;
+        if (groups.empty() || groups.size() > RDF_MAX_GROUP_KEYS)
+            throw DataFrameError(DataFrameError::ComputeError, "GroupAggregate: 1.." + std::to_string(RDF_MAX_GROUP_KEYS) + " grouping columns");
+        bool any_text = false;
+        for (auto& n : groups) any_text |= frame.column_by_name(n).data_type() == DataType::Utf8;
+        if (any_text) return group_aggregate_text(frame, t);
+        Evaluate ev(frame);
+        ev.step_group_aggregate(t);
+        return ev.flush();
+    }
     // Evaluate::evaluate (:66-96): computations newest-first (Expression::unroll order), each applied to
     // the running frame.  Calculate / Filter / Select / Drop / Rename stay lazy and are flushed as fused
     // passes; Limit and the end of the plan materialise; GroupAggregate with no groups is the fused
@@ -2990,6 +3068,137 @@ class Evaluate {
     // GroupAggregate WITH grouping columns: the reference plans it (Dataset::try_aggregate, src/expression.rs:114-221)
     // and panics on execution (src/evaluation.rs:73).  Here: one integer grouping column, Sum / Count / Avg per group
     // through rdf_groupby_sum; rows of the result are ordered by key (NULL group last) so every aggregate column lines up.
+    // Utf8 grouping columns, alone or next to integer ones, go through Evaluate::group_aggregate (rdf_groupby_agg_keys).
+
+    // One aggregate column of a GROUP BY result from the per-group sums (or extrema) and counts, already in result order.
+    static void append_aggregate_column(plan::AggregateFunction fn, const std::string& col, DataType vdt, DataType sdt, const std::vector<ArrayRef>& sums,
+                                        const std::vector<ArrayRef>& counts, std::vector<Column>& out_cols) {
+        using AF = plan::AggregateFunction;
+        if (fn == AF::Sum) {
+            out_cols.push_back(Column::from_arrays(sdt == vdt ? sums : ScalarFunctions::cast(sums, vdt), Field{"sum(" + col + ")", vdt, true}));
+        } else if (fn == AF::Min || fn == AF::Max) {   // typed like the input (try_aggregate): the extremum of a group always fits
+            out_cols.push_back(Column::from_arrays(sdt == vdt ? sums : ScalarFunctions::cast(sums, vdt), Field{std::string(fn == AF::Min ? "min(" : "max(") + col + ")", vdt, true}));
+        } else if (fn == AF::Count) {
+            out_cols.push_back(Column::from_arrays(ScalarFunctions::cast(counts, DataType::UInt32), Field{"count(" + col + ")", DataType::UInt32, true}));
+        } else {   // avg = sum / count, NULL for a group without a non-null value (AggregateFunctions::avg, src/functions/aggregate.rs:32-65)
+            std::vector<ArrayRef> out;
+            const std::vector<ArrayRef> fs = sdt == DataType::Float64 ? sums : ScalarFunctions::cast(sums, DataType::Float64);
+            for (size_t i = 0; i < fs.size(); ++i) {
+                const std::vector<double> sv = fs[i]->values_to_host<double>();
+                const std::vector<int64_t> cv = counts[i]->values_to_host<int64_t>();
+                std::vector<double> m(sv.size());
+                std::vector<bool> valid(sv.size());
+                for (size_t r = 0; r < sv.size(); ++r) { valid[r] = cv[r] > 0; m[r] = cv[r] > 0 ? sv[r] / (double)cv[r] : 0.0; }
+                out.push_back(Array::from_vec(m, &valid));
+            }
+            out_cols.push_back(Column::from_arrays(out, Field{"avg(" + col + ")", DataType::Float64, true}));
+        }
+    }
+
+    // GroupAggregate whose grouping columns include Utf8 ones: one rdf_groupby_agg_keys per aggregation (the text keys are
+    // dictionary-encoded on the device, the codes grouped next to the integer keys, the dictionary taken by the result's code
+    // column); results ordered by the grouping columns — text in byte order, the NULL group last.
+    static DataFrame group_aggregate_text(const DataFrame& f, const plan::Transformation& t) {
+        using AF = plan::AggregateFunction;
+        std::vector<const Column*> kcs;
+        for (auto& n : t.names) {
+            kcs.push_back(&f.column_by_name(n));
+            if (!is_integer(kcs.back()->data_type()) && kcs.back()->data_type() != DataType::Utf8)
+                throw DataFrameError(DataFrameError::ComputeError, "GroupAggregate: the grouping columns must be integer or Utf8 columns");
+        }
+        const size_t nk = kcs.size(), nch = kcs[0]->data().num_chunks();
+        const int64_t nrows = (int64_t)f.num_rows();
+        const bool on_host = f.numeric_columns_on_host();
+        std::vector<DataFrame::SortCriteria> crit;
+        for (auto& n : t.names) crit.push_back(DataFrame::SortCriteria{n, false, false});
+        const DataFrame::SortKeys sk = f.sort_keys(crit, on_host);
+        std::vector<bool> key_nulls(nk, false);
+        std::vector<int64_t> key_bytes(nk, 0);
+        for (size_t k = 0; k < nk; ++k) {
+            for (auto& a : kcs[k]->data().chunks()) if (a->validity != nullptr) key_nulls[k] = true;
+            for (auto& u : sk.txt[k]) key_bytes[k] += u.data.length;   // the key column's input bytes always suffice
+        }
+        std::vector<Column> out_cols;
+        auto one = [&](AF fn, const std::string& col) {
+            if (fn != AF::Sum && fn != AF::Count && fn != AF::Avg && fn != AF::Min && fn != AF::Max) throw DataFrameError(DataFrameError::ComputeError, "Aggregation not yet supported");
+            const Column& vc = f.column_by_name(col);
+            const DataType vdt = vc.data_type();
+            if (!(is_integer(vdt) || is_float(vdt))) throw DataFrameError(DataFrameError::ComputeError, "Aggregating column must be numeric");
+            std::vector<rdf_array> vals;
+            bool val_nulls = false;
+            for (auto& a : vc.data().chunks()) { vals.push_back(a->view()); val_nulls |= a->validity != nullptr; }
+            const int32_t agg = fn == AF::Min ? RDF_AGG_MIN : fn == AF::Max ? RDF_AGG_MAX : RDF_AGG_SUM;
+            const bool extremum = agg != RDF_AGG_SUM;
+            const DataType sdt = is_float(vdt) ? DataType::Float64 : (extremum && vdt == DataType::UInt64) ? DataType::UInt64 : DataType::Int64;
+            int64_t mg = std::max<int64_t>(1, std::min<int64_t>(nrows, (int64_t)1 << 20));
+            std::vector<ArrayRef> ok(nk);
+            std::shared_ptr<Array> os, oc;
+            for (;;) {   // the number of groups is not known in advance: grow the promise until it holds
+                std::vector<std::shared_ptr<Array>> num(nk), offs(nk), data(nk);
+                std::vector<rdf_out> vk(nk), vo(nk), vd(nk);
+                std::vector<rdf_key_out> ko(nk);
+                for (size_t k = 0; k < nk; ++k) {
+                    if (kcs[k]->data_type() == DataType::Utf8) {
+                        offs[k] = Array::make_out(DataType::Int32, mg + 3, true, on_host);
+                        data[k] = Array::make_out(DataType::UInt8, key_bytes[k] + 8, false, on_host);
+                        vo[k] = offs[k]->out_view(mg + 3);
+                        vd[k] = data[k]->out_view(key_bytes[k] + 8);
+                        ko[k] = rdf_key_out{nullptr, &vo[k], &vd[k]};
+                    } else {
+                        num[k] = Array::make_out(kcs[k]->data_type(), mg + 2, key_nulls[k], on_host);
+                        vk[k] = num[k]->out_view(mg + 2);
+                        ko[k] = rdf_key_out{&vk[k], nullptr, nullptr};
+                    }
+                }
+                os = Array::make_out(sdt, mg + 2, extremum && val_nulls, on_host);
+                oc = Array::make_out(DataType::Int64, mg + 2, false, on_host);
+                rdf_out vs = os->out_view(mg + 2), vcn = oc->out_view(mg + 2);
+                const rdf_status st = rdf_groupby_agg_keys(sk.keys.data(), (int32_t)nk, vals.data(), (int64_t)nch, agg, mg, ko.data(), &vs, &vcn);
+                if (st == RDF_MEMORY_ERROR && mg < nrows) { mg = std::min<int64_t>(nrows, mg * 16); continue; }
+                check(st);
+                const int64_t groups = vcn.length;
+                for (size_t k = 0; k < nk; ++k) {
+                    if (num[k]) { num[k]->length = vk[k].length; num[k]->null_count = vk[k].null_count; ok[k] = num[k]; continue; }
+                    offs[k]->length = groups + 1;
+                    data[k]->length = vd[k].length;
+                    const std::vector<int32_t> o = offs[k]->values_to_host<int32_t>();
+                    const std::vector<uint8_t> bytes = data[k]->values_to_host<uint8_t>();
+                    offs[k]->length = groups;
+                    const std::vector<bool> valid = offs[k]->valid_to_host();
+                    std::vector<std::string> rows((size_t)groups);
+                    for (int64_t g = 0; g < groups; ++g) rows[(size_t)g].assign((const char*)bytes.data() + o[(size_t)g], (size_t)(o[(size_t)g + 1] - o[(size_t)g]));
+                    auto a = std::const_pointer_cast<Array>(Array::from_strings(std::move(rows)));
+                    if (vo[k].null_count > 0) {
+                        const auto bits = pack_bits(valid);
+                        a->validity = std::make_shared<DeviceBuffer>((int64_t)bits.size());
+                        check(rdf_copy_h2d(a->validity->data(), bits.data(), (int64_t)bits.size()));
+                        a->null_count = vo[k].null_count;
+                    }
+                    ok[k] = a;
+                }
+                os->length = oc->length = vs.length;
+                os->null_count = vs.null_count;
+                break;
+            }
+            std::vector<Column> gc;
+            std::vector<DataFrame::SortCriteria> order;
+            for (size_t k = 0; k < nk; ++k) {
+                gc.push_back(Column::from_arrays({ok[k]}, Field{"k" + std::to_string(k), kcs[k]->data_type(), true}));
+                order.push_back(DataFrame::SortCriteria{"k" + std::to_string(k), false, false});
+            }
+            gc.push_back(Column::from_arrays({os}, Field{"s", sdt, true}));
+            gc.push_back(Column::from_arrays({oc}, Field{"c", DataType::Int64, false}));
+            DataFrame g = DataFrame::from_columns(gc).sort(order);
+            if (out_cols.empty())
+                for (size_t k = 0; k < nk; ++k) out_cols.push_back(Column::from_arrays(g.column_by_name("k" + std::to_string(k)).data().chunks(), Field{t.names[k], kcs[k]->data_type(), true}));
+            append_aggregate_column(fn, col, vdt, sdt, g.column_by_name("s").data().chunks(), g.column_by_name("c").data().chunks(), out_cols);
+        };
+        for (auto& a : t.aggregations)
+            for (auto& c : a.columns) one(a.function, c);
+        if (out_cols.empty()) throw DataFrameError(DataFrameError::ComputeError, "GroupAggregate without aggregations");
+        return DataFrame::from_columns(out_cols);
+    }
+
     void step_group_aggregate(const plan::Transformation& t) {
         using AF = plan::AggregateFunction;
         if (fused_dense_group_aggregate(t)) return;   // small dense key domain(s): filter + expressions + grouping in one pass
@@ -3051,26 +3260,7 @@ class Evaluate {
             DataFrame g = DataFrame::from_columns(gc).sort(order);
             if (out_cols.empty())
                 for (size_t k = 0; k < nk; ++k) out_cols.push_back(Column::from_arrays(g.column_by_name("k" + std::to_string(k)).data().chunks(), Field{t.names[k], kcs[k]->data_type(), true}));
-            const std::vector<ArrayRef> sums = g.column_by_name("s").data().chunks(), counts = g.column_by_name("c").data().chunks();
-            if (fn == AF::Sum) {
-                out_cols.push_back(Column::from_arrays(sdt == vdt ? sums : ScalarFunctions::cast(sums, vdt), Field{"sum(" + col + ")", vdt, true}));
-            } else if (fn == AF::Min || fn == AF::Max) {   // typed like the input (try_aggregate): the extremum of a group always fits
-                out_cols.push_back(Column::from_arrays(sdt == vdt ? sums : ScalarFunctions::cast(sums, vdt), Field{std::string(fn == AF::Min ? "min(" : "max(") + col + ")", vdt, true}));
-            } else if (fn == AF::Count) {
-                out_cols.push_back(Column::from_arrays(ScalarFunctions::cast(counts, DataType::UInt32), Field{"count(" + col + ")", DataType::UInt32, true}));
-            } else {   // avg = sum / count, NULL for a group without a non-null value (AggregateFunctions::avg, src/functions/aggregate.rs:32-65)
-                std::vector<ArrayRef> out;
-                const std::vector<ArrayRef> fs = sdt == DataType::Float64 ? sums : ScalarFunctions::cast(sums, DataType::Float64);
-                for (size_t i = 0; i < fs.size(); ++i) {
-                    const std::vector<double> sv = fs[i]->values_to_host<double>();
-                    const std::vector<int64_t> cv = counts[i]->values_to_host<int64_t>();
-                    std::vector<double> m(sv.size());
-                    std::vector<bool> valid(sv.size());
-                    for (size_t r = 0; r < sv.size(); ++r) { valid[r] = cv[r] > 0; m[r] = cv[r] > 0 ? sv[r] / (double)cv[r] : 0.0; }
-                    out.push_back(Array::from_vec(m, &valid));
-                }
-                out_cols.push_back(Column::from_arrays(out, Field{"avg(" + col + ")", DataType::Float64, true}));
-            }
+            append_aggregate_column(fn, col, vdt, sdt, g.column_by_name("s").data().chunks(), g.column_by_name("c").data().chunks(), out_cols);
         };
         for (auto& a : t.aggregations)
             for (auto& c : a.columns) one(a.function, c);

@@ -466,6 +466,59 @@ rdf_status rdf_uniques(const rdf_array* chunks, int64_t nchunks, rdf_out* out_va
 rdf_status rdf_utf8_uniques(const rdf_utf8_array* chunks, int64_t nchunks, rdf_out* out_offsets, rdf_out* out_data,
                             int64_t* out_count);
 
+/* ------------------------------------------------------------------ text keys: dictionary encoding, GROUP BY, join */
+
+/* Dictionary encoding of a Utf8 column: dense UInt32 codes per row and the dictionary of the distinct values.  The code of
+ * a row is the number of distinct values whose first occurrence precedes the first occurrence of the row's value, over
+ * the concatenation of the chunks (first-occurrence order: pandas.factorize) — a function of the input alone, whichever
+ * route computes it.  Dictionary row k holds the bytes of the value with code k; it has no NULLs (no validity buffer
+ * needed) and its offsets start at 0.  A NULL row gives a NULL code: validity bit clear, value 0.  Equality is byte
+ * equality; the empty string is a value, 0x00 an ordinary byte, the bytes are not validated.
+ * out_codes: nchunks RDF_U32 outputs, out_codes[i] of chunk i's rows (length and null_count set per chunk; a validity
+ *   buffer is required when chunk i carries one, and filled with ones when the chunk carries none);
+ * out_dict_offsets / out_dict_data: ONE Utf8 chunk; *out_count = the distinct values.
+ * rdf_utf8_array conventions as for rdf_utf8_uniques; inputs and outputs all in host memory or all in device memory.
+ * Sizing as for rdf_utf8_uniques: *out_count and every needed length (out_codes[i].length, out_dict_offsets->length,
+ * out_dict_data->length) are always set; a short out_dict_data, out_dict_offsets or out_codes[i].capacity is
+ * RDF_MEMORY_ERROR and nothing is written; out_dict_data with values == NULL, capacity == 0 is the sizing call;
+ * out_dict_offsets needs a buffer of at least one entry; rows + 1 entries and the input's bytes always suffice.  2^32 rows
+ * or more: RDF_INVALID_ARGUMENT; a dictionary beyond 2^31-1 bytes: RDF_COMPUTE_ERROR.  Rows are matched as in
+ * rdf_utf8_uniques (64-bit hash, every row compared with its hash's smallest row); a hash shared by two strings, more
+ * values than the table was sized for, or "uniques_route" 1 send the call to the exact route (rdf_lexsort_to_indices'
+ * stable order, the first row of every run of equal values), with bit-identical codes and dictionary. */
+rdf_status rdf_utf8_dictionary_encode(const rdf_utf8_array* chunks, int64_t nchunks, rdf_out* out_codes,
+                                      rdf_out* out_dict_offsets, rdf_out* out_dict_data, int64_t* out_count);
+
+/* One key column of a GROUP BY result: `values` for a numeric grouping column, or the (utf8_offsets, utf8_data) pair —
+ * ONE Utf8 chunk — for a Utf8 one.  Exactly one of the two forms is set, matching the key. */
+typedef struct { rdf_out* values; rdf_out* utf8_offsets; rdf_out* utf8_data; } rdf_key_out;
+
+/* rdf_groupby_agg over 1..RDF_MAX_GROUP_KEYS grouping columns of which each is integer or Utf8.  keys[k] sets `values`
+ * (nchunks integer chunks) or `utf8` (nchunks Utf8 chunks); its `options` are ignored.  Everything rdf_groupby_agg
+ * documents holds: a NULL key is a group of its own, NULL values are skipped, the output dtypes, the capacities
+ * (>= min(max_groups, rows) + 2 for every numeric output), RDF_MEMORY_ERROR beyond max_groups groups, unspecified group
+ * order.  A Utf8 grouping column comes back as one Utf8 chunk whose row g belongs to out_values[g] / out_counts[g]; it is
+ * NULL for the NULL group (validity required when the key carries a validity buffer) and sizes like every Utf8 output:
+ * lengths reported, RDF_MEMORY_ERROR and nothing written when short; groups + 1 offsets and the key column's input bytes
+ * always suffice.  Utf8 keys are dictionary-encoded (rdf_utf8_dictionary_encode), the codes grouped next to the numeric
+ * keys by rdf_groupby_agg, and the dictionary taken by the result's code column.  With numeric keys only the call IS
+ * rdf_groupby_agg.  Errors before any device work: a key or key output setting both forms or neither, wrong dtypes, mixed
+ * memory kinds, nkeys outside 1..4 RDF_INVALID_ARGUMENT; chunk row counts that differ between columns RDF_COMPUTE_ERROR. */
+rdf_status rdf_groupby_agg_keys(const rdf_sort_key* keys, int32_t nkeys, const rdf_array* values, int64_t nchunks,
+                                int32_t agg, int64_t max_groups, rdf_key_out* out_keys, rdf_out* out_values,
+                                rdf_out* out_counts);
+
+/* rdf_equijoin_indices_multi over 1..4 key pairs of which each is Utf8 on both sides or numeric of one dtype on both
+ * sides (anything else: RDF_INVALID_ARGUMENT).  left_keys[k] / right_keys[k] hold left_nchunks / right_nchunks chunks.  A
+ * Utf8 pair is encoded against one shared dictionary (the left chunks followed by the right chunks in one
+ * rdf_utf8_dictionary_encode call) and the codes are joined.  Everything rdf_equijoin_indices_multi documents is
+ * inherited: NULL never matches, the LEFT / RIGHT / INNER / FULL semantics, the pair order, the count-only call with
+ * NULL outputs, the capacity rule.  The two sides together hold fewer than 2^32 rows; the key columns of one side agree
+ * in their chunks' rows (RDF_COMPUTE_ERROR otherwise). */
+rdf_status rdf_equijoin_indices_keys(const rdf_sort_key* left_keys, int64_t left_nchunks, const rdf_sort_key* right_keys,
+                                     int64_t right_nchunks, int32_t nkeys, int32_t join_type, rdf_out* out_left,
+                                     rdf_out* out_right, int64_t* out_rows);
+
 /* ------------------------------------------------------------------ window functions */
 
 /* SQL window functions over partitions: row_number / rank / dense_rank / percent_rank / cume_dist / ntile / lag / lead.

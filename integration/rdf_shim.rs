@@ -61,6 +61,9 @@ pub mod sys {
     // one criterion of rdf_lexsort_to_indices: exactly one of values / utf8 points at nchunks chunks
     #[repr(C)] #[derive(Clone, Copy)]
     pub struct rdf_sort_key { pub values: *const rdf_array, pub utf8: *const rdf_utf8_array, pub options: rdf_sort_options }
+    // one key column of rdf_groupby_agg_keys' result: `values` for a numeric key, the (utf8_offsets, utf8_data) pair for a Utf8 one
+    #[repr(C)] #[derive(Clone, Copy)]
+    pub struct rdf_key_out { pub values: *mut rdf_out, pub utf8_offsets: *mut rdf_out, pub utf8_data: *mut rdf_out }
     // one call of rdf_window: fn = RDF_WIN_*, param = ntile buckets / lag, lead offset
     #[repr(C)] #[derive(Clone, Copy)] pub struct rdf_window_call { pub fn_: i32, pub pad: i32, pub param: i64 }
     pub const RDF_WIN_ROW_NUMBER: i32 = 0; pub const RDF_WIN_RANK: i32 = 1; pub const RDF_WIN_DENSE_RANK: i32 = 2;
@@ -127,6 +130,14 @@ pub mod sys {
         pub fn rdf_uniques(chunks: *const rdf_array, nchunks: i64, out_values: *mut rdf_out, out_count: *mut i64) -> i32;
         pub fn rdf_utf8_uniques(chunks: *const rdf_utf8_array, nchunks: i64, out_offsets: *mut rdf_out, out_data: *mut rdf_out,
                                 out_count: *mut i64) -> i32;
+        // text keys: dictionary codes in first-occurrence order, GROUP BY and join whose keys may be StringArray columns
+        pub fn rdf_utf8_dictionary_encode(chunks: *const rdf_utf8_array, nchunks: i64, out_codes: *mut rdf_out,
+                                          out_dict_offsets: *mut rdf_out, out_dict_data: *mut rdf_out, out_count: *mut i64) -> i32;
+        pub fn rdf_groupby_agg_keys(keys: *const rdf_sort_key, nkeys: i32, values: *const rdf_array, nchunks: i64, agg: i32,
+                                    max_groups: i64, out_keys: *mut rdf_key_out, out_values: *mut rdf_out, out_counts: *mut rdf_out) -> i32;
+        pub fn rdf_equijoin_indices_keys(left_keys: *const rdf_sort_key, left_nchunks: i64, right_keys: *const rdf_sort_key,
+                                         right_nchunks: i64, nkeys: i32, join_type: i32, out_left: *mut rdf_out,
+                                         out_right: *mut rdf_out, out_rows: *mut i64) -> i32;
         // WindowSpec / WindowFunctions (src/window.rs, src/functions/window.rs: declared, bodies empty) + ntile (scalar.rs:345)
         pub fn rdf_window(partition_by: *const rdf_sort_key, npartition: i32, order_by: *const rdf_sort_key, norder: i32,
                           nchunks: i64, nrows_if_no_keys: i64, calls: *const rdf_window_call, ncalls: i32, outs: *mut rdf_out) -> i32;

@@ -106,6 +106,10 @@ class rdf_sort_key(C.Structure):
     _fields_ = [("values", C.POINTER(rdf_array)), ("utf8", C.POINTER(rdf_utf8_array)), ("options", rdf_sort_options)]
 
 
+class rdf_key_out(C.Structure):
+    _fields_ = [("values", C.POINTER(rdf_out)), ("utf8_offsets", C.POINTER(rdf_out)), ("utf8_data", C.POINTER(rdf_out))]
+
+
 class rdf_window_call(C.Structure):
     _fields_ = [("fn", C.c_int32), ("pad", C.c_int32), ("param", C.c_int64)]
 
@@ -1432,6 +1436,111 @@ class Api:
             h = r.to_host() if device else r
             r = h.to_pylist() if as_arrow == "pylist" else h.to_arrow()
         return r
+
+    # ---- text keys: dictionary encoding, GROUP BY and join whose keys may be Utf8 columns
+    @staticmethod
+    def _is_utf8(chunks) -> bool:
+        return len(chunks) > 0 and all(isinstance(c, (HostUtf8, DeviceUtf8)) for c in chunks)
+
+    @staticmethod
+    def _utf8_bytes(chunks) -> int:
+        return sum(c.data_length if isinstance(c, DeviceUtf8) else len(c.data) - c.data_offset for c in chunks)
+
+    @staticmethod
+    def _utf8_result(co, cd, keep, device: bool, nullable: bool):
+        """Output 0 of _utf8_outs after a call, as a HostUtf8 / DeviceUtf8."""
+        rows = co[0].length - 1
+        if device:
+            ot, dt, vt = keep[0]
+            return DeviceUtf8(ot.data_ptr(), dt.data_ptr() if dt is not None else 0, cd[0].length, rows,
+                              vt.data_ptr() if (vt is not None and nullable) else None, 0, 0, co[0].null_count if nullable else 0, keep=(ot, dt, vt))
+        ob, db, vb = keep[0]
+        return HostUtf8(ob, db if db is not None else np.zeros(8, dtype=np.uint8), vb if nullable else None, 0, rows, 0, co[0].null_count if nullable else 0)
+
+    def utf8_dictionary_encode(self, chunks: Sequence):
+        """rdf_utf8_dictionary_encode -> (codes, dictionary, count): one UInt32 array per input chunk (with validity; NULL rows
+        give NULL codes), ONE Utf8 chunk of the distinct values in first-occurrence order, and their number.  The buffers
+        are sized from the input (rows + 1 offsets, the input's bytes), so one call is made."""
+        n = len(chunks)
+        carr = (rdf_utf8_array * max(1, n))(*[c.c_struct() for c in chunks])
+        device = any(isinstance(c, DeviceUtf8) for c in chunks)
+        codes = [self._window_out(U32, c.length, device, True) for c in chunks]
+        cc = (rdf_out * max(1, n))(*[o.out_struct() for o in codes])
+        co, cd, keep = self._utf8_outs(chunks, [sum(c.length for c in chunks)], [False], device, [max(1, self._utf8_bytes(chunks))])
+        count = C.c_int64(-1)
+        fn = self._utf8_fn("utf8_dictionary_encode")
+        self._check(fn(carr, C.c_int64(n), cc, co, cd, C.byref(count)))
+        self._finish(codes, cc)
+        return codes, self._utf8_result(co, cd, keep, device, False), count.value
+
+    def groupby_agg_keys(self, key_cols: Sequence[Sequence], values: Optional[Sequence], agg, max_groups: int):
+        """rdf_groupby_agg_keys: GROUP BY over 1..4 grouping columns, each a list of numeric chunks or of Utf8 chunks.
+        -> ([key column: array | HostUtf8 / DeviceUtf8], values, counts), one chunk each, in unspecified group order."""
+        code = self.AGGS[agg] if isinstance(agg, str) else int(agg)
+        nk, n = len(key_cols), len(key_cols[0])
+        ck, keep_k = self._sort_keys(list(key_cols))
+        device = any(isinstance(c, (DeviceArray, DeviceUtf8)) for col in key_cols for c in col)
+        vdt = values[0].dtype if values is not None and code != 3 else None
+        cap = max_groups + 2
+        kouts = (rdf_key_out * max(1, nk))()
+        holders = []
+        for k, col in enumerate(key_cols):
+            nullable = any((c.validity is not None) if isinstance(c, (HostArray, HostUtf8)) else bool(c.validity_ptr) for c in col)
+            if self._is_utf8(col):
+                co, cd, keep = self._utf8_outs(col, [cap], [nullable], device, [max(1, self._utf8_bytes(col))])
+                kouts[k] = rdf_key_out(None, C.cast(co, C.POINTER(rdf_out)), C.cast(cd, C.POINTER(rdf_out)))
+                holders.append(("utf8", co, cd, keep, nullable))
+            else:
+                o = self._window_out(col[0].dtype, cap, device, nullable)
+                co = (rdf_out * 1)(o.out_struct())
+                kouts[k] = rdf_key_out(C.cast(co, C.POINTER(rdf_out)), None, None)
+                holders.append(("num", o, co))
+        nullable_v = values is not None and any(v.validity is not None for v in values)
+        ov = self._window_out(self._agg_out_dtype(code, vdt), cap, device, nullable_v and code in (1, 2))
+        oc = self._window_out(I64, cap, device, False)
+        cv, ccnt = (rdf_out * 1)(ov.out_struct()), (rdf_out * 1)(oc.out_struct())
+        cvals = _flat([values], n) if values is not None else None
+        fn = self._fn("groupby_agg_keys")
+        fn.restype = C.c_int
+        self._check(fn(ck, C.c_int32(nk), cvals, C.c_int64(n), C.c_int32(code), C.c_int64(max_groups), kouts, cv, ccnt))
+        keys = []
+        for h in holders:
+            if h[0] == "utf8":
+                keys.append(self._utf8_result(h[1], h[2], h[3], device, h[4]))
+            else:
+                keys.append(self._finish([h[1]], h[2])[0])
+        self._finish([ov], cv)
+        self._finish([oc], ccnt)
+        return keys, ov, oc
+
+    def equijoin_indices_keys(self, left_cols: Sequence[Sequence], right_cols: Sequence[Sequence], how: str, count_only: bool = False, outs=None):
+        """rdf_equijoin_indices_keys: left_cols[k] pairs with right_cols[k]; a pair is Utf8 on both sides or numeric of one
+        dtype on both sides.  -> (left_indices, right_indices) as UInt32 arrays with validity, or the row count alone.
+        `outs` = caller-allocated (left, right) outputs: the sizing call is skipped."""
+        jt = self.JOIN_TYPES[how] if isinstance(how, str) else int(how)
+        lk, keep_l = self._sort_keys(list(left_cols))
+        rk, keep_r = self._sort_keys(list(right_cols))
+        nk, lnc, rnc = len(left_cols), len(left_cols[0]), len(right_cols[0])
+        device = any(isinstance(c, (DeviceArray, DeviceUtf8)) for col in list(left_cols) + list(right_cols) for c in col)
+        rows = C.c_int64(-1)
+        fn = self._fn("equijoin_indices_keys")
+        fn.restype = C.c_int
+        if outs is not None:
+            ol, orr = outs
+            cl, cr = (rdf_out * 1)(ol.out_struct()), (rdf_out * 1)(orr.out_struct())
+            self._check(fn(lk, C.c_int64(lnc), rk, C.c_int64(rnc), C.c_int32(nk), C.c_int32(jt), cl, cr, C.byref(rows)))
+            self._finish([ol], cl)
+            self._finish([orr], cr)
+            return ol, orr
+        self._check(fn(lk, C.c_int64(lnc), rk, C.c_int64(rnc), C.c_int32(nk), C.c_int32(jt), None, None, C.byref(rows)))
+        if count_only:
+            return rows.value
+        ol, orr = self._window_out(U32, rows.value, device, True), self._window_out(U32, rows.value, device, True)
+        cl, cr = (rdf_out * 1)(ol.out_struct()), (rdf_out * 1)(orr.out_struct())
+        self._check(fn(lk, C.c_int64(lnc), rk, C.c_int64(rnc), C.c_int32(nk), C.c_int32(jt), cl, cr, C.byref(rows)))
+        self._finish([ol], cl)
+        self._finish([orr], cr)
+        return ol, orr
 
     # ---- fused grouped aggregation over a small dense domain (TPC-H Q1 shape)
     def group_pipeline(self, expr: Expr, cols: Sequence[Sequence], value_roots: Sequence[int], group_root: int, ngroups: int,

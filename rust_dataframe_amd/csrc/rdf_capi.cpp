@@ -4187,6 +4187,7 @@ rdf_status groupby_sum_fallback(const rdf_array* keys, const rdf_array* values, 
 #include "rdf_capi_utf8.inc"
 #include "rdf_capi_sort_utf8.inc"
 #include "rdf_capi_colstats.inc"
+#include "rdf_capi_dict.inc"
 #include "rdf_capi_window.inc"
 #include "rdf_capi_window_agg.inc"
 

@@ -76,6 +76,32 @@ struct CsUtf8Args {
     uint32_t*        out32;    // exact route: first row of every run (nullptr = count only)
 };
 
+// ---- dictionary encoding of a Utf8 column (rdf_utf8_dictionary_encode).  Both routes end in rep[row] = the smallest row
+// that holds the row's value (kCsNoRow for a NULL row) and flags[row] = 1 where a row is its own representative; the
+// exclusive scan of the flags is the rank of a value's first occurrence, which is the code.
+constexpr uint32_t kCsNoRow = 0xFFFFFFFFu;
+
+// one output chunk of codes; tiles of kCsThreads rows never cross a chunk, so no validity byte has two writers
+struct CsDictOut {
+    uint32_t* codes;       // [rows]
+    uint8_t*  valid;       // [(rows + 7) / 8] or nullptr
+    int64_t   row_start;   // first row of the chunk in the concatenation
+    int64_t   tile_start;  // first tile of the chunk
+    int64_t   rows;
+};
+
+struct CsDictArgs {
+    CsUtf8Args       u;        // chunks, n; hash route: hash, set; exact route: perm
+    uint32_t*        rep;      // [n]
+    int64_t*         flags;    // [n] exact route, first by sorted position: 1 = the position starts a run of equal values
+    const int64_t*   scan;     // [n + 1] exclusive scan of flags (of the run starts / of the first occurrences)
+    uint32_t*        heads;    // exact route: [runs] the first (smallest) row of every run
+    uint32_t*        firsts;   // [count] the representatives in first-occurrence order
+    const CsDictOut* outs;     // [nouts]
+    int64_t          nouts, ntiles;
+    unsigned long long* nulls; // [nouts] zeroed: NULL rows per chunk
+};
+
 int        cs_grid(int64_t items);
 hipError_t launch_cs_hist(const CsHistArgs& a, hipStream_t s);
 hipError_t launch_cs_fill64(uint64_t* p, int64_t n, uint64_t v, hipStream_t s);
@@ -85,3 +111,8 @@ hipError_t launch_cs_runs(const CsRunArgs& a, hipStream_t s);
 hipError_t launch_cs_utf8_hash(const CsUtf8Args& a, hipStream_t s);      // hash[], table, rep
 hipError_t launch_cs_utf8_verify(const CsUtf8Args& a, hipStream_t s);    // every row against its hash's representative
 hipError_t launch_cs_utf8_runs(const CsUtf8Args& a, hipStream_t s);
+hipError_t launch_cs_dict_rep(const CsDictArgs& a, hipStream_t s);       // hash route: verify + rep[], flags[]
+hipError_t launch_cs_dict_heads(const CsDictArgs& a, hipStream_t s);     // exact route: run starts by sorted position, NULL rows marked in rep[]
+hipError_t launch_cs_dict_spread(const CsDictArgs& a, hipStream_t s);    // exact route, two launches: heads[] <- run starts, then rep[], flags[] by row
+hipError_t launch_cs_dict_firsts(const CsDictArgs& a, hipStream_t s);    // firsts[rank] <- the rows that are their own representative
+hipError_t launch_cs_dict_codes(const CsDictArgs& a, hipStream_t s);     // codes, validity bytes and NULL counts of every output chunk

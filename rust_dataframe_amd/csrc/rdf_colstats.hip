@@ -15,6 +15,10 @@
 //   utf8      hash every valid row's bytes to 64 bits (a lane per row below 512 bytes, a wave per longer row — the same
 //             function either way), insert (hash -> smallest row), then verify every row's bytes against its hash's
 //             representative; a mismatch sends the call to the exact route (sorted order, neighbours compared).
+//   dict      rdf_utf8_dictionary_encode on the utf8 passes: the verify pass's sibling keeps every row's representative
+//             (the exact route: the first row of every sorted run, spread over the run), an exclusive scan of "is its own
+//             representative" ranks the first occurrences, and the codes pass writes rank[rep[row]] and whole validity
+//             bytes per output chunk.
 // Every byte of a Utf8 row is read inside the chunk's value-offset range the host checked.
 #include <algorithm>
 
@@ -523,6 +527,132 @@ __global__ __launch_bounds__(kCsThreads) void cs_utf8_runs_kernel(CsUtf8Args a) 
     }
 }
 
+// ---------------------------------------------------------------- Utf8 dictionary encoding
+
+// The hash route: cs_utf8_verify_kernel's pass that also keeps what it finds — the representative of every row (the
+// smallest row with the row's hash, compared byte for byte) and a flag where a row is its own representative.
+__global__ __launch_bounds__(kCsThreads) void cs_dict_rep_kernel(CsDictArgs a) {
+    const CsUtf8Args& u = a.u;
+    for (int64_t i0 = (int64_t)blockIdx.x * kCsThreads; i0 < u.n; i0 += (int64_t)gridDim.x * kCsThreads) {
+        const int64_t i = i0 + threadIdx.x;
+        CsRow r{nullptr, 0, false}, q{nullptr, 0, false};
+        if (i < u.n) r = cs_row(u, i);
+        bool need = false, lost = false;
+        uint32_t rep = kCsNoRow;
+        if (r.valid) {
+            const uint64_t h = u.hash[i];
+            uint64_t s = (h >> 20) & u.set.mask;
+            lost = true;
+            for (uint64_t probe = 0; probe <= u.set.mask; ++probe) {
+                const uint64_t cur = u.set.table[s];
+                if (cur == h) { lost = false; break; }
+                if (cur == kCsEmpty) break;
+                s = (s + 1) & u.set.mask;
+            }
+            if (!lost) {
+                rep = u.set.rep[s];
+                if ((int64_t)rep >= u.n) { lost = true; rep = kCsNoRow; }
+                else if ((int64_t)rep != i) { need = true; q = cs_row(u, rep); }
+            }
+        }
+        const bool eq = cs_rows_equal(need, r, q);
+        if (lost || (need && !eq)) __atomic_store_n(&u.set.g[CS_G_MISMATCH], 1ull, __ATOMIC_RELAXED);
+        if (i < u.n) {
+            a.rep[i] = rep;
+            a.flags[i] = (int64_t)rep == i ? 1 : 0;
+        }
+    }
+}
+
+// The exact route, by sorted position (NULL rows last): flags[i] = 1 where position i starts a run of equal values; rep[]
+// of the position's row says whether the row is NULL (kCsNoRow) or has a value (0, replaced by cs_dict_spread_kernel).
+__global__ __launch_bounds__(kCsThreads) void cs_dict_heads_kernel(CsDictArgs a) {
+    const CsUtf8Args& u = a.u;
+    for (int64_t i0 = (int64_t)blockIdx.x * kCsThreads; i0 < u.n; i0 += (int64_t)gridDim.x * kCsThreads) {
+        const int64_t i = i0 + threadIdx.x;
+        CsRow r{nullptr, 0, false}, q{nullptr, 0, false};
+        uint32_t row = kCsNoRow;
+        if (i < u.n) {
+            row = u.perm[i];
+            if ((int64_t)row < u.n) r = cs_row(u, row);
+        }
+        bool need = false;
+        if (r.valid && i > 0) {
+            const uint32_t prev = u.perm[i - 1];
+            if ((int64_t)prev < u.n) q = cs_row(u, prev);
+            need = q.valid;
+        }
+        const bool eq = cs_rows_equal(need, r, q);
+        if (i < u.n) {
+            a.flags[i] = r.valid && !(need && eq) ? 1 : 0;
+            if ((int64_t)row < u.n) a.rep[row] = r.valid ? 0u : kCsNoRow;
+        }
+    }
+}
+
+// phase 0: heads[run] = the row at the run's first position — the sort is stable, so that is the run's smallest row;
+// phase 1: every row of a run gets the run's head as its representative, and flags[] (now by row) marks the heads.
+template <int PHASE>
+__global__ __launch_bounds__(kCsThreads) void cs_dict_spread_kernel(CsDictArgs a) {
+    const int64_t n = a.u.n;
+    for (int64_t i = (int64_t)blockIdx.x * kCsThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kCsThreads) {
+        const uint32_t row = a.u.perm[i];
+        if ((int64_t)row >= n) continue;
+        const int64_t before = a.scan[i], upto = a.scan[i + 1];   // run starts in front of / up to and including position i
+        if (PHASE == 0) {
+            if (upto != before) a.heads[before] = row;
+        } else {
+            uint32_t rep = kCsNoRow;
+            if (a.rep[row] != kCsNoRow && upto > 0) rep = a.heads[upto - 1];
+            a.rep[row] = rep;
+            a.flags[row] = rep == row ? 1 : 0;
+        }
+    }
+}
+
+__global__ __launch_bounds__(kCsThreads) void cs_dict_firsts_kernel(CsDictArgs a) {
+    const int64_t n = a.u.n;
+    for (int64_t i = (int64_t)blockIdx.x * kCsThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kCsThreads)
+        if ((int64_t)a.rep[i] == i) a.firsts[a.scan[i]] = (uint32_t)i;
+}
+
+// code = rank of the representative's first occurrence.  A tile is kCsThreads rows of ONE output chunk starting at a
+// multiple of kCsThreads, a wave's 64 rows make 8 whole validity bytes: no byte is written by two waves.  NULL rows are
+// counted per wave and added to the chunk's counter when the wave moves to another chunk.
+__global__ __launch_bounds__(kCsThreads) void cs_dict_codes_kernel(CsDictArgs a) {
+    const int lane = threadIdx.x & 63;
+    int64_t pend_c = -1;
+    unsigned int pend = 0;
+    for (int64_t t = blockIdx.x; t < a.ntiles; t += gridDim.x) {
+        int64_t lo = 0, hi = a.nouts;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (a.outs[mid].tile_start <= t) lo = mid + 1; else hi = mid;
+        }
+        const int64_t c = lo - 1;
+        const CsDictOut o = a.outs[c];
+        const int64_t e = (t - o.tile_start) * kCsThreads + threadIdx.x;
+        const bool in = e < o.rows;
+        bool valid = false;
+        if (in) {
+            const uint32_t rep = a.rep[o.row_start + e];
+            valid = rep != kCsNoRow;
+            o.codes[e] = valid ? (uint32_t)a.scan[rep] : 0u;
+        }
+        const unsigned long long vm = __ballot(valid);
+        const unsigned int nulls = (unsigned int)__popcll(__ballot(in && !valid));
+        const int64_t e0 = e - lane;   // the wave's first row: a multiple of 64
+        if (o.valid && lane < 8 && e0 + lane * 8 < o.rows) o.valid[(e0 >> 3) + lane] = (uint8_t)(vm >> (8 * lane));
+        if (c != pend_c) {
+            if (pend && lane == 0) atomicAdd(&a.nulls[pend_c], (unsigned long long)pend);
+            pend_c = c;
+            pend = 0;
+        }
+        pend += nulls;
+    }
+    if (pend && lane == 0) atomicAdd(&a.nulls[pend_c], (unsigned long long)pend);
+}
+
 }  // namespace
 
 int cs_grid(int64_t items) {
@@ -582,5 +712,32 @@ hipError_t launch_cs_utf8_verify(const CsUtf8Args& a, hipStream_t s) {
 hipError_t launch_cs_utf8_runs(const CsUtf8Args& a, hipStream_t s) {
     if (a.n <= 0) return hipSuccess;
     hipLaunchKernelGGL(cs_utf8_runs_kernel, dim3(cs_grid(a.n)), dim3(kCsThreads), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t launch_cs_dict_rep(const CsDictArgs& a, hipStream_t s) {
+    if (a.u.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(cs_dict_rep_kernel, dim3(cs_grid(a.u.n)), dim3(kCsThreads), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t launch_cs_dict_heads(const CsDictArgs& a, hipStream_t s) {
+    if (a.u.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(cs_dict_heads_kernel, dim3(cs_grid(a.u.n)), dim3(kCsThreads), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t launch_cs_dict_spread(const CsDictArgs& a, hipStream_t s) {
+    if (a.u.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(cs_dict_spread_kernel<0>, dim3(cs_grid(a.u.n)), dim3(kCsThreads), 0, s, a);
+    hipLaunchKernelGGL(cs_dict_spread_kernel<1>, dim3(cs_grid(a.u.n)), dim3(kCsThreads), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t launch_cs_dict_firsts(const CsDictArgs& a, hipStream_t s) {
+    if (a.u.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(cs_dict_firsts_kernel, dim3(cs_grid(a.u.n)), dim3(kCsThreads), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t launch_cs_dict_codes(const CsDictArgs& a, hipStream_t s) {
+    if (a.ntiles <= 0) return hipSuccess;
+    const int64_t grid = std::min<int64_t>(a.ntiles, eval_grid_limit());
+    hipLaunchKernelGGL(cs_dict_codes_kernel, dim3((unsigned)grid), dim3(kCsThreads), 0, s, a);
     return hipGetLastError();
 }
