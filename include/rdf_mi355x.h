@@ -246,7 +246,10 @@ typedef enum { RDF_JOIN_LEFT = 0, RDF_JOIN_RIGHT = 1, RDF_JOIN_INNER = 2, RDF_JO
  * Column::take (src/dataframe.rs:705-711).  NULL keys never match; LEFT/RIGHT/FULL keep them with a
  * NULL partner.  FULL is a true full outer join (the reference's FullJoin arm drops unmatched non-NULL
  * rows: not copied).  Pair order: probe rows ascending, partners ascending, then (FULL) the unmatched
- * build rows in unspecified order — the reference's order is HashMap iteration order.
+ * build rows in unspecified order — the reference's order is HashMap iteration order.  (RIGHT probes with
+ * the right rows: right rows ascending, their left partners ascending.)
+ * Keys are equal when their BITS are equal, as in the reference's HashMap over key bytes: a Float32 /
+ * Float64 key -0.0 does not join +0.0, and a NaN joins exactly the NaNs of its own sign and payload.
  * *out_rows = rows of the result; with out_left == out_right == NULL only the count is computed;
  * capacity too small -> RDF_MEMORY_ERROR with *out_rows set. */
 rdf_status rdf_equijoin_indices(const rdf_array* left_keys, int64_t left_nchunks, const rdf_array* right_keys,

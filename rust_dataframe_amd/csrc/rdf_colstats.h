@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "rdf_device.h"
+#include "rdf_hash.h"
 #include "rdf_utf8.h"
 
 // edges[i] of numpy.histogram(bins = nbins, range = (lo, hi)): lo + i * step with two roundings (the library is compiled
@@ -21,8 +22,8 @@ constexpr int kCsTile = kCsThreads * kCsRowsPerLane;   // rows of one tile of a 
 constexpr int kCsHistLdsBins = 4096;                   // up to here the counters of a block live in LDS (16 KiB of 32-bit words)
 constexpr int kCsHistWaveBins = 1024;                  // up to here every wave of the block has its own copy of them
 constexpr int kCsLdsSetSlots = 2048;                   // the block's LDS set of the numeric distinct pass (16 KiB), filled to half
-constexpr int kCsLongRow = 512;                        // Utf8 rows of this many bytes or more are hashed / compared by a whole wave
-constexpr uint64_t kCsEmpty = 0xFFF7A5A55A5A0001ull;   // free slot of the sets: a NaN payload no normalised Float64 key has
+using rdfk::kCsLongRow;                                // (rdf_hash.h: they are part of what a Utf8 row's hash is)
+using rdfk::kCsEmpty;
 
 // A chunked 8-byte column cut into tiles that never cross a chunk: tile t belongs to the chunk c with
 // tile_start[c] <= t < tile_start[c + 1].

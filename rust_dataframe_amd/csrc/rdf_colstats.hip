@@ -60,13 +60,6 @@ __device__ __forceinline__ unsigned long long block_reserve(unsigned int mine, u
     return pos;
 }
 
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdull;
-    x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull;
-    x ^= x >> 33;
-    return x;
-}
-
 // ---------------------------------------------------------------- tiles of a chunked 8-byte column
 
 struct CsTileView { GlobalPtr<uint64_t> v; const uint8_t* valid; int64_t bit0; int rows; };
@@ -385,24 +378,7 @@ __device__ __forceinline__ CsRow cs_row(const CsUtf8Args& a, int64_t row) {
     return r;
 }
 
-// bytes [8w, 8w + 8) of a row as a little-endian word, zero beyond the row's end (nothing past the row is read)
-__device__ __forceinline__ uint64_t cs_word(const uint8_t* p, int32_t len, int32_t w) {
-    const int32_t o = w * 8;
-    uint64_t x = 0;
-    if (o + 8 <= len) { __builtin_memcpy(&x, p + o, 8); return x; }
-    for (int b = 0; o + b < len; ++b) x |= (uint64_t)p[o + b] << (8 * b);
-    return x;
-}
-// The hash of a row: word w goes into stream w mod 64, a stream chains its words, the streams are added, the length closes
-// it.  A row below 512 bytes has at most one word per stream, so one lane can add its terms in a loop; a wave takes a
-// longer row with lane j on stream j.  Same value either way.
-__device__ __forceinline__ uint64_t cs_term(uint64_t st, uint64_t word, int32_t w) {
-    return mix64(st ^ (word + (uint64_t)(w + 1) * 0x9E3779B97F4A7C15ull));
-}
-__device__ __forceinline__ uint64_t cs_hash_close(uint64_t acc, int32_t len) {
-    const uint64_t h = mix64(acc ^ ((uint64_t)(uint32_t)len * 0xD6E8FEB86659FD93ull));
-    return h == kCsEmpty ? h ^ 1 : h;
-}
+// cs_word / cs_term / cs_stream / cs_hash_close, the hash of a row: rdf_hash.h
 
 // need: this lane wants ra == rb decided.  Called by all lanes of the wave (long rows are compared by the whole wave).
 __device__ bool cs_rows_equal(bool need, const CsRow& ra, const CsRow& rb) {
@@ -455,9 +431,8 @@ __global__ __launch_bounds__(kCsThreads) void cs_utf8_hash_kernel(CsUtf8Args a) 
             m &= m - 1;
             const uint8_t* p = (const uint8_t*)(uintptr_t)shfl64((uint64_t)(uintptr_t)r.p, src);
             const int32_t len = __shfl(r.len, src);
-            const int32_t nw = (len + 7) >> 3;
-            uint64_t st = 0;
-            for (int32_t w = lane; w < nw; w += 64) st = cs_term(st, cs_word(p, len, w), w);
+            static_assert(kCsStreams == 64, "one stream per lane of the wave");
+            uint64_t st = cs_stream(p, len, lane);
 #pragma unroll
             for (int x = 32; x >= 1; x >>= 1) st += shfl_xor64(st, x);
             if (lane == src) acc = st;

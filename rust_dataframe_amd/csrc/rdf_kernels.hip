@@ -22,6 +22,7 @@
 //                             [Column::take src/table.rs:218-241]
 //   fill_*                    counter-based synthetic data (bench / tests)
 #include "rdf_common.hip.h"
+#include "rdf_hash.h"
 #include "rdf_join_place.h"
 
 namespace rdfk {
@@ -450,18 +451,13 @@ __global__ __launch_bounds__(kBlock) void sort_keys_kernel(const SortKeyArgs a, 
 
 // multi-column join keys: one 64-bit hash per row over the columns' order-preserving key bits (SplitMix64 finaliser per
 // column, chained); rows with a NULL in any key column keep hash 0 and are excluded through nullflags
-constexpr uint64_t kJoinMul = 0x9E3779B97F4A7C15ull;     // slot = (key * kJoinMul) >> tshift; odd: key -> key * kJoinMul is a bijection
-__device__ __forceinline__ uint64_t join_mix(uint64_t z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+// (kJoinMul, join_mix and the chain over the columns: rdf_hash.h)
 __global__ __launch_bounds__(kBlock) void join_combine_kernel(const JoinCombineArgs a) {
     uint64_t kmin = ~0ull, kmax = 0;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * kBlock) {
         const bool isnull = a.nullflags && a.nullflags[i];
-        uint64_t h = 0x9E3779B97F4A7C15ull;
-        for (int k = 0; k < a.nkeys; ++k) h = join_mix(h ^ a.bits[k][i]) + 0x9E3779B97F4A7C15ull * (uint64_t)(k + 1);
+        uint64_t h = kJoinSeed;
+        for (int k = 0; k < a.nkeys; ++k) h = join_tuple_step(h, a.bits[k][i], k);
         if (isnull) h = 0;
         a.out[i] = h;
         if (!isnull) { kmin = h < kmin ? h : kmin; kmax = h > kmax ? h : kmax; }

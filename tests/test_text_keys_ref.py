@@ -52,3 +52,17 @@ def test_join_duplicates_multiply_and_two_column_keys():
     assert R.equijoin(left, right, "inner") == Counter({(0, 0): 1, (0, 1): 1})
     assert R.ordered_pairs(left, right, "inner") == [(0, 0), (0, 1)]
     assert R.equijoin(left, right, "full") == Counter({(0, 0): 1, (0, 1): 1, (1, None): 1, (None, 2): 1})
+
+
+def test_ordered_pairs_right_and_full():
+    left = [["a", None, "b", "a"]]
+    right = [[None, "a", "c", "a"]]
+    assert R.ordered_pairs(left, right, "inner") == [(0, 1), (0, 3), (3, 1), (3, 3)]
+    # RIGHT probes with the right rows: right rows ascending, their left partners ascending
+    assert R.ordered_pairs(left, right, "right") == [(None, 0), (0, 1), (3, 1), (None, 2), (0, 3), (3, 3)]
+    full = R.ordered_pairs(left, right, "full")
+    assert full == [(0, 1), (0, 3), (1, None), (2, None), (3, 1), (3, 3), (None, 0), (None, 2)]
+    assert R.full_probe_rows(left, right) == 6
+    for how in ("inner", "left", "right", "full"):
+        assert Counter(R.ordered_pairs(left, right, how)) == R.equijoin(left, right, how)
+    R.assert_ordered(full[:6] + [(None, 2), (None, 0)], left, right, "full")      # the tail is a set

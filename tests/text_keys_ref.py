@@ -77,19 +77,42 @@ def equijoin(left, right, how):
 
 
 def ordered_pairs(left, right, how):
-    """The documented order of INNER / LEFT results: probe (left) rows ascending, partners ascending."""
-    assert how in ("inner", "left")
-    nl, nr = len(left[0]), len(right[0])
+    """The documented order of the results.  INNER / LEFT / FULL probe with the left rows, RIGHT with the right rows: probe
+    rows ascending, every probe row's partners ascending (an outer join's probe row without a partner once, with None),
+    then for FULL the unmatched build (right) rows — in unspecified order, listed ascending here: see full_probe_rows."""
+    assert how in ("inner", "left", "right", "full")
+    probe, build = (right, left) if how == "right" else (left, right)
+    np_, nb = len(probe[0]), len(build[0])
     index = {}
-    for j in range(nr):
-        k = tuple(c[j] for c in right)
+    for j in range(nb):
+        k = tuple(c[j] for c in build)
         if None not in k:
             index.setdefault(k, []).append(j)
     out = []
-    for i in range(nl):
-        k = tuple(c[i] for c in left)
+    matched = set()
+    for i in range(np_):
+        k = tuple(c[i] for c in probe)
         partners = index.get(k, []) if None not in k else []
         out.extend((i, j) for j in partners)
-        if not partners and how == "left":
+        matched.update(partners)
+        if not partners and how != "inner":
             out.append((i, None))
+    if how == "right":
+        return [(b, p) for p, b in out]
+    if how == "full":
+        out.extend((None, j) for j in range(nb) if j not in matched)
     return out
+
+
+def full_probe_rows(left, right):
+    """Rows of a FULL join's result that come from its probe pass (their order is fixed; the rest is a set)."""
+    return len(ordered_pairs(left, right, "left"))
+
+
+def assert_ordered(pairs, left, right, how):
+    """pairs == the documented order; the unmatched build rows behind a FULL join's probe pass compare as a set."""
+    exp = ordered_pairs(left, right, how)
+    assert len(pairs) == len(exp), (len(pairs), len(exp))
+    n = full_probe_rows(left, right) if how == "full" else len(exp)
+    assert pairs[:n] == exp[:n], next((i, pairs[i], exp[i]) for i in range(n) if pairs[i] != exp[i])
+    assert sorted(pairs[n:], key=lambda p: p[1]) == exp[n:]
