@@ -1,7 +1,10 @@
 """Helpers for the parity tests: seeded Arrow-shaped inputs and comparisons.
 
 Parity bar (BASELINE.json north_star): bit-exact for integer / index / bitmap results; f64/f32
-arithmetic, trig and sums within RTOL = 1e-6 relative of the oracle.
+arithmetic, trig and sums within RTOL = 1e-6 relative of the oracle.  Two suites hold floats to more than that, against
+exact references instead of the oracle: test_float_accuracy_gpu.py (hard arguments) and test_spec_catalog.py (every kernel
+of the specialised catalog, by name) — stored + - * / bit-exact, math functions within the ulp bounds of ulp_bounds.py,
+sums within the bound that holds for any summation order.
 """
 import numpy as np
 
