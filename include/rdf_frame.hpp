@@ -2783,6 +2783,63 @@ struct AggregateFunctions {  // src/functions/aggregate.rs:12-93
         check(rdf_avg(v.data(), (int64_t)v.size(), &out, &some));
         return some ? std::optional<double>(out) : std::nullopt;
     }
+
+    // variance / stddev / skewness / kurtosis (:94-102, declared with empty bodies and a TODO for "population and sample")
+    // and ScalarFunctions::corr (src/functions/scalar.rs:184) with Spark's definitions: ONE pass over the column gives a
+    // state, every statistic is read off it, and states of shards merge.  `mask` (a Boolean column chunked like the data)
+    // is Column::filter's condition: filter -> variance without the compacted copy.
+    struct Moments {
+        rdf_moments_state state{};
+        int64_t count() const { return state.count; }
+        Moments& merge(const Moments& other) { check(rdf_moments_merge(&state, &other.state)); return *this; }
+        std::optional<double> stat(rdf_stat which) const {
+            double out = 0; int32_t some = 0;
+            check(rdf_moments_stat(&state, (int32_t)which, &out, &some));
+            return some ? std::optional<double>(out) : std::nullopt;
+        }
+    };
+    struct Comoments {
+        rdf_comoments_state state{};
+        int64_t count() const { return state.count; }
+        Comoments& merge(const Comoments& other) { check(rdf_comoments_merge(&state, &other.state)); return *this; }
+        std::optional<double> stat(rdf_costat which) const {
+            double out = 0; int32_t some = 0;
+            check(rdf_comoments_stat(&state, (int32_t)which, &out, &some));
+            return some ? std::optional<double>(out) : std::nullopt;
+        }
+    };
+    static Moments moments(const ChunkedArray& c, const ChunkedArray* mask = nullptr) {
+        const auto v = c.views();
+        const auto m = mask_views(mask, v.size());
+        Moments r;
+        check(rdf_moments(v.data(), mask ? m.data() : nullptr, (int64_t)v.size(), &r.state));
+        return r;
+    }
+    static Comoments comoments(const ChunkedArray& x, const ChunkedArray& y, const ChunkedArray* mask = nullptr) {
+        const auto vx = x.views(), vy = y.views();
+        if (vx.size() != vy.size()) throw DataFrameError(DataFrameError::ComputeError, "comoments: chunk counts differ");
+        const auto m = mask_views(mask, vx.size());
+        Comoments r;
+        check(rdf_comoments(vx.data(), vy.data(), mask ? m.data() : nullptr, (int64_t)vx.size(), &r.state));
+        return r;
+    }
+    // the sample forms, as Spark's `variance` / `stddev`
+    static std::optional<double> variance(const ChunkedArray& c, const ChunkedArray* mask = nullptr) { return moments(c, mask).stat(RDF_STAT_VAR_SAMP); }
+    static std::optional<double> stddev(const ChunkedArray& c, const ChunkedArray* mask = nullptr) { return moments(c, mask).stat(RDF_STAT_STDDEV_SAMP); }
+    static std::optional<double> var_pop(const ChunkedArray& c, const ChunkedArray* mask = nullptr) { return moments(c, mask).stat(RDF_STAT_VAR_POP); }
+    static std::optional<double> stddev_pop(const ChunkedArray& c, const ChunkedArray* mask = nullptr) { return moments(c, mask).stat(RDF_STAT_STDDEV_POP); }
+    static std::optional<double> skewness(const ChunkedArray& c, const ChunkedArray* mask = nullptr) { return moments(c, mask).stat(RDF_STAT_SKEWNESS); }
+    static std::optional<double> kurtosis(const ChunkedArray& c, const ChunkedArray* mask = nullptr) { return moments(c, mask).stat(RDF_STAT_KURTOSIS); }
+    static std::optional<double> corr(const ChunkedArray& x, const ChunkedArray& y, const ChunkedArray* mask = nullptr) { return comoments(x, y, mask).stat(RDF_COSTAT_CORR); }
+    static std::optional<double> covar_pop(const ChunkedArray& x, const ChunkedArray& y, const ChunkedArray* mask = nullptr) { return comoments(x, y, mask).stat(RDF_COSTAT_COVAR_POP); }
+    static std::optional<double> covar_samp(const ChunkedArray& x, const ChunkedArray& y, const ChunkedArray* mask = nullptr) { return comoments(x, y, mask).stat(RDF_COSTAT_COVAR_SAMP); }
+
+  private:
+    static std::vector<rdf_array> mask_views(const ChunkedArray* mask, size_t nchunks) {
+        if (!mask) return {};
+        if (mask->num_chunks() != nchunks) throw DataFrameError(DataFrameError::ComputeError, "moments: the mask's chunk count differs");
+        return mask->views();
+    }
 };
 
 // ------------------------------------------------------------------------------------------------

@@ -180,6 +180,52 @@ rdf_status rdf_count(const rdf_array* a, int64_t nchunks, int64_t* out_count, in
 /* AggregateFunctions::avg (:32-65): mean of the valid values as f64, None when there are none. */
 rdf_status rdf_avg(const rdf_array* a, int64_t nchunks, double* out_mean, int32_t* out_is_some);
 
+/* ------------------------------------------------------------------ moments: variance, stddev, skewness, kurtosis, corr
+ *
+ * AggregateFunctions::variance / stddev / skewness / kurtosis (declared with empty bodies and a TODO for "population and
+ * sample" forms, src/functions/aggregate.rs:94-102) and ScalarFunctions::corr (src/functions/scalar.rs:184), with Spark's
+ * semantics.  One pass over the column produces a STATE; the statistics are read off the state on the host, and states
+ * of shards, ranks or slabs combine with rdf_moments_merge (Chan / Pebay's pairwise update).
+ *
+ *   count            rows that count
+ *   mean + mean_lo   their mean as an unevaluated sum of two doubles
+ *   m2, m3, m4       sum (x - mean)^k over them
+ *   m2x, m2y, cxy    the same sums per column, and sum (x - mean_x)(y - mean_y)
+ * Zero rows give a state of all zeros.
+ *
+ * a / x / y: any of the ten numeric dtypes (x and y may differ), every value converted `as f64` like rdf_avg; chunks may
+ * carry any offset and validity.  mask: NULL, or nchunks RDF_BOOL chunks of the same lengths.  A row counts when its value
+ * is valid (rdf_comoments: both values), the mask slot is valid and the mask bit is set — Column::filter's rule, so
+ * filter -> variance is one pass with no compacted copy.
+ *
+ * The kernel never forms sum x^2: every tile of rows is centred on its own mean first and tile states are merged, so a
+ * column such as 1e9 + noise keeps every digit (DESIGN.md 13 has the bound).  The same input gives the same bytes on
+ * every call, from host and from device memory.  A non-finite valid value makes every statistic except the count NaN
+ * (rdf_avg stays the way to an infinite mean).  Deviations whose fourth power overflows a double (|x - mean| >~ 1e77) give
+ * inf or NaN in m4 (m3 from ~1e102, m2 from ~1e154).
+ *
+ * Refused with RDF_INVALID_ARGUMENT before any device work: a non-numeric dtype or chunks of different dtypes, chunk
+ * lengths that differ between x, y and mask, a mask that is not RDF_BOOL, a NULL `out`, an unknown stat.  nchunks == 0
+ * (and zero rows) is the zero state and RDF_OK.  The merge and stat functions run on the host and need no device.
+ *
+ * Statistics (out_is_some = 0: count == 0; a _SAMP statistic with count < 2; SKEWNESS / KURTOSIS with m2 == 0; CORR with
+ * m2x or m2y == 0):
+ *   VAR_POP m2 / n, VAR_SAMP m2 / (n - 1), STDDEV_* their square roots, SKEWNESS sqrt(n) m3 / m2^1.5,
+ *   KURTOSIS n m4 / m2^2 - 3 (excess), COVAR_POP cxy / n, COVAR_SAMP cxy / (n - 1), CORR cxy / sqrt(m2x m2y). */
+typedef struct { int64_t count; double mean, mean_lo, m2, m3, m4; } rdf_moments_state;
+typedef struct { int64_t count; double mean_x, mean_x_lo, mean_y, mean_y_lo, m2x, m2y, cxy; } rdf_comoments_state;
+typedef enum { RDF_STAT_MEAN = 0, RDF_STAT_VAR_POP, RDF_STAT_VAR_SAMP, RDF_STAT_STDDEV_POP, RDF_STAT_STDDEV_SAMP,
+               RDF_STAT_SKEWNESS, RDF_STAT_KURTOSIS } rdf_stat;
+typedef enum { RDF_COSTAT_COVAR_POP = 0, RDF_COSTAT_COVAR_SAMP, RDF_COSTAT_CORR } rdf_costat;
+
+rdf_status rdf_moments(const rdf_array* a, const rdf_array* mask, int64_t nchunks, rdf_moments_state* out);
+rdf_status rdf_comoments(const rdf_array* x, const rdf_array* y, const rdf_array* mask, int64_t nchunks, rdf_comoments_state* out);
+/* into <- the state of the rows of `into` and of `other` together.  Merging with the zero state is the identity. */
+rdf_status rdf_moments_merge(rdf_moments_state* into, const rdf_moments_state* other);
+rdf_status rdf_comoments_merge(rdf_comoments_state* into, const rdf_comoments_state* other);
+rdf_status rdf_moments_stat(const rdf_moments_state* s, int32_t stat, double* out, int32_t* out_is_some);
+rdf_status rdf_comoments_stat(const rdf_comoments_state* s, int32_t stat, double* out, int32_t* out_is_some);
+
 /* ------------------------------------------------------------------ expressions */
 
 typedef enum { RDF_NODE_COLUMN = 0, RDF_NODE_SCALAR = 1, RDF_NODE_OP = 2 } rdf_node_kind;

@@ -78,6 +78,15 @@ pub mod sys {
     pub const RDF_BOUND_FOLLOWING: i32 = 3; pub const RDF_BOUND_UNBOUNDED_FOLLOWING: i32 = 4;
     pub const RDF_WAGG_SUM: i32 = 0; pub const RDF_WAGG_MIN: i32 = 1; pub const RDF_WAGG_MAX: i32 = 2; pub const RDF_WAGG_COUNT: i32 = 3;
     pub const RDF_WAGG_AVG: i32 = 4; pub const RDF_WAGG_FIRST_VALUE: i32 = 5; pub const RDF_WAGG_LAST_VALUE: i32 = 6;
+    // the state of rdf_moments / rdf_comoments: count, the mean(s) as two doubles each, the central sums
+    #[repr(C)] #[derive(Clone, Copy, Default)]
+    pub struct rdf_moments_state { pub count: i64, pub mean: f64, pub mean_lo: f64, pub m2: f64, pub m3: f64, pub m4: f64 }
+    #[repr(C)] #[derive(Clone, Copy, Default)]
+    pub struct rdf_comoments_state { pub count: i64, pub mean_x: f64, pub mean_x_lo: f64, pub mean_y: f64, pub mean_y_lo: f64,
+                                     pub m2x: f64, pub m2y: f64, pub cxy: f64 }
+    pub const RDF_STAT_MEAN: i32 = 0; pub const RDF_STAT_VAR_POP: i32 = 1; pub const RDF_STAT_VAR_SAMP: i32 = 2; pub const RDF_STAT_STDDEV_POP: i32 = 3;
+    pub const RDF_STAT_STDDEV_SAMP: i32 = 4; pub const RDF_STAT_SKEWNESS: i32 = 5; pub const RDF_STAT_KURTOSIS: i32 = 6;
+    pub const RDF_COSTAT_COVAR_POP: i32 = 0; pub const RDF_COSTAT_COVAR_SAMP: i32 = 1; pub const RDF_COSTAT_CORR: i32 = 2;
     #[repr(C)] pub struct rdf_frame { _opaque: [u8; 0] }
     #[repr(C)] pub struct rdf_comm { _opaque: [u8; 0] }
     #[repr(C)] #[derive(Clone, Copy, Default)]
@@ -110,6 +119,13 @@ pub mod sys {
         pub fn rdf_max(a: *const rdf_array, nchunks: i64, out_scalar: *mut c_void, out_is_some: *mut i32) -> i32;
         pub fn rdf_count(a: *const rdf_array, nchunks: i64, out_count: *mut i64, out_is_some: *mut i32) -> i32;
         pub fn rdf_avg(a: *const rdf_array, nchunks: i64, out_mean: *mut f64, out_is_some: *mut i32) -> i32;
+        // variance / stddev / skewness / kurtosis (aggregate.rs:94-102) and corr (scalar.rs:184): one pass -> a state, statistics off the state
+        pub fn rdf_moments(a: *const rdf_array, mask: *const rdf_array, nchunks: i64, out: *mut rdf_moments_state) -> i32;
+        pub fn rdf_comoments(x: *const rdf_array, y: *const rdf_array, mask: *const rdf_array, nchunks: i64, out: *mut rdf_comoments_state) -> i32;
+        pub fn rdf_moments_merge(into: *mut rdf_moments_state, other: *const rdf_moments_state) -> i32;
+        pub fn rdf_comoments_merge(into: *mut rdf_comoments_state, other: *const rdf_comoments_state) -> i32;
+        pub fn rdf_moments_stat(s: *const rdf_moments_state, stat: i32, out: *mut f64, out_is_some: *mut i32) -> i32;
+        pub fn rdf_comoments_stat(s: *const rdf_comoments_state, stat: i32, out: *mut f64, out_is_some: *mut i32) -> i32;
         // BooleanFilter / filter / take (src/expression.rs:766-861, src/table.rs:97-107,213-241)
         pub fn rdf_predicate(nodes: *const rdf_expr_node, nnodes: i32, root: i32, cols: *const rdf_array, ncols: i32,
                              nchunks: i64, mask: *mut rdf_out) -> i32;
@@ -356,6 +372,37 @@ pub fn sum<T: ArrowNumericType>(chunks: &[&PrimitiveArray<T>]) -> Result<Option<
     let (mut value, mut is_some) = (T::Native::default(), 0i32);
     status(unsafe { rdf_sum(a.as_ptr(), a.len() as i64, &mut value as *mut T::Native as *mut c_void, &mut is_some) })?;
     Ok(if is_some != 0 { Some(value) } else { None })
+}
+
+/// AggregateFunctions::variance / stddev / skewness / kurtosis (src/functions/aggregate.rs:94-102, empty there): one pass for the
+/// state, any number of statistics off it.  `stat` = RDF_STAT_*; variance and stddev are the sample forms (VAR_SAMP, STDDEV_SAMP).
+pub fn moments<T: ArrowNumericType>(chunks: &[&PrimitiveArray<T>], mask: Option<&[&BooleanArray]>) -> Result<rdf_moments_state, ArrowError> {
+    let a = views(chunks);
+    let m = mask.map(|m| m.iter().map(|x| view(*x)).collect::<Vec<_>>());
+    let mut st = rdf_moments_state::default();
+    status(unsafe { rdf_moments(a.as_ptr(), m.as_ref().map_or(std::ptr::null(), |v| v.as_ptr()), a.len() as i64, &mut st) })?;
+    Ok(st)
+}
+pub fn moments_stat(st: &rdf_moments_state, stat: i32) -> Result<Option<f64>, ArrowError> {
+    let (mut v, mut is_some) = (0f64, 0i32);
+    status(unsafe { rdf_moments_stat(st, stat, &mut v, &mut is_some) })?;
+    Ok(if is_some != 0 { Some(v) } else { None })
+}
+/// shards, ranks or slabs: `into` becomes the state of both row sets
+pub fn moments_merge(into: &mut rdf_moments_state, other: &rdf_moments_state) -> Result<(), ArrowError> {
+    status(unsafe { rdf_moments_merge(into, other) })
+}
+/// ScalarFunctions::corr (src/functions/scalar.rs:184, empty there) and the covariances; `stat` = RDF_COSTAT_*.
+pub fn comoments<T: ArrowNumericType, U: ArrowNumericType>(x: &[&PrimitiveArray<T>], y: &[&PrimitiveArray<U>], stat: i32) -> Result<Option<f64>, ArrowError> {
+    let (a, b) = (views(x), views(y));
+    let mut st = rdf_comoments_state::default();
+    status(unsafe { rdf_comoments(a.as_ptr(), b.as_ptr(), std::ptr::null(), a.len() as i64, &mut st) })?;
+    let (mut v, mut is_some) = (0f64, 0i32);
+    status(unsafe { rdf_comoments_stat(&st, stat, &mut v, &mut is_some) })?;
+    Ok(if is_some != 0 { Some(v) } else { None })
+}
+pub fn comoments_merge(into: &mut rdf_comoments_state, other: &rdf_comoments_state) -> Result<(), ArrowError> {
+    status(unsafe { rdf_comoments_merge(into, other) })
 }
 
 /// ChunkedArray::filter / Column::filter (src/table.rs:97-107, 213-215): chunk boundaries are kept.

@@ -160,6 +160,23 @@ def window_frame(unit, start, end) -> rdf_window_frame:
     return rdf_window_frame({"rows": FRAME_ROWS, "range": FRAME_RANGE}[unit], sk, ek, 0, so, eo)
 
 
+class rdf_moments_state(C.Structure):
+    _fields_ = [("count", C.c_int64), ("mean", C.c_double), ("mean_lo", C.c_double), ("m2", C.c_double), ("m3", C.c_double), ("m4", C.c_double)]
+
+
+class rdf_comoments_state(C.Structure):
+    _fields_ = [("count", C.c_int64), ("mean_x", C.c_double), ("mean_x_lo", C.c_double), ("mean_y", C.c_double), ("mean_y_lo", C.c_double),
+                ("m2x", C.c_double), ("m2y", C.c_double), ("cxy", C.c_double)]
+
+
+# rdf_stat / rdf_costat
+STAT_MEAN, STAT_VAR_POP, STAT_VAR_SAMP, STAT_STDDEV_POP, STAT_STDDEV_SAMP, STAT_SKEWNESS, STAT_KURTOSIS = range(7)
+STATS = {"mean": STAT_MEAN, "var_pop": STAT_VAR_POP, "var_samp": STAT_VAR_SAMP, "stddev_pop": STAT_STDDEV_POP,
+         "stddev_samp": STAT_STDDEV_SAMP, "skewness": STAT_SKEWNESS, "kurtosis": STAT_KURTOSIS}
+COSTAT_COVAR_POP, COSTAT_COVAR_SAMP, COSTAT_CORR = range(3)
+COSTATS = {"covar_pop": COSTAT_COVAR_POP, "covar_samp": COSTAT_COVAR_SAMP, "corr": COSTAT_CORR}
+
+
 class rdf_exchange_stats(C.Structure):
     _fields_ = [("exchange", C.c_int32), ("rounds", C.c_int32), ("local_groups", C.c_int64), ("rows_sent", C.c_int64),
                 ("rows_sent_remote", C.c_int64), ("rows_received", C.c_int64), ("bytes_sent", C.c_int64),
@@ -788,6 +805,48 @@ class Api:
         out, some = C.c_double(0), C.c_int32(0)
         self._check(self._fn("avg")(ca, C.c_int64(len(a)), C.byref(out), C.byref(some)))
         return out.value if some.value else None
+
+    # ---- moments (variance, stddev, skewness, kurtosis; covariance and corr): a state per call, statistics read off it
+    def moments(self, chunks: Sequence, mask: Optional[Sequence] = None) -> rdf_moments_state:
+        """rdf_moments: the state (count, mean as two doubles, m2, m3, m4) of the rows that count."""
+        n = len(chunks)
+        st = rdf_moments_state()
+        fn = self._fn("moments")
+        fn.restype = C.c_int
+        self._check(fn(_flat([chunks], n), _flat([mask], n) if mask is not None else None, C.c_int64(n), C.byref(st)))
+        return st
+
+    def comoments(self, x: Sequence, y: Sequence, mask: Optional[Sequence] = None) -> rdf_comoments_state:
+        n = len(x)
+        if len(y) != n:
+            raise ValueError("chunk lists differ in length")
+        st = rdf_comoments_state()
+        fn = self._fn("comoments")
+        fn.restype = C.c_int
+        self._check(fn(_flat([x], n), _flat([y], n), _flat([mask], n) if mask is not None else None, C.c_int64(n), C.byref(st)))
+        return st
+
+    def moments_merge(self, into, other):
+        """into <- the state of both row sets (rdf_moments_merge / rdf_comoments_merge by the state's type); returns `into`."""
+        fn = self._fn("comoments_merge" if isinstance(into, rdf_comoments_state) else "moments_merge")
+        fn.restype = C.c_int
+        self._check(fn(C.byref(into), C.byref(other)))
+        return into
+
+    def _stat(self, name: str, state, stat: int):
+        out, some = C.c_double(0), C.c_int32(0)
+        fn = self._fn(name)
+        fn.restype = C.c_int
+        self._check(fn(C.byref(state), C.c_int32(stat), C.byref(out), C.byref(some)))
+        return out.value if some.value else None
+
+    def moments_stat(self, state: rdf_moments_state, stat):
+        """A statistic of the state ("mean", "var_pop", "var_samp", "stddev_pop", "stddev_samp", "skewness", "kurtosis"), or None."""
+        return self._stat("moments_stat", state, STATS[stat] if isinstance(stat, str) else stat)
+
+    def comoments_stat(self, state: rdf_comoments_state, stat):
+        """"covar_pop", "covar_samp" or "corr" of the state, or None."""
+        return self._stat("comoments_stat", state, COSTATS[stat] if isinstance(stat, str) else stat)
 
     # ---- expressions
     def predicate(self, expr: Expr, root: int, cols: Sequence[Sequence], outs=None):

@@ -30,6 +30,7 @@
 #include "rdf_colstats.h"
 #include "rdf_window.h"
 #include "rdf_window_agg.h"
+#include "rdf_moments.h"
 
 using namespace rdfk;
 
@@ -4190,6 +4191,7 @@ rdf_status groupby_sum_fallback(const rdf_array* keys, const rdf_array* values, 
 #include "rdf_capi_dict.inc"
 #include "rdf_capi_window.inc"
 #include "rdf_capi_window_agg.inc"
+#include "rdf_capi_moments.inc"
 
 extern "C" {
 
