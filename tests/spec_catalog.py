@@ -15,7 +15,7 @@ distinct and columns are pairwise distinct seeded data with their own NULL fract
 column or operator changes the answer.  A draw the numpy reference (tests/spec_ref.py) reports a zero divisor for is
 rejected and the next seed taken (at most MAX_DRAWS per entry and variant).
 
-The host tries the exact catalog before the shape catalog (run_program, rdf_capi.cpp), so a shape entry's program whose
+The host tries the exact catalog before the shape catalog (spec_choose, rdf_capi_program.inc), so a shape entry's program whose
 exact signature is registered too runs on that exact kernel: `exact_signature` restates the host's exact-signature builder,
 draws that would be taken away like that are passed over while another draw reaches the entry, and `Program.expect` names
 the kernel that has to run.  Entries no variant reaches are listed in UNREACHABLE.

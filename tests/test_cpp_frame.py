@@ -75,6 +75,16 @@ def test_join_place_cpp():
     run(out)
 
 
+def test_program_plan_cpp():
+    """The launch policy of the program path (csrc/rdf_program_plan.h, the code run_program's phases call) on the CPU: blocks per CU,
+    grid and tile walk of the specialised kernels for every kind of program and every pinned option, the grouped kernel's grid cap,
+    the LDS copies of the interpreted grouped sink, the tile prefix and its 128-bit reciprocal — against figures written out from
+    the rules."""
+    out = os.path.join(tempfile.gettempdir(), f"rdf_test_program_plan_{os.getpid()}")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", os.path.join(ROOT, "tests", "cpp", "test_program_plan.cpp"), "-o", out])
+    run(out)
+
+
 @pytest.mark.gpu
 def test_frame_mirror_cpp():
     run(build("test_frame", True), os.path.join(ROOT, "tests", "golden", "uk_cities_with_headers.csv"),
