@@ -2320,6 +2320,41 @@ class DataFrame {
         idx->length = ov.length;
         return idx;
     }
+    // rdf_groupby_sorted over columns of this frame: `groups` (0 .. 4 names) are the grouping columns, `value` the ONE column
+    // the calls read (nullptr with no calls).  -> the group count, the UInt32 row index of every group's first row (groups in
+    // ascending key order, NULL last) and one array per call: Int64 counts / sums, Float64 sums of a float column, UInt32 row
+    // indices for first / last (with validity when ignore_nulls is set).  A capacity of the rows always suffices: one call.
+    struct SortedGroups { int64_t groups = 0; ArrayRef group_rows; std::vector<ArrayRef> outs; };
+    SortedGroups sorted_groups(const std::vector<std::string>& groups, const std::string* value, const std::vector<rdf_group_call>& calls) const {
+        const bool host = numeric_columns_on_host();
+        std::vector<SortCriteria> crit;
+        for (auto& g : groups) crit.push_back(SortCriteria{g, false, false});
+        if (value) crit.push_back(SortCriteria{*value, false, false});
+        const SortKeys sk = sort_keys(crit, host);
+        const int64_t cap = (int64_t)num_rows();
+        const bool value_float = value && is_float(column_by_name(*value).data_type());
+        auto rows = Array::make_out(DataType::UInt32, cap, false, host);
+        rdf_out orow = rows->out_view(cap);
+        std::vector<std::shared_ptr<Array>> outs;
+        std::vector<rdf_out> ov;
+        for (auto& c : calls) {
+            const DataType dt = c.fn == RDF_GRP_COUNT_DISTINCT ? DataType::Int64 : c.fn == RDF_GRP_SUM_DISTINCT ? (value_float ? DataType::Float64 : DataType::Int64) : DataType::UInt32;
+            outs.push_back(Array::make_out(dt, cap, c.fn >= RDF_GRP_FIRST && c.ignore_nulls, host));
+            ov.push_back(outs.back()->out_view(cap));
+        }
+        SortedGroups r;
+        check(rdf_groupby_sorted(groups.empty() ? nullptr : sk.keys.data(), (int32_t)groups.size(), value ? &sk.keys[groups.size()] : nullptr, (int64_t)num_chunks(),
+                                 calls.empty() ? nullptr : calls.data(), (int32_t)calls.size(), &orow, calls.empty() ? nullptr : ov.data(), &r.groups));
+        rows->length = orow.length;
+        r.group_rows = rows;
+        for (size_t c = 0; c < outs.size(); ++c) {
+            outs[c]->length = ov[c].length;
+            outs[c]->null_count = ov[c].null_count;
+            if (ov[c].null_count == 0) outs[c]->validity = nullptr;
+            r.outs.push_back(outs[c]);
+        }
+        return r;
+    }
     // sort_by_indices (:216-222): Column::take of every column (chunk size 4096 as in the reference)
     DataFrame take(const ArrayRef& indices) const {
         std::vector<Column> cols;
@@ -2834,7 +2869,64 @@ struct AggregateFunctions {  // src/functions/aggregate.rs:12-93
     static std::optional<double> covar_pop(const ChunkedArray& x, const ChunkedArray& y, const ChunkedArray* mask = nullptr) { return comoments(x, y, mask).stat(RDF_COSTAT_COVAR_POP); }
     static std::optional<double> covar_samp(const ChunkedArray& x, const ChunkedArray& y, const ChunkedArray* mask = nullptr) { return comoments(x, y, mask).stat(RDF_COSTAT_COVAR_SAMP); }
 
+    // count_distinct / sum_distinct / first / last (:66-93, declared with empty bodies) of a whole column, numeric or Utf8:
+    // rdf_groupby_sorted with no grouping columns — distinctness as Column::uniques (floats canonical, Utf8 by bytes), NULL
+    // rows never counted or summed.  An empty column gives 0 / 0 / none / none.
+    //   count_distinct  keeps the hash route of rdf_uniques / rdf_utf8_uniques (count-only calls) for the dtypes those take
+    //   sum_distinct<T> T = double for a float column, int64_t / uint64_t (wrapping) for an integer one; Utf8 is refused
+    //   first / last    the row as a ONE-row column typed like the input (its row is NULL where the column's is), or, with
+    //                   ignore_nulls, the first / last row that is not NULL; none for an empty column or one without such a row
+    static int64_t count_distinct(const Column& c) {
+        int64_t count = 0;
+        const DataType dt = c.data_type();
+        if (c.num_rows() == 0) return 0;
+        if (dt == DataType::Int64 || dt == DataType::UInt64 || dt == DataType::Float64) {
+            const auto v = c.data().views();
+            check(rdf_uniques(v.data(), (int64_t)v.size(), nullptr, &count));
+            return count;
+        }
+        const std::string name = c.name();
+        const DataFrame f = DataFrame::from_columns({c});
+        if (dt == DataType::Utf8) {
+            // rdf_utf8_uniques has no count-only form of its own, so this is its SIZING call: an offsets buffer of one entry
+            // and no data buffer can hold no distinct string, the call sets `count`, writes nothing and answers
+            // RDF_MEMORY_ERROR — the one status that is not an error here; every other one is raised.
+            // host = true whatever the frame holds: the mirror keeps a Utf8 column's strings on the host, and `host` only
+            // says whether sort_keys copies them to the device to match numeric columns in the same call.  This call has no
+            // numeric column to match and its two outputs are host memory, so the strings are handed over where they are.
+            const DataFrame::SortKeys sk = f.sort_keys({DataFrame::SortCriteria{name, false, false}}, true);
+            int32_t one = 0;
+            rdf_out oo{&one, nullptr, 1, 0, 0, RDF_I32, RDF_MEM_HOST}, od{nullptr, nullptr, 0, 0, 0, RDF_U8, RDF_MEM_HOST};
+            const rdf_status st = rdf_utf8_uniques(sk.txt[0].data(), (int64_t)sk.txt[0].size(), &oo, &od, &count);
+            if (st != RDF_MEMORY_ERROR) check(st);
+            return count;
+        }
+        const DataFrame::SortedGroups g = f.sorted_groups({}, &name, {rdf_group_call{RDF_GRP_COUNT_DISTINCT, 0}});
+        return g.groups ? g.outs[0]->values_to_host<int64_t>()[0] : 0;
+    }
+    template <class T> static T sum_distinct(const Column& c) {
+        static_assert(std::is_same<T, double>::value || std::is_same<T, int64_t>::value || std::is_same<T, uint64_t>::value, "double, int64_t or uint64_t");
+        const DataType dt = c.data_type();
+        if (!(is_integer(dt) || is_float(dt))) throw DataFrameError(DataFrameError::ComputeError, "Aggregating column must be numeric");
+        if (is_float(dt) != std::is_same<T, double>::value) throw DataFrameError(DataFrameError::ComputeError, "sum_distinct: double for a float column, a 64-bit integer otherwise");
+        if (c.num_rows() == 0) return T(0);
+        const std::string name = c.name();
+        const DataFrame::SortedGroups g = DataFrame::from_columns({c}).sorted_groups({}, &name, {rdf_group_call{RDF_GRP_SUM_DISTINCT, 0}});
+        if (!g.groups) return T(0);
+        if (is_float(dt)) return (T)g.outs[0]->values_to_host<double>()[0];
+        return (T)g.outs[0]->values_to_host<int64_t>()[0];
+    }
+    static std::optional<Column> first(const Column& c, bool ignore_nulls = false) { return first_or_last(c, RDF_GRP_FIRST, ignore_nulls); }
+    static std::optional<Column> last(const Column& c, bool ignore_nulls = false) { return first_or_last(c, RDF_GRP_LAST, ignore_nulls); }
+
   private:
+    static std::optional<Column> first_or_last(const Column& c, int32_t fn, bool ignore_nulls) {
+        if (c.num_rows() == 0) return std::nullopt;
+        const std::string name = c.name();
+        const DataFrame::SortedGroups g = DataFrame::from_columns({c}).sorted_groups({}, &name, {rdf_group_call{fn, ignore_nulls ? 1 : 0}});
+        if (!g.groups || g.outs[0]->null_count > 0) return std::nullopt;
+        return c.take(g.outs[0], 4096);
+    }
     static std::vector<rdf_array> mask_views(const ChunkedArray* mask, size_t nchunks) {
         if (!mask) return {};
         if (mask->num_chunks() != nchunks) throw DataFrameError(DataFrameError::ComputeError, "moments: the mask's chunk count differs");
@@ -3152,6 +3244,28 @@ class Evaluate {
         }
     }
 
+    // CountDistinct / First / Last of one column per group: one rdf_groupby_sorted (one sort over the grouping columns and the
+    // column), whose groups come in ascending key order with the NULL group last — the order every other aggregate column of
+    // the step is put into, so the rows line up.  count_distinct(x) is UInt32 like count(x); first(x) / last(x) are typed like
+    // x (numeric or Utf8) and gathered by the row indices the call returns: the first / last row of the group, NULL if x is.
+    static void append_sorted_aggregate(const DataFrame& f, const std::vector<std::string>& names, plan::AggregateFunction fn, const std::string& col,
+                                        std::vector<Column>& out_cols) {
+        using AF = plan::AggregateFunction;
+        const Column& vc = f.column_by_name(col);
+        const int32_t gfn = fn == AF::CountDistinct ? RDF_GRP_COUNT_DISTINCT : fn == AF::First ? RDF_GRP_FIRST : RDF_GRP_LAST;
+        const DataFrame::SortedGroups g = f.sorted_groups(names, &col, {rdf_group_call{gfn, 0}});
+        if (out_cols.empty())
+            for (auto& n : names) {
+                const Column& kc = f.column_by_name(n);
+                out_cols.push_back(Column::from_arrays(kc.take(g.group_rows, 4096).data().chunks(), Field{n, kc.data_type(), true}));
+            }
+        if (fn == AF::CountDistinct) {
+            out_cols.push_back(Column::from_arrays(ScalarFunctions::cast({g.outs[0]}, DataType::UInt32), Field{"count_distinct(" + col + ")", DataType::UInt32, true}));
+            return;
+        }
+        out_cols.push_back(Column::from_arrays(vc.take(g.outs[0], 4096).data().chunks(), Field{std::string(fn == AF::First ? "first(" : "last(") + col + ")", vc.data_type(), true}));
+    }
+
     // GroupAggregate whose grouping columns include Utf8 ones: one rdf_groupby_agg_keys per aggregation (the text keys are
     // dictionary-encoded on the device, the codes grouped next to the integer keys, the dictionary taken by the result's code
     // column); results ordered by the grouping columns — text in byte order, the NULL group last.
@@ -3177,6 +3291,7 @@ class Evaluate {
         }
         std::vector<Column> out_cols;
         auto one = [&](AF fn, const std::string& col) {
+            if (fn == AF::CountDistinct || fn == AF::First || fn == AF::Last) { append_sorted_aggregate(f, t.names, fn, col, out_cols); return; }
             if (fn != AF::Sum && fn != AF::Count && fn != AF::Avg && fn != AF::Min && fn != AF::Max) throw DataFrameError(DataFrameError::ComputeError, "Aggregation not yet supported");
             const Column& vc = f.column_by_name(col);
             const DataType vdt = vc.data_type();
@@ -3278,6 +3393,7 @@ class Evaluate {
         // Sparse or NULL-holding keys: one rdf_groupby_agg per aggregation (hash GROUP BY; several grouping columns are
         // range-compressed into one 64-bit key on the device), results ordered by the grouping columns
         auto one = [&](AF fn, const std::string& col) {
+            if (fn == AF::CountDistinct || fn == AF::First || fn == AF::Last) { append_sorted_aggregate(f, t.names, fn, col, out_cols); return; }
             if (fn != AF::Sum && fn != AF::Count && fn != AF::Avg && fn != AF::Min && fn != AF::Max) throw DataFrameError(DataFrameError::ComputeError, "Aggregation not yet supported");
             const Column& vc = f.column_by_name(col);
             const DataType vdt = vc.data_type();

@@ -568,6 +568,58 @@ rdf_status rdf_equijoin_indices_keys(const rdf_sort_key* left_keys, int64_t left
                                      int64_t right_nchunks, int32_t nkeys, int32_t join_type, rdf_out* out_left,
                                      rdf_out* out_right, int64_t* out_rows);
 
+/* ------------------------------------------------------------------ sorted GROUP BY: count_distinct, sum_distinct, first, last */
+
+/* The aggregations of a GROUP BY that need the rows of a group in an order: AggregateFunctions::count_distinct,
+ * sum_distinct, first and last (src/functions/aggregate.rs declares them with empty bodies; Dataset::try_aggregate,
+ * src/expression.rs:114-221, plans CountDistinct / First / Last), so the semantics are SQL's / Spark's, written down here.
+ * One call answers up to 8 functions of ONE value column from ONE sort over (grouping keys, value) — rdf_window's sort and
+ * peer rules (see below), with the grouping columns as partition keys and the value column as the one order key.
+ *
+ * group_by: 0 .. 4 rdf_sort_key (numeric or Utf8 chunks per key, rdf_lexsort_to_indices' conventions); value: ONE
+ * rdf_sort_key, numeric or Utf8, NULL iff ncalls == 0.  The `options` of every key are ignored.  Rows are numbered over the
+ * concatenation of the chunks.  Inputs and outputs all in host memory or all in device memory.
+ *   - Groups: rows that agree on every grouping key; NULL is a key value of its own.  Float keys compare as in rdf_window /
+ *     rdf_uniques: -0.0 == +0.0, one NaN.  ngroup == 0: all rows are one group.  Zero rows give zero groups and a valid
+ *     call (so does a call with no keys and no value: it has no rows).
+ *   - Groups are emitted in ascending key order: key 0 most significant, NULLs last, NaN after +inf.  *out_groups = the
+ *     number of groups.
+ *   - out_group_rows[g] (RDF_U32, or NULL): the row index of the first row of group g in row order; gather the key columns,
+ *     numeric or Utf8, with rdf_take / rdf_utf8_take.  ncalls == 0 returns only this: the distinct key tuples.
+ *   - outs[c] is ONE array of one entry per group for calls[c]:
+ *       COUNT_DISTINCT  RDF_I64: the distinct non-NULL values of the group, by the sort's peer rule (floats canonical, Utf8
+ *                       by bytes, the empty string is a value); 0 for a group without a non-NULL value.
+ *       SUM_DISTINCT    RDF_F64 for Float32 / Float64 values (Float32 widened to double before adding), RDF_I64 otherwise
+ *                       (wrapping mod 2^64, as rdf_groupby_agg's sums): the sum of the distinct non-NULL values; 0 for a
+ *                       group without one, as rdf_groupby_agg — COUNT_DISTINCT tells the two apart.  -0.0 / +0.0 count once,
+ *                       as +0.0.  IEEE otherwise: a NaN among the values gives NaN, +inf with -inf gives NaN.  With m
+ *                       distinct finite values v the result is within gamma(m - 1) * sum|v| of the exact sum, whatever the
+ *                       grouping.  A Utf8 value column: RDF_INVALID_ARGUMENT.
+ *       FIRST / LAST    RDF_U32 ROW INDICES, the LAG / LEAD convention: the smallest / largest row index of the group; with
+ *                       ignore_nulls != 0 the smallest / largest among the rows whose value is not NULL, NULL when the
+ *                       group has none (a validity bitmap is then required if any value chunk carries validity; it is
+ *                       written where given).  Without ignore_nulls every index is valid, and rdf_take / rdf_utf8_take of
+ *                       the value column returns NULL where that row's value is NULL: SQL's first(x).
+ *     ignore_nulls is read by FIRST / LAST only.
+ *   - The result is a function of the multiset of rows alone: groups come in key order and a Float64 sum is accumulated in
+ *     an order fixed by the sorted distinct values and the group boundaries — no atomics — so row order (after mapping
+ *     FIRST / LAST back), chunking, memory kind and repetition do not change a byte.
+ * Sizing: *out_groups, out_group_rows->length and every outs[c].length are set once the groups are counted; any given
+ * capacity below the group count is RDF_MEMORY_ERROR with nothing written; a capacity of the rows always suffices;
+ * out_group_rows == NULL with ncalls == 0 is the count-only call.
+ * Errors, all before any device work: an unknown fn, more than 8 calls or 4 keys, a key or the value setting both pointers
+ * or neither, wrong dtypes or output dtypes, a missing validity bitmap, mixed memory kinds, 2^32 rows or more
+ * RDF_INVALID_ARGUMENT; chunk row counts that differ between columns RDF_COMPUTE_ERROR.
+ * RDF_GROUP_SORTED_TILE is the tile of the fold over the distinct (group, value) pairs (rdf_group_sorted.hip): tests place
+ * group boundaries around its multiples. */
+#define RDF_GROUP_MAX_CALLS 8
+#define RDF_GROUP_SORTED_TILE 256
+typedef enum { RDF_GRP_COUNT_DISTINCT = 0, RDF_GRP_SUM_DISTINCT = 1, RDF_GRP_FIRST = 2, RDF_GRP_LAST = 3 } rdf_group_fn;
+typedef struct { int32_t fn; int32_t ignore_nulls; } rdf_group_call;
+rdf_status rdf_groupby_sorted(const rdf_sort_key* group_by, int32_t ngroup, const rdf_sort_key* value, int64_t nchunks,
+                              const rdf_group_call* calls, int32_t ncalls, rdf_out* out_group_rows, rdf_out* outs,
+                              int64_t* out_groups);
+
 /* ------------------------------------------------------------------ window functions */
 
 /* SQL window functions over partitions: row_number / rank / dense_rank / percent_rank / cume_dist / ntile / lag / lead.

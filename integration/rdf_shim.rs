@@ -78,6 +78,10 @@ pub mod sys {
     pub const RDF_BOUND_FOLLOWING: i32 = 3; pub const RDF_BOUND_UNBOUNDED_FOLLOWING: i32 = 4;
     pub const RDF_WAGG_SUM: i32 = 0; pub const RDF_WAGG_MIN: i32 = 1; pub const RDF_WAGG_MAX: i32 = 2; pub const RDF_WAGG_COUNT: i32 = 3;
     pub const RDF_WAGG_AVG: i32 = 4; pub const RDF_WAGG_FIRST_VALUE: i32 = 5; pub const RDF_WAGG_LAST_VALUE: i32 = 6;
+    // one call of rdf_groupby_sorted: fn = RDF_GRP_*, ignore_nulls read by FIRST / LAST
+    #[repr(C)] #[derive(Clone, Copy)] pub struct rdf_group_call { pub fn_: i32, pub ignore_nulls: i32 }
+    pub const RDF_GRP_COUNT_DISTINCT: i32 = 0; pub const RDF_GRP_SUM_DISTINCT: i32 = 1; pub const RDF_GRP_FIRST: i32 = 2; pub const RDF_GRP_LAST: i32 = 3;
+    pub const RDF_GROUP_MAX_CALLS: i32 = 8;
     // the state of rdf_moments / rdf_comoments: count, the mean(s) as two doubles each, the central sums
     #[repr(C)] #[derive(Clone, Copy, Default)]
     pub struct rdf_moments_state { pub count: i64, pub mean: f64, pub mean_lo: f64, pub m2: f64, pub m3: f64, pub m4: f64 }
@@ -154,6 +158,10 @@ pub mod sys {
         pub fn rdf_equijoin_indices_keys(left_keys: *const rdf_sort_key, left_nchunks: i64, right_keys: *const rdf_sort_key,
                                          right_nchunks: i64, nkeys: i32, join_type: i32, out_left: *mut rdf_out,
                                          out_right: *mut rdf_out, out_rows: *mut i64) -> i32;
+        // AggregateFunctions::count_distinct / sum_distinct / first / last (aggregate.rs, declared with empty bodies) per group
+        pub fn rdf_groupby_sorted(group_by: *const rdf_sort_key, ngroup: i32, value: *const rdf_sort_key, nchunks: i64,
+                                  calls: *const rdf_group_call, ncalls: i32, out_group_rows: *mut rdf_out, outs: *mut rdf_out,
+                                  out_groups: *mut i64) -> i32;
         // WindowSpec / WindowFunctions (src/window.rs, src/functions/window.rs: declared, bodies empty) + ntile (scalar.rs:345)
         pub fn rdf_window(partition_by: *const rdf_sort_key, npartition: i32, order_by: *const rdf_sort_key, norder: i32,
                           nchunks: i64, nrows_if_no_keys: i64, calls: *const rdf_window_call, ncalls: i32, outs: *mut rdf_out) -> i32;
@@ -615,6 +623,49 @@ pub fn lexsort_to_indices(criteria: &[(Vec<&dyn Array>, bool)]) -> Result<ArrayR
     let mut out = buf.as_out();
     status(unsafe { rdf_lexsort_to_indices(keys.as_ptr(), keys.len() as i32, nchunks as i64, &mut out) })?;
     Ok(buf.finish(&out))
+}
+
+/// AggregateFunctions::count_distinct / sum_distinct / first / last (src/functions/aggregate.rs, empty there) per group of 0 .. 4
+/// grouping columns, and the CountDistinct / First / Last a GroupAggregate plans (src/expression.rs:114-221): `calls` are
+/// (RDF_GRP_*, ignore_nulls) over ONE value column, numeric or Utf8, all answered from one sort.  -> (row index of every group's
+/// first row as a UInt32Array, groups in ascending key order with the NULL group last: `take` / `utf8_take` the key columns
+/// with it; one array per call): Int64Array for COUNT_DISTINCT, Float64Array / Int64Array for SUM_DISTINCT of a float / an
+/// integer column, UInt32Array of ROW INDICES for FIRST / LAST (NULL with ignore_nulls where the group has no non-NULL value).
+/// No calls and `value` = None: the distinct key tuples.  The result does not depend on row order, chunking or memory kind.
+pub fn groupby_sorted(group_by: &[Vec<&dyn Array>], value: Option<&Vec<&dyn Array>>, calls: &[(i32, bool)]) -> Result<(ArrayRef, Vec<ArrayRef>), ArrowError> {
+    let cols: Vec<&Vec<&dyn Array>> = group_by.iter().chain(value.into_iter()).collect();
+    let nchunks = cols.first().map_or(0, |c| c.len());
+    let rows: usize = cols.first().map_or(0, |c| c.iter().map(|a| a.len()).sum());
+    let mut num: Vec<Vec<rdf_array>> = Vec::new();
+    let mut txt: Vec<Vec<rdf_utf8_array>> = Vec::new();
+    for chunks in cols.iter() {
+        match chunks.first().map(|a| a.data_type()) {
+            Some(DataType::Utf8) => { txt.push(chunks.iter().map(|a| utf8_view(a.as_any().downcast_ref::<StringArray>().unwrap())).collect()); num.push(Vec::new()); }
+            _ => { num.push(chunks.iter().map(|a| view(*a)).collect()); txt.push(Vec::new()); }
+        }
+    }
+    let keys: Vec<rdf_sort_key> = (0..cols.len()).map(|k| rdf_sort_key {
+        values: if num[k].is_empty() { std::ptr::null() } else { num[k].as_ptr() },
+        utf8: if txt[k].is_empty() { std::ptr::null() } else { txt[k].as_ptr() },
+        options: rdf_sort_options { descending: 0, nulls_first: 0 },
+    }).collect();
+    let ng = group_by.len();
+    let float_value = value.and_then(|v| v.first()).map_or(false, |a| matches!(a.data_type(), DataType::Float32 | DataType::Float64));
+    let ccalls: Vec<rdf_group_call> = calls.iter().map(|(f, ign)| rdf_group_call { fn_: *f, ignore_nulls: *ign as i32 }).collect();
+    let mut bufs: Vec<OutBuf> = calls.iter().map(|(f, ign)| match *f {
+        RDF_GRP_COUNT_DISTINCT => OutBuf::new(DataType::Int64, rows, false),
+        RDF_GRP_SUM_DISTINCT => OutBuf::new(if float_value { DataType::Float64 } else { DataType::Int64 }, rows, false),
+        _ => OutBuf::new(DataType::UInt32, rows, *ign),
+    }).collect();
+    let mut outs: Vec<rdf_out> = bufs.iter_mut().map(|b| b.as_out()).collect();
+    let mut rbuf = OutBuf::new(DataType::UInt32, rows, false);
+    let mut rout = rbuf.as_out();
+    let mut groups = 0i64;
+    status(unsafe { rdf_groupby_sorted(if ng > 0 { keys.as_ptr() } else { std::ptr::null() }, ng as i32,
+                                       if value.is_some() { keys[ng..].as_ptr() } else { std::ptr::null() }, nchunks as i64,
+                                       if ccalls.is_empty() { std::ptr::null() } else { ccalls.as_ptr() }, ccalls.len() as i32,
+                                       &mut rout, if outs.is_empty() { std::ptr::null_mut() } else { outs.as_mut_ptr() }, &mut groups) })?;
+    Ok((rbuf.finish(&rout), bufs.into_iter().zip(outs.iter()).map(|(b, o)| b.finish(o)).collect()))
 }
 
 /// WindowSpec { partition_by, order_by } (src/window.rs) + one WindowFunctions entry (src/functions/window.rs; `ntile` of

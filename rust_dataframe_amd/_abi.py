@@ -125,6 +125,25 @@ def window_out_dtype(fn: int) -> int:
     return F64 if fn in (WIN_PERCENT_RANK, WIN_CUME_DIST) else U32 if fn in (WIN_LAG, WIN_LEAD) else I64
 
 
+class rdf_group_call(C.Structure):
+    _fields_ = [("fn", C.c_int32), ("ignore_nulls", C.c_int32)]
+
+
+# rdf_group_fn
+GRP_COUNT_DISTINCT, GRP_SUM_DISTINCT, GRP_FIRST, GRP_LAST = range(4)
+GROUP_FNS = {"count_distinct": GRP_COUNT_DISTINCT, "sum_distinct": GRP_SUM_DISTINCT, "first": GRP_FIRST, "last": GRP_LAST}
+GROUP_MAX_CALLS = 8
+GROUP_SORTED_TILE = 256   # RDF_GROUP_SORTED_TILE: the fold's tile over the distinct (group, value) pairs
+
+
+def group_sorted_out_dtype(fn: int, value_dtype: int = I64) -> int:
+    if fn == GRP_COUNT_DISTINCT:
+        return I64
+    if fn == GRP_SUM_DISTINCT:
+        return F64 if value_dtype in (F32, F64) else I64
+    return U32
+
+
 class rdf_window_frame(C.Structure):
     _fields_ = [("unit", C.c_int32), ("start_kind", C.c_int32), ("end_kind", C.c_int32), ("pad", C.c_int32), ("start", C.c_int64), ("end", C.c_int64)]
 
@@ -1471,6 +1490,48 @@ class Api:
             vals = t.cpu().numpy().view(NP_OF[out.dtype])[:out.length].copy()
             valid = unpack_bits(v.cpu().numpy(), 0, out.length) if v is not None else None
         return vals, (valid if valid is not None else np.ones(out.length, dtype=bool))
+
+    # ---- sorted GROUP BY: count_distinct / sum_distinct / first / last per group
+    def groupby_sorted(self, group_by: Sequence, value, calls: Sequence, group_rows: bool = True, outs=None, rows_out=None,
+                       raw: bool = False):
+        """rdf_groupby_sorted: group_by = [chunks, ...] (0 .. 4 numeric or Utf8 columns), value = chunks of ONE numeric or Utf8
+        column (None with no calls), calls = [name | (name, ignore_nulls), ...] with the names of GROUP_FNS.  Groups come in
+        ascending key order, NULL last.  -> (groups, group_rows, results): the number of groups, the UInt32 row index of every
+        group's first row (None with group_rows=False) and per call a numpy array, first / last as (row indices, valid).
+        Without `outs` / `rows_out` the buffers hold one entry per row, which always suffices; raw=True returns the output
+        arrays as they are."""
+        cols = list(group_by) + ([value] if value is not None else [])
+        gk, keep_g = self._sort_keys(group_by)
+        vk, keep_v = self._sort_keys([value] if value is not None else [])
+        nchunks = len(cols[0]) if cols else 0
+        n = sum(c.length for c in cols[0]) if cols else 0
+        device = any(isinstance(c, (DeviceArray, DeviceUtf8)) for k in cols for c in k)
+        vdt = value[0].dtype if value is not None and len(value) and not self._is_utf8(value) else I64
+        cc = (rdf_group_call * max(1, len(calls)))()
+        for i, c in enumerate(calls):
+            name, ign = c if isinstance(c, tuple) else (c, 0)
+            cc[i] = rdf_group_call(GROUP_FNS[name] if isinstance(name, str) else int(name), int(ign))
+        if outs is None:
+            outs = [self._window_out(group_sorted_out_dtype(cc[i].fn, vdt), n, device, cc[i].fn in (GRP_FIRST, GRP_LAST)) for i in range(len(calls))]
+        if rows_out is None and group_rows:
+            rows_out = self._window_out(U32, n, device, False)
+        carr = (rdf_out * max(1, len(outs)))(*[o.out_struct() for o in outs])
+        crow = (rdf_out * 1)(rows_out.out_struct()) if rows_out is not None else None
+        groups = C.c_int64(-1)
+        fn = self._fn("groupby_sorted")
+        fn.restype = C.c_int
+        try:
+            self._check(fn(gk if group_by else None, C.c_int32(len(group_by)), vk if value is not None else None, C.c_int64(nchunks),
+                           cc if calls else None, C.c_int32(len(calls)), crow, carr if calls else None, C.byref(groups)))
+        finally:
+            self._finish(outs, carr)
+            if rows_out is not None:
+                self._finish([rows_out], crow)
+            self.last_groups = groups.value
+        if raw:
+            return groups.value, rows_out, outs
+        rows = self.window_to_numpy(rows_out)[0] if rows_out is not None else None
+        return groups.value, rows, [self.window_to_numpy(o) for o in outs]
 
     def utf8_uniques(self, chunks: Sequence, as_arrow=False):
         """Column::uniques of a Utf8 column -> ONE Utf8 chunk of the distinct strings (no NULLs, unspecified order).  The

@@ -32,6 +32,7 @@
 #include "rdf_window.h"
 #include "rdf_window_agg.h"
 #include "rdf_moments.h"
+#include "rdf_group_sorted.h"
 
 using namespace rdfk;
 
@@ -2863,6 +2864,7 @@ rdf_status groupby_sum_fallback(const rdf_array* keys, const rdf_array* values, 
 #include "rdf_capi_window.inc"
 #include "rdf_capi_window_agg.inc"
 #include "rdf_capi_moments.inc"
+#include "rdf_capi_group_sorted.inc"
 
 extern "C" {
 
