@@ -2355,6 +2355,40 @@ class DataFrame {
         }
         return r;
     }
+    // rdf_groupby_collect over columns of this frame: `groups` (0 .. 4 names) are the grouping columns, `value` the ONE column
+    // collected, kind RDF_COLLECT_LIST / RDF_COLLECT_SET.  -> the group and element counts, the UInt32 row index of every
+    // group's first row (groups in ascending key order, NULL last), the Int32 offsets (groups + 1 entries), the UInt32 row
+    // index of every element and, for a numeric value column, the elements themselves (nullptr for Utf8).  A capacity of
+    // the rows always suffices: one call.  A frame without rows gives empty arrays and offsets of the one entry 0.
+    struct CollectedGroups { int64_t groups = 0, elements = 0; ArrayRef group_rows, offsets, child_rows, values; };
+    CollectedGroups collected_groups(const std::vector<std::string>& groups, const std::string& value, int32_t kind) const {
+        const bool host = numeric_columns_on_host();
+        std::vector<SortCriteria> crit;
+        for (auto& g : groups) crit.push_back(SortCriteria{g, false, false});
+        crit.push_back(SortCriteria{value, false, false});
+        const SortKeys sk = sort_keys(crit, host);
+        const int64_t cap = (int64_t)num_rows();
+        const DataType vdt = column_by_name(value).data_type();
+        CollectedGroups r;
+        if (cap == 0) {
+            r.group_rows = Array::from_vec<uint32_t>({});
+            r.offsets = Array::from_vec<int32_t>({0});
+            r.child_rows = Array::from_vec<uint32_t>({});
+            if (vdt != DataType::Utf8) { auto v = Array::make_out(vdt, 0, false, host); r.values = v; }
+            return r;
+        }
+        auto rows = Array::make_out(DataType::UInt32, cap, false, host), offs = Array::make_out(DataType::Int32, cap + 1, false, host);
+        auto child = Array::make_out(DataType::UInt32, cap, false, host);
+        auto vals = vdt == DataType::Utf8 ? nullptr : Array::make_out(vdt, cap, false, host);
+        rdf_out orow = rows->out_view(cap), ooff = offs->out_view(cap + 1), ochild = child->out_view(cap), oval{};
+        if (vals) oval = vals->out_view(cap);
+        check(rdf_groupby_collect(groups.empty() ? nullptr : sk.keys.data(), (int32_t)groups.size(), &sk.keys[groups.size()], (int64_t)num_chunks(), kind,
+                                  &orow, &ooff, &ochild, vals ? &oval : nullptr, &r.groups, &r.elements));
+        rows->length = orow.length; offs->length = ooff.length; child->length = ochild.length;
+        if (vals) vals->length = oval.length;
+        r.group_rows = rows; r.offsets = offs; r.child_rows = child; r.values = vals;
+        return r;
+    }
     // sort_by_indices (:216-222): Column::take of every column (chunk size 4096 as in the reference)
     DataFrame take(const ArrayRef& indices) const {
         std::vector<Column> cols;
@@ -2736,7 +2770,17 @@ class ShardedFrame {
 // ------------------------------------------------------------------------------------------------
 // ScalarFunctions / AggregateFunctions over device columns (chunk list in, chunk list out)
 
+struct ListArray;
+
 struct ScalarFunctions {
+    // explode (src/functions/scalar.rs:237, declared with an empty body: Spark's semantics, written down at rdf_list_explode).
+    // `list` has one row per row of `frame`.  Every element of every non-NULL list becomes one row: every column of `frame`
+    // taken by the element's list row, then the element column `name`, taken from the list's child.  outer (explode_outer):
+    // a NULL or empty list keeps its row, with a NULL element.  posexplode adds the 0-based position inside the list as the
+    // Int32 column `pos_name` in front of the element column (NULL where the element is).  Defined below ListArray.
+    static inline DataFrame explode(const DataFrame& frame, const ListArray& list, const std::string& name, bool outer = false);
+    static inline DataFrame explode_outer(const DataFrame& frame, const ListArray& list, const std::string& name);
+    static inline DataFrame posexplode(const DataFrame& frame, const ListArray& list, const std::string& pos_name, const std::string& name, bool outer = false);
     static std::vector<ArrayRef> binary(int32_t op, const std::vector<ArrayRef>& left, const std::vector<ArrayRef>& right) {
         if (left.size() != right.size()) throw DataFrameError(DataFrameError::ComputeError, "chunk lists differ in length");
         std::vector<rdf_array> a, b;
@@ -2791,6 +2835,7 @@ struct ScalarFunctions {
     static std::vector<ArrayRef> acos(const std::vector<ArrayRef>& a) { return unary(RDF_OP_ACOS, a); }
 
   private:
+    static inline DataFrame explode_rows(const DataFrame& frame, const ListArray& list, const std::string* pos_name, const std::string& name, bool outer);
     static std::vector<ArrayRef> finish(std::vector<std::shared_ptr<Array>>& outs, std::vector<rdf_out>& ov) {
         std::vector<ArrayRef> res;
         for (size_t i = 0; i < outs.size(); ++i) { outs[i]->length = ov[i].length; outs[i]->null_count = ov[i].null_count; res.push_back(outs[i]); }
@@ -3050,7 +3095,20 @@ struct ArrayFunctions {
         return ListArray::from_parts(off, vals, array.offsets->validity ? &valid : nullptr);
     }
 
+    // collect_list() / collect_set() (array.rs:404-405, declared with empty bodies: Spark's semantics, written down at
+    // rdf_groupby_collect) of a whole numeric column, no grouping: a ONE-row ListArray of the non-NULL values in row order
+    // (list), or of the distinct non-NULL values ascending, floats canonical (set).  An empty or all-NULL column gives one
+    // empty list.  Per group: Evaluate::group_collect.
+    static ListArray collect_list(const Column& c) { return collect(c, RDF_COLLECT_LIST); }
+    static ListArray collect_set(const Column& c) { return collect(c, RDF_COLLECT_SET); }
+
   private:
+    static ListArray collect(const Column& c, int32_t kind) {
+        if (c.data_type() == DataType::Utf8 || c.data_type() == DataType::Boolean)
+            throw DataFrameError(DataFrameError::ComputeError, "collect: a ListArray holds a numeric child (Utf8: Evaluate::group_collect)");
+        const DataFrame::CollectedGroups g = DataFrame::from_columns({c}).collected_groups({}, c.name(), kind);
+        return ListArray::from_parts({0, (int32_t)g.elements}, g.values);
+    }
     template <class T> static void expect_child(const ListArray& a, const char* fn) {
         if (a.value_type() != TypeOf<T>::value) throw DataFrameError(DataFrameError::ComputeError, std::string(fn) + ": the list's value type is not the requested one");
     }
@@ -3071,6 +3129,51 @@ struct ArrayFunctions {
         off->length = oo.length;
         vals->length = ov.length;
         return ListArray{off, vals};
+    }
+};
+
+inline DataFrame ScalarFunctions::explode_rows(const DataFrame& frame, const ListArray& list, const std::string* pos_name, const std::string& name, bool outer) {
+    if (frame.num_columns() > 0 && (int64_t)frame.num_rows() != list.len())
+        throw DataFrameError(DataFrameError::ComputeError, "explode: the list column and the frame differ in length");
+    const bool host = list.offsets->host;
+    const rdf_list_array l = list.view();
+    int64_t rows = 0;
+    check(rdf_list_explode(&l, outer ? 1 : 0, nullptr, nullptr, nullptr, &rows));          // the count-only call sizes the outputs
+    auto parent = Array::make_out(DataType::UInt32, rows, false, host), child = Array::make_out(DataType::UInt32, rows, outer, host);
+    auto pos = pos_name ? Array::make_out(DataType::Int32, rows, outer, host) : nullptr;
+    rdf_out op = parent->out_view(rows), oc = child->out_view(rows), opos{};
+    if (pos) opos = pos->out_view(rows);
+    check(rdf_list_explode(&l, outer ? 1 : 0, &op, &oc, pos ? &opos : nullptr, &rows));
+    parent->length = op.length;
+    child->length = oc.length; child->null_count = oc.null_count;
+    if (oc.null_count == 0) child->validity = nullptr;
+    if (pos) { pos->length = opos.length; pos->null_count = opos.null_count; if (opos.null_count == 0) pos->validity = nullptr; }
+    DataFrame out = frame.take(parent);
+    if (pos) out = out.with_column(*pos_name, Column::from_arrays({pos}, Field{*pos_name, DataType::Int32, true}));
+    const Column elements = Column::from_arrays({list.child}, Field{name, list.value_type(), true});
+    return out.with_column(name, elements.take(child, 4096));
+}
+inline DataFrame ScalarFunctions::explode(const DataFrame& frame, const ListArray& list, const std::string& name, bool outer) { return explode_rows(frame, list, nullptr, name, outer); }
+inline DataFrame ScalarFunctions::explode_outer(const DataFrame& frame, const ListArray& list, const std::string& name) { return explode_rows(frame, list, nullptr, name, true); }
+inline DataFrame ScalarFunctions::posexplode(const DataFrame& frame, const ListArray& list, const std::string& pos_name, const std::string& name, bool outer) {
+    return explode_rows(frame, list, &pos_name, name, outer);
+}
+
+// What Evaluate::group_collect returns: one List row per group, for a numeric and for a Utf8 value column alike.
+//   keys     the grouping columns gathered by every group's first row: ascending, the NULL group last (no columns when the
+//            call had no grouping columns: one group)
+//   offsets  Int32, groups + 1 entries starting at 0; every list is valid, a group without a non-NULL value has an empty one
+//   child    the elements, ONE chunk named and typed like the value column: numeric (collect_set: floats canonical) or Utf8
+//            (the mirror keeps text on the host and gathers it there by the element rows the call returns)
+// lists(): the (offsets, child) pair as a ListArray, for a numeric child.
+struct GroupedLists {
+    DataFrame keys;
+    ArrayRef offsets;
+    Column child;
+    int64_t groups() const { return offsets->length - 1; }
+    ListArray lists() const {
+        if (child.data_type() == DataType::Utf8) throw DataFrameError(DataFrameError::ComputeError, "a ListArray holds a numeric child");
+        return ListArray{offsets, child.data().chunks().at(0)};
     }
 };
 
@@ -3095,6 +3198,22 @@ class Evaluate {
         Evaluate ev(frame);
         ev.step_calculate(calc);
         return ev.flush();
+    }
+    // collect_list / collect_set per group (ArrayFunction::CollectList / CollectSet, src/expression.rs:691-692): one
+    // rdf_groupby_collect over 0..4 grouping columns, numeric or Utf8, and ONE value column, numeric or Utf8.  The groups come
+    // in the order group_aggregate puts its rows into, so the two line up row for row.  The plan's GroupAggregate keeps its
+    // set of aggregations: the reference files these two under ArrayFunction, not AggregateFunction.
+    static GroupedLists group_collect(const DataFrame& frame, const std::vector<std::string>& groups, const std::string& column, int32_t kind) {
+        const DataFrame::CollectedGroups g = frame.collected_groups(groups, column, kind);
+        const Column& vc = frame.column_by_name(column);
+        std::vector<Column> keys;
+        for (auto& n : groups) {
+            const Column& kc = frame.column_by_name(n);
+            keys.push_back(Column::from_arrays(kc.take(g.group_rows, 4096).data().chunks(), Field{n, kc.data_type(), true}));
+        }
+        Column child = g.values ? Column::from_arrays({g.values}, Field{column, vc.data_type(), true})
+                                : Column::from_arrays(vc.take(g.child_rows, 4096).data().chunks(), Field{column, vc.data_type(), true});
+        return GroupedLists{DataFrame::from_columns(std::move(keys)), g.offsets, std::move(child)};
     }
     // GROUP BY, eager, over 1..4 grouping columns of which each is an integer or a Utf8 column: the grouping columns, then one
     // column per (aggregation, input column), named and typed as Dataset::try_aggregate plans them; rows ordered by the

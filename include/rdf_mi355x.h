@@ -620,6 +620,62 @@ rdf_status rdf_groupby_sorted(const rdf_sort_key* group_by, int32_t ngroup, cons
                               const rdf_group_call* calls, int32_t ncalls, rdf_out* out_group_rows, rdf_out* outs,
                               int64_t* out_groups);
 
+/* ------------------------------------------------------------------ collect per group and explode: collect_list, collect_set, explode */
+
+/* The three operations that connect rows with lists: ArrayFunction::CollectList / CollectSet (src/expression.rs:691-692,
+ * collect_list() / collect_set() in src/functions/array.rs:404-405) and ScalarFunctions::explode() (src/functions/scalar.rs:237).
+ * All three have empty bodies in the reference, so the semantics are SQL's / Spark's, written down here.
+ *
+ * rdf_groupby_collect: ONE List row per group of 0 .. 4 grouping keys, collected from ONE value column; keys and value are
+ * rdf_sort_key under rdf_groupby_sorted's conventions (numeric or Utf8 chunks, `options` ignored, rows numbered over the
+ * concatenation of the chunks, inputs and outputs all in host memory or all in device memory, fewer than 2^32 rows).
+ *   - Groups as in rdf_groupby_sorted: NULL is a key value of its own, floats compare canonically (-0.0 == +0.0, one NaN),
+ *     groups come in ascending key order with NULL last, out_group_rows[g] (RDF_U32) is the first row of group g,
+ *     ngroup == 0 makes all rows one group.  Zero rows give zero groups and a valid call that writes nothing (every
+ *     length 0, out_offsets' included: a List of no rows has no offsets to read).
+ *   - out_offsets (RDF_I32): G + 1 entries starting at 0.  Every list is valid; a group without a non-NULL value gets an
+ *     EMPTY list, as in Spark.
+ *   - kind RDF_COLLECT_LIST: the group's rows whose value is not NULL, in ascending row order.
+ *     kind RDF_COLLECT_SET:  the group's distinct non-NULL values by the sort's peer rule (-0.0 == +0.0, one NaN, Utf8 by
+ *     bytes, the empty string is a value), each once, in ascending value order (NaN after +inf): no hash order shows.
+ *   - The child as row indices: out_child_rows (RDF_U32, E entries, the FIRST / LAG convention) holds the row index of every
+ *     element, for SET the smallest row index holding that value.  rdf_take / rdf_utf8_take of the value column by it build
+ *     the child array, so one output form serves every value type.
+ *   - The child as values: out_values (optional, numeric value columns only; with a Utf8 value RDF_INVALID_ARGUMENT) has the
+ *     value's dtype and is written in the same pass.  For SET floats come out canonical: +0.0 for either zero and the quiet
+ *     NaN 0x7ff8000000000000 / 0x7fc00000, so out_values is a function of the multiset of rows alone.  LIST copies bits.
+ *   - Determinism: no atomics on data.  Chunking, memory kind and repetition change no byte; for SET the row order changes
+ *     no byte of out_offsets and out_values, and out_child_rows only through the row mapping.
+ * Sizing: *out_groups (G) and *out_elements (E) and every length are set once known; any given capacity that is too small
+ * (G for the group rows, G + 1 for the offsets, E for the child) is RDF_MEMORY_ERROR with nothing written; capacities of the
+ * rows (rows + 1 for the offsets) always suffice; every output may be NULL, and all four NULL is the count-only call.
+ * E > 2^31 - 1 is RDF_COMPUTE_ERROR (Int32 offsets; it takes 2^31 rows, which no test reaches).
+ * Errors, all before any device work: an unknown kind, more than 4 keys, a NULL value, a key or the value setting both
+ * pointers or neither, wrong dtypes or output dtypes, out_values with a Utf8 value, mixed memory kinds, 2^32 rows or more
+ * RDF_INVALID_ARGUMENT; chunk row counts that differ between columns RDF_COMPUTE_ERROR.
+ * RDF_COLLECT_TILE: items per tile of the compaction and expansion passes (rdf_collect.hip); tests place boundaries around
+ * its multiples.
+ *
+ * rdf_list_explode: every element of every non-NULL list becomes one output row, ordered by list row, then by position.
+ * Only list->offsets (and its validity / offset fields) is read; list->values is the caller's to gather from.
+ *   - out_parent_rows (RDF_U32): the list row; it feeds rdf_take_columns for the frame's other columns.
+ *     out_child_index (RDF_U32): the element's index into list->values; it feeds rdf_take.
+ *     out_pos (optional, RDF_I32): the 0-based position inside the list (posexplode).
+ *   - The slice of a NULL list is skipped even where its offsets span elements (Arrow allows that; rdf_list_remove treats
+ *     it the same way).  Offsets need not start at 0, and the array may be sliced (`offset` fields).
+ *   - outer != 0 (explode_outer): a NULL or empty list yields ONE row whose out_child_index and out_pos are NULL (their
+ *     values are 0); validity bitmaps are then required for both, as for FIRST with ignore_nulls.
+ * Sizing and errors as above: *out_rows and every length are set once known, a capacity below it is RDF_MEMORY_ERROR with
+ * nothing written, all three outputs NULL is the count-only call, zero list rows is a valid call that writes nothing;
+ * non-Int32 offsets, wrong output dtypes, a missing bitmap, mixed memory kinds, 2^32 list rows: RDF_INVALID_ARGUMENT. */
+#define RDF_COLLECT_TILE 1024
+typedef enum { RDF_COLLECT_LIST = 0, RDF_COLLECT_SET = 1 } rdf_collect_kind;
+rdf_status rdf_groupby_collect(const rdf_sort_key* group_by, int32_t ngroup, const rdf_sort_key* value, int64_t nchunks,
+                               int32_t kind, rdf_out* out_group_rows, rdf_out* out_offsets, rdf_out* out_child_rows,
+                               rdf_out* out_values, int64_t* out_groups, int64_t* out_elements);
+rdf_status rdf_list_explode(const rdf_list_array* list, int32_t outer, rdf_out* out_parent_rows, rdf_out* out_child_index,
+                            rdf_out* out_pos, int64_t* out_rows);
+
 /* ------------------------------------------------------------------ window functions */
 
 /* SQL window functions over partitions: row_number / rank / dense_rank / percent_rank / cume_dist / ntile / lag / lead.

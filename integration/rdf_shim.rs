@@ -82,6 +82,8 @@ pub mod sys {
     #[repr(C)] #[derive(Clone, Copy)] pub struct rdf_group_call { pub fn_: i32, pub ignore_nulls: i32 }
     pub const RDF_GRP_COUNT_DISTINCT: i32 = 0; pub const RDF_GRP_SUM_DISTINCT: i32 = 1; pub const RDF_GRP_FIRST: i32 = 2; pub const RDF_GRP_LAST: i32 = 3;
     pub const RDF_GROUP_MAX_CALLS: i32 = 8;
+    // rdf_groupby_collect's kind, and the tile of its compaction / of explode's expansion
+    pub const RDF_COLLECT_LIST: i32 = 0; pub const RDF_COLLECT_SET: i32 = 1; pub const RDF_COLLECT_TILE: i32 = 1024;
     // the state of rdf_moments / rdf_comoments: count, the mean(s) as two doubles each, the central sums
     #[repr(C)] #[derive(Clone, Copy, Default)]
     pub struct rdf_moments_state { pub count: i64, pub mean: f64, pub mean_lo: f64, pub m2: f64, pub m3: f64, pub m4: f64 }
@@ -162,6 +164,13 @@ pub mod sys {
         pub fn rdf_groupby_sorted(group_by: *const rdf_sort_key, ngroup: i32, value: *const rdf_sort_key, nchunks: i64,
                                   calls: *const rdf_group_call, ncalls: i32, out_group_rows: *mut rdf_out, outs: *mut rdf_out,
                                   out_groups: *mut i64) -> i32;
+        // ArrayFunction::CollectList / CollectSet (expression.rs:691-692; collect_list() / collect_set(), array.rs:404-405) per group,
+        // and ScalarFunctions::explode (scalar.rs:237): all declared with empty bodies
+        pub fn rdf_groupby_collect(group_by: *const rdf_sort_key, ngroup: i32, value: *const rdf_sort_key, nchunks: i64, kind: i32,
+                                   out_group_rows: *mut rdf_out, out_offsets: *mut rdf_out, out_child_rows: *mut rdf_out,
+                                   out_values: *mut rdf_out, out_groups: *mut i64, out_elements: *mut i64) -> i32;
+        pub fn rdf_list_explode(list: *const rdf_list_array, outer: i32, out_parent_rows: *mut rdf_out, out_child_index: *mut rdf_out,
+                                out_pos: *mut rdf_out, out_rows: *mut i64) -> i32;
         // WindowSpec / WindowFunctions (src/window.rs, src/functions/window.rs: declared, bodies empty) + ntile (scalar.rs:345)
         pub fn rdf_window(partition_by: *const rdf_sort_key, npartition: i32, order_by: *const rdf_sort_key, norder: i32,
                           nchunks: i64, nrows_if_no_keys: i64, calls: *const rdf_window_call, ncalls: i32, outs: *mut rdf_out) -> i32;
@@ -666,6 +675,51 @@ pub fn groupby_sorted(group_by: &[Vec<&dyn Array>], value: Option<&Vec<&dyn Arra
                                        if ccalls.is_empty() { std::ptr::null() } else { ccalls.as_ptr() }, ccalls.len() as i32,
                                        &mut rout, if outs.is_empty() { std::ptr::null_mut() } else { outs.as_mut_ptr() }, &mut groups) })?;
     Ok((rbuf.finish(&rout), bufs.into_iter().zip(outs.iter()).map(|(b, o)| b.finish(o)).collect()))
+}
+
+/// collect_list() / collect_set() (src/functions/array.rs:404-405, ArrayFunction::CollectList / CollectSet, empty there) per
+/// group of 0 .. 4 grouping columns over ONE value column, numeric or Utf8; `kind` = RDF_COLLECT_LIST (the non-NULL values in
+/// row order) or RDF_COLLECT_SET (the distinct non-NULL values ascending).  -> (row index of every group's first row, groups in
+/// ascending key order with the NULL group last; Int32 offsets, groups + 1 entries; UInt32 row index of every element): `take`
+/// / `utf8_take` the key columns by the first and the value column by the third, and wrap offsets + child as a ListArray.
+pub fn groupby_collect(group_by: &[Vec<&dyn Array>], value: &Vec<&dyn Array>, kind: i32) -> Result<(ArrayRef, ArrayRef, ArrayRef), ArrowError> {
+    let cols: Vec<&Vec<&dyn Array>> = group_by.iter().chain(std::iter::once(value)).collect();
+    let nchunks = value.len();
+    let rows: usize = value.iter().map(|a| a.len()).sum();
+    let mut num: Vec<Vec<rdf_array>> = Vec::new();
+    let mut txt: Vec<Vec<rdf_utf8_array>> = Vec::new();
+    for chunks in cols.iter() {
+        match chunks.first().map(|a| a.data_type()) {
+            Some(DataType::Utf8) => { txt.push(chunks.iter().map(|a| utf8_view(a.as_any().downcast_ref::<StringArray>().unwrap())).collect()); num.push(Vec::new()); }
+            _ => { num.push(chunks.iter().map(|a| view(*a)).collect()); txt.push(Vec::new()); }
+        }
+    }
+    let keys: Vec<rdf_sort_key> = (0..cols.len()).map(|k| rdf_sort_key {
+        values: if num[k].is_empty() { std::ptr::null() } else { num[k].as_ptr() },
+        utf8: if txt[k].is_empty() { std::ptr::null() } else { txt[k].as_ptr() },
+        options: rdf_sort_options { descending: 0, nulls_first: 0 },
+    }).collect();
+    let ng = group_by.len();
+    let (mut rbuf, mut obuf, mut cbuf) = (OutBuf::new(DataType::UInt32, rows, false), OutBuf::new(DataType::Int32, rows + 1, false), OutBuf::new(DataType::UInt32, rows, false));
+    let (mut rout, mut oout, mut cout) = (rbuf.as_out(), obuf.as_out(), cbuf.as_out());
+    let (mut groups, mut elements) = (0i64, 0i64);
+    status(unsafe { rdf_groupby_collect(if ng > 0 { keys.as_ptr() } else { std::ptr::null() }, ng as i32, keys[ng..].as_ptr(), nchunks as i64, kind,
+                                        &mut rout, &mut oout, &mut cout, std::ptr::null_mut(), &mut groups, &mut elements) })?;
+    Ok((rbuf.finish(&rout), obuf.finish(&oout), cbuf.finish(&cout)))
+}
+
+/// ScalarFunctions::explode (src/functions/scalar.rs:237, empty there) of a ListArray with primitive children; `outer` keeps a
+/// NULL or empty list as one row with a NULL element.  -> (UInt32 list row of every output row: `take` the frame's other
+/// columns by it; UInt32 index into the list's child values: `take` the child by it; Int32 position inside the list).
+pub fn list_explode<T: ArrowNumericType>(array: &ListArray, outer: bool) -> Result<(ArrayRef, ArrayRef, ArrayRef), ArrowError> {
+    let l = list_view::<T>(array);
+    let mut rows = 0i64;
+    status(unsafe { rdf_list_explode(&l, outer as i32, std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), &mut rows) })?;   // the count-only call
+    let (mut pbuf, mut cbuf, mut sbuf) = (OutBuf::new(DataType::UInt32, rows as usize, false), OutBuf::new(DataType::UInt32, rows as usize, true),
+                                          OutBuf::new(DataType::Int32, rows as usize, true));
+    let (mut pout, mut cout, mut sout) = (pbuf.as_out(), cbuf.as_out(), sbuf.as_out());
+    status(unsafe { rdf_list_explode(&l, outer as i32, &mut pout, &mut cout, &mut sout, &mut rows) })?;
+    Ok((pbuf.finish(&pout), cbuf.finish(&cout), sbuf.finish(&sout)))
 }
 
 /// WindowSpec { partition_by, order_by } (src/window.rs) + one WindowFunctions entry (src/functions/window.rs; `ntile` of

@@ -144,6 +144,12 @@ def group_sorted_out_dtype(fn: int, value_dtype: int = I64) -> int:
     return U32
 
 
+# rdf_collect_kind
+COLLECT_LIST, COLLECT_SET = 0, 1
+COLLECT_KINDS = {"list": COLLECT_LIST, "set": COLLECT_SET}
+COLLECT_TILE = 1024   # RDF_COLLECT_TILE: items per tile of the compaction (collect) and expansion (explode) passes
+
+
 class rdf_window_frame(C.Structure):
     _fields_ = [("unit", C.c_int32), ("start_kind", C.c_int32), ("end_kind", C.c_int32), ("pad", C.c_int32), ("start", C.c_int64), ("end", C.c_int64)]
 
@@ -1532,6 +1538,93 @@ class Api:
             return groups.value, rows_out, outs
         rows = self.window_to_numpy(rows_out)[0] if rows_out is not None else None
         return groups.value, rows, [self.window_to_numpy(o) for o in outs]
+
+    # ---- collect per group and explode: collect_list / collect_set / explode
+    @staticmethod
+    def _out_values(out):
+        """The values of one output array as numpy, `length` entries."""
+        if out is None:
+            return None
+        if isinstance(out, HostArray):
+            return out.values[:out.length].copy()
+        return out.keep[0].cpu().numpy().view(NP_OF[out.dtype])[:out.length].copy()
+
+    def groupby_collect(self, group_by: Sequence, value, kind, values: bool = True, group_rows: bool = True, outs=None,
+                        raw: bool = False):
+        """rdf_groupby_collect: group_by = [chunks, ...] (0 .. 4 numeric or Utf8 columns), value = chunks of ONE numeric or Utf8
+        column, kind = "list" | "set" (COLLECT_KINDS).  One List row per group, groups in ascending key order, NULL last.
+        -> (groups, group_rows, offsets, child_rows, values | None): the number of groups, the UInt32 row index of every
+        group's first row (None with group_rows=False), the Int32 offsets (groups + 1 entries), the UInt32 row index of every
+        element and the elements themselves (numeric value columns with values=True, else None).  Without `outs` the buffers
+        hold one entry per row (rows + 1 offsets), which always suffices; `outs` = (group_rows, offsets, child_rows, values)
+        are the caller's output arrays, None where one is not wanted, and (None, None, None, None) is the count-only call
+        (the counts are then in last_groups / last_elements).  raw=True returns the output arrays as they are."""
+        cols = list(group_by) + [value]
+        gk, keep_g = self._sort_keys(group_by)
+        vk, keep_v = self._sort_keys([value])
+        nchunks = len(value)
+        n = sum(c.length for c in value)
+        device = any(isinstance(c, (DeviceArray, DeviceUtf8)) for k in cols for c in k)
+        if outs is None:
+            numeric = len(value) > 0 and not self._is_utf8(value)
+            outs = (self._window_out(U32, n, device, False) if group_rows else None,
+                    self._window_out(I32, n + 1, device, False),
+                    self._window_out(U32, n, device, False),
+                    self._window_out(value[0].dtype, n, device, False) if values and numeric else None)
+        cs = [(rdf_out * 1)(o.out_struct()) if o is not None else None for o in outs]
+        groups, elements = C.c_int64(-1), C.c_int64(-1)
+        fn = self._fn("groupby_collect")
+        fn.restype = C.c_int
+        try:
+            self._check(fn(gk if group_by else None, C.c_int32(len(group_by)), vk, C.c_int64(nchunks),
+                           C.c_int32(COLLECT_KINDS[kind] if isinstance(kind, str) else int(kind)), cs[0], cs[1], cs[2], cs[3],
+                           C.byref(groups), C.byref(elements)))
+        finally:
+            for o, c in zip(outs, cs):
+                if o is not None:
+                    self._finish([o], c)
+            self.last_groups, self.last_elements = groups.value, elements.value
+        if raw:
+            return (groups.value,) + tuple(outs)
+        return (groups.value,) + tuple(self._out_values(o) for o in outs)
+
+    def list_explode(self, lst, outer: bool = False, pos: bool = False, outs=None, raw: bool = False):
+        """rdf_list_explode of a HostList / DeviceList: one output row per element of every non-NULL list (outer=True: one
+        row with a NULL element for a NULL or empty list).  -> (parent_rows, (child_index, valid), pos | None): the list row
+        of every output row, the element's index into the list's child values with its validity (all True without outer),
+        and with pos=True the 0-based position inside the list as (pos, valid).  Without `outs` one count-only call sizes
+        the buffers; `outs` = (parent_rows, child_index, pos) are the caller's arrays, None where one is not wanted.
+        raw=True returns the output arrays as they are.  The row count is in last_rows."""
+        fn = self._fn("list_explode")
+        fn.restype = C.c_int
+        ls = lst.c_struct()
+        rows = C.c_int64(-1)
+        device = isinstance(lst, DeviceList)
+        if outs is None:
+            self._check(fn(C.byref(ls), C.c_int32(int(outer)), None, None, None, C.byref(rows)))
+            r = rows.value
+            outs = (self._window_out(U32, r, device, False), self._window_out(U32, r, device, True),
+                    self._window_out(I32, r, device, True) if pos else None)
+        cs = [(rdf_out * 1)(o.out_struct()) if o is not None else None for o in outs]
+        try:
+            self._check(fn(C.byref(ls), C.c_int32(int(outer)), cs[0], cs[1], cs[2], C.byref(rows)))
+        finally:
+            for o, c in zip(outs, cs):
+                if o is not None:
+                    self._finish([o], c)
+            self.last_rows = rows.value
+        if raw:
+            return tuple(outs)
+
+        def masked(o):
+            if o is None:
+                return None
+            if isinstance(o, HostArray):
+                valid = unpack_bits(o.validity, 0, o.length) if o.validity is not None else None
+            else:
+                valid = unpack_bits(o.keep[1].cpu().numpy(), 0, o.length) if o.keep[1] is not None else None
+            return self._out_values(o), (valid if valid is not None else np.ones(o.length, dtype=bool))
+        return self._out_values(outs[0]), masked(outs[1]), masked(outs[2])
 
     def utf8_uniques(self, chunks: Sequence, as_arrow=False):
         """Column::uniques of a Utf8 column -> ONE Utf8 chunk of the distinct strings (no NULLs, unspecified order).  The

@@ -33,6 +33,7 @@
 #include "rdf_window_agg.h"
 #include "rdf_moments.h"
 #include "rdf_group_sorted.h"
+#include "rdf_collect.h"
 
 using namespace rdfk;
 
@@ -2865,6 +2866,7 @@ rdf_status groupby_sum_fallback(const rdf_array* keys, const rdf_array* values, 
 #include "rdf_capi_window_agg.inc"
 #include "rdf_capi_moments.inc"
 #include "rdf_capi_group_sorted.inc"
+#include "rdf_capi_collect.inc"
 
 extern "C" {
 
