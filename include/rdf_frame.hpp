@@ -2819,6 +2819,85 @@ struct ScalarFunctions {
         check(rdf_hour(a.data(), (int64_t)a.size(), (int32_t)unit, ov.data()));
         return finish(outs, ov);
     }
+    // The calendar functions src/functions/scalar.rs declares with empty bodies (year .. date_diff): Spark 3's semantics as
+    // written down at rdf_datetime_fields in rdf_mi355x.h.  Like hour, a temporal column is its Int32 / Int64 storage + time unit.
+    // datetime_fields reads the column ONCE for up to 8 fields and returns one chunk list per field, in the order asked for.
+    static std::vector<std::vector<ArrayRef>> datetime_fields(const std::vector<ArrayRef>& arr, rdf_time_unit unit, const std::vector<rdf_datetime_field>& fields) {
+        std::vector<rdf_array> a;
+        std::vector<std::shared_ptr<Array>> outs;
+        std::vector<rdf_out> ov;
+        std::vector<int32_t> codes(fields.begin(), fields.end());
+        for (auto& x : arr) a.push_back(x->view());
+        for (size_t f = 0; f < fields.size(); ++f)
+            for (auto& x : arr) { outs.push_back(Array::make_out(DataType::Int32, x->length, x->validity != nullptr, x->host)); ov.push_back(outs.back()->out_view(x->length)); }
+        check(rdf_datetime_fields(a.data(), (int64_t)a.size(), (int32_t)unit, codes.data(), (int32_t)codes.size(), ov.data()));
+        const std::vector<ArrayRef> flat = finish(outs, ov);
+        std::vector<std::vector<ArrayRef>> per_field(fields.size());
+        for (size_t f = 0; f < fields.size(); ++f) per_field[f].assign(flat.begin() + f * arr.size(), flat.begin() + (f + 1) * arr.size());
+        return per_field;
+    }
+    static std::vector<ArrayRef> datetime_field(const std::vector<ArrayRef>& arr, rdf_time_unit unit, rdf_datetime_field field) { return datetime_fields(arr, unit, {field})[0]; }
+    static std::vector<ArrayRef> year(const std::vector<ArrayRef>& a, rdf_time_unit unit) { return datetime_field(a, unit, RDF_DT_YEAR); }
+    static std::vector<ArrayRef> quarter(const std::vector<ArrayRef>& a, rdf_time_unit unit) { return datetime_field(a, unit, RDF_DT_QUARTER); }
+    static std::vector<ArrayRef> month(const std::vector<ArrayRef>& a, rdf_time_unit unit) { return datetime_field(a, unit, RDF_DT_MONTH); }
+    static std::vector<ArrayRef> day_of_month(const std::vector<ArrayRef>& a, rdf_time_unit unit) { return datetime_field(a, unit, RDF_DT_DAY_OF_MONTH); }
+    static std::vector<ArrayRef> day_of_week(const std::vector<ArrayRef>& a, rdf_time_unit unit) { return datetime_field(a, unit, RDF_DT_DAY_OF_WEEK); }   // 1 = Sunday
+    static std::vector<ArrayRef> day_of_year(const std::vector<ArrayRef>& a, rdf_time_unit unit) { return datetime_field(a, unit, RDF_DT_DAY_OF_YEAR); }
+    static std::vector<ArrayRef> week_of_year(const std::vector<ArrayRef>& a, rdf_time_unit unit) { return datetime_field(a, unit, RDF_DT_WEEK_OF_YEAR); }   // ISO-8601
+    static std::vector<ArrayRef> minute(const std::vector<ArrayRef>& a, rdf_time_unit unit) { return datetime_field(a, unit, RDF_DT_MINUTE); }
+    static std::vector<ArrayRef> second(const std::vector<ArrayRef>& a, rdf_time_unit unit) { return datetime_field(a, unit, RDF_DT_SECOND); }
+    static std::vector<ArrayRef> to_date(const std::vector<ArrayRef>& a, rdf_time_unit unit) { return datetime_field(a, unit, RDF_DT_DATE); }   // Int32 day numbers
+    // date_trunc(level, ts): same storage and unit out; trunc(date, level) is date_trunc over Int32 day numbers
+    static std::vector<ArrayRef> date_trunc(const std::vector<ArrayRef>& arr, rdf_time_unit unit, rdf_trunc_level level) {
+        std::vector<rdf_array> a;
+        std::vector<std::shared_ptr<Array>> outs;
+        std::vector<rdf_out> ov;
+        for (auto& x : arr) { a.push_back(x->view()); outs.push_back(Array::make_out(x->dtype, x->length, x->validity != nullptr, x->host)); ov.push_back(outs.back()->out_view(x->length)); }
+        check(rdf_datetime_trunc(a.data(), (int64_t)a.size(), (int32_t)unit, (int32_t)level, ov.data()));
+        return finish(outs, ov);
+    }
+    static std::vector<ArrayRef> trunc(const std::vector<ArrayRef>& dates, rdf_trunc_level level) { return date_trunc(dates, RDF_TIME_DAY, level); }
+    // date_add / date_sub / add_months / last_day / next_day -> Int32 day numbers; the amount is one number or an Int32 column
+    static std::vector<ArrayRef> date_shift(const std::vector<ArrayRef>& arr, rdf_time_unit unit, rdf_date_shift_op op, const std::vector<ArrayRef>* amounts, int32_t amount) {
+        if (amounts && amounts->size() != arr.size()) throw DataFrameError(DataFrameError::ComputeError, "chunk lists differ in length");
+        std::vector<rdf_array> a, k;
+        std::vector<std::shared_ptr<Array>> outs;
+        std::vector<rdf_out> ov;
+        for (size_t i = 0; i < arr.size(); ++i) {
+            a.push_back(arr[i]->view());
+            if (amounts) k.push_back((*amounts)[i]->view());
+            const bool nullable = arr[i]->validity || (amounts && ((*amounts)[i]->validity || op == RDF_SHIFT_NEXT_DAY));   // (a per-row weekday outside 1..7 is a NULL row)
+            outs.push_back(Array::make_out(DataType::Int32, arr[i]->length, nullable, arr[i]->host));
+            ov.push_back(outs.back()->out_view(arr[i]->length));
+        }
+        check(::rdf_date_shift(a.data(), (int64_t)a.size(), (int32_t)unit, (int32_t)op, amounts ? k.data() : nullptr, amount, ov.data()));
+        return finish(outs, ov);
+    }
+    static std::vector<ArrayRef> date_add(const std::vector<ArrayRef>& a, rdf_time_unit unit, int32_t days) { return date_shift(a, unit, RDF_SHIFT_DAYS, nullptr, days); }
+    static std::vector<ArrayRef> date_add(const std::vector<ArrayRef>& a, rdf_time_unit unit, const std::vector<ArrayRef>& days) { return date_shift(a, unit, RDF_SHIFT_DAYS, &days, 0); }
+    static std::vector<ArrayRef> date_sub(const std::vector<ArrayRef>& a, rdf_time_unit unit, int32_t days) { return date_shift(a, unit, RDF_SHIFT_DAYS, nullptr, (int32_t)(0u - (uint32_t)days)); }
+    static std::vector<ArrayRef> date_sub(const std::vector<ArrayRef>& a, rdf_time_unit unit, const std::vector<ArrayRef>& days) {
+        return binary(RDF_OP_SUB, to_date(a, unit), days);   // day number - days: Int32, wrapping, validity ANDed
+    }
+    static std::vector<ArrayRef> add_months(const std::vector<ArrayRef>& a, rdf_time_unit unit, int32_t months) { return date_shift(a, unit, RDF_SHIFT_MONTHS, nullptr, months); }
+    static std::vector<ArrayRef> add_months(const std::vector<ArrayRef>& a, rdf_time_unit unit, const std::vector<ArrayRef>& months) { return date_shift(a, unit, RDF_SHIFT_MONTHS, &months, 0); }
+    static std::vector<ArrayRef> last_day(const std::vector<ArrayRef>& a, rdf_time_unit unit) { return date_shift(a, unit, RDF_SHIFT_LAST_DAY, nullptr, 0); }
+    static std::vector<ArrayRef> next_day(const std::vector<ArrayRef>& a, rdf_time_unit unit, int32_t weekday) { return date_shift(a, unit, RDF_SHIFT_NEXT_DAY, nullptr, weekday); }   // 1 = Sunday .. 7
+    static std::vector<ArrayRef> next_day(const std::vector<ArrayRef>& a, rdf_time_unit unit, const std::vector<ArrayRef>& weekdays) { return date_shift(a, unit, RDF_SHIFT_NEXT_DAY, &weekdays, 0); }
+    // date_diff(end, start) = day(end) - day(start), each column with its own storage and unit
+    static std::vector<ArrayRef> date_diff(const std::vector<ArrayRef>& end, rdf_time_unit end_unit, const std::vector<ArrayRef>& start, rdf_time_unit start_unit) {
+        if (end.size() != start.size()) throw DataFrameError(DataFrameError::ComputeError, "chunk lists differ in length");
+        std::vector<rdf_array> a, b;
+        std::vector<std::shared_ptr<Array>> outs;
+        std::vector<rdf_out> ov;
+        for (size_t i = 0; i < end.size(); ++i) {
+            a.push_back(end[i]->view()); b.push_back(start[i]->view());
+            outs.push_back(Array::make_out(DataType::Int32, end[i]->length, end[i]->validity || start[i]->validity, end[i]->host));
+            ov.push_back(outs.back()->out_view(end[i]->length));
+        }
+        check(rdf_date_diff(a.data(), (int32_t)end_unit, b.data(), (int32_t)start_unit, (int64_t)a.size(), ov.data()));
+        return finish(outs, ov);
+    }
     // src/functions/scalar.rs:16-103
     static std::vector<ArrayRef> add(const std::vector<ArrayRef>& l, const std::vector<ArrayRef>& r) { return binary(RDF_OP_ADD, l, r); }
     static std::vector<ArrayRef> subtract(const std::vector<ArrayRef>& l, const std::vector<ArrayRef>& r) { return binary(RDF_OP_SUB, l, r); }

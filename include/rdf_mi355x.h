@@ -165,6 +165,61 @@ rdf_status rdf_cast(const rdf_array* a, int64_t nchunks, rdf_out* out);
  * formula instead. */
 rdf_status rdf_hour(const rdf_array* a, int64_t nchunks, int32_t unit, rdf_out* out);
 
+/* ------------------------------------------------------------------ date and time functions
+ *
+ * ScalarFunctions::{year, quarter, month, day_of_month, day_of_week, day_of_year, week_of_year, minute, second, to_date,
+ * date_trunc, trunc, date_add, date_sub, add_months, last_day, next_day, date_diff} (src/functions/scalar.rs declares them
+ * with empty bodies): Spark 3's semantics over a temporal column passed as rdf_hour takes it — its Int32 / Int64 storage plus
+ * its rdf_time_unit; no time zones.  Every unit but RDF_TIME_DAY accepts either storage type, RDF_TIME_DAY (Date32) is Int32.
+ *
+ * Calendar: proleptic Gregorian, astronomical year numbering (year 0 = 1 BC), day 0 = 1970-01-01, a Thursday.
+ * Domain ("integers wrap", as rdf_binary): the day number of a value is floor_div(value, units per day) computed in Int64 and
+ * truncated to Int32 by wrapping — only Int64 seconds / milliseconds beyond year +-5.8 million reach the wrap; the calendar
+ * conversion is exact for every Int32 day number (-5877641-06-23 .. 5881580-07-11); hour, minute and second are exact for every
+ * Int64.  No call fails or yields NULL because of a value's magnitude: an output needs a validity buffer only when an input
+ * of its chunk has one (and for per-row next_day weekdays, see below).  NULL rows hold 0; an output's bitmap is the input's
+ * re-based to bit 0 (two inputs: their AND), bits past `length` in its last byte are 0, as rdf_unary writes them.
+ *
+ * Fields, each RDF_I32: YEAR; QUARTER 1..4; MONTH 1..12; DAY_OF_MONTH 1..31; DAY_OF_WEEK 1 = Sunday .. 7 = Saturday;
+ * DAY_OF_YEAR 1..366; WEEK_OF_YEAR the ISO-8601 week 1..53 (weeks start on Monday, week 1 holds the year's first Thursday);
+ * HOUR 0..23 — the bytes rdf_hour returns; MINUTE 0..59; SECOND the whole second 0..59, the fraction dropped by floor;
+ * DATE (to_date) the Int32 day number.  RDF_TIME_DAY values have hour = minute = second = 0.
+ *
+ * Refused with RDF_INVALID_ARGUMENT before any device work and with nothing written: an unknown unit, field, level or
+ * operation; nfields outside 1..8 or a repeated field; a NULL list with nchunks > 0, negative nchunks; chunk lengths that
+ * differ between paired columns; two memory kinds in one call; an input with validity but an output without; an output of
+ * the wrong dtype; Int64 storage with RDF_TIME_DAY; chunks of two storage types.  An output capacity below its chunk's rows
+ * is RDF_MEMORY_ERROR; a storage dtype other than Int32 / Int64 is RDF_COMPUTE_ERROR ("... does not support type").
+ * nchunks == 0 is RDF_OK.  Without a device a valid call returns RDF_DEVICE_ERROR (no CPU fallback). */
+typedef enum { RDF_DT_YEAR = 0, RDF_DT_QUARTER, RDF_DT_MONTH, RDF_DT_DAY_OF_MONTH, RDF_DT_DAY_OF_WEEK, RDF_DT_DAY_OF_YEAR,
+               RDF_DT_WEEK_OF_YEAR, RDF_DT_HOUR, RDF_DT_MINUTE, RDF_DT_SECOND, RDF_DT_DATE } rdf_datetime_field;
+typedef enum { RDF_TRUNC_YEAR = 0, RDF_TRUNC_QUARTER, RDF_TRUNC_MONTH, RDF_TRUNC_WEEK, RDF_TRUNC_DAY, RDF_TRUNC_HOUR,
+               RDF_TRUNC_MINUTE, RDF_TRUNC_SECOND } rdf_trunc_level;
+typedef enum { RDF_SHIFT_DAYS = 0, RDF_SHIFT_MONTHS, RDF_SHIFT_LAST_DAY, RDF_SHIFT_NEXT_DAY } rdf_date_shift_op;   /* (rdf_date_shift is the function) */
+
+/* year / quarter / month / ... of one column in ONE read of it.  outs[f * nchunks + c]: field f of chunk c, RDF_I32.
+ * 1 <= nfields <= 8, a field may not repeat. */
+rdf_status rdf_datetime_fields(const rdf_array* a, int64_t nchunks, int32_t unit, const int32_t* fields, int32_t nfields, rdf_out* outs);
+/* date_trunc(level, ts); trunc(date, fmt) is this call on RDF_TIME_DAY.  out: the input's storage type, same unit.
+ * YEAR / QUARTER / MONTH: the first day of the period at midnight; WEEK: its Monday; DAY and finer: v - floor_mod(v, step).
+ * Results wrap modulo 2^64 (2^32 for Int32 storage), reached only within the first or last partial period of a unit's range.
+ * A level whose step is shorter than one unit (HOUR / MINUTE / SECOND on RDF_TIME_DAY) is RDF_INVALID_ARGUMENT; SECOND on
+ * seconds is the identity. */
+rdf_status rdf_datetime_trunc(const rdf_array* a, int64_t nchunks, int32_t unit, int32_t level, rdf_out* out);
+/* date_add / date_sub / add_months / last_day / next_day.  out: always the RDF_I32 day number (Spark casts timestamps to
+ * dates first); results wrap.  amounts == NULL: `amount` for every row; else an Int32 column chunked like a (validity
+ * ANDed) and `amount` ignored.
+ *   DAYS      date_add; a negative amount is date_sub
+ *   MONTHS    add_months: the day of the month is kept and clamped to the last day of the target month
+ *             (2016-08-31 + 1 -> 2016-09-30, 2019-02-28 + 1 -> 2019-03-28)
+ *   LAST_DAY  the last day of the value's month; the amount is ignored, passing `amounts` is RDF_INVALID_ARGUMENT
+ *   NEXT_DAY  the amount is the target weekday, 1 = Sunday .. 7 = Saturday: the first date STRICTLY later than the input on
+ *             that weekday.  A scalar outside 1..7 is RDF_INVALID_ARGUMENT; a per-row amount outside 1..7 gives a NULL row,
+ *             so that call needs an output bitmap (RDF_INVALID_ARGUMENT without one). */
+rdf_status rdf_date_shift(const rdf_array* a, int64_t nchunks, int32_t unit, int32_t op, const rdf_array* amounts, int32_t amount, rdf_out* out);
+/* date_diff(end, start) = day(end) - day(start) as RDF_I32, wrapping; each column has its own storage type and unit. */
+rdf_status rdf_date_diff(const rdf_array* end, int32_t end_unit, const rdf_array* start, int32_t start_unit, int64_t nchunks, rdf_out* out);
+
 /* ------------------------------------------------------------------ aggregate kernels */
 
 /* AggregateFunctions::sum (src/functions/aggregate.rs:82-93): nulls skipped, empty/all-null -> 0,

@@ -119,6 +119,12 @@ pub mod sys {
         pub fn rdf_unary(op: i32, a: *const rdf_array, nchunks: i64, out: *mut rdf_out) -> i32;
         pub fn rdf_cast(a: *const rdf_array, nchunks: i64, out: *mut rdf_out) -> i32;
         pub fn rdf_hour(a: *const rdf_array, nchunks: i64, unit: i32, out: *mut rdf_out) -> i32;
+        // year .. date_diff (scalar.rs declares them with empty bodies): Spark 3's semantics, see rdf_mi355x.h.  fields: rdf_datetime_field
+        // codes (0 = year .. 10 = date), level: rdf_trunc_level (0 = year .. 7 = second), op: rdf_date_shift_op (0 = days .. 3 = next_day)
+        pub fn rdf_datetime_fields(a: *const rdf_array, nchunks: i64, unit: i32, fields: *const i32, nfields: i32, outs: *mut rdf_out) -> i32;
+        pub fn rdf_datetime_trunc(a: *const rdf_array, nchunks: i64, unit: i32, level: i32, out: *mut rdf_out) -> i32;
+        pub fn rdf_date_shift(a: *const rdf_array, nchunks: i64, unit: i32, op: i32, amounts: *const rdf_array, amount: i32, out: *mut rdf_out) -> i32;
+        pub fn rdf_date_diff(end: *const rdf_array, end_unit: i32, start: *const rdf_array, start_unit: i32, nchunks: i64, out: *mut rdf_out) -> i32;
         // AggregateFunctions (src/functions/aggregate.rs)
         pub fn rdf_sum(a: *const rdf_array, nchunks: i64, out_scalar: *mut c_void, out_is_some: *mut i32) -> i32;
         pub fn rdf_min(a: *const rdf_array, nchunks: i64, out_scalar: *mut c_void, out_is_some: *mut i32) -> i32;

@@ -27,6 +27,17 @@ MEM_HOST, MEM_DEVICE = 0, 1
 OP_HOUR_S, OP_HOUR_MS, OP_HOUR_US, OP_HOUR_NS, OP_HOUR_DAY = range(39, 44)
 OP_COT, OP_SEC, OP_CSC = range(44, 47)
 TIME_SECOND, TIME_MILLISECOND, TIME_MICROSECOND, TIME_NANOSECOND, TIME_DAY = range(5)
+# rdf_datetime_field / rdf_trunc_level / rdf_date_shift_op
+(DT_YEAR, DT_QUARTER, DT_MONTH, DT_DAY_OF_MONTH, DT_DAY_OF_WEEK, DT_DAY_OF_YEAR, DT_WEEK_OF_YEAR, DT_HOUR, DT_MINUTE, DT_SECOND,
+ DT_DATE) = range(11)
+DT_FIELDS = {"year": DT_YEAR, "quarter": DT_QUARTER, "month": DT_MONTH, "day_of_month": DT_DAY_OF_MONTH, "day_of_week": DT_DAY_OF_WEEK,
+             "day_of_year": DT_DAY_OF_YEAR, "week_of_year": DT_WEEK_OF_YEAR, "hour": DT_HOUR, "minute": DT_MINUTE, "second": DT_SECOND,
+             "date": DT_DATE}
+TRUNC_YEAR, TRUNC_QUARTER, TRUNC_MONTH, TRUNC_WEEK, TRUNC_DAY, TRUNC_HOUR, TRUNC_MINUTE, TRUNC_SECOND = range(8)
+TRUNC_LEVELS = {"year": TRUNC_YEAR, "quarter": TRUNC_QUARTER, "month": TRUNC_MONTH, "week": TRUNC_WEEK, "day": TRUNC_DAY,
+                "hour": TRUNC_HOUR, "minute": TRUNC_MINUTE, "second": TRUNC_SECOND}
+SHIFT_DAYS, SHIFT_MONTHS, SHIFT_LAST_DAY, SHIFT_NEXT_DAY = range(4)
+DATE_SHIFTS = {"days": SHIFT_DAYS, "months": SHIFT_MONTHS, "last_day": SHIFT_LAST_DAY, "next_day": SHIFT_NEXT_DAY}
 
 OP_NAMES = {
     "add": OP_ADD, "subtract": OP_SUB, "multiply": OP_MUL, "divide": OP_DIV, "atan2": OP_ATAN2,
@@ -796,6 +807,75 @@ class Api:
         else:
             carr = (rdf_out * max(1, n))(*[o.out_struct() for o in outs])
         self._check(self._fn("hour")(ca, C.c_int64(n), C.c_int32(unit), carr))
+        return self._finish(outs, carr)
+
+    # ---- date and time functions (ScalarFunctions::year .. date_diff: declared by the reference, empty there)
+    def _dt_outs(self, dtype: int, a: Sequence, nullable: Sequence[bool], nout: int = 1):
+        """nout outputs per chunk of `a`, laid out [f * nchunks + c], in the memory the inputs live in."""
+        device = any(isinstance(x, DeviceArray) for x in a)
+        outs = [self._window_out(dtype, x.length, device, nl) for _ in range(nout) for x, nl in zip(a, nullable)]
+        return outs, (rdf_out * max(1, len(outs)))(*[o.out_struct() for o in outs])
+
+    def _dt_fn(self, name):
+        fn = self._fn(name)
+        fn.restype = C.c_int
+        return fn
+
+    def datetime_fields(self, a: Sequence, unit: int, fields: Sequence, outs=None):
+        """rdf_datetime_fields: the calendar fields (names of DT_FIELDS or their codes) of a temporal column given as its Int32 /
+        Int64 storage with time unit `unit`, from ONE read of it -> one Int32 chunk list per field."""
+        codes = [DT_FIELDS[f] if isinstance(f, str) else int(f) for f in fields]
+        n = len(a)
+        if outs is None:
+            outs, carr = self._dt_outs(I32, a, [x.validity is not None for x in a], len(codes))
+        else:
+            outs = [o for per_field in outs for o in per_field]
+            carr = (rdf_out * max(1, len(outs)))(*[o.out_struct() for o in outs])
+        cf = (C.c_int32 * max(1, len(codes)))(*codes)
+        self._check(self._dt_fn("datetime_fields")(_flat([a], n), C.c_int64(n), C.c_int32(unit), cf, C.c_int32(len(codes)), carr))
+        self._finish(outs, carr)
+        return [outs[f * n:(f + 1) * n] for f in range(len(codes))]
+
+    def datetime_trunc(self, a: Sequence, unit: int, level, outs=None):
+        """rdf_datetime_trunc: date_trunc(level, column) (a name of TRUNC_LEVELS or its code); trunc(date, level) with
+        unit = TIME_DAY -> chunks of the input's storage type and unit."""
+        code = TRUNC_LEVELS[level] if isinstance(level, str) else int(level)
+        n = len(a)
+        if outs is None:
+            outs, carr = self._dt_outs(a[0].dtype if n else I64, a, [x.validity is not None for x in a])
+        else:
+            carr = (rdf_out * max(1, n))(*[o.out_struct() for o in outs])
+        self._check(self._dt_fn("datetime_trunc")(_flat([a], n), C.c_int64(n), C.c_int32(unit), C.c_int32(code), carr))
+        return self._finish(outs, carr)
+
+    def date_shift(self, a: Sequence, unit: int, op, amount=0, outs=None):
+        """rdf_date_shift: date_add / add_months / last_day / next_day (a name of DATE_SHIFTS or its code) -> Int32 day numbers.
+        amount: an int for every row, or an Int32 chunk list chunked like `a`."""
+        code = DATE_SHIFTS[op] if isinstance(op, str) else int(op)
+        n = len(a)
+        column = not isinstance(amount, (int, np.integer))
+        if outs is None:
+            per_row = column and code == SHIFT_NEXT_DAY
+            outs, carr = self._dt_outs(I32, a, [per_row or x.validity is not None or (column and k.validity is not None)
+                                                for x, k in zip(a, amount if column else a)])
+        else:
+            carr = (rdf_out * max(1, n))(*[o.out_struct() for o in outs])
+        if column and len(amount) != n:
+            raise ValueError("chunk lists differ in length")
+        self._check(self._dt_fn("date_shift")(_flat([a], n), C.c_int64(n), C.c_int32(unit), C.c_int32(code), _flat([amount], n) if column else None,
+                                              C.c_int32(0 if column else int(amount)), carr))
+        return self._finish(outs, carr)
+
+    def date_diff(self, end: Sequence, end_unit: int, start: Sequence, start_unit: int, outs=None):
+        """rdf_date_diff: day(end) - day(start) -> Int32 chunks; each column has its own storage type and unit."""
+        n = len(end)
+        if len(start) != n:
+            raise ValueError("chunk lists differ in length")
+        if outs is None:
+            outs, carr = self._dt_outs(I32, end, [x.validity is not None or y.validity is not None for x, y in zip(end, start)])
+        else:
+            carr = (rdf_out * max(1, n))(*[o.out_struct() for o in outs])
+        self._check(self._dt_fn("date_diff")(_flat([end], n), C.c_int32(end_unit), _flat([start], n), C.c_int32(start_unit), C.c_int64(n), carr))
         return self._finish(outs, carr)
 
     # ---- aggregates (AggregateFunctions, src/functions/aggregate.rs)

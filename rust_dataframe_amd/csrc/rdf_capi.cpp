@@ -34,6 +34,7 @@
 #include "rdf_moments.h"
 #include "rdf_group_sorted.h"
 #include "rdf_collect.h"
+#include "rdf_datetime.h"
 
 using namespace rdfk;
 
@@ -2867,6 +2868,7 @@ rdf_status groupby_sum_fallback(const rdf_array* keys, const rdf_array* values, 
 #include "rdf_capi_moments.inc"
 #include "rdf_capi_group_sorted.inc"
 #include "rdf_capi_collect.inc"
+#include "rdf_capi_datetime.inc"
 
 extern "C" {
 
