@@ -673,6 +673,74 @@ class Column {
         }
         return tc;
     }
+    // One result array per text chunk, computed into host memory (text columns are host-carried, so the call is a host call)
+    // and handed back in page-locked host memory (`on_host`) or on the device, where the frame's other columns are.
+    template <class Call>
+    Column text_result(DataType t, const TextChunks& tc, const std::vector<bool>& nullable, const std::string& name, bool on_host, Call call) const {
+        const size_t n = tc.txt.size();
+        std::vector<std::vector<uint8_t>> vals(n), valid(n);
+        std::vector<rdf_out> ov(n);
+        for (size_t i = 0; i < n; ++i) {
+            const int64_t rows = tc.txt[i].offsets.length - 1, cap = (rows + 63) / 64 * 64;
+            vals[i].assign((size_t)(t == DataType::Boolean ? cap / 8 + 8 : cap * type_size(t) + 8), 0);
+            if (nullable[i]) valid[i].assign((size_t)(cap / 8 + 8), 0);
+            ov[i] = rdf_out{vals[i].data(), nullable[i] ? valid[i].data() : nullptr, rows, 0, 0, (int32_t)t, RDF_MEM_HOST};
+        }
+        call(ov.data());
+        std::vector<ArrayRef> res;
+        for (size_t i = 0; i < n; ++i) {
+            auto a = Array::make_out(t, ov[i].length, nullable[i], on_host);
+            auto put = [&](const BufferRef& dst, const std::vector<uint8_t>& src) {
+                if (on_host) std::memcpy(dst->data(), src.data(), src.size());
+                else check(rdf_copy_h2d(dst->data(), src.data(), (int64_t)src.size()));
+            };
+            put(a->values, vals[i]);
+            if (nullable[i]) put(a->validity, valid[i]);
+            a->length = ov[i].length;
+            a->null_count = ov[i].null_count;
+            res.push_back(a);
+        }
+        return Column::from_arrays(res, Field{name, t, true});
+    }
+    void need_text(const char* what) const {
+        if (data_type() != DataType::Utf8) throw DataFrameError(DataFrameError::ComputeError, std::string(what) + ": Utf8 columns only");
+    }
+  public:
+    // Masks and integers from text, on the device (rdf_utf8_predicate / rdf_utf8_compare / rdf_utf8_measure; SQL / Spark
+    // semantics, see the C header).  A NULL row gives a NULL result.
+    //   utf8_predicate  op = RDF_UTF8_EQ .. RDF_UTF8_LIKE against a literal / LIKE pattern (escape: -1 = none) -> Boolean
+    //   utf8_compare    op = RDF_UTF8_EQ .. RDF_UTF8_GE against another Utf8 column with the same chunking      -> Boolean
+    //   utf8_measure    RDF_UTF8_LENGTH / OCTET_LENGTH / LOCATE (needle, 1-based code-point position `pos`)      -> Int32
+    Column utf8_predicate(int32_t op, const std::string& pattern, int32_t escape = -1, bool on_host = false) const {
+        need_text("utf8_predicate");
+        const TextChunks tc = text_chunks("utf8_predicate");
+        std::vector<bool> nullable;
+        for (auto& a : data_.chunks()) nullable.push_back(a->validity != nullptr);
+        return text_result(DataType::Boolean, tc, nullable, "bool_filter", on_host, [&](rdf_out* outs) {
+            check(rdf_utf8_predicate(op, tc.txt.data(), (int64_t)tc.txt.size(), (const uint8_t*)pattern.data(), (int64_t)pattern.size(), escape, outs));
+        });
+    }
+    Column utf8_compare(int32_t op, const Column& other, bool on_host = false) const {
+        need_text("utf8_compare");
+        other.need_text("utf8_compare");
+        if (other.data_.num_chunks() != data_.num_chunks()) throw DataFrameError(DataFrameError::ComputeError, "utf8_compare: chunk lists differ in length");
+        const TextChunks ta = text_chunks("utf8_compare"), tb = other.text_chunks("utf8_compare");
+        std::vector<bool> nullable;
+        for (size_t i = 0; i < data_.num_chunks(); ++i) nullable.push_back(data_.chunk(i)->validity != nullptr || other.data_.chunk(i)->validity != nullptr);
+        return text_result(DataType::Boolean, ta, nullable, "bool_filter", on_host, [&](rdf_out* outs) {
+            check(rdf_utf8_compare(op, ta.txt.data(), tb.txt.data(), (int64_t)ta.txt.size(), outs));
+        });
+    }
+    Column utf8_measure(int32_t what, const std::string& pattern = std::string(), int64_t pos = 1, bool on_host = false) const {
+        need_text("utf8_measure");
+        const TextChunks tc = text_chunks("utf8_measure");
+        std::vector<bool> nullable;
+        for (auto& a : data_.chunks()) nullable.push_back(a->validity != nullptr);
+        return text_result(DataType::Int32, tc, nullable, field_.name, on_host, [&](rdf_out* outs) {
+            check(rdf_utf8_measure(what, tc.txt.data(), (int64_t)tc.txt.size(), (const uint8_t*)pattern.data(), (int64_t)pattern.size(), pos, outs));
+        });
+    }
+  private:
     ChunkedArray data_;
     Field field_;
 };
@@ -681,10 +749,13 @@ class Column {
 // Scalar / BooleanFilter (src/expression.rs:718-870)
 
 struct Scalar {
-    enum Kind { Null, Int32, Int64, Float32, Float64, Boolean } kind = Null;
+    enum Kind { Null, Int32, Int64, Float32, Float64, Boolean, String } kind = Null;   // Scalar::String: src/expression.rs:725,797-802
     double f = 0;
     int64_t i = 0;
+    std::string s;
     Scalar() = default;
+    Scalar(std::string v) : kind(String), s(std::move(v)) {}
+    Scalar(const char* v) : kind(String), s(v) {}   // (without it a string literal picks the bool constructor)
     Scalar(int32_t v) : kind(Int32), i(v) {}
     Scalar(int64_t v) : kind(Int64), i(v) {}
     Scalar(float v) : kind(Float32), f(v) {}
@@ -699,9 +770,10 @@ struct Scalar {
 struct BooleanFilter;
 using FilterRef = std::shared_ptr<const BooleanFilter>;
 struct BooleanFilter {
-    enum Kind { InputScalar, InputColumn, Not, And, Or, Gt, Ge, Eq, Ne, Lt, Le } kind;
+    enum Kind { InputScalar, InputColumn, Not, And, Or, Gt, Ge, Eq, Ne, Lt, Le, StartsWith, EndsWith, Contains, Like } kind;
     Scalar scalar_v;
     std::string column_name;
+    int32_t escape = -1;   // Like: -1 = none, or one ASCII byte
     FilterRef l, r;
     static FilterRef scalar(Scalar s) { auto f = std::make_shared<BooleanFilter>(); f->kind = InputScalar; f->scalar_v = s; return f; }
     static FilterRef column(const std::string& name) { auto f = std::make_shared<BooleanFilter>(); f->kind = InputColumn; f->column_name = name; return f; }
@@ -715,6 +787,13 @@ struct BooleanFilter {
     static FilterRef and_(FilterRef a, FilterRef b) { return make(And, a, b); }
     static FilterRef or_(FilterRef a, FilterRef b) { return make(Or, a, b); }
     static FilterRef not_(FilterRef a) { return make(Not, a); }
+    // text predicates: a Utf8 column against a String scalar (SQL LIKE: '%' any run, '_' one code point, `escape` or -1)
+    static FilterRef starts_with(FilterRef a, FilterRef b) { return make(StartsWith, a, b); }
+    static FilterRef ends_with(FilterRef a, FilterRef b) { return make(EndsWith, a, b); }
+    static FilterRef contains(FilterRef a, FilterRef b) { return make(Contains, a, b); }
+    static FilterRef like(FilterRef a, FilterRef b, int32_t escape = -1) {
+        auto f = std::make_shared<BooleanFilter>(); f->kind = Like; f->l = std::move(a); f->r = std::move(b); f->escape = escape; return f;
+    }
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -740,7 +819,11 @@ struct Expr {
 
 inline ExprRef filter_to_expr(const FilterRef& f, const std::function<ExprRef(const std::string&)>& resolve) {
     switch (f->kind) {
-        case BooleanFilter::InputScalar: return Expr::literal(f->scalar_v, f->scalar_v.rdf_type());
+        case BooleanFilter::InputScalar:
+            if (f->scalar_v.kind == Scalar::String) throw DataFrameError(DataFrameError::ComputeError, "a String scalar compares with Utf8 columns only");
+            return Expr::literal(f->scalar_v, f->scalar_v.rdf_type());
+        case BooleanFilter::StartsWith: case BooleanFilter::EndsWith: case BooleanFilter::Contains: case BooleanFilter::Like:
+            throw DataFrameError(DataFrameError::ComputeError, "starts_with / ends_with / contains / like take a Utf8 column and a String scalar");
         case BooleanFilter::InputColumn: return resolve(f->column_name);
         case BooleanFilter::Not: return Expr::make(RDF_OP_NOT, filter_to_expr(f->l, resolve));
         default: break;
@@ -2036,12 +2119,66 @@ class DataFrame {
 
     // evaluate_boolean_filter (:612-624): one BooleanArray mask per RecordBatch, computed in ONE launch
     Column evaluate_boolean_filter(const FilterRef& filter) const {
+        // The text leaves — a comparison or starts_with / ends_with / contains / like over a Utf8 column and a String scalar,
+        // or a comparison of two Utf8 columns — are evaluated on their own (rdf_utf8_predicate / rdf_utf8_compare) into Boolean
+        // columns that stand in for them, under private names, in what rdf_predicate then evaluates.
+        std::vector<std::pair<std::string, Column>> leaves;
+        const FilterRef rest = lower_text_leaves(filter, leaves);
+        if (!leaves.empty()) {
+            if (rest->kind == BooleanFilter::InputColumn) return leaves[0].second;   // the tree was one text leaf
+            DataFrame with = *this;
+            for (auto& l : leaves) with = with.with_column(l.first, l.second);
+            return with.evaluate_boolean_filter(rest);
+        }
         Lowered low;
         const int root = low.add(filter_to_expr(filter, [this](const std::string& n) {
             if (!has_column(n)) throw DataFrameError(DataFrameError::ComputeError, "Cannot find column " + n);  // expression.rs:812-815
             return Expr::col(n);
         }));
         return run_predicate(low, root);
+    }
+    bool is_text_column(const FilterRef& f) const {
+        return f && f->kind == BooleanFilter::InputColumn && has_column(f->column_name) && column_by_name(f->column_name).data_type() == DataType::Utf8;
+    }
+    static bool is_text_scalar(const FilterRef& f) { return f && f->kind == BooleanFilter::InputScalar && f->scalar_v.kind == Scalar::String; }
+    FilterRef lower_text_leaves(const FilterRef& f, std::vector<std::pair<std::string, Column>>& leaves) const {
+        if (!f) return f;
+        int32_t op = -1;
+        bool comparison = true;
+        switch (f->kind) {
+            case BooleanFilter::Eq: op = RDF_UTF8_EQ; break;
+            case BooleanFilter::Ne: op = RDF_UTF8_NE; break;
+            case BooleanFilter::Lt: op = RDF_UTF8_LT; break;
+            case BooleanFilter::Le: op = RDF_UTF8_LE; break;
+            case BooleanFilter::Gt: op = RDF_UTF8_GT; break;
+            case BooleanFilter::Ge: op = RDF_UTF8_GE; break;
+            case BooleanFilter::StartsWith: op = RDF_UTF8_STARTS_WITH; comparison = false; break;
+            case BooleanFilter::EndsWith: op = RDF_UTF8_ENDS_WITH; comparison = false; break;
+            case BooleanFilter::Contains: op = RDF_UTF8_CONTAINS; comparison = false; break;
+            case BooleanFilter::Like: op = RDF_UTF8_LIKE; comparison = false; break;
+            case BooleanFilter::Not: case BooleanFilter::And: case BooleanFilter::Or: {
+                auto g = std::make_shared<BooleanFilter>(*f);
+                g->l = lower_text_leaves(f->l, leaves);
+                g->r = lower_text_leaves(f->r, leaves);
+                return g;
+            }
+            default: return f;
+        }
+        const bool on_host = is_host();
+        Column mask;
+        if (is_text_column(f->l) && is_text_scalar(f->r)) {
+            mask = column_by_name(f->l->column_name).utf8_predicate(op, f->r->scalar_v.s, f->escape, on_host);
+        } else if (comparison && is_text_scalar(f->l) && is_text_column(f->r)) {   // 'x' < col  is  col > 'x'
+            static const int32_t flipped[6] = {RDF_UTF8_EQ, RDF_UTF8_NE, RDF_UTF8_GT, RDF_UTF8_GE, RDF_UTF8_LT, RDF_UTF8_LE};
+            mask = column_by_name(f->r->column_name).utf8_predicate(flipped[op], f->l->scalar_v.s, -1, on_host);
+        } else if (comparison && is_text_column(f->l) && is_text_column(f->r)) {
+            mask = column_by_name(f->l->column_name).utf8_compare(op, column_by_name(f->r->column_name), on_host);
+        } else {
+            return f;   // not a text leaf: the numeric path takes it, or refuses it
+        }
+        const std::string name = std::string("\x01utf8_pred_") + std::to_string(leaves.size());
+        leaves.emplace_back(name, mask);
+        return BooleanFilter::column(name);
     }
     Column run_predicate(const Lowered& low, int root) const {
         const size_t nch = num_chunks();
@@ -2818,6 +2955,32 @@ struct ScalarFunctions {
         for (auto& x : arr) { a.push_back(x->view()); outs.push_back(Array::make_out(DataType::Int32, x->length, x->validity != nullptr, x->host)); ov.push_back(outs.back()->out_view(x->length)); }
         check(rdf_hour(a.data(), (int64_t)a.size(), (int32_t)unit, ov.data()));
         return finish(outs, ov);
+    }
+    // length / octet_length / locate / instr and the text predicates over Utf8 arrays (length, locate, ... are declared with
+    // empty bodies, src/functions/scalar.rs:287-290): SQL / Spark semantics on the device (rdf_utf8_measure / rdf_utf8_predicate)
+    // -> Int32 / Boolean arrays on the device, a NULL row gives NULL.  locate: the 1-based code-point position of the first
+    // `substr` at or after position `pos`, 0 = none or pos < 1 (Python's s.find(sub, pos - 1) + 1); instr is pos = 1.
+    static Column text_column(const std::vector<ArrayRef>& arr, const char* what) {
+        for (auto& a : arr) if (a->dtype != DataType::Utf8) throw DataFrameError(DataFrameError::ComputeError, std::string(what) + ": Utf8 arrays only");
+        return Column::from_arrays(arr, Field{what, DataType::Utf8, true});
+    }
+    static std::vector<ArrayRef> length(const std::vector<ArrayRef>& arr) { return text_column(arr, "length").utf8_measure(RDF_UTF8_LENGTH).data().chunks(); }
+    static std::vector<ArrayRef> octet_length(const std::vector<ArrayRef>& arr) { return text_column(arr, "octet_length").utf8_measure(RDF_UTF8_OCTET_LENGTH).data().chunks(); }
+    static std::vector<ArrayRef> locate(const std::string& substr, const std::vector<ArrayRef>& arr, int64_t pos = 1) {
+        return text_column(arr, "locate").utf8_measure(RDF_UTF8_LOCATE, substr, pos).data().chunks();
+    }
+    static std::vector<ArrayRef> instr(const std::vector<ArrayRef>& arr, const std::string& substr) { return locate(substr, arr, 1); }
+    static std::vector<ArrayRef> starts_with(const std::vector<ArrayRef>& arr, const std::string& prefix) {
+        return text_column(arr, "starts_with").utf8_predicate(RDF_UTF8_STARTS_WITH, prefix).data().chunks();
+    }
+    static std::vector<ArrayRef> ends_with(const std::vector<ArrayRef>& arr, const std::string& suffix) {
+        return text_column(arr, "ends_with").utf8_predicate(RDF_UTF8_ENDS_WITH, suffix).data().chunks();
+    }
+    static std::vector<ArrayRef> contains(const std::vector<ArrayRef>& arr, const std::string& substr) {
+        return text_column(arr, "contains").utf8_predicate(RDF_UTF8_CONTAINS, substr).data().chunks();
+    }
+    static std::vector<ArrayRef> like(const std::vector<ArrayRef>& arr, const std::string& pattern, int32_t escape = -1) {
+        return text_column(arr, "like").utf8_predicate(RDF_UTF8_LIKE, pattern, escape).data().chunks();
     }
     // The calendar functions src/functions/scalar.rs declares with empty bodies (year .. date_diff): Spark 3's semantics as
     // written down at rdf_datetime_fields in rdf_mi355x.h.  Like hour, a temporal column is its Int32 / Int64 storage + time unit.

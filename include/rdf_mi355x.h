@@ -507,6 +507,50 @@ rdf_status rdf_utf8_substring(const rdf_utf8_array* chunks, int64_t nchunks, int
 rdf_status rdf_utf8_lower(const rdf_utf8_array* chunks, int64_t nchunks, rdf_out* out_offsets, rdf_out* out_data);
 rdf_status rdf_utf8_upper(const rdf_utf8_array* chunks, int64_t nchunks, rdf_out* out_offsets, rdf_out* out_data);
 
+/* ------------------------------------------------------------------ Utf8 predicates and measures */
+
+/* Masks and integers from text: WHERE city = 'London', name LIKE 'A%', length(s) > 10.  The reference declares length,
+ * locate, ... as empty stubs (src/functions/scalar.rs:287-290) and compares strings as Float64 (src/expression.rs:844-845),
+ * so these follow SQL / Spark; the executable model is tests/utf8_pred_ref.py.
+ * Inputs follow the rdf_utf8_array conventions exactly as rdf_utf8_trim takes them (row `offset`, value offsets that need
+ * not start at 0, validity at any bit offset, host or device memory, all one kind).  mask[i] is an RDF_BOOL output per
+ * chunk, out[i] an RDF_I32 one; both have length == rows and offset 0.  A NULL row gives a NULL result (validity bit 0,
+ * value bit / value 0); null_count is set.  An output needs a `validity` buffer whenever its chunk (for rdf_utf8_compare:
+ * either of its chunks) has one.  Bits beyond the last row in the last byte are 0; nothing is written past (rows + 7) / 8
+ * bytes of a caller's bitmap.  The results feed rdf_utf8_filter, rdf_filter, rdf_filter_columns, rdf_moments' mask, and
+ * rdf_predicate as Boolean input columns.  Neither the rows nor the pattern are validated as UTF-8: literals compare as
+ * bytes, and a code point begins at a byte that is not a continuation byte, as rdf_utf8_substring counts them.
+ *   EQ .. GE:  unsigned byte order, the same as rdf_lexsort_to_indices: a proper prefix sorts first, 0x00 is an ordinary
+ *              byte, "é" > "z".  rdf_utf8_predicate compares every row with the `pattern_bytes` bytes of `pattern`;
+ *              rdf_utf8_compare is the column-against-column form and takes these six ops only: a and b have the same
+ *              chunking, a row is NULL if either side is.
+ *   STARTS_WITH / ENDS_WITH / CONTAINS: the bytes of `pattern` as a literal; an empty pattern is true for every non-NULL
+ *              row; a match never extends past its own row.
+ *   LIKE:      '%' matches any run of code points, the empty run included, '_' exactly one code point; the whole row must
+ *              match.  `escape` is -1 (none) or one ASCII byte 1..127 other than '%' and '_'; the escape followed by any
+ *              character means that character literally; a pattern ending in a lone escape is RDF_INVALID_ARGUMENT, and so
+ *              is one with more than 32 non-empty segments between its '%'.  `escape` is checked for every op and used by
+ *              LIKE only.
+ *   LENGTH / OCTET_LENGTH: code points / bytes of the row; `pattern` and `pos` are ignored.
+ *   LOCATE:    the 1-based code-point position of the first occurrence of `pattern` at or after code-point position `pos`,
+ *              0 if there is none or pos < 1: s.find(sub, pos - 1) + 1 if pos >= 1 else 0 on a Python str, the empty
+ *              needle included (locate("", "abc", 4) == 4, pos 5 gives 0).  instr is pos = 1.
+ * Errors, all before any device work, in this order: an unknown op or a non-comparison op given to rdf_utf8_compare;
+ * pattern_bytes < 0 or > RDF_UTF8_PATTERN_MAX; pattern == NULL with pattern_bytes > 0; a bad escape; wrong dtypes; mixed
+ * memory kinds; a missing validity buffer: RDF_INVALID_ARGUMENT.  Chunk row counts that differ between a and b:
+ * RDF_COMPUTE_ERROR.  A capacity below the rows: RDF_MEMORY_ERROR with `length` set.  No device: RDF_DEVICE_ERROR.
+ * nchunks == 0 is RDF_OK. */
+typedef enum { RDF_UTF8_EQ = 0, RDF_UTF8_NE, RDF_UTF8_LT, RDF_UTF8_LE, RDF_UTF8_GT, RDF_UTF8_GE,
+               RDF_UTF8_STARTS_WITH, RDF_UTF8_ENDS_WITH, RDF_UTF8_CONTAINS, RDF_UTF8_LIKE } rdf_utf8_pred_op;
+typedef enum { RDF_UTF8_LENGTH = 0, RDF_UTF8_OCTET_LENGTH = 1, RDF_UTF8_LOCATE = 2 } rdf_utf8_measure_op;
+#define RDF_UTF8_PATTERN_MAX 1024   /* bytes of a literal / pattern */
+
+rdf_status rdf_utf8_predicate(int32_t op, const rdf_utf8_array* chunks, int64_t nchunks,
+                              const uint8_t* pattern, int64_t pattern_bytes, int32_t escape, rdf_out* mask);
+rdf_status rdf_utf8_compare(int32_t op, const rdf_utf8_array* a, const rdf_utf8_array* b, int64_t nchunks, rdf_out* mask);
+rdf_status rdf_utf8_measure(int32_t what, const rdf_utf8_array* chunks, int64_t nchunks,
+                            const uint8_t* pattern, int64_t pattern_bytes, int64_t pos, rdf_out* out);
+
 /* DataFrame::sort (src/dataframe.rs:194-222) whose criteria may be Utf8 columns: arrow's lexsort_to_indices over numeric
  * and StringArray columns alike.  keys[k] is criterion k (key 0 most significant) and sets exactly one of
  *   values  nchunks numeric chunks (one dtype), ordered as by rdf_sort_to_indices, or

@@ -246,6 +246,9 @@ pub mod sys {
         pub fn rdf_utf8_substring(chunks: *const rdf_utf8_array, nchunks: i64, pos: i64, len: i64, out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
         pub fn rdf_utf8_lower(chunks: *const rdf_utf8_array, nchunks: i64, out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
         pub fn rdf_utf8_upper(chunks: *const rdf_utf8_array, nchunks: i64, out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
+        pub fn rdf_utf8_predicate(op: i32, chunks: *const rdf_utf8_array, nchunks: i64, pattern: *const u8, pattern_bytes: i64, escape: i32, mask: *mut rdf_out) -> i32;
+        pub fn rdf_utf8_compare(op: i32, a: *const rdf_utf8_array, b: *const rdf_utf8_array, nchunks: i64, mask: *mut rdf_out) -> i32;
+        pub fn rdf_utf8_measure(what: i32, chunks: *const rdf_utf8_array, nchunks: i64, pattern: *const u8, pattern_bytes: i64, pos: i64, out: *mut rdf_out) -> i32;
         // the fused batch loop (src/evaluation.rs:66-96); host-resident frames above one slab are streamed (rdf_stream_stats says how)
         pub fn rdf_jit_status() -> *const c_char;          // the run-time compiler: found or not, cache directory, counts
         pub fn rdf_stream_stats(slabs: *mut i64, bytes_staged: *mut i64, bytes_direct: *mut i64) -> i32;

@@ -525,6 +525,10 @@ class DeviceUtf8:
 
 
 UTF8_UNARY = ("trim", "ltrim", "rtrim", "substring", "lower", "upper")
+# rdf_utf8_pred_op / rdf_utf8_measure_op
+UTF8_PRED_OPS = {"eq": 0, "ne": 1, "lt": 2, "le": 3, "gt": 4, "ge": 5, "starts_with": 6, "ends_with": 7, "contains": 8, "like": 9}
+UTF8_MEASURE_OPS = {"length": 0, "octet_length": 1, "locate": 2}
+UTF8_PATTERN_MAX = 1024
 
 
 class Expr:
@@ -1411,6 +1415,57 @@ class Api:
             call = lambda co, cd: fn(carr, C.c_int64(n), co, cd)  # noqa: E731
         return self._utf8_run(call, chunks, [c.length for c in chunks],
                               [c.validity is not None if isinstance(c, HostUtf8) else bool(c.validity_ptr) for c in chunks], as_arrow)
+
+    # ---- Utf8 predicates and measures: masks and integers from text (rdf_utf8_predicate / _compare / _measure)
+    @staticmethod
+    def _utf8_nullable(c) -> bool:
+        return c.validity is not None if isinstance(c, HostUtf8) else bool(c.validity_ptr)
+
+    def _utf8_pred_outs(self, dtype: int, chunks: Sequence, nullable: Sequence[bool], outs):
+        if outs is None:
+            device = any(isinstance(c, DeviceUtf8) for c in chunks)
+            outs = [self._window_out(dtype, c.length, device, nl) for c, nl in zip(chunks, nullable)]
+        return outs, (rdf_out * max(1, len(outs)))(*[o.out_struct() for o in outs])
+
+    @staticmethod
+    def _utf8_pattern(pattern):
+        raw = b"" if pattern is None else (pattern.encode("utf-8") if isinstance(pattern, str) else bytes(pattern))
+        return raw, (C.c_uint8 * max(1, len(raw))).from_buffer_copy(raw or b"\0")
+
+    def utf8_predicate(self, op, chunks: Sequence, pattern, escape=None, outs=None):
+        """rdf_utf8_predicate: every row against a literal or a LIKE pattern (a name of UTF8_PRED_OPS or its code; `pattern`
+        is str, encoded as UTF-8, or bytes; `escape` a one-character str, a byte value or None) -> one Boolean array per chunk."""
+        code = UTF8_PRED_OPS[op] if isinstance(op, str) else int(op)
+        esc = -1 if escape is None else (escape if isinstance(escape, (int, np.integer)) else ord(escape))
+        n = len(chunks)
+        carr = (rdf_utf8_array * max(1, n))(*[c.c_struct() for c in chunks])
+        raw, cp = self._utf8_pattern(pattern)
+        outs, co = self._utf8_pred_outs(BOOL, chunks, [self._utf8_nullable(c) for c in chunks], outs)
+        self._check(self._utf8_fn("utf8_predicate")(C.c_int32(code), carr, C.c_int64(n), cp, C.c_int64(len(raw)), C.c_int32(int(esc)), co))
+        return self._finish(outs, co)
+
+    def utf8_compare(self, op, a: Sequence, b: Sequence, outs=None):
+        """rdf_utf8_compare: column against column, one of the six comparisons -> one Boolean array per chunk."""
+        code = UTF8_PRED_OPS[op] if isinstance(op, str) else int(op)
+        n = len(a)
+        if len(b) != n:
+            raise ValueError("chunk lists differ in length")
+        ca = (rdf_utf8_array * max(1, n))(*[c.c_struct() for c in a])
+        cb = (rdf_utf8_array * max(1, n))(*[c.c_struct() for c in b])
+        outs, co = self._utf8_pred_outs(BOOL, a, [self._utf8_nullable(x) or self._utf8_nullable(y) for x, y in zip(a, b)], outs)
+        self._check(self._utf8_fn("utf8_compare")(C.c_int32(code), ca, cb, C.c_int64(n), co))
+        return self._finish(outs, co)
+
+    def utf8_measure(self, what, chunks: Sequence, pattern=None, pos: int = 1, outs=None):
+        """rdf_utf8_measure: "length" (code points), "octet_length" (bytes) or "locate" (1-based code-point position of
+        `pattern` at or after `pos`, 0 = none; instr is pos = 1) -> one Int32 array per chunk."""
+        code = UTF8_MEASURE_OPS[what] if isinstance(what, str) else int(what)
+        n = len(chunks)
+        carr = (rdf_utf8_array * max(1, n))(*[c.c_struct() for c in chunks])
+        raw, cp = self._utf8_pattern(pattern)
+        outs, co = self._utf8_pred_outs(I32, chunks, [self._utf8_nullable(c) for c in chunks], outs)
+        self._check(self._utf8_fn("utf8_measure")(C.c_int32(code), carr, C.c_int64(n), cp, C.c_int64(len(raw)), C.c_int64(int(pos)), co))
+        return self._finish(outs, co)
 
     # ---- Column::hist / Column::uniques (bound lazily: only the product has them)
     @staticmethod

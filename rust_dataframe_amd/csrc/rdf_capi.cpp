@@ -35,6 +35,7 @@
 #include "rdf_group_sorted.h"
 #include "rdf_collect.h"
 #include "rdf_datetime.h"
+#include "rdf_utf8_pattern.h"
 
 using namespace rdfk;
 
@@ -2869,6 +2870,7 @@ rdf_status groupby_sum_fallback(const rdf_array* keys, const rdf_array* values, 
 #include "rdf_capi_group_sorted.inc"
 #include "rdf_capi_collect.inc"
 #include "rdf_capi_datetime.inc"
+#include "rdf_capi_utf8_pred.inc"
 
 extern "C" {
 

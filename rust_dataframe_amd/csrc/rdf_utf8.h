@@ -125,3 +125,29 @@ hipError_t launch_utf8_sort_keys(const Utf8SortArgs& a, hipStream_t s);   // wor
 hipError_t launch_utf8_sort_seg_keys(const Utf8SortArgs& a, hipStream_t s);   // keys[t] = useg[order[t]]
 hipError_t launch_utf8_sort_mark(const Utf8SortArgs& a, hipStream_t s);   // trow .. tnull, perm written back, fu, fh
 hipError_t launch_utf8_sort_next(const Utf8SortArgs& a, hipStream_t s);   // nupos .. nsfirst, slcp reset
+
+// ---- predicates and measures over Utf8 (rdf_utf8_pred.hip; host side: rdf_capi_utf8_pred.inc; what is decided about one
+// row: rdf_utf8_pattern.h).  One streaming kernel per call: a block of kUtf8PredThreads lanes takes tiles of as many rows
+// that never straddle a chunk (tile_start: the prefix of the chunks' tile counts), a wave 64 consecutive rows.
+struct Utf8Pattern;
+constexpr int kUtf8PredThreads = 256;
+constexpr int kUtf8ShortRow = 256;     // bytes: a scanning op finishes a row up to this length on its lane, a longer one on the wave
+enum : int32_t { UTF8_FAM_LITERAL = 0, UTF8_FAM_SCAN = 1, UTF8_FAM_COMPARE = 2 };
+struct Utf8PredOut {
+    void*    values;       // the Boolean bitmap, or Int32 values
+    uint8_t* valid;        // nullptr = not requested
+};
+struct Utf8PredArgs {
+    const Utf8Chunk*    a;            // nchunks chunks
+    const Utf8Chunk*    b;            // UTF8_FAM_COMPARE: the other column, chunked alike
+    int64_t             nchunks;
+    const int64_t*      tile_start;   // nchunks + 1 entries
+    int64_t             ntiles;
+    const Utf8PredOut*  outs;         // per chunk
+    const Utf8Pattern*  pattern;      // device copy, nullptr for the ops that take none
+    int32_t             family, measure;
+    int32_t             op;           // compare: U8P_EQ .. U8P_GE; measure: U8M_*; predicate: the pattern's kind decides
+    int32_t             pos;          // locate
+    unsigned long long* nulls;        // per chunk: NULL rows added up (nullptr: the host knows them)
+};
+hipError_t launch_utf8_pred(const Utf8PredArgs& a, hipStream_t s);

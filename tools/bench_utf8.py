@@ -18,6 +18,7 @@ host.  The rounds each sort took come from rdf_last_kernel.
 
     python tools/bench_utf8.py [--rows 100000000] [--reps 5] [--out FILE]
     python tools/bench_utf8.py --sort [--sort-rows 10000000] [--reps 3] [--out FILE]
+    python tools/bench_utf8.py --pred [--rows 100000000] [--long-rows 100000] [--out profiles/utf8_pred.jsonl]
 """
 import argparse
 import ctypes as C
@@ -233,6 +234,128 @@ def sort_bench(args, api, torch):
                 f.write(json.dumps(r) + "\n")
 
 
+def pred_bench(args, api, torch):
+    """--pred: rdf_utf8_predicate / rdf_utf8_compare / rdf_utf8_measure on device-resident rows.  Per case: the HIP-event
+    kernel time, the algorithmic bytes (Int32 offsets + the data bytes the op must look at + 2 bits, or 4 bytes + 1 bit, per
+    row out) and their rate as a fraction of rdf_probe_stream's READ rate in the same process; pyarrow.compute on the host
+    over --arrow-rows of the same rows; rdf_utf8_trim on the same column for context."""
+    import time
+    import pyarrow as pa
+    import pyarrow.compute as pc
+    so = lib.load()
+    so.rdf_utf8_trim.restype = C.c_int
+    rng = np.random.default_rng(29)
+    n, nch = args.rows, args.chunks
+    assert n % nch == 0
+    cr = n // nch
+    pb = 1 << 31
+    probe = torch.empty(pb, dtype=torch.uint8, device="cuda")
+    read_gbps, read_shape = lib.probe_stream(0, probe.data_ptr(), 0, 0, pb, 10)
+    del probe
+    lines = []
+    hit = "London, UK"
+
+    def column(strings):
+        col, nbytes = device_column(torch, strings, cr)
+        reps, rem = divmod(cr, len(strings))
+        lens = np.array([len(x.encode()) for x in strings], dtype=np.int64)
+        return col, lens, reps, rem
+
+    def looked(lens, reps, rem, f):
+        """bytes of the rows an op must look at: f(row lengths) summed over the tiled column"""
+        v = f(lens)
+        return int(v.sum()) * reps * nch + int(v[:rem].sum()) * nch
+
+    def arrow_time(fn, strings):
+        k = min(args.arrow_rows, n)
+        arr = pa.array((strings * (k // len(strings) + 1))[:k], type=pa.string())
+        fn(arr)
+        best = 1e30
+        for _ in range(3):
+            t0 = time.perf_counter()
+            fn(arr)
+            best = min(best, (time.perf_counter() - t0) * 1e3)
+        return k, best
+
+    def run(name, call, rows, data_bytes, out_bytes_per_row, arrow=None, strings=None, chunks=nch):
+        for _ in range(args.warmup):
+            call()
+        ms = []
+        for _ in range(args.reps):
+            lib.kernel_timing_reset(True)
+            res = call()
+            ms.append(lib.kernel_timing_get()[0])
+        lib.kernel_timing_reset(False)
+        alg = 4 * (rows + chunks) + data_bytes + int(rows * out_bytes_per_row)
+        best = min(ms)
+        rec = {"op": name, "rows": rows, "chunks": chunks, "bytes_looked_at": data_bytes, "alg_bytes": alg, "kernel": lib.last_kernel(),
+               "kernel_ms": round(best, 3), "kernel_ms_median": round(float(np.median(ms)), 3), "GBps": round(alg / best / 1e6, 1),
+               "read_probe_GBps": round(read_gbps, 1), "frac_of_read": round(alg / best / 1e6 / read_gbps, 3), "read_probe_shape": read_shape,
+               "short_row_bytes": 256}
+        if res is not None and hasattr(res[0], "null_count"):
+            rec["result_rows"] = sum(r.length for r in res)
+        if arrow is not None:
+            k, t = arrow_time(arrow, strings)
+            rec["pyarrow_rows"], rec["pyarrow_ms"] = k, round(t, 3)
+        print(json.dumps(rec), flush=True)
+        lines.append(rec)
+
+    BIT2, I32 = 0.25, 4.125
+    for label, mixed in (("ascii", False), ("mixed", True)):
+        strings = pool(rng, 1 << 20, mixed)
+        for i in range(0, len(strings), 16):
+            strings[i] = hit
+        col, lens, reps, rem = column(strings)
+        cols = [col] * nch
+        bo = [api._window_out(A.BOOL, cr, True, False) for _ in range(nch)]     # outputs allocated once
+        io = [api._window_out(A.I32, cr, True, False) for _ in range(nch)]
+        allb = looked(lens, reps, rem, lambda v: v)
+        m = len(hit)
+        run(f"eq_1_16_{label}", lambda: api.utf8_predicate("eq", cols, hit, outs=bo), n, looked(lens, reps, rem, lambda v: np.where(v == m, v, 0)), BIT2,
+            lambda a: pc.equal(a, hit), strings)
+        run(f"starts_with_3_{label}", lambda: api.utf8_predicate("starts_with", cols, "Lon", outs=bo), n, looked(lens, reps, rem, lambda v: np.minimum(v, 3)), BIT2,
+            lambda a: pc.starts_with(a, "Lon"), strings)
+        run(f"contains_3_{label}", lambda: api.utf8_predicate("contains", cols, "don", outs=bo), n, allb, BIT2, lambda a: pc.match_substring(a, "don"), strings)
+        run(f"like_ab_cd_{label}", lambda: api.utf8_predicate("like", cols, "%ab%cd%", outs=bo), n, allb, BIT2, lambda a: pc.match_like(a, "%ab%cd%"), strings)
+        run(f"length_{label}", lambda: api.utf8_measure("length", cols, outs=io), n, allb, I32, lambda a: pc.utf8_length(a), strings)
+        run(f"octet_length_{label}", lambda: api.utf8_measure("octet_length", cols, outs=io), n, 0, I32, lambda a: pc.binary_length(a), strings)
+        run(f"locate_3_{label}", lambda: api.utf8_measure("locate", cols, "don", 1, outs=io), n, allb, I32, lambda a: pc.find_substring(a, "don"), strings)
+        run(f"compare_eq_columns_{label}", lambda: api.utf8_compare("eq", cols, cols, outs=bo), n, 2 * allb, BIT2, lambda a: pc.equal(a, a), strings)
+        run(f"compare_lt_columns_{label}", lambda: api.utf8_compare("lt", cols, cols, outs=bo), n, 2 * allb, BIT2)
+        # today's text reader on the same column: rdf_utf8_trim (the span pass + the copy)
+        carr = (A.rdf_utf8_array * nch)(*[col.c_struct()] * nch)
+        ot = [torch.empty(cr + 1 + 64, dtype=torch.int32, device="cuda") for _ in range(nch)]
+        dt = [torch.empty(int(lens.sum()) * (reps + 1) + 64, dtype=torch.uint8, device="cuda") for _ in range(nch)]
+        oo = (A.rdf_out * nch)(*[A.rdf_out(t.data_ptr(), None, cr + 1, 0, 0, A.I32, A.MEM_DEVICE) for t in ot])
+        od = (A.rdf_out * nch)(*[A.rdf_out(t.data_ptr(), None, t.numel() - 64, 0, 0, A.U8, A.MEM_DEVICE) for t in dt])
+
+        def trim():
+            assert so.rdf_utf8_trim(carr, C.c_int64(nch), oo, od) == A.RDF_OK, so.rdf_last_error()
+        run(f"utf8_trim_{label}", trim, n, 2 * allb, 4)
+        del ot, dt, col, cols, bo, io
+    # the long-row path: rows of 16 KiB
+    lrows = args.long_rows
+    long_pool = ["".join(rng.choice(list("abcdefghijklmnop "), size=16384)) for _ in range(64)]
+    h = A.HostUtf8.from_pylist(long_pool)
+    po = torch.from_numpy(h.offsets.astype(np.int64)).cuda()
+    pd = torch.from_numpy(h.data[:int(h.offsets[-1])].copy()).cuda()
+    per = min(lrows, (2**31 - 1) // 16384 // 64 * 64)
+    chunks = []
+    for c0 in range(0, lrows, per):
+        k = min(per, lrows - c0)
+        offs = (torch.arange(k + 1, device="cuda", dtype=torch.int64) * 16384).to(torch.int32)
+        data = pd.repeat((k + 63) // 64)[:k * 16384].contiguous()
+        chunks.append(A.DeviceUtf8(offs.data_ptr(), data.data_ptr(), k * 16384, k, None, 0, 0, 0, keep=(offs, data, None)))
+    lb = lrows * 16384
+    run("contains_none_16KiB_rows", lambda: api.utf8_predicate("contains", chunks, "zzz"), lrows, lb, BIT2, chunks=len(chunks))
+    run("contains_3_16KiB_rows", lambda: api.utf8_predicate("contains", chunks, "abc"), lrows, lb, BIT2, chunks=len(chunks))
+    run("length_16KiB_rows", lambda: api.utf8_measure("length", chunks), lrows, lb, I32, chunks=len(chunks))
+    if args.out:
+        with open(args.out, "a") as f:
+            for r in lines:
+                f.write(json.dumps(r) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=100_000_000)
@@ -242,6 +365,9 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--sort", action="store_true", help="measure rdf_lexsort_to_indices instead of the other operators")
     ap.add_argument("--sort-rows", type=int, default=10_000_000)
+    ap.add_argument("--pred", action="store_true", help="measure rdf_utf8_predicate / _compare / _measure instead (profiles/utf8_pred.jsonl)")
+    ap.add_argument("--long-rows", type=int, default=100_000, help="--pred: rows of 16 KiB for the long-row path")
+    ap.add_argument("--arrow-rows", type=int, default=10_000_000, help="--pred: rows pyarrow.compute is timed on")
     args = ap.parse_args()
     import torch
     api = lib.api()
@@ -249,6 +375,9 @@ def main():
     lib.set_device(0)
     if args.sort:
         sort_bench(args, api, torch)
+        return
+    if args.pred:
+        pred_bench(args, api, torch)
         return
     so = lib.load()
     for n in ("filter", "take", "trim", "lower"):
