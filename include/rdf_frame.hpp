@@ -740,7 +740,124 @@ class Column {
             check(rdf_utf8_measure(what, tc.txt.data(), (int64_t)tc.txt.size(), (const uint8_t*)pattern.data(), (int64_t)pattern.size(), pos, outs));
         });
     }
+
+    // Text columns made of more than one source, on the device (rdf_utf8_concat / _pad / _repeat / _reverse /
+    // _substring_index; Spark 3's semantics, see the C header): each call runs twice under the sizing rule and returns an
+    // ordinary Utf8 column with the input's chunking, carried like every text column of this mirror, so with_column,
+    // group_aggregate, joins and sort take it as a key as it is.
+    //   concat / concat_ws   parts are Utf8 columns of one chunking and literals; concat is NULL where a column part is,
+    //                        concat_ws skips NULL parts and is never NULL
+    //   lpad / rpad          to `len` code points with the pad cycled; a longer row is truncated
+    //   repeat, reverse, substring_index(delim, count)   (count < 0 counts from the right; occurrences may overlap)
+    struct Utf8Part {
+        const Column* column = nullptr;
+        std::string literal;
+        Utf8Part(const Column& c) : column(&c) {}
+        Utf8Part(std::string s) : literal(std::move(s)) {}
+        Utf8Part(const char* s) : literal(s) {}
+    };
+    static Column concat(const std::vector<Utf8Part>& parts, const std::string& name = "concat") { return concat_parts(parts, false, std::string(), name); }
+    static Column concat_ws(const std::string& sep, const std::vector<Utf8Part>& parts, const std::string& name = "concat_ws") { return concat_parts(parts, true, sep, name); }
+    Column lpad(int64_t len, const std::string& pad) const { return pad_side(0, len, pad); }
+    Column rpad(int64_t len, const std::string& pad) const { return pad_side(1, len, pad); }
+    Column repeat(int64_t times) const {
+        need_text("repeat");
+        const TextChunks tc = text_chunks("repeat");
+        return text_build(tc, chunk_nullable(), field_.name, [&](rdf_out* oo, rdf_out* od) { return rdf_utf8_repeat(tc.txt.data(), (int64_t)tc.txt.size(), times, oo, od); });
+    }
+    Column reverse() const {
+        need_text("reverse");
+        const TextChunks tc = text_chunks("reverse");
+        return text_build(tc, chunk_nullable(), field_.name, [&](rdf_out* oo, rdf_out* od) { return rdf_utf8_reverse(tc.txt.data(), (int64_t)tc.txt.size(), oo, od); });
+    }
+    Column substring_index(const std::string& delim, int64_t count) const {
+        need_text("substring_index");
+        const TextChunks tc = text_chunks("substring_index");
+        return text_build(tc, chunk_nullable(), field_.name, [&](rdf_out* oo, rdf_out* od) {
+            return rdf_utf8_substring_index(tc.txt.data(), (int64_t)tc.txt.size(), (const uint8_t*)delim.data(), (int64_t)delim.size(), count, oo, od);
+        });
+    }
   private:
+    std::vector<bool> chunk_nullable() const {
+        std::vector<bool> nullable;
+        for (auto& a : data_.chunks()) nullable.push_back(a->validity != nullptr);
+        return nullable;
+    }
+    Column pad_side(int32_t side, int64_t len, const std::string& pad) const {
+        need_text(side ? "rpad" : "lpad");
+        const TextChunks tc = text_chunks(side ? "rpad" : "lpad");
+        return text_build(tc, chunk_nullable(), field_.name, [&](rdf_out* oo, rdf_out* od) {
+            return rdf_utf8_pad(side, tc.txt.data(), (int64_t)tc.txt.size(), len, (const uint8_t*)pad.data(), (int64_t)pad.size(), oo, od);
+        });
+    }
+    static Column concat_parts(const std::vector<Utf8Part>& parts, bool ws, const std::string& sep, const std::string& name) {
+        const char* what = ws ? "concat_ws" : "concat";
+        std::vector<TextChunks> tcs;
+        tcs.reserve(parts.size());
+        std::vector<rdf_utf8_part> cp;
+        const Column* first = nullptr;
+        for (auto& p : parts) {
+            if (!p.column) { cp.push_back(rdf_utf8_part{nullptr, (const uint8_t*)p.literal.data(), (int64_t)p.literal.size()}); continue; }
+            p.column->need_text(what);
+            if (!first) first = p.column;
+            if (p.column->data_.num_chunks() != first->data_.num_chunks()) throw DataFrameError(DataFrameError::ComputeError, std::string(what) + ": chunk lists differ in length");
+            tcs.push_back(p.column->text_chunks(what));
+            cp.push_back(rdf_utf8_part{tcs.back().txt.data(), nullptr, 0});
+        }
+        if (!first) throw DataFrameError(DataFrameError::ComputeError, std::string(what) + ": at least one part must be a column");
+        std::vector<bool> nullable(first->data_.num_chunks(), false);
+        if (!ws)
+            for (auto& p : parts)
+                if (p.column)
+                    for (size_t i = 0; i < nullable.size(); ++i) nullable[i] = nullable[i] || p.column->data_.chunk(i)->validity != nullptr;
+        return text_build(tcs[0], nullable, name, [&](rdf_out* oo, rdf_out* od) {
+            return rdf_utf8_concat(cp.data(), (int32_t)cp.size(), (int64_t)nullable.size(), ws ? 1 : 0, (const uint8_t*)sep.data(), (int64_t)sep.size(), oo, od);
+        });
+    }
+    // One Utf8 result chunk per text chunk of `shape`: the sizing call, then the call into exactly sized host buffers
+    template <class Call>
+    static Column text_build(const TextChunks& shape, const std::vector<bool>& nullable, const std::string& name, Call call) {
+        const size_t n = shape.txt.size();
+        std::vector<std::vector<int32_t>> offs(n);
+        std::vector<std::vector<uint8_t>> valid(n), data(n);
+        std::vector<rdf_out> oo(n), od(n);
+        for (size_t i = 0; i < n; ++i) {
+            const int64_t rows = shape.txt[i].offsets.length - 1;
+            offs[i].assign((size_t)rows + 1, 0);
+            if (nullable[i]) valid[i].assign((size_t)((rows + 63) / 64 * 8 + 8), 0);
+            oo[i] = rdf_out{offs[i].data(), nullable[i] ? valid[i].data() : nullptr, rows + 1, 0, 0, RDF_I32, RDF_MEM_HOST};
+            od[i] = rdf_out{nullptr, nullptr, 0, 0, 0, RDF_U8, RDF_MEM_HOST};
+        }
+        rdf_status st = call(oo.data(), od.data());
+        if (st == RDF_MEMORY_ERROR) {
+            for (size_t i = 0; i < n; ++i) {
+                data[i].assign((size_t)od[i].length + 8, 0);
+                od[i].values = data[i].data();
+                od[i].capacity = od[i].length;
+            }
+            st = call(oo.data(), od.data());
+        }
+        check(st);
+        std::vector<ArrayRef> res;
+        bool any_null = false;
+        for (size_t i = 0; i < n; ++i) {
+            const int64_t rows = oo[i].length - 1;
+            std::vector<std::string> strs((size_t)rows);
+            for (int64_t r = 0; r < rows; ++r)
+                strs[(size_t)r].assign((const char*)data[i].data() + offs[i][(size_t)r], (size_t)(offs[i][(size_t)r + 1] - offs[i][(size_t)r]));
+            auto a = std::const_pointer_cast<Array>(Array::from_strings(std::move(strs)));
+            if (nullable[i]) {
+                const size_t nb = (size_t)((rows + 63) / 64 * 8);
+                a->validity = std::make_shared<DeviceBuffer>((int64_t)nb + 8);
+                check(rdf_copy_h2d(a->validity->data(), valid[i].data(), (int64_t)nb + 8));
+                a->null_count = oo[i].null_count;
+                any_null = true;
+            }
+            res.push_back(a);
+        }
+        if (res.empty()) res.push_back(Array::from_strings({}));
+        return Column::from_arrays(res, Field{name, DataType::Utf8, any_null});
+    }
     ChunkedArray data_;
     Field field_;
 };
@@ -2981,6 +3098,39 @@ struct ScalarFunctions {
     }
     static std::vector<ArrayRef> like(const std::vector<ArrayRef>& arr, const std::string& pattern, int32_t escape = -1) {
         return text_column(arr, "like").utf8_predicate(RDF_UTF8_LIKE, pattern, escape).data().chunks();
+    }
+    // concat / concat_ws / lpad / rpad / repeat / reverse / substring_index over Utf8 arrays (declared with empty bodies in
+    // src/functions/scalar.rs): Spark 3's semantics on the device (rdf_utf8_concat .. rdf_utf8_substring_index), Utf8 arrays
+    // out.  A concat part is a chunk list or a std::string literal; all chunk lists of one call share one chunking.
+    struct TextPart {
+        std::vector<ArrayRef> arrays;
+        std::string literal;
+        bool is_literal;
+        TextPart(std::vector<ArrayRef> a) : arrays(std::move(a)), is_literal(false) {}
+        TextPart(std::string s) : literal(std::move(s)), is_literal(true) {}
+        TextPart(const char* s) : literal(s), is_literal(true) {}
+    };
+    static std::vector<ArrayRef> concat_parts(const std::vector<TextPart>& parts, bool ws, const std::string& sep) {
+        std::vector<Column> cols;
+        cols.reserve(parts.size());
+        for (auto& p : parts)
+            if (!p.is_literal) cols.push_back(text_column(p.arrays, ws ? "concat_ws" : "concat"));
+        std::vector<Column::Utf8Part> cp;
+        size_t k = 0;
+        for (auto& p : parts) {
+            if (p.is_literal) cp.emplace_back(p.literal);
+            else cp.emplace_back(cols[k++]);
+        }
+        return (ws ? Column::concat_ws(sep, cp) : Column::concat(cp)).data().chunks();
+    }
+    static std::vector<ArrayRef> concat(const std::vector<TextPart>& parts) { return concat_parts(parts, false, std::string()); }
+    static std::vector<ArrayRef> concat_ws(const std::string& sep, const std::vector<TextPart>& parts) { return concat_parts(parts, true, sep); }
+    static std::vector<ArrayRef> lpad(const std::vector<ArrayRef>& arr, int64_t len, const std::string& pad) { return text_column(arr, "lpad").lpad(len, pad).data().chunks(); }
+    static std::vector<ArrayRef> rpad(const std::vector<ArrayRef>& arr, int64_t len, const std::string& pad) { return text_column(arr, "rpad").rpad(len, pad).data().chunks(); }
+    static std::vector<ArrayRef> repeat(const std::vector<ArrayRef>& arr, int64_t times) { return text_column(arr, "repeat").repeat(times).data().chunks(); }
+    static std::vector<ArrayRef> reverse(const std::vector<ArrayRef>& arr) { return text_column(arr, "reverse").reverse().data().chunks(); }
+    static std::vector<ArrayRef> substring_index(const std::vector<ArrayRef>& arr, const std::string& delim, int64_t count) {
+        return text_column(arr, "substring_index").substring_index(delim, count).data().chunks();
     }
     // The calendar functions src/functions/scalar.rs declares with empty bodies (year .. date_diff): Spark 3's semantics as
     // written down at rdf_datetime_fields in rdf_mi355x.h.  Like hour, a temporal column is its Int32 / Int64 storage + time unit.

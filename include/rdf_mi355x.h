@@ -551,6 +551,58 @@ rdf_status rdf_utf8_compare(int32_t op, const rdf_utf8_array* a, const rdf_utf8_
 rdf_status rdf_utf8_measure(int32_t what, const rdf_utf8_array* chunks, int64_t nchunks,
                             const uint8_t* pattern, int64_t pattern_bytes, int64_t pos, rdf_out* out);
 
+/* ------------------------------------------------------------------ Utf8 builders */
+
+/* Text columns made of more than one source: city || ', ' || country as a GROUP BY key, a zero-padded id, the host part of
+ * a URL.  The reference declares concat, concat_ws, lpad, rpad, repeat, reverse and substring_index with empty bodies
+ * (src/functions/scalar.rs), so these follow Spark 3; the executable model is tests/utf8_build_ref.py.
+ * Inputs follow the rdf_utf8_array conventions exactly as rdf_utf8_trim takes them (row `offset`, value offsets that need
+ * not start at 0, validity at any bit offset, host or device memory, all one kind).  Outputs are chunked like the inputs:
+ * out_offsets[i] / out_data[i] hold the rows of input chunk i, under the one sizing rule of rdf_utf8_filter .. _upper
+ * (values == NULL, capacity == 0 is the sizing call; a capacity that is too small gives RDF_MEMORY_ERROR with every length
+ * set and nothing written; an output chunk beyond 2^31-1 bytes is RDF_COMPUTE_ERROR).  An output whose rows can be NULL
+ * needs out_offsets[i].validity; null_count is set.  A code point begins at every byte that is not a continuation byte,
+ * as rdf_utf8_measure(LENGTH) counts them; bytes are not validated.
+ *   concat     (with_separator == 0; sep_bytes must be 0) the parts joined in order; a part is a column (nchunks chunks) or
+ *              a literal; a row is NULL if any column part is NULL in that row.
+ *   concat_ws  (with_separator == 1) NULL parts are skipped and `sep` stands between the remaining ones; empty strings are
+ *              not skipped; the result is never NULL (a row without a non-NULL part is the empty string): a validity buffer,
+ *              if given, is written all ones and null_count is 0.
+ *              Both: all column parts share one chunking; at least one part is a column (the row count is its).
+ *   pad        side 0 = lpad, 1 = rpad.  With n the row's and p the pad's code points: len <= 0 gives the empty string;
+ *              n >= len or an empty pad gives the first min(n, len) code points of the row (the row is TRUNCATED);
+ *              otherwise the pad repeated (len - n) / p times followed by its first (len - n) % p code points stands left
+ *              (right) of the row.
+ *   repeat     the row `times` times; times <= 0 gives the empty string.
+ *   reverse    the row's code points in reverse order, each one's bytes kept in order (not grapheme clusters).  On bytes
+ *              that are not valid UTF-8 the output row has the input row's length and nothing outside the row is touched.
+ *   substring_index  byte-wise: for count > 0 everything left of the count-th occurrence of `delim` from the left, for
+ *              count < 0 everything right of the |count|-th from the right; each search resumes one byte after (before) the
+ *              START of the previous hit, so occurrences may overlap ('aaaa', 'aa', 2 -> 'a'); with fewer occurrences the
+ *              whole row; an empty delim or count == 0 gives the empty string.
+ *   A NULL row gives NULL for pad, repeat, reverse and substring_index.  len and times are clamped to 2^31, and so is a
+ *   single row's computed length: a size never wraps, the call returns RDF_COMPUTE_ERROR.
+ * Errors, all before any device work, in this order, RDF_INVALID_ARGUMENT unless said otherwise: nparts outside
+ * 1..RDF_UTF8_PARTS_MAX or a bad side; a part that sets both pointers or neither, or no column part; a literal, sep, pad or
+ * delim whose length is negative or above RDF_UTF8_PATTERN_MAX, or a NULL pointer with a positive length; sep_bytes != 0
+ * with with_separator == 0; wrong dtypes, mixed memory kinds, a missing validity buffer; chunk row counts that differ
+ * between parts: RDF_COMPUTE_ERROR; no device: RDF_DEVICE_ERROR.  nchunks == 0 is RDF_OK. */
+#define RDF_UTF8_PARTS_MAX 8
+typedef struct {                 /* exactly one of utf8 / literal is set */
+    const rdf_utf8_array* utf8;  /* nchunks chunks of this part, or NULL */
+    const uint8_t* literal;      /* literal_bytes bytes (may be 0 bytes with a non-NULL pointer), or NULL */
+    int64_t literal_bytes;       /* 0 .. RDF_UTF8_PATTERN_MAX */
+} rdf_utf8_part;
+
+rdf_status rdf_utf8_concat(const rdf_utf8_part* parts, int32_t nparts, int64_t nchunks, int32_t with_separator,
+                           const uint8_t* sep, int64_t sep_bytes, rdf_out* out_offsets, rdf_out* out_data);
+rdf_status rdf_utf8_pad(int32_t side /* 0 = lpad, 1 = rpad */, const rdf_utf8_array* chunks, int64_t nchunks, int64_t len,
+                        const uint8_t* pad, int64_t pad_bytes, rdf_out* out_offsets, rdf_out* out_data);
+rdf_status rdf_utf8_repeat(const rdf_utf8_array* chunks, int64_t nchunks, int64_t times, rdf_out* out_offsets, rdf_out* out_data);
+rdf_status rdf_utf8_reverse(const rdf_utf8_array* chunks, int64_t nchunks, rdf_out* out_offsets, rdf_out* out_data);
+rdf_status rdf_utf8_substring_index(const rdf_utf8_array* chunks, int64_t nchunks, const uint8_t* delim, int64_t delim_bytes,
+                                    int64_t count, rdf_out* out_offsets, rdf_out* out_data);
+
 /* DataFrame::sort (src/dataframe.rs:194-222) whose criteria may be Utf8 columns: arrow's lexsort_to_indices over numeric
  * and StringArray columns alike.  keys[k] is criterion k (key 0 most significant) and sets exactly one of
  *   values  nchunks numeric chunks (one dtype), ordered as by rdf_sort_to_indices, or

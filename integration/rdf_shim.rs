@@ -58,6 +58,10 @@ pub mod sys {
     #[repr(C)] #[derive(Clone, Copy)] pub struct rdf_sort_options { pub descending: i32, pub nulls_first: i32 }
     #[repr(C)] #[derive(Clone, Copy)] pub struct rdf_list_array { pub offsets: rdf_array, pub values: rdf_array }
     #[repr(C)] #[derive(Clone, Copy)] pub struct rdf_utf8_array { pub offsets: rdf_array, pub data: rdf_array }
+    // one part of rdf_utf8_concat: exactly one of utf8 (nchunks chunks) / literal (literal_bytes bytes) is set
+    #[repr(C)] #[derive(Clone, Copy)]
+    pub struct rdf_utf8_part { pub utf8: *const rdf_utf8_array, pub literal: *const u8, pub literal_bytes: i64 }
+    pub const RDF_UTF8_PARTS_MAX: i32 = 8;
     // one criterion of rdf_lexsort_to_indices: exactly one of values / utf8 points at nchunks chunks
     #[repr(C)] #[derive(Clone, Copy)]
     pub struct rdf_sort_key { pub values: *const rdf_array, pub utf8: *const rdf_utf8_array, pub options: rdf_sort_options }
@@ -249,6 +253,15 @@ pub mod sys {
         pub fn rdf_utf8_predicate(op: i32, chunks: *const rdf_utf8_array, nchunks: i64, pattern: *const u8, pattern_bytes: i64, escape: i32, mask: *mut rdf_out) -> i32;
         pub fn rdf_utf8_compare(op: i32, a: *const rdf_utf8_array, b: *const rdf_utf8_array, nchunks: i64, mask: *mut rdf_out) -> i32;
         pub fn rdf_utf8_measure(what: i32, chunks: *const rdf_utf8_array, nchunks: i64, pattern: *const u8, pattern_bytes: i64, pos: i64, out: *mut rdf_out) -> i32;
+        // Utf8 builders (concat / concat_ws, lpad / rpad, repeat, reverse, substring_index): the sizing rule of rdf_utf8_trim
+        pub fn rdf_utf8_concat(parts: *const rdf_utf8_part, nparts: i32, nchunks: i64, with_separator: i32, sep: *const u8, sep_bytes: i64,
+                               out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
+        pub fn rdf_utf8_pad(side: i32, chunks: *const rdf_utf8_array, nchunks: i64, len: i64, pad: *const u8, pad_bytes: i64,
+                            out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
+        pub fn rdf_utf8_repeat(chunks: *const rdf_utf8_array, nchunks: i64, times: i64, out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
+        pub fn rdf_utf8_reverse(chunks: *const rdf_utf8_array, nchunks: i64, out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
+        pub fn rdf_utf8_substring_index(chunks: *const rdf_utf8_array, nchunks: i64, delim: *const u8, delim_bytes: i64, count: i64,
+                                        out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
         // the fused batch loop (src/evaluation.rs:66-96); host-resident frames above one slab are streamed (rdf_stream_stats says how)
         pub fn rdf_jit_status() -> *const c_char;          // the run-time compiler: found or not, cache directory, counts
         pub fn rdf_stream_stats(slabs: *mut i64, bytes_staged: *mut i64, bytes_direct: *mut i64) -> i32;

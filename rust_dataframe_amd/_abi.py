@@ -113,6 +113,10 @@ class rdf_utf8_array(C.Structure):
     _fields_ = [("offsets", rdf_array), ("data", rdf_array)]
 
 
+class rdf_utf8_part(C.Structure):
+    _fields_ = [("utf8", C.POINTER(rdf_utf8_array)), ("literal", C.POINTER(C.c_uint8)), ("literal_bytes", C.c_int64)]
+
+
 class rdf_sort_key(C.Structure):
     _fields_ = [("values", C.POINTER(rdf_array)), ("utf8", C.POINTER(rdf_utf8_array)), ("options", rdf_sort_options)]
 
@@ -529,6 +533,7 @@ UTF8_UNARY = ("trim", "ltrim", "rtrim", "substring", "lower", "upper")
 UTF8_PRED_OPS = {"eq": 0, "ne": 1, "lt": 2, "le": 3, "gt": 4, "ge": 5, "starts_with": 6, "ends_with": 7, "contains": 8, "like": 9}
 UTF8_MEASURE_OPS = {"length": 0, "octet_length": 1, "locate": 2}
 UTF8_PATTERN_MAX = 1024
+UTF8_PARTS_MAX = 8
 
 
 class Expr:
@@ -1466,6 +1471,65 @@ class Api:
         outs, co = self._utf8_pred_outs(I32, chunks, [self._utf8_nullable(c) for c in chunks], outs)
         self._check(self._utf8_fn("utf8_measure")(C.c_int32(code), carr, C.c_int64(n), cp, C.c_int64(len(raw)), C.c_int64(int(pos)), co))
         return self._finish(outs, co)
+
+    # ---- Utf8 builders: text columns made of more than one source (rdf_utf8_concat / _pad / _repeat / _reverse / _substring_index)
+    def utf8_build_call(self, op: str, chunks, *args):
+        """-> (call(out_offsets, out_data) -> status, the column chunks that give the row counts, nullable per chunk) of one
+        builder call; utf8_build runs it under the sizing rule, tests call it with buffers of their own.
+          ("concat", parts) / ("concat_ws", parts, sep): parts = chunk lists and str / bytes literals (chunks = None)
+          ("lpad" | "rpad", chunks, len, pad), ("repeat", chunks, times), ("reverse", chunks), ("substring_index", chunks, delim, count)"""
+        if op in ("concat", "concat_ws"):
+            parts = args[0]
+            raw, cp = self._utf8_pattern(args[1] if op == "concat_ws" else None)
+            cols = [p for p in parts if not isinstance(p, (str, bytes, bytearray))]
+            n = len(cols[0]) if cols else 0
+            keep, cparts = [raw, cp], (rdf_utf8_part * max(1, len(parts)))()
+            for k, p in enumerate(parts):
+                if isinstance(p, (str, bytes, bytearray)):
+                    lraw, lp = self._utf8_pattern(p)
+                    keep.append(lp)
+                    cparts[k] = rdf_utf8_part(None, C.cast(lp, C.POINTER(C.c_uint8)), len(lraw))
+                else:
+                    if len(p) != n:
+                        raise ValueError("chunk lists differ in length")
+                    carr = (rdf_utf8_array * max(1, n))(*[c.c_struct() for c in p])
+                    keep.append(carr)
+                    cparts[k] = rdf_utf8_part(carr, None, 0)
+            fn = self._utf8_fn("utf8_concat")
+            ws = op == "concat_ws"
+            call = lambda co, cd, keep=keep: fn(cparts, C.c_int32(len(parts)), C.c_int64(n), C.c_int32(int(ws)), cp, C.c_int64(len(raw)), co, cd)  # noqa: E731
+            nullable = [False if ws else any(self._utf8_nullable(col[i]) for col in cols) for i in range(n)]
+            return call, (cols[0] if cols else []), nullable
+        n = len(chunks)
+        carr = (rdf_utf8_array * max(1, n))(*[c.c_struct() for c in chunks])
+        nullable = [self._utf8_nullable(c) for c in chunks]
+        if op in ("lpad", "rpad"):
+            raw, cp = self._utf8_pattern(args[1])
+            fn = self._utf8_fn("utf8_pad")
+            call = lambda co, cd: fn(C.c_int32(int(op == "rpad")), carr, C.c_int64(n), C.c_int64(int(args[0])), cp, C.c_int64(len(raw)), co, cd)  # noqa: E731
+        elif op == "repeat":
+            fn = self._utf8_fn("utf8_repeat")
+            call = lambda co, cd: fn(carr, C.c_int64(n), C.c_int64(int(args[0])), co, cd)  # noqa: E731
+        elif op == "reverse":
+            fn = self._utf8_fn("utf8_reverse")
+            call = lambda co, cd: fn(carr, C.c_int64(n), co, cd)  # noqa: E731
+        elif op == "substring_index":
+            raw, cp = self._utf8_pattern(args[0])
+            fn = self._utf8_fn("utf8_substring_index")
+            call = lambda co, cd: fn(carr, C.c_int64(n), cp, C.c_int64(len(raw)), C.c_int64(int(args[1])), co, cd)  # noqa: E731
+        else:
+            raise ValueError(f"unknown Utf8 builder {op!r}")
+        return call, chunks, nullable
+
+    def utf8_build(self, op: str, chunks, *args, as_arrow=False):
+        """One builder call under the sizing rule (the sizing call, then the call into exactly sized buffers): one result per
+        chunk.  Arguments as for utf8_build_call."""
+        call, shape, nullable = self.utf8_build_call(op, chunks, *args)
+        return self._utf8_run(call, shape, [c.length for c in shape], nullable, as_arrow)
+
+    def utf8_concat(self, parts: Sequence, sep=None, as_arrow=False):
+        """concat (sep is None) / concat_ws of chunk lists and str / bytes literals."""
+        return self.utf8_build("concat", None, parts, as_arrow=as_arrow) if sep is None else self.utf8_build("concat_ws", None, parts, sep, as_arrow=as_arrow)
 
     # ---- Column::hist / Column::uniques (bound lazily: only the product has them)
     @staticmethod

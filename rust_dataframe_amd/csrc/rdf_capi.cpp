@@ -36,6 +36,7 @@
 #include "rdf_collect.h"
 #include "rdf_datetime.h"
 #include "rdf_utf8_pattern.h"
+#include "rdf_utf8_build.h"
 
 using namespace rdfk;
 
@@ -2871,6 +2872,7 @@ rdf_status groupby_sum_fallback(const rdf_array* keys, const rdf_array* values, 
 #include "rdf_capi_collect.inc"
 #include "rdf_capi_datetime.inc"
 #include "rdf_capi_utf8_pred.inc"
+#include "rdf_capi_utf8_build.inc"
 
 extern "C" {
 

@@ -151,3 +151,36 @@ struct Utf8PredArgs {
     unsigned long long* nulls;        // per chunk: NULL rows added up (nullptr: the host knows them)
 };
 hipError_t launch_utf8_pred(const Utf8PredArgs& a, hipStream_t s);
+
+// ---- builders of Utf8 columns (rdf_utf8_build.hip; host side: rdf_capi_utf8_build.inc; what is decided about one row:
+// rdf_utf8_build.h).  The three steps of the byte-gather above with a row made of several pieces: a size pass in the tiles
+// of the predicates (256 rows of one chunk a block, long rows on the wave), the scans, and a write pass driven by the
+// destination.  Output chunk c has the rows of input chunk c.
+struct Utf8BuildPart {
+    const Utf8Chunk* col;      // nchunks chunks of a column part, or nullptr
+    const uint8_t*   lit;      // a literal part's bytes
+    int32_t          lit_bytes;
+};
+struct Utf8BuildArgs {
+    const Utf8BuildPart* parts;      // device copy: nparts (1 for every op but concat)
+    int32_t          nparts, op;     // op: U8B_*
+    const Utf8Chunk* shape;          // the first column part's chunks: rows and row_start of every chunk
+    int64_t          nchunks;
+    const int64_t*   tile_start;     // size pass: nchunks + 1 entries, tiles of kUtf8PredThreads rows
+    int64_t          nsize_tiles;
+    const uint8_t*   lit;            // separator / pad / delimiter (device copy)
+    int32_t          lit_bytes, lit_cp;
+    int64_t          param;          // pad: len; repeat: times (both clamped to [0, 2^31]); substring_index: count
+    int64_t          n;              // rows
+    int64_t*         blen;           // per row: output bytes (scanned into bscan)
+    uint32_t*        aux;            // per row: bit 31 = valid; concat: the present parts' bits; pad: kept bytes; substring_index: the span's start
+    const int64_t*   bscan;          // n + 1 entries
+    int64_t*         tot;            // per chunk: bytes, rows
+    unsigned long long* null_counts; // per chunk
+    const Utf8OutChunk* outs;
+    int64_t          ntiles;         // copy tiles
+    int64_t*         tile_row;       // per copy tile: the row (of its chunk) that holds the tile's first byte
+};
+hipError_t launch_utf8_build_size(const Utf8BuildArgs& a, hipStream_t s);     // blen, aux, null_counts
+hipError_t launch_utf8_build_totals(const Utf8BuildArgs& a, hipStream_t s);   // tot
+hipError_t launch_utf8_build_write(const Utf8BuildArgs& a, hipStream_t s);    // offsets, validity, the bytes

@@ -19,6 +19,7 @@ host.  The rounds each sort took come from rdf_last_kernel.
     python tools/bench_utf8.py [--rows 100000000] [--reps 5] [--out FILE]
     python tools/bench_utf8.py --sort [--sort-rows 10000000] [--reps 3] [--out FILE]
     python tools/bench_utf8.py --pred [--rows 100000000] [--long-rows 100000] [--out profiles/utf8_pred.jsonl]
+    python tools/bench_utf8.py --build [--rows 100000000] [--long-rows 100000] [--out profiles/utf8_build.jsonl]
 """
 import argparse
 import ctypes as C
@@ -356,6 +357,119 @@ def pred_bench(args, api, torch):
                 f.write(json.dumps(r) + "\n")
 
 
+def build_bench(args, api, torch):
+    """--build: rdf_utf8_concat / _pad / _repeat / _reverse / _substring_index on device-resident rows.  Per case: the HIP-event
+    kernel time of the call into buffers sized beforehand (size pass + scan + write pass), the bytes moved (Int32 offsets in and
+    out, the source bytes once, the output bytes once) and their rate as a fraction of rdf_probe_stream's COPY rate in the same
+    process; rdf_utf8_trim on the same column (today's writer: the same passes with one source span) for context."""
+    so = lib.load()
+    so.rdf_utf8_trim.restype = C.c_int
+    rng = np.random.default_rng(31)
+    n, nch = args.rows, args.chunks
+    assert n % nch == 0
+    cr = n // nch
+    pb = 1 << 30
+    pa_, pb_ = torch.empty(pb, dtype=torch.uint8, device="cuda"), torch.empty(pb, dtype=torch.uint8, device="cuda")
+    copy_gbps, copy_shape = lib.probe_stream(1, pa_.data_ptr(), pb_.data_ptr(), 0, pb, 10)
+    del pa_, pb_
+    def emit(rec):          # a line at a time: a later case that fails loses nothing
+        print(json.dumps(rec), flush=True)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write(json.dumps(rec) + "\n")
+
+    def run(name, op, chunks, *a, rows, in_bytes, note=None):
+        """the sizing call, buffers of those sizes, then warm-up and the timed calls"""
+        call, shape, nullable = api.utf8_build_call(op, chunks, *a)
+        k = len(shape)
+        ot = [torch.empty(c.length + 1 + 64, dtype=torch.int32, device="cuda") for c in shape]
+        vt = [torch.empty((c.length + 63) // 64 * 8 + 8, dtype=torch.uint8, device="cuda") if nl else None for c, nl in zip(shape, nullable)]
+        oo = (A.rdf_out * k)(*[A.rdf_out(t.data_ptr(), v.data_ptr() if v is not None else None, c.length + 1, 0, 0, A.I32, A.MEM_DEVICE) for t, v, c in zip(ot, vt, shape)])
+        od = (A.rdf_out * k)(*[A.rdf_out(None, None, 0, 0, 0, A.U8, A.MEM_DEVICE) for _ in shape])
+        st = call(oo, od)
+        assert st in (A.RDF_OK, A.RDF_MEMORY_ERROR), so.rdf_last_error()
+        out_bytes = [od[i].length for i in range(k)]
+        dt = [torch.empty(b + 64, dtype=torch.uint8, device="cuda") for b in out_bytes]
+        od = (A.rdf_out * k)(*[A.rdf_out(t.data_ptr(), None, b, 0, 0, A.U8, A.MEM_DEVICE) for t, b in zip(dt, out_bytes)])
+        for _ in range(args.warmup):
+            assert call(oo, od) == A.RDF_OK, so.rdf_last_error()
+        ms = []
+        for _ in range(3):
+            lib.kernel_timing_reset(True)
+            assert call(oo, od) == A.RDF_OK, so.rdf_last_error()
+            ms.append(lib.kernel_timing_get()[0])
+        lib.kernel_timing_reset(False)
+        best = min(ms)
+        moved = 4 * (rows + k) * 2 + in_bytes + sum(out_bytes)
+        rec = {"op": name, "rows": rows, "chunks": k, "in_bytes": in_bytes, "out_bytes": sum(out_bytes), "moved_bytes": moved, "kernel": lib.last_kernel(),
+               "kernel_ms": round(best, 3), "kernel_ms_median": round(float(np.median(ms)), 3), "GBps": round(moved / best / 1e6, 1),
+               "ns_per_out_byte": round(best * 1e6 / max(1, sum(out_bytes)), 4),
+               "copy_probe_GBps": round(copy_gbps, 1), "frac_of_copy": round(moved / best / 1e6 / copy_gbps, 3), "copy_probe_shape": copy_shape}
+        if note:
+            rec["note"] = note
+        emit(rec)
+        del ot, vt, dt
+        return best
+
+    for label, mixed in (("ascii", False), ("mixed", True)):
+        strings = pool(rng, 1 << 20, mixed)
+        for i in range(0, len(strings), 16):
+            strings[i] = "www.apache.org"
+        x, xb = device_column(torch, strings, cr)
+        y, yb = device_column(torch, strings[::-1], cr)
+        xs, ys = [x] * nch, [y] * nch
+        # the same columns with 10 % NULL rows
+        vx = torch.zeros((cr + 63) // 64 * 8 + 8, dtype=torch.uint8, device="cuda")
+        vy = torch.zeros_like(vx)
+        torch.cuda.synchronize()
+        lib.fill_validity(vx.data_ptr(), cr, 7, 0, 0, 0.1)
+        lib.fill_validity(vy.data_ptr(), cr, 7, 1, 0, 0.1)
+        xn = [A.DeviceUtf8(x.offsets_ptr, x.data_ptr, x.data_length, cr, vx.data_ptr(), 0, 0, -1, keep=(x.keep, vx))] * nch
+        yn = [A.DeviceUtf8(y.offsets_ptr, y.data_ptr, y.data_length, cr, vy.data_ptr(), 0, 0, -1, keep=(y.keep, vy))] * nch
+        # today's writer on the same column: rdf_utf8_trim
+        carr = (A.rdf_utf8_array * nch)(*[x.c_struct()] * nch)
+        ot = [torch.empty(cr + 1 + 64, dtype=torch.int32, device="cuda") for _ in range(nch)]
+        dt = [torch.empty(xb + 64, dtype=torch.uint8, device="cuda") for _ in range(nch)]
+        oo = (A.rdf_out * nch)(*[A.rdf_out(t.data_ptr(), None, cr + 1, 0, 0, A.I32, A.MEM_DEVICE) for t in ot])
+        od = (A.rdf_out * nch)(*[A.rdf_out(t.data_ptr(), None, xb, 0, 0, A.U8, A.MEM_DEVICE) for t in dt])
+        tms = []
+        for i in range(args.warmup + 3):
+            lib.kernel_timing_reset(True)
+            assert so.rdf_utf8_trim(carr, C.c_int64(nch), oo, od) == A.RDF_OK, so.rdf_last_error()
+            tms.append(lib.kernel_timing_get()[0])
+        lib.kernel_timing_reset(False)
+        trim_ms = min(tms[args.warmup:])
+        rec = {"op": f"utf8_trim_{label}", "rows": n, "chunks": nch, "in_bytes": xb * nch, "kernel": lib.last_kernel(), "kernel_ms": round(trim_ms, 3)}
+        emit(rec)
+        del ot, dt
+        run(f"concat_x_lit_y_{label}", "concat", None, [xs, ", ", ys], rows=n, in_bytes=(xb + yb) * nch, note="compare with two trims")
+        run(f"concat_ws_10pct_nulls_{label}", "concat_ws", None, [xn, yn], ", ", rows=n, in_bytes=(xb + yb) * nch, note="in_bytes counts the NULL rows' bytes too")
+        run(f"lpad_32_space_{label}", "lpad", xs, 32, " ", rows=n, in_bytes=xb * nch)
+        run(f"repeat_3_{label}", "repeat", xs, 3, rows=n, in_bytes=xb * nch)
+        run(f"reverse_{label}", "reverse", xs, rows=n, in_bytes=xb * nch)
+        run(f"substring_index_dot_2_{label}", "substring_index", xs, ".", 2, rows=n, in_bytes=xb * nch, note="1 row in 16 holds the delimiter twice; the others are searched to their end")
+        run(f"substring_index_space_m1_{label}", "substring_index", xs, " ", -1, rows=n, in_bytes=xb * nch)
+        del x, y, xs, ys, xn, yn, vx, vy
+    # rows of 16 KiB: the copy must cost their bytes, not their count
+    lrows = args.long_rows
+    long_pool = ["".join(rng.choice(list("abcdefghijklmnop "), size=16384)) for _ in range(64)]
+    h = A.HostUtf8.from_pylist(long_pool)
+    pd = torch.from_numpy(h.data[:int(h.offsets[-1])].copy()).cuda()
+    per = 32768          # 2 x 16 KiB x 32768 rows stay below 2^31 bytes a chunk
+    chunks = []
+    for c0 in range(0, lrows, per):
+        k = min(per, lrows - c0)
+        offs = (torch.arange(k + 1, device="cuda", dtype=torch.int64) * 16384).to(torch.int32)
+        data = pd.repeat((k + 63) // 64)[:k * 16384].contiguous()
+        chunks.append(A.DeviceUtf8(offs.data_ptr(), data.data_ptr(), k * 16384, k, None, 0, 0, 0, keep=(offs, data, None)))
+    lb = lrows * 16384
+    torch.cuda.synchronize()          # (the library runs on its own stream: torch's fills must have landed before the sizing call reads the offsets)
+    run("reverse_16KiB_rows", "reverse", chunks, rows=lrows, in_bytes=lb)
+    run("repeat_2_16KiB_rows", "repeat", chunks, 2, rows=lrows, in_bytes=lb)
+    run("lpad_20000_16KiB_rows", "lpad", chunks, 20000, "ab", rows=lrows, in_bytes=lb)
+    run("substring_index_16KiB_rows", "substring_index", chunks, "ab", 100, rows=lrows, in_bytes=lb)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=100_000_000)
@@ -366,7 +480,8 @@ def main():
     ap.add_argument("--sort", action="store_true", help="measure rdf_lexsort_to_indices instead of the other operators")
     ap.add_argument("--sort-rows", type=int, default=10_000_000)
     ap.add_argument("--pred", action="store_true", help="measure rdf_utf8_predicate / _compare / _measure instead (profiles/utf8_pred.jsonl)")
-    ap.add_argument("--long-rows", type=int, default=100_000, help="--pred: rows of 16 KiB for the long-row path")
+    ap.add_argument("--build", action="store_true", help="measure rdf_utf8_concat / _pad / _repeat / _reverse / _substring_index instead (profiles/utf8_build.jsonl)")
+    ap.add_argument("--long-rows", type=int, default=100_000, help="--pred / --build: rows of 16 KiB for the long-row path")
     ap.add_argument("--arrow-rows", type=int, default=10_000_000, help="--pred: rows pyarrow.compute is timed on")
     args = ap.parse_args()
     import torch
@@ -378,6 +493,9 @@ def main():
         return
     if args.pred:
         pred_bench(args, api, torch)
+        return
+    if args.build:
+        build_bench(args, api, torch)
         return
     so = lib.load()
     for n in ("filter", "take", "trim", "lower"):
