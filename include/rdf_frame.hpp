@@ -640,14 +640,22 @@ class Column {
   private:
     // text columns are carried on the host: every chunk as offsets + bytes built from the mirror's strings, in host memory
     struct TextChunks {
-        struct Text { std::vector<int32_t> offs; std::string bytes; std::vector<uint8_t> valid; };
+        struct Text { std::vector<int32_t> offs; std::string bytes; std::vector<uint8_t> valid; std::vector<std::shared_ptr<DeviceBuffer>> dev; };
         std::vector<std::unique_ptr<Text>> keep;
         std::vector<rdf_utf8_array> txt;
         int64_t rows = 0, bytes = 0;
     };
-    TextChunks text_chunks(const char* what) const {
+    // (host = false: the buffers are copied to the device, for calls whose other columns live there)
+    TextChunks text_chunks(const char* what, bool host = true) const {
         using Text = TextChunks::Text;
         TextChunks tc;
+        const int32_t mem = host ? RDF_MEM_HOST : RDF_MEM_DEVICE;
+        auto place = [&](Text& t, const void* src, int64_t bytes) -> const void* {
+            if (host) return src;
+            t.dev.push_back(std::make_shared<DeviceBuffer>(bytes + 8));
+            if (bytes > 0) check(rdf_copy_h2d(t.dev.back()->data(), src, bytes));
+            return t.dev.back()->data();
+        };
         for (auto& a : data_.chunks()) {
             tc.keep.push_back(std::make_unique<Text>());
             Text& t = *tc.keep.back();
@@ -661,12 +669,12 @@ class Column {
             if (a->validity) { t.valid = pack_bits(a->valid_to_host()); t.valid.resize(t.valid.size() + 8, 0); }
             t.bytes.append(8, '\0');
             rdf_utf8_array u;
-            u.offsets.values = t.offs.data();
-            u.offsets.validity = t.valid.empty() ? nullptr : t.valid.data();
-            u.offsets.offset = 0; u.offsets.length = a->length + 1; u.offsets.null_count = -1; u.offsets.dtype = RDF_I32; u.offsets.mem = RDF_MEM_HOST;
-            u.data.values = t.bytes.data();
+            u.offsets.values = place(t, t.offs.data(), (int64_t)t.offs.size() * 4);
+            u.offsets.validity = t.valid.empty() ? nullptr : (const uint8_t*)place(t, t.valid.data(), (int64_t)t.valid.size());
+            u.offsets.offset = 0; u.offsets.length = a->length + 1; u.offsets.null_count = -1; u.offsets.dtype = RDF_I32; u.offsets.mem = mem;
+            u.data.values = place(t, t.bytes.data(), (int64_t)t.bytes.size());
             u.data.validity = nullptr;
-            u.data.offset = 0; u.data.length = (int64_t)t.bytes.size() - 8; u.data.null_count = 0; u.data.dtype = RDF_U8; u.data.mem = RDF_MEM_HOST;
+            u.data.offset = 0; u.data.length = (int64_t)t.bytes.size() - 8; u.data.null_count = 0; u.data.dtype = RDF_U8; u.data.mem = mem;
             tc.txt.push_back(u);
             tc.rows += a->length;
             tc.bytes += u.data.length;
@@ -775,6 +783,76 @@ class Column {
         const TextChunks tc = text_chunks("substring_index");
         return text_build(tc, chunk_nullable(), field_.name, [&](rdf_out* oo, rdf_out* od) {
             return rdf_utf8_substring_index(tc.txt.data(), (int64_t)tc.txt.size(), (const uint8_t*)delim.data(), (int64_t)delim.size(), count, oo, od);
+        });
+    }
+
+    // Row hashes and digests, on the device (rdf_hash_columns / rdf_utf8_digest / rdf_utf8_crc32; Spark 3's semantics, see the
+    // C header).
+    //   hash / xxhash64   Spark's Murmur3_x86_32 / XXH64 over the columns in order with a seed (42 is Spark's), NULLs skipped:
+    //                     an ordinary Int32 / Int64 column that is never NULL, a key for group_aggregate, joins, windows
+    //   md5 / sha1 / sha2(bits) / crc32   of a Utf8 column: lowercase hex text / Int64; a NULL row gives NULL.  sha2 takes
+    //                     bits 0 (= 256), 224, 256, 384, 512 and refuses anything else (Spark returns NULL there)
+    static Column hash_columns(int32_t kind, const std::vector<const Column*>& cols, int64_t seed = 42, const std::string& name = "hash") {
+        if (cols.empty()) throw DataFrameError(DataFrameError::ComputeError, "hash: at least one column");
+        const DataType t = kind == RDF_HASH_XXHASH64 ? DataType::Int64 : DataType::Int32;
+        const size_t nch = cols[0]->data_.num_chunks();
+        // the call runs where the numeric columns are (text is host-carried and copied there); text alone: on the device,
+        // where a frame's numeric columns usually live, so that the result is a key next to them
+        bool host = true, any_numeric = false;
+        for (const Column* c : cols) {
+            if (c->data_.num_chunks() != nch) throw DataFrameError(DataFrameError::ComputeError, "hash: chunk lists differ in length");
+            if (c->data_type() != DataType::Utf8)
+                for (auto& a : c->data_.chunks()) { host &= a->host; any_numeric = true; }
+        }
+        if (!any_numeric) host = false;
+        std::vector<TextChunks> tcs;
+        tcs.reserve(cols.size());
+        std::vector<std::vector<rdf_array>> num(cols.size());
+        std::vector<rdf_sort_key> keys(cols.size());
+        for (size_t k = 0; k < cols.size(); ++k) {
+            keys[k] = rdf_sort_key{nullptr, nullptr, rdf_sort_options{0, 0}};
+            if (cols[k]->data_type() == DataType::Utf8) {
+                tcs.push_back(cols[k]->text_chunks("hash", host));
+                keys[k].utf8 = tcs.back().txt.data();
+            } else {
+                for (auto& a : cols[k]->data_.chunks()) num[k].push_back(a->view());
+                keys[k].values = num[k].data();
+            }
+        }
+        std::vector<std::shared_ptr<Array>> outs;
+        std::vector<rdf_out> ov;
+        for (auto& a : cols[0]->data_.chunks()) {
+            outs.push_back(Array::make_out(t, a->length, false, host));
+            ov.push_back(outs.back()->out_view(a->length));
+        }
+        if (nch > 0) check(rdf_hash_columns(kind, keys.data(), (int32_t)keys.size(), (int64_t)nch, seed, ov.data()));
+        std::vector<ArrayRef> res;
+        for (size_t i = 0; i < outs.size(); ++i) { outs[i]->length = ov[i].length; outs[i]->null_count = 0; res.push_back(outs[i]); }
+        return Column::from_arrays(res, Field{name, t, false});
+    }
+    Column hash(int64_t seed = 42) const { return hash_columns(RDF_HASH_MURMUR3_32, {this}, seed, field_.name); }
+    Column xxhash64(int64_t seed = 42) const { return hash_columns(RDF_HASH_XXHASH64, {this}, seed, field_.name); }
+    Column utf8_digest(int32_t kind, const char* what) const {
+        need_text(what);
+        const TextChunks tc = text_chunks(what);
+        return text_build(tc, chunk_nullable(), field_.name, [&](rdf_out* oo, rdf_out* od) { return rdf_utf8_digest(kind, tc.txt.data(), (int64_t)tc.txt.size(), oo, od); });
+    }
+    Column md5() const { return utf8_digest(RDF_DIGEST_MD5, "md5"); }
+    Column sha1() const { return utf8_digest(RDF_DIGEST_SHA1, "sha1"); }
+    Column sha2(int32_t bits) const {
+        switch (bits) {
+            case 0: case 256: return utf8_digest(RDF_DIGEST_SHA256, "sha2");
+            case 224: return utf8_digest(RDF_DIGEST_SHA224, "sha2");
+            case 384: return utf8_digest(RDF_DIGEST_SHA384, "sha2");
+            case 512: return utf8_digest(RDF_DIGEST_SHA512, "sha2");
+            default: throw DataFrameError(DataFrameError::ComputeError, "sha2: bits must be 0, 224, 256, 384 or 512");
+        }
+    }
+    Column crc32(bool on_host = false) const {
+        need_text("crc32");
+        const TextChunks tc = text_chunks("crc32");
+        return text_result(DataType::Int64, tc, chunk_nullable(), field_.name, on_host, [&](rdf_out* outs) {
+            check(rdf_utf8_crc32(tc.txt.data(), (int64_t)tc.txt.size(), outs));
         });
     }
   private:
@@ -3132,6 +3210,27 @@ struct ScalarFunctions {
     static std::vector<ArrayRef> substring_index(const std::vector<ArrayRef>& arr, const std::string& delim, int64_t count) {
         return text_column(arr, "substring_index").substring_index(delim, count).data().chunks();
     }
+    // hash / xxhash64 / crc32 / md5 / sha1 / sha2 (declared with empty bodies, src/functions/scalar.rs:205, :265, :338, :389, :390):
+    // Spark 3's semantics on the device (rdf_hash_columns / rdf_utf8_crc32 / rdf_utf8_digest).  hash and xxhash64 take the columns
+    // as chunk lists of one chunking, numeric, Boolean or Utf8, and return Int32 / Int64 arrays that are never NULL; the digests
+    // take Utf8 arrays and return Utf8 arrays (lowercase hex), crc32 Int64 arrays; a NULL row gives NULL.
+    static std::vector<ArrayRef> hash_kind(int32_t kind, const std::vector<std::vector<ArrayRef>>& cols, int64_t seed) {
+        std::vector<Column> cs;
+        cs.reserve(cols.size());
+        for (auto& arr : cols) {
+            if (arr.empty()) throw DataFrameError(DataFrameError::ComputeError, "hash: a column without chunks");
+            cs.push_back(Column::from_arrays(arr, Field{"hash", arr[0]->dtype, true}));
+        }
+        std::vector<const Column*> ptrs;
+        for (auto& c : cs) ptrs.push_back(&c);
+        return Column::hash_columns(kind, ptrs, seed).data().chunks();
+    }
+    static std::vector<ArrayRef> hash(const std::vector<std::vector<ArrayRef>>& cols, int64_t seed = 42) { return hash_kind(RDF_HASH_MURMUR3_32, cols, seed); }
+    static std::vector<ArrayRef> xxhash64(const std::vector<std::vector<ArrayRef>>& cols, int64_t seed = 42) { return hash_kind(RDF_HASH_XXHASH64, cols, seed); }
+    static std::vector<ArrayRef> crc32(const std::vector<ArrayRef>& arr) { return text_column(arr, "crc32").crc32().data().chunks(); }
+    static std::vector<ArrayRef> md5(const std::vector<ArrayRef>& arr) { return text_column(arr, "md5").md5().data().chunks(); }
+    static std::vector<ArrayRef> sha1(const std::vector<ArrayRef>& arr) { return text_column(arr, "sha1").sha1().data().chunks(); }
+    static std::vector<ArrayRef> sha2(const std::vector<ArrayRef>& arr, int32_t bits) { return text_column(arr, "sha2").sha2(bits).data().chunks(); }
     // The calendar functions src/functions/scalar.rs declares with empty bodies (year .. date_diff): Spark 3's semantics as
     // written down at rdf_datetime_fields in rdf_mi355x.h.  Like hour, a temporal column is its Int32 / Int64 storage + time unit.
     // datetime_fields reads the column ONCE for up to 8 fields and returns one chunk list per field, in the order asked for.

@@ -624,6 +624,49 @@ typedef struct {
 } rdf_sort_key;
 rdf_status rdf_lexsort_to_indices(const rdf_sort_key* keys, int32_t nkeys, int64_t nchunks, rdf_out* out_indices);
 
+/* ------------------------------------------------------------------ row hashes and digests */
+
+/* hash, xxhash64, crc32, md5, sha1 and sha2 per row.  The reference declares hash, crc32, md5, sha1 and sha2 with empty
+ * bodies (src/functions/scalar.rs:205, :265, :338, :389, :390), so these follow Spark 3; the executable model is
+ * tests/digest_ref.py.  Inputs follow the rdf_utf8_array conventions exactly as rdf_utf8_trim takes them (row `offset`,
+ * value offsets that need not start at 0, validity at any bit offset, host or device memory, all one kind).
+ *   rdf_hash_columns   Spark's hash (RDF_HASH_MURMUR3_32: Murmur3_x86_32, out[i] RDF_I32, the seed must fit Int32) or
+ *              xxhash64 (RDF_HASH_XXHASH64, out[i] RDF_I64) over 1 .. RDF_HASH_COLS_MAX columns; Spark's default seed is 42.
+ *              cols[k] sets exactly one of values (nchunks numeric or RDF_BOOL chunks of one dtype) / utf8, as for
+ *              rdf_groupby_agg_keys; `options` is ignored.  h = seed; for each column in order, a row that is not NULL in it
+ *              gives h = H(value, h), a NULL leaves h unchanged.  Bool hashes as hashInt(1 / 0); I8 / I16 / I32 as hashInt
+ *              of the sign-extended value; U8 / U16 as hashInt of the zero-extended value and U32 as hashInt of its bits
+ *              (Spark has no unsigned types: this defines them); I64 / U64 as hashLong of the bits; F32 / F64 as hashInt /
+ *              hashLong of the bits with every NaN taken as the canonical quiet NaN and -0.0 as +0.0; Utf8 as
+ *              hashUnsafeBytes (Murmur3's tail is Spark's: every byte after the 4-byte words alone, as a SIGNED byte).
+ *              Temporal columns hash as their Int32 / Int64 storage.  out[i] has the rows of chunk i; the result is never
+ *              NULL: a validity buffer, if given, is written all ones and null_count is 0.  The results are ordinary keys
+ *              for rdf_groupby_agg, rdf_uniques, rdf_window and rdf_equijoin_indices.
+ *   rdf_utf8_digest    md5 / sha1 / sha2 of every row as lowercase hex text of 32 / 40 / 56 / 64 / 96 / 128 bytes; a NULL
+ *              row gives NULL with zero bytes.  Outputs are chunked like the input under the one sizing rule of
+ *              rdf_utf8_filter .. _upper: out_data[i].length = non-NULL rows x width (values == NULL, capacity == 0 is the
+ *              sizing call; a capacity that is too small gives RDF_MEMORY_ERROR with every length set and nothing written;
+ *              an output chunk beyond 2^31-1 bytes is RDF_COMPUTE_ERROR).  out_offsets[i].validity is required when chunk i
+ *              has one.  Spark's sha2(col, bits) maps bits 0 and 256 to RDF_DIGEST_SHA256; any other value of `kind` is an
+ *              error here where Spark returns NULL.
+ *   rdf_utf8_crc32     zlib's CRC-32 of every row as RDF_I64 in 0 .. 2^32-1, under rdf_utf8_measure's output rules: length
+ *              == rows, a NULL row gives NULL (value 0), validity required when the chunk has one, null_count set.
+ * Errors, all before any device work, in this order: (1) an unknown kind; (2) ncols outside 1 .. RDF_HASH_COLS_MAX, or a
+ * column that sets both pointers or neither; (3) a Murmur3 seed outside Int32; (4) wrong dtypes, mixed memory kinds, a
+ * missing validity buffer: all RDF_INVALID_ARGUMENT; (5) chunk row counts that differ between columns: RDF_COMPUTE_ERROR;
+ * (6) a capacity below the rows (rdf_utf8_digest: offsets below rows + 1): RDF_MEMORY_ERROR with `length` set; (7) no
+ * device: RDF_DEVICE_ERROR.  The data capacity of rdf_utf8_digest is judged after the count, on the device.
+ * nchunks == 0 is RDF_OK. */
+typedef enum { RDF_HASH_MURMUR3_32 = 0, RDF_HASH_XXHASH64 = 1 } rdf_hash_kind;
+typedef enum { RDF_DIGEST_MD5 = 0, RDF_DIGEST_SHA1, RDF_DIGEST_SHA224, RDF_DIGEST_SHA256,
+               RDF_DIGEST_SHA384, RDF_DIGEST_SHA512 } rdf_digest_kind;
+#define RDF_HASH_COLS_MAX 8
+rdf_status rdf_hash_columns(int32_t kind, const rdf_sort_key* cols, int32_t ncols, int64_t nchunks,
+                            int64_t seed, rdf_out* out);
+rdf_status rdf_utf8_digest(int32_t kind, const rdf_utf8_array* chunks, int64_t nchunks,
+                           rdf_out* out_offsets, rdf_out* out_data);
+rdf_status rdf_utf8_crc32(const rdf_utf8_array* chunks, int64_t nchunks, rdf_out* out);
+
 /* ------------------------------------------------------------------ Column::hist / Column::uniques */
 
 /* Column::hist (src/table.rs:244-290): the histogram of an Int64 or Float64 column over `nbins` equal-width buckets.  The

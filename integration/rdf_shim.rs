@@ -262,6 +262,12 @@ pub mod sys {
         pub fn rdf_utf8_reverse(chunks: *const rdf_utf8_array, nchunks: i64, out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
         pub fn rdf_utf8_substring_index(chunks: *const rdf_utf8_array, nchunks: i64, delim: *const u8, delim_bytes: i64, count: i64,
                                         out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
+        // row hashes and digests (src/functions/scalar.rs: hash :265, crc32 :205, md5 :338, sha1 :389, sha2 :390): kind 0 = Spark's
+        // Murmur3_x86_32 (Int32 out, seed 42 by default), 1 = xxhash64 (Int64 out); digests 0 .. 5 = md5, sha1, sha224, sha256, sha384,
+        // sha512 as lowercase hex text under the sizing rule of rdf_utf8_trim; crc32 as Int64
+        pub fn rdf_hash_columns(kind: i32, cols: *const rdf_sort_key, ncols: i32, nchunks: i64, seed: i64, out: *mut rdf_out) -> i32;
+        pub fn rdf_utf8_digest(kind: i32, chunks: *const rdf_utf8_array, nchunks: i64, out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
+        pub fn rdf_utf8_crc32(chunks: *const rdf_utf8_array, nchunks: i64, out: *mut rdf_out) -> i32;
         // the fused batch loop (src/evaluation.rs:66-96); host-resident frames above one slab are streamed (rdf_stream_stats says how)
         pub fn rdf_jit_status() -> *const c_char;          // the run-time compiler: found or not, cache directory, counts
         pub fn rdf_stream_stats(slabs: *mut i64, bytes_staged: *mut i64, bytes_direct: *mut i64) -> i32;

@@ -534,6 +534,11 @@ UTF8_PRED_OPS = {"eq": 0, "ne": 1, "lt": 2, "le": 3, "gt": 4, "ge": 5, "starts_w
 UTF8_MEASURE_OPS = {"length": 0, "octet_length": 1, "locate": 2}
 UTF8_PATTERN_MAX = 1024
 UTF8_PARTS_MAX = 8
+# rdf_hash_kind / rdf_digest_kind
+HASH_KINDS = {"hash": 0, "murmur3": 0, "xxhash64": 1}
+DIGEST_KINDS = {"md5": 0, "sha1": 1, "sha224": 2, "sha256": 3, "sha384": 4, "sha512": 5}
+DIGEST_HEX_BYTES = (32, 40, 56, 64, 96, 128)
+HASH_COLS_MAX = 8
 
 
 class Expr:
@@ -1530,6 +1535,44 @@ class Api:
     def utf8_concat(self, parts: Sequence, sep=None, as_arrow=False):
         """concat (sep is None) / concat_ws of chunk lists and str / bytes literals."""
         return self.utf8_build("concat", None, parts, as_arrow=as_arrow) if sep is None else self.utf8_build("concat_ws", None, parts, sep, as_arrow=as_arrow)
+
+    # ---- row hashes and digests (rdf_hash_columns / rdf_utf8_digest / rdf_utf8_crc32)
+    def hash_columns(self, kind, cols: Sequence[Sequence], seed: int = 42, outs=None):
+        """rdf_hash_columns: Spark's hash ("hash" / "murmur3") or "xxhash64" over 1..8 columns, each a list of numeric /
+        Boolean or Utf8 chunks -> one Int32 / Int64 array per chunk, never NULL."""
+        code = HASH_KINDS[kind] if isinstance(kind, str) else int(kind)
+        ck, keep = self._sort_keys([list(c) for c in cols])
+        shape = cols[0] if len(cols) else []
+        n = len(shape)
+        if outs is None:
+            device = any(isinstance(c, (DeviceArray, DeviceUtf8)) for c in shape)
+            outs = [self._window_out(I64 if code == 1 else I32, c.length, device, False) for c in shape]
+        co = (rdf_out * max(1, len(outs)))(*[o.out_struct() for o in outs])
+        self._check(self._utf8_fn("hash_columns")(C.c_int32(code), ck, C.c_int32(len(cols)), C.c_int64(n), C.c_int64(int(seed)), co))
+        return self._finish(outs, co)
+
+    def utf8_crc32(self, chunks: Sequence, outs=None):
+        """rdf_utf8_crc32: zlib's CRC-32 of every row -> one Int64 array per chunk."""
+        n = len(chunks)
+        carr = (rdf_utf8_array * max(1, n))(*[c.c_struct() for c in chunks])
+        outs, co = self._utf8_pred_outs(I64, chunks, [self._utf8_nullable(c) for c in chunks], outs)
+        self._check(self._utf8_fn("utf8_crc32")(carr, C.c_int64(n), co))
+        return self._finish(outs, co)
+
+    def utf8_digest_call(self, kind, chunks: Sequence):
+        """-> (call(out_offsets, out_data) -> status, chunks, nullable per chunk) of one rdf_utf8_digest call; utf8_digest runs
+        it under the sizing rule, tests call it with buffers of their own."""
+        code = DIGEST_KINDS[kind] if isinstance(kind, str) else int(kind)
+        n = len(chunks)
+        carr = (rdf_utf8_array * max(1, n))(*[c.c_struct() for c in chunks])
+        fn = self._utf8_fn("utf8_digest")
+        call = lambda co, cd: fn(C.c_int32(code), carr, C.c_int64(n), co, cd)  # noqa: E731
+        return call, chunks, [self._utf8_nullable(c) for c in chunks]
+
+    def utf8_digest(self, kind, chunks: Sequence, as_arrow=False):
+        """md5 / sha1 / sha224 / sha256 / sha384 / sha512 of every row as lowercase hex text: one result per chunk."""
+        call, shape, nullable = self.utf8_digest_call(kind, chunks)
+        return self._utf8_run(call, shape, [c.length for c in shape], nullable, as_arrow)
 
     # ---- Column::hist / Column::uniques (bound lazily: only the product has them)
     @staticmethod

@@ -37,6 +37,8 @@
 #include "rdf_datetime.h"
 #include "rdf_utf8_pattern.h"
 #include "rdf_utf8_build.h"
+#include "rdf_digest.h"
+#include "rdf_digest_kernels.h"
 
 using namespace rdfk;
 
@@ -2873,6 +2875,7 @@ rdf_status groupby_sum_fallback(const rdf_array* keys, const rdf_array* values, 
 #include "rdf_capi_datetime.inc"
 #include "rdf_capi_utf8_pred.inc"
 #include "rdf_capi_utf8_build.inc"
+#include "rdf_capi_digest.inc"
 
 extern "C" {
 

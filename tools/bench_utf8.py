@@ -20,6 +20,7 @@ host.  The rounds each sort took come from rdf_last_kernel.
     python tools/bench_utf8.py --sort [--sort-rows 10000000] [--reps 3] [--out FILE]
     python tools/bench_utf8.py --pred [--rows 100000000] [--long-rows 100000] [--out profiles/utf8_pred.jsonl]
     python tools/bench_utf8.py --build [--rows 100000000] [--long-rows 100000] [--out profiles/utf8_build.jsonl]
+    python tools/bench_utf8.py --digest [--rows 100000000] [--long-rows 100000] [--out profiles/digest_bench.jsonl]
 """
 import argparse
 import ctypes as C
@@ -470,6 +471,129 @@ def build_bench(args, api, torch):
     run("substring_index_16KiB_rows", "substring_index", chunks, "ab", 100, rows=lrows, in_bytes=lb)
 
 
+def digest_bench(args, api, torch):
+    """--digest: rdf_hash_columns / rdf_utf8_digest / rdf_utf8_crc32 on device-resident rows.  Per case: the HIP-event kernel
+    time (best of --reps after warm-up; for the digests the count pass, the scan and the write pass of the call into buffers
+    sized beforehand), the bytes the function must read (Int32 offsets + the rows' bytes) and their rate as a fraction of
+    rdf_probe_stream's READ rate in the same process, next to rdf_utf8_measure(LENGTH) on the same column as the reader's
+    floor.  Then rdf_hash_columns over an Int64 column and over (Int64, Utf8), rows of 16 KiB, a skewed column (1 % of the
+    rows 16 KiB, the rest short: a lane per row, the only form there is) and hashlib / zlib on one host thread."""
+    import hashlib
+    import time
+    import zlib
+    rng = np.random.default_rng(31)
+    n, nch = args.rows, max(args.chunks, 8)      # 8 chunks: 12.5 M rows x 128 hex bytes stay below 2^31 bytes a chunk
+    assert n % nch == 0
+    cr = n // nch
+    pb = 1 << 31
+    probe = torch.empty(pb, dtype=torch.uint8, device="cuda")
+    read_gbps, read_shape = lib.probe_stream(0, probe.data_ptr(), 0, 0, pb, 10)
+    del probe
+    lines = []
+
+    def run(name, call, rows, data_bytes, chunks, floor_ms=None, extra_in=0):
+        for _ in range(args.warmup):
+            call()
+        ms = []
+        for _ in range(args.reps):
+            lib.kernel_timing_reset(True)
+            call()
+            ms.append(lib.kernel_timing_get()[0])
+        lib.kernel_timing_reset(False)
+        read = 4 * (rows + chunks) + data_bytes + extra_in
+        best = min(ms)
+        rec = {"op": name, "rows": rows, "chunks": chunks, "bytes_read": read, "kernel": lib.last_kernel(), "kernel_ms": round(best, 3),
+               "kernel_ms_median": round(float(np.median(ms)), 3), "read_GBps": round(read / best / 1e6, 1), "read_probe_GBps": round(read_gbps, 1),
+               "frac_of_read": round(read / best / 1e6 / read_gbps, 4), "read_probe_shape": read_shape}
+        if floor_ms is not None:
+            rec["length_floor_ms"] = round(floor_ms, 3)
+        print(json.dumps(rec), flush=True)
+        lines.append(rec)
+        return best
+
+    def digest_call(fn, cols, rows_per_chunk):
+        width = A.DIGEST_HEX_BYTES[A.DIGEST_KINDS[fn]]
+        ot = [torch.empty(r + 1 + 64, dtype=torch.int32, device="cuda") for r in rows_per_chunk]
+        dt = [torch.empty(r * width + 64, dtype=torch.uint8, device="cuda") for r in rows_per_chunk]
+        oo = (A.rdf_out * len(cols))(*[A.rdf_out(t.data_ptr(), None, r + 1, 0, 0, A.I32, A.MEM_DEVICE) for t, r in zip(ot, rows_per_chunk)])
+        od = (A.rdf_out * len(cols))(*[A.rdf_out(t.data_ptr(), None, r * width, 0, 0, A.U8, A.MEM_DEVICE) for t, r in zip(dt, rows_per_chunk)])
+        call, _, _ = api.utf8_digest_call(fn, cols)
+
+        def go(keep=(ot, dt)):
+            st = call(oo, od)
+            assert st == A.RDF_OK, st
+        return go
+
+    def all_functions(label, cols, rows_per_chunk, data_bytes, digests=A.DIGEST_KINDS):
+        rows, k = sum(rows_per_chunk), len(cols)
+        io32 = [api._window_out(A.I32, r, True, False) for r in rows_per_chunk]
+        io64 = [api._window_out(A.I64, r, True, False) for r in rows_per_chunk]
+        floor = run(f"length_{label}", lambda: api.utf8_measure("length", cols, outs=io32), rows, data_bytes, k)
+        for fn in digests:
+            run(f"{fn}_{label}", digest_call(fn, cols, rows_per_chunk), rows, data_bytes, k, floor)
+            torch.cuda.empty_cache()
+        run(f"crc32_{label}", lambda: api.utf8_crc32(cols, outs=io64), rows, data_bytes, k, floor)
+        run(f"hash_{label}", lambda: api.hash_columns("hash", [cols], outs=io32), rows, data_bytes, k, floor)
+        run(f"xxhash64_{label}", lambda: api.hash_columns("xxhash64", [cols], outs=io64), rows, data_bytes, k, floor)
+        return io32, io64, floor
+
+    for label, mixed in (("ascii", False), ("mixed", True)):
+        strings = pool(rng, 1 << 20, mixed)
+        col, nbytes = device_column(torch, strings, cr)
+        cols = [col] * nch
+        io32, io64, floor = all_functions(label, cols, [cr] * nch, nbytes * nch)
+        if not mixed:
+            ints = torch.randint(-2**62, 2**62, (cr,), dtype=torch.int64, device="cuda")
+            icols = [A.DeviceArray(ints.data_ptr(), None, 0, cr, A.I64, 0, keep=ints)] * nch
+            for fn, outs in (("hash", io32), ("xxhash64", io64)):
+                run(f"{fn}_int64_column", lambda: api.hash_columns(fn, [icols], outs=outs), n, 0, nch, extra_in=8 * n - 4 * (n + nch))
+                run(f"{fn}_int64_and_utf8_{label}", lambda: api.hash_columns(fn, [icols, cols], outs=outs), n, nbytes * nch, nch, floor, extra_in=8 * n)
+            del ints, icols
+        # hashlib / zlib on one host thread over the pool (2^20 rows), for scale
+        raw_rows = [x.encode() for x in strings]
+        for name, f in (("md5", lambda b: hashlib.md5(b).hexdigest()), ("sha1", lambda b: hashlib.sha1(b).hexdigest()),
+                        ("sha256", lambda b: hashlib.sha256(b).hexdigest()), ("sha512", lambda b: hashlib.sha512(b).hexdigest()), ("crc32", zlib.crc32)):
+            t0 = time.perf_counter()
+            for b in raw_rows:
+                f(b)
+            rec = {"op": f"host_{name}_{label}", "rows": len(raw_rows), "host_ms": round((time.perf_counter() - t0) * 1e3, 1), "threads": 1}
+            print(json.dumps(rec), flush=True)
+            lines.append(rec)
+        del col, cols, io32, io64
+        torch.cuda.empty_cache()
+
+    # rows of 16 KiB
+    lrows = args.long_rows
+    long_pool = ["".join(rng.choice(list("abcdefghijklmnop "), size=16384)) for _ in range(64)]
+    h = A.HostUtf8.from_pylist(long_pool)
+    pd = torch.from_numpy(h.data[:int(h.offsets[-1])].copy()).cuda()
+    per = min(lrows, (2**31 - 1) // 16384 // 64 * 64)
+    chunks = []
+    for c0 in range(0, lrows, per):
+        k = min(per, lrows - c0)
+        offs = (torch.arange(k + 1, device="cuda", dtype=torch.int64) * 16384).to(torch.int32)
+        data = pd.repeat((k + 63) // 64)[:k * 16384].contiguous()
+        chunks.append(A.DeviceUtf8(offs.data_ptr(), data.data_ptr(), k * 16384, k, None, 0, 0, 0, keep=(offs, data, None)))
+    all_functions("16KiB_rows", chunks, [c.length for c in chunks], lrows * 16384, digests=("md5", "sha1", "sha256", "sha512"))
+    del chunks
+
+    # the skewed column: 1 % of the rows 16 KiB, the rest 12 .. 36 bytes, one chunk
+    srows = 4_000_000
+    lens = torch.randint(12, 37, (srows,), dtype=torch.int64, device="cuda")
+    lens[::100] = 16384
+    offs64 = torch.cat([torch.zeros(1, dtype=torch.int64, device="cuda"), torch.cumsum(lens, 0)])
+    total = int(offs64[-1].item())
+    assert total < 2**31
+    data = torch.randint(97, 123, (total,), dtype=torch.uint8, device="cuda")
+    offs = offs64.to(torch.int32)
+    skew = [A.DeviceUtf8(offs.data_ptr(), data.data_ptr(), total, srows, None, 0, 0, 0, keep=(offs, data, None))]
+    all_functions("skewed_1pct_16KiB", skew, [srows], total, digests=("md5", "sha256"))
+    if args.out:
+        with open(args.out, "a") as f:
+            for r in lines:
+                f.write(json.dumps(r) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=100_000_000)
@@ -481,7 +605,8 @@ def main():
     ap.add_argument("--sort-rows", type=int, default=10_000_000)
     ap.add_argument("--pred", action="store_true", help="measure rdf_utf8_predicate / _compare / _measure instead (profiles/utf8_pred.jsonl)")
     ap.add_argument("--build", action="store_true", help="measure rdf_utf8_concat / _pad / _repeat / _reverse / _substring_index instead (profiles/utf8_build.jsonl)")
-    ap.add_argument("--long-rows", type=int, default=100_000, help="--pred / --build: rows of 16 KiB for the long-row path")
+    ap.add_argument("--digest", action="store_true", help="measure rdf_hash_columns / rdf_utf8_digest / rdf_utf8_crc32 instead (profiles/digest_bench.jsonl)")
+    ap.add_argument("--long-rows", type=int, default=100_000, help="--pred / --build / --digest: rows of 16 KiB for the long-row path")
     ap.add_argument("--arrow-rows", type=int, default=10_000_000, help="--pred: rows pyarrow.compute is timed on")
     args = ap.parse_args()
     import torch
@@ -496,6 +621,9 @@ def main():
         return
     if args.build:
         build_bench(args, api, torch)
+        return
+    if args.digest:
+        digest_bench(args, api, torch)
         return
     so = lib.load()
     for n in ("filter", "take", "trim", "lower"):
