@@ -460,6 +460,7 @@ struct GenericVector {
 // ------------------------------------------------------------------------------------------------
 // Column (src/table.rs:134-344)
 
+struct Scalar;   // (Column::fill_null takes one; defined below)
 class Column {
   public:
     Column() = default;
@@ -492,6 +493,83 @@ class Column {
         return Column(data_.slice(offset, length), field_);
     }
     Column filter(const Column& condition) const { return Column(data_.filter(condition.data()), field_); }  // :213-215
+    // The conditional and NULL functions (rdf_coalesce .. rdf_null_test and, for Utf8 columns, rdf_utf8_coalesce /
+    // rdf_utf8_case_when; defined below ScalarFunctions, which the numeric ones go through).  A literal is converted to the
+    // column's type; a text column takes a Scalar::String.
+    inline Column coalesce(const Column& other) const;          // this where it is not NULL, else other
+    inline Column fill_null(const Scalar& value) const;         // coalesce(this, value)
+    inline Column greatest(const Column& other) const;          // Spark's ordering: NaN above every number, NULLs skipped
+    inline Column least(const Column& other) const;
+    inline Column nanvl(const Column& other) const;             // Float32 / Float64: this unless it is NaN, then other
+    inline Column is_null() const;                              // Boolean, never NULL; Utf8 columns by their rows' bitmap
+    inline Column is_not_null() const;
+    inline Column is_nan() const;
+    // coalesce / CASE WHEN over text (rdf_utf8_coalesce / rdf_utf8_case_when), staged as concat stages its parts: a value is a
+    // Utf8 column, a literal or the NULL literal; conds are Boolean columns of the same chunking (none: coalesce); `otherwise`
+    // may be nullptr (NULL).  The result is an ordinary Utf8 column: a key for group_aggregate, joins and sort.
+    struct TextValue {
+        const Column* column = nullptr;
+        std::string literal;
+        bool null = false;
+        TextValue(const Column& c) : column(&c) {}
+        TextValue(std::string s) : literal(std::move(s)) {}
+        TextValue(const char* s) : literal(s) {}
+        static TextValue null_literal() { TextValue v(""); v.null = true; return v; }
+    };
+    static Column text_select(const std::vector<const Column*>& conds, const std::vector<TextValue>& values, const TextValue* otherwise, const std::string& name) {
+        const bool cw = !conds.empty();
+        const char* what = cw ? "when" : "coalesce";
+        if (cw && conds.size() != values.size()) throw DataFrameError(DataFrameError::ComputeError, "when: one value per condition");
+        std::vector<const TextValue*> slots;
+        for (auto& v : values) slots.push_back(&v);
+        if (otherwise) slots.push_back(otherwise);
+        std::vector<TextChunks> tcs;
+        tcs.reserve(slots.size());
+        std::vector<rdf_utf8_part> cp;
+        const Column* first = nullptr;
+        for (auto* v : slots) {
+            if (!v->column) { cp.push_back(rdf_utf8_part{nullptr, v->null ? nullptr : (const uint8_t*)v->literal.data(), v->null ? 0 : (int64_t)v->literal.size()}); continue; }
+            v->column->need_text(what);
+            if (!first) first = v->column;
+            if (v->column->data_.num_chunks() != first->data_.num_chunks()) throw DataFrameError(DataFrameError::ComputeError, std::string(what) + ": chunk lists differ in length");
+            tcs.push_back(v->column->text_chunks(what));
+            cp.push_back(rdf_utf8_part{tcs.back().txt.data(), nullptr, 0});
+        }
+        if (!first) throw DataFrameError(DataFrameError::ComputeError, std::string(what) + ": at least one part must be a column");
+        const size_t n = first->data_.num_chunks();
+        // the conditions, on the host like the text: values and validity as bitmaps at offset 0
+        std::vector<std::vector<uint8_t>> bits;
+        std::vector<std::vector<rdf_array>> cviews(conds.size());
+        bits.reserve(conds.size() * n * 2);
+        for (size_t k = 0; k < conds.size(); ++k) {
+            if (conds[k]->data_type() != DataType::Boolean) throw DataFrameError(DataFrameError::ComputeError, "when: a condition is a Boolean column");
+            if (conds[k]->data_.num_chunks() != n) throw DataFrameError(DataFrameError::ComputeError, "when: chunk lists differ in length");
+            for (auto& a : conds[k]->data_.chunks()) {
+                bits.push_back(pack_bits(a->bools_to_host()));
+                const uint8_t* vals = bits.back().data();
+                const uint8_t* valid = nullptr;
+                if (a->validity) { bits.push_back(pack_bits(a->valid_to_host())); valid = bits.back().data(); }
+                cviews[k].push_back(rdf_array{vals, valid, 0, a->length, -1, RDF_BOOL, RDF_MEM_HOST});
+            }
+        }
+        std::vector<const rdf_array*> cptr;
+        for (auto& v : cviews) cptr.push_back(v.data());
+        std::vector<bool> nullable(n, false);
+        for (size_t i = 0; i < n; ++i) {
+            bool any = cw && !otherwise, all = true;
+            for (auto* v : slots) {
+                const bool nl = v->column ? v->column->data_.chunk(i)->validity != nullptr : v->null;
+                any = any || nl;
+                all = all && nl;
+            }
+            nullable[i] = cw ? any : all;
+        }
+        const size_t nv = values.size();
+        return text_build(tcs[0], nullable, name, [&](rdf_out* oo, rdf_out* od) {
+            if (!cw) return rdf_utf8_coalesce(cp.data(), (int32_t)nv, (int64_t)n, oo, od);
+            return rdf_utf8_case_when(cptr.data(), cp.data(), (int32_t)nv, otherwise ? &cp[nv] : nullptr, (int64_t)n, oo, od);
+        });
+    }
     Column renamed(const std::string& n) const { Column c = *this; c.field_.name = n; return c; }
 
     // src/table.rs:218-241: gather over the concatenation of the chunks; the result is ONE chunk whatever
@@ -856,6 +934,7 @@ class Column {
         });
     }
   private:
+    inline Column text_null_test(int32_t op) const;
     std::vector<bool> chunk_nullable() const {
         std::vector<bool> nullable;
         for (auto& a : data_.chunks()) nullable.push_back(a->validity != nullptr);
@@ -3325,7 +3404,133 @@ struct ScalarFunctions {
     static std::vector<ArrayRef> csc(const std::vector<ArrayRef>& a) { return unary(RDF_OP_CSC, a); }
     static std::vector<ArrayRef> acos(const std::vector<ArrayRef>& a) { return unary(RDF_OP_ACOS, a); }
 
+    // coalesce / greatest / least / nanv1 / when, which src/functions/scalar.rs declares with empty bodies, and is_null /
+    // is_not_null / isnan as masks: Spark 3's semantics as written down at rdf_coalesce in rdf_mi355x.h.  A Value is a column's
+    // chunks or a Scalar literal (Scalar() is the NULL literal), converted to the dtype of the call's first column.
+    struct Value {
+        std::vector<ArrayRef> column;
+        Scalar literal;
+        bool is_column;
+        Value(std::vector<ArrayRef> c) : column(std::move(c)), is_column(true) {}
+        Value(Scalar s) : literal(std::move(s)), is_column(false) {}
+    };
+    static std::vector<ArrayRef> coalesce(const std::vector<Value>& parts) { return select_call(0, parts, {}, nullptr, false); }
+    static std::vector<ArrayRef> greatest(const std::vector<Value>& parts) { return select_call(2, parts, {}, nullptr, true); }
+    static std::vector<ArrayRef> least(const std::vector<Value>& parts) { return select_call(2, parts, {}, nullptr, false); }
+    static std::vector<ArrayRef> nanvl(const Value& a, const Value& b) { return select_call(3, {a, b}, {}, nullptr, false); }
+    // when(c0, v0).when(c1, v1).otherwise(v): the first condition that is valid AND true chooses; end(): no otherwise, NULL
+    struct When {
+        std::vector<std::vector<ArrayRef>> conds;
+        std::vector<Value> values;
+        When& when(std::vector<ArrayRef> cond, Value value) { conds.push_back(std::move(cond)); values.push_back(std::move(value)); return *this; }
+        std::vector<ArrayRef> otherwise(const Value& value) const { return select_call(1, values, conds, &value, false); }
+        std::vector<ArrayRef> end() const { return select_call(1, values, conds, nullptr, false); }
+    };
+    static When when(std::vector<ArrayRef> cond, Value value) { When w; w.when(std::move(cond), std::move(value)); return w; }
+    static std::vector<ArrayRef> null_test(rdf_null_test_op op, const std::vector<ArrayRef>& arr) {
+        if (!arr.empty() && arr[0]->dtype == DataType::Utf8) {   // a text column: the rows' bitmap
+            const Column c = text_column(arr, "is_null");
+            return (op == RDF_IS_NULL ? c.is_null() : op == RDF_IS_NOT_NULL ? c.is_not_null() : c.is_nan()).data().chunks();
+        }
+        std::vector<rdf_array> a;
+        std::vector<std::shared_ptr<Array>> outs;
+        std::vector<rdf_out> ov;
+        for (auto& x : arr) { a.push_back(x->view()); outs.push_back(Array::make_out(DataType::Boolean, x->length, false, x->host)); ov.push_back(outs.back()->out_view(x->length)); }
+        check(rdf_null_test((int32_t)op, a.data(), (int64_t)a.size(), ov.data()));
+        return finish(outs, ov);
+    }
+    static std::vector<ArrayRef> is_null(const std::vector<ArrayRef>& a) { return null_test(RDF_IS_NULL, a); }
+    static std::vector<ArrayRef> is_not_null(const std::vector<ArrayRef>& a) { return null_test(RDF_IS_NOT_NULL, a); }
+    static std::vector<ArrayRef> is_nan(const std::vector<ArrayRef>& a) { return null_test(RDF_IS_NAN, a); }
+
   private:
+    static uint64_t literal_bits(const Scalar& s, DataType dt) {
+        const bool fl = s.kind == Scalar::Float32 || s.kind == Scalar::Float64;
+        if (!fl && s.kind != Scalar::Int32 && s.kind != Scalar::Int64) throw DataFrameError(DataFrameError::ComputeError, "a literal of these functions is a number or NULL");
+        uint64_t bits = 0;
+        if (dt == DataType::Float64) { const double d = fl ? s.f : (double)s.i; std::memcpy(&bits, &d, 8); }
+        else if (dt == DataType::Float32) { const float f = fl ? (float)s.f : (float)s.i; std::memcpy(&bits, &f, 4); }
+        else bits = (uint64_t)(fl ? (int64_t)s.f : s.i);            // (the library keeps the low bytes of the call's dtype)
+        return bits;
+    }
+    // coalesce / when over Utf8 chunk lists: columns staged as concat stages them, Scalar::String literals, Scalar() = NULL
+    static std::vector<ArrayRef> text_select_call(int kind, const std::vector<const Value*>& slots, size_t nvalues, const std::vector<std::vector<ArrayRef>>& conds, bool has_otherwise) {
+        if (kind > 1) throw DataFrameError(DataFrameError::ComputeError, "greatest / least / nanvl do not support type Utf8");
+        const char* what = kind ? "when" : "coalesce";
+        std::vector<Column> cols, ccols;
+        cols.reserve(slots.size());
+        ccols.reserve(conds.size());
+        for (auto* v : slots)
+            if (v->is_column) cols.push_back(text_column(v->column, what));
+        for (auto& c : conds) {
+            for (auto& x : c)
+                if (x->dtype != DataType::Boolean) throw DataFrameError(DataFrameError::ComputeError, "when: a condition is a Boolean column");
+            ccols.push_back(Column::from_arrays(c, Field{"when", DataType::Boolean, true}));
+        }
+        std::vector<Column::TextValue> tv;
+        size_t k = 0;
+        for (auto* v : slots) {
+            if (v->is_column) tv.emplace_back(cols[k++]);
+            else if (v->literal.kind == Scalar::Null) tv.push_back(Column::TextValue::null_literal());
+            else if (v->literal.kind == Scalar::String) tv.emplace_back(v->literal.s);
+            else throw DataFrameError(DataFrameError::ComputeError, std::string(what) + ": a literal for a Utf8 column is a Scalar::String or NULL");
+        }
+        std::vector<const Column*> cp;
+        for (auto& c : ccols) cp.push_back(&c);
+        const std::vector<Column::TextValue> values(tv.begin(), tv.begin() + (std::ptrdiff_t)nvalues);
+        return Column::text_select(cp, values, has_otherwise ? &tv[nvalues] : nullptr, what).data().chunks();
+    }
+    // kind: 0 coalesce, 1 case_when (values + conds + otherwise), 2 extremum, 3 nanvl
+    static std::vector<ArrayRef> select_call(int kind, const std::vector<Value>& values, const std::vector<std::vector<ArrayRef>>& conds, const Value* otherwise, bool greatest) {
+        std::vector<const Value*> slots;
+        for (auto& v : values) slots.push_back(&v);
+        if (otherwise) slots.push_back(otherwise);
+        const std::vector<ArrayRef>* first = nullptr;
+        for (auto* v : slots) if (v->is_column && !first) first = &v->column;
+        if (!first) throw DataFrameError(DataFrameError::ComputeError, "at least one part must be a column");
+        const size_t n = first->size();
+        const DataType dt = n ? (*first)[0]->dtype : DataType::Float64;
+        if (kind == 1 && conds.size() != values.size()) throw DataFrameError(DataFrameError::ComputeError, "one value per condition");
+        if (dt == DataType::Utf8) return text_select_call(kind, slots, values.size(), conds, otherwise != nullptr);
+        std::vector<std::vector<rdf_array>> views(slots.size()), cviews(conds.size());
+        std::vector<rdf_value_part> parts(slots.size());
+        for (size_t k = 0; k < slots.size(); ++k) {
+            parts[k] = rdf_value_part{nullptr, 0, 0};
+            if (slots[k]->is_column) {
+                if (slots[k]->column.size() != n) throw DataFrameError(DataFrameError::ComputeError, "chunk lists differ in length");
+                for (auto& x : slots[k]->column) views[k].push_back(x->view());
+                parts[k].column = views[k].data();
+            } else if (slots[k]->literal.kind == Scalar::Null) parts[k].literal_is_null = 1;
+            else parts[k].literal_bits = literal_bits(slots[k]->literal, dt);
+        }
+        std::vector<const rdf_array*> cptr;
+        for (size_t k = 0; k < conds.size(); ++k) {
+            if (conds[k].size() != n) throw DataFrameError(DataFrameError::ComputeError, "chunk lists differ in length");
+            for (auto& x : conds[k]) cviews[k].push_back(x->view());
+            cptr.push_back(cviews[k].data());
+        }
+        std::vector<std::shared_ptr<Array>> outs;
+        std::vector<rdf_out> ov;
+        for (size_t c = 0; c < n; ++c) {
+            bool any_nullable = kind == 1 && !otherwise, all_nullable = true;
+            for (auto* v : slots) {
+                const bool nullable = v->is_column ? v->column[c]->validity != nullptr : v->literal.kind == Scalar::Null;
+                any_nullable = any_nullable || nullable;
+                all_nullable = all_nullable && nullable;
+            }
+            const bool with_validity = (kind == 0 || kind == 2) ? all_nullable : any_nullable;
+            outs.push_back(Array::make_out(dt, (*first)[c]->length, with_validity, (*first)[c]->host));
+            ov.push_back(outs.back()->out_view((*first)[c]->length));
+        }
+        const size_t nv = values.size();
+        switch (kind) {
+            case 0: check(rdf_coalesce(parts.data(), (int32_t)nv, (int64_t)n, ov.data())); break;
+            case 1: check(rdf_case_when(cptr.data(), parts.data(), (int32_t)nv, otherwise ? &parts[nv] : nullptr, (int64_t)n, ov.data())); break;
+            case 2: check(rdf_extremum(greatest ? 1 : 0, parts.data(), (int32_t)nv, (int64_t)n, ov.data())); break;
+            default: check(rdf_nanvl(&parts[0], &parts[1], (int64_t)n, ov.data())); break;
+        }
+        return finish(outs, ov);
+    }
     static inline DataFrame explode_rows(const DataFrame& frame, const ListArray& list, const std::string* pos_name, const std::string& name, bool outer);
     static std::vector<ArrayRef> finish(std::vector<std::shared_ptr<Array>>& outs, std::vector<rdf_out>& ov) {
         std::vector<ArrayRef> res;
@@ -3333,6 +3538,43 @@ struct ScalarFunctions {
         return res;
     }
 };
+
+inline Column Column::coalesce(const Column& other) const {
+    if (data_type() == DataType::Utf8) return text_select({}, {TextValue(*this), TextValue(other)}, nullptr, field_.name);
+    return Column::from_arrays(ScalarFunctions::coalesce({data_.chunks(), other.data().chunks()}), field_);
+}
+inline Column Column::fill_null(const Scalar& value) const {
+    if (data_type() == DataType::Utf8) {
+        if (value.kind != Scalar::String) throw DataFrameError(DataFrameError::ComputeError, "fill_null: a Utf8 column takes a Scalar::String");
+        return text_select({}, {TextValue(*this), TextValue(value.s)}, nullptr, field_.name);
+    }
+    return Column::from_arrays(ScalarFunctions::coalesce({data_.chunks(), value}), field_);
+}
+inline Column Column::greatest(const Column& other) const { return Column::from_arrays(ScalarFunctions::greatest({data_.chunks(), other.data().chunks()}), field_); }
+inline Column Column::least(const Column& other) const { return Column::from_arrays(ScalarFunctions::least({data_.chunks(), other.data().chunks()}), field_); }
+inline Column Column::nanvl(const Column& other) const { return Column::from_arrays(ScalarFunctions::nanvl(data_.chunks(), other.data().chunks()), field_); }
+inline Column Column::text_null_test(int32_t op) const {   // the rows' bitmap of the staged offsets array; values are never read
+    if (op == RDF_IS_NAN) throw DataFrameError(DataFrameError::ComputeError, "is_nan does not support type Utf8");
+    const TextChunks tc = text_chunks("is_null");
+    std::vector<rdf_array> a;
+    for (auto& u : tc.txt) a.push_back(rdf_array{nullptr, u.offsets.validity, u.offsets.offset, u.offsets.length - 1, -1, RDF_I32, RDF_MEM_HOST});
+    Column r = text_result(DataType::Boolean, tc, std::vector<bool>(a.size(), false), field_.name, false, [&](rdf_out* outs) {
+        check(rdf_null_test(op, a.data(), (int64_t)a.size(), outs));
+    });
+    return Column(r.data(), Field{field_.name, DataType::Boolean, false});
+}
+inline Column Column::is_null() const {
+    if (data_type() == DataType::Utf8) return text_null_test(RDF_IS_NULL);
+    return Column::from_arrays(ScalarFunctions::is_null(data_.chunks()), Field{field_.name, DataType::Boolean, false});
+}
+inline Column Column::is_not_null() const {
+    if (data_type() == DataType::Utf8) return text_null_test(RDF_IS_NOT_NULL);
+    return Column::from_arrays(ScalarFunctions::is_not_null(data_.chunks()), Field{field_.name, DataType::Boolean, false});
+}
+inline Column Column::is_nan() const {
+    if (data_type() == DataType::Utf8) return text_null_test(RDF_IS_NAN);
+    return Column::from_arrays(ScalarFunctions::is_nan(data_.chunks()), Field{field_.name, DataType::Boolean, false});
+}
 
 struct AggregateFunctions {  // src/functions/aggregate.rs:12-93
     template <class T> static std::optional<T> call(rdf_status (*fn)(const rdf_array*, int64_t, void*, int32_t*), const ChunkedArray& c) {

@@ -220,6 +220,59 @@ rdf_status rdf_date_shift(const rdf_array* a, int64_t nchunks, int32_t unit, int
 /* date_diff(end, start) = day(end) - day(start) as RDF_I32, wrapping; each column has its own storage type and unit. */
 rdf_status rdf_date_diff(const rdf_array* end, int32_t end_unit, const rdf_array* start, int32_t start_unit, int64_t nchunks, rdf_out* out);
 
+/* ------------------------------------------------------------------ conditional and NULL functions */
+
+/* ScalarFunctions::coalesce / greatest / least / nanv1 / when and Column::is_null (src/functions/scalar.rs declares them
+ * with empty bodies): the row-wise choice between columns and literals, with Spark 3's semantics.  Stand-alone streaming
+ * calls with the conventions of rdf_datetime_*: inputs are chunk lists of rdf_array (element offset, bit offset and chunking
+ * are free; host or device memory, all of one kind), outputs are one rdf_out per chunk at offset 0, NULL rows hold 0, bits
+ * past `length` in a bitmap's last byte are 0, null_count is set.  One kernel per call, plus the NULL-count reduce.
+ *
+ * A value part is a column (nchunks chunks) or a literal; all value parts and the output share ONE dtype, one of the ten
+ * fixed-width numeric types RDF_I8 .. RDF_F64 (Boolean-valued and List-valued results: RDF_COMPUTE_ERROR, "does not support
+ * type").  At least one part must be a column; its chunking gives the row counts.
+ *
+ *   null_test  IS_NULL / IS_NOT_NULL take any dtype, RDF_BOOL included; `values` is never read and may be NULL.  IS_NAN takes
+ *              RDF_F32 / RDF_F64; isnan(NULL) is false.  The output is RDF_BOOL and never NULL: a bitmap, if given, is
+ *              written all ones and null_count is 0.
+ *   coalesce   1..8 parts: the first part that is not NULL in the row, its bits unchanged (NaN payloads and -0.0 kept); NULL
+ *              when there is none.
+ *   case_when  1..8 branches: conds[k] is nchunks RDF_BOOL chunks.  The row takes values[k] of the first k whose condition
+ *              is valid AND true (a NULL condition is false), else `otherwise` (NULL pointer: NULL).  The result is NULL
+ *              when the chosen value is.  One branch plus `otherwise` is if_else.
+ *   extremum   2..8 parts: greatest != 0 gives greatest, else least.  NULL parts are skipped; the result is NULL only when
+ *              every part is NULL.  Integers compare in their own signedness; floats under Spark's ordering: -0.0 == 0.0,
+ *              NaN equals NaN and is greater than every number.  The fold is strict, so on a tie the LEFTMOST part's bits
+ *              are returned: greatest(NaN, 1) = NaN, least(NaN, 1) = 1, greatest(-0.0, 0.0) is -0.0.
+ *   nanvl      RDF_F32 / RDF_F64: a where a is not NaN, else b.  NULL when a is NULL, and when a is NaN and b is NULL.
+ *
+ * out[c].validity is required when the result of chunk c can be NULL, judged from the arguments alone — coalesce / extremum:
+ * no part is never-NULL in chunk c (never-NULL: a non-NULL literal, or a column whose chunk c has no validity buffer);
+ * case_when: `otherwise` is absent, or any value or `otherwise` can be NULL; nanvl: a or b can be NULL.  A bitmap given
+ * without need is written (all ones).
+ *
+ * Refused before any device work and with nothing written, in this order, RDF_INVALID_ARGUMENT unless said otherwise: an
+ * unknown test; nparts / nbranches outside their range; a NULL list with nchunks > 0, or negative nchunks; no column part; a
+ * column part together with literal_is_null != 0; a condition that is not RDF_BOOL; value dtypes that differ from each other
+ * or from the output; mixed memory kinds; a missing required bitmap; an unsupported dtype (RDF_COMPUTE_ERROR); chunk row
+ * counts that differ between parts or conditions (RDF_COMPUTE_ERROR); a capacity below the rows (RDF_MEMORY_ERROR; every
+ * chunk's `length` is set to the rows it needs, nothing else is written).  nchunks == 0 is RDF_OK.  Without a device a valid
+ * call returns RDF_DEVICE_ERROR (no CPU fallback). */
+#define RDF_SELECT_PARTS_MAX 8
+typedef struct {
+    const rdf_array* column;     /* nchunks chunks of this part, or NULL: the part is a literal      */
+    uint64_t literal_bits;       /* the literal in the call's dtype, little endian in the low bytes  */
+    int32_t  literal_is_null;    /* the literal is NULL (literal_bits ignored)                       */
+} rdf_value_part;
+typedef enum { RDF_IS_NULL = 0, RDF_IS_NOT_NULL = 1, RDF_IS_NAN = 2 } rdf_null_test_op;
+
+rdf_status rdf_null_test(int32_t op, const rdf_array* a, int64_t nchunks, rdf_out* mask);
+rdf_status rdf_coalesce(const rdf_value_part* parts, int32_t nparts, int64_t nchunks, rdf_out* out);
+rdf_status rdf_case_when(const rdf_array* const* conds, const rdf_value_part* values, int32_t nbranches,
+                         const rdf_value_part* otherwise, int64_t nchunks, rdf_out* out);
+rdf_status rdf_extremum(int32_t greatest, const rdf_value_part* parts, int32_t nparts, int64_t nchunks, rdf_out* out);
+rdf_status rdf_nanvl(const rdf_value_part* a, const rdf_value_part* b, int64_t nchunks, rdf_out* out);
+
 /* ------------------------------------------------------------------ aggregate kernels */
 
 /* AggregateFunctions::sum (src/functions/aggregate.rs:82-93): nulls skipped, empty/all-null -> 0,
@@ -593,6 +646,21 @@ typedef struct {                 /* exactly one of utf8 / literal is set */
     const uint8_t* literal;      /* literal_bytes bytes (may be 0 bytes with a non-NULL pointer), or NULL */
     int64_t literal_bytes;       /* 0 .. RDF_UTF8_PATTERN_MAX */
 } rdf_utf8_part;
+
+/* coalesce / case_when over text (the numeric forms and their semantics: rdf_coalesce, rdf_case_when).  They reuse rdf_utf8_part;
+ * for these two calls ONLY, a part with NEITHER pointer set is the NULL literal.  A row is the chosen part's whole row or the
+ * literal, copied into every row that takes it; NULL when the chosen part is.  Outputs follow rdf_utf8_trim's sizing rule
+ * unchanged: values == NULL / capacity == 0 is the sizing call, a short data capacity gives RDF_MEMORY_ERROR with every length
+ * set and nothing written, an output chunk above 2^31-1 bytes is RDF_COMPUTE_ERROR.  out_offsets[c].validity is required when
+ * chunk c can be NULL (coalesce: no part is never-NULL in it; case_when: `otherwise` is absent or any value can be NULL).
+ * Refused before any device work, in this order, RDF_INVALID_ARGUMENT unless said otherwise: nparts / nbranches outside 1..8; a
+ * NULL list with nchunks > 0, or negative nchunks; no column part; a part that sets both pointers; a literal longer than
+ * RDF_UTF8_PATTERN_MAX (or of negative length); a condition that is not RDF_BOOL; offsets / data / outputs of the wrong dtype;
+ * mixed memory kinds; a missing required bitmap; chunk row counts that differ between parts or conditions (RDF_COMPUTE_ERROR);
+ * an offsets capacity below rows + 1 (RDF_MEMORY_ERROR).  nchunks == 0 is RDF_OK. */
+rdf_status rdf_utf8_coalesce(const rdf_utf8_part* parts, int32_t nparts, int64_t nchunks, rdf_out* out_offsets, rdf_out* out_data);
+rdf_status rdf_utf8_case_when(const rdf_array* const* conds, const rdf_utf8_part* values, int32_t nbranches,
+                              const rdf_utf8_part* otherwise, int64_t nchunks, rdf_out* out_offsets, rdf_out* out_data);
 
 rdf_status rdf_utf8_concat(const rdf_utf8_part* parts, int32_t nparts, int64_t nchunks, int32_t with_separator,
                            const uint8_t* sep, int64_t sep_bytes, rdf_out* out_offsets, rdf_out* out_data);

@@ -97,6 +97,10 @@ pub mod sys {
     pub const RDF_STAT_MEAN: i32 = 0; pub const RDF_STAT_VAR_POP: i32 = 1; pub const RDF_STAT_VAR_SAMP: i32 = 2; pub const RDF_STAT_STDDEV_POP: i32 = 3;
     pub const RDF_STAT_STDDEV_SAMP: i32 = 4; pub const RDF_STAT_SKEWNESS: i32 = 5; pub const RDF_STAT_KURTOSIS: i32 = 6;
     pub const RDF_COSTAT_COVAR_POP: i32 = 0; pub const RDF_COSTAT_COVAR_SAMP: i32 = 1; pub const RDF_COSTAT_CORR: i32 = 2;
+    #[repr(C)] #[derive(Clone, Copy)]
+    pub struct rdf_value_part { pub column: *const rdf_array, pub literal_bits: u64, pub literal_is_null: i32 }   // column == null: a literal
+    pub const RDF_IS_NULL: i32 = 0; pub const RDF_IS_NOT_NULL: i32 = 1; pub const RDF_IS_NAN: i32 = 2;
+    pub const RDF_SELECT_PARTS_MAX: i32 = 8;
     #[repr(C)] pub struct rdf_frame { _opaque: [u8; 0] }
     #[repr(C)] pub struct rdf_comm { _opaque: [u8; 0] }
     #[repr(C)] #[derive(Clone, Copy, Default)]
@@ -129,6 +133,21 @@ pub mod sys {
         pub fn rdf_datetime_trunc(a: *const rdf_array, nchunks: i64, unit: i32, level: i32, out: *mut rdf_out) -> i32;
         pub fn rdf_date_shift(a: *const rdf_array, nchunks: i64, unit: i32, op: i32, amounts: *const rdf_array, amount: i32, out: *mut rdf_out) -> i32;
         pub fn rdf_date_diff(end: *const rdf_array, end_unit: i32, start: *const rdf_array, start_unit: i32, nchunks: i64, out: *mut rdf_out) -> i32;
+        // coalesce / greatest / least / nanv1 / when (scalar.rs declares them with empty bodies) and is_null / is_not_null / isnan as masks:
+        // Spark 3's semantics, see rdf_mi355x.h.  A value part is a column's chunks or a literal (its bits in the call's dtype, or NULL); all
+        // parts and the output share one numeric dtype; op: rdf_null_test_op (0 = is_null, 1 = is_not_null, 2 = is_nan); conds[k]: nchunks
+        // Boolean chunks; otherwise may be null (NULL).  Outputs need a bitmap unless some part can never be NULL (see the header).
+        pub fn rdf_null_test(op: i32, a: *const rdf_array, nchunks: i64, mask: *mut rdf_out) -> i32;
+        pub fn rdf_coalesce(parts: *const rdf_value_part, nparts: i32, nchunks: i64, out: *mut rdf_out) -> i32;
+        pub fn rdf_case_when(conds: *const *const rdf_array, values: *const rdf_value_part, nbranches: i32, otherwise: *const rdf_value_part,
+                             nchunks: i64, out: *mut rdf_out) -> i32;
+        pub fn rdf_extremum(greatest: i32, parts: *const rdf_value_part, nparts: i32, nchunks: i64, out: *mut rdf_out) -> i32;
+        pub fn rdf_nanvl(a: *const rdf_value_part, b: *const rdf_value_part, nchunks: i64, out: *mut rdf_out) -> i32;
+        // coalesce / when over StringArrays: rdf_utf8_part as in rdf_utf8_concat, but a part with neither pointer set is the NULL literal;
+        // outputs under the sizing rule of rdf_utf8_trim (call once with data capacity 0, then with the lengths reported)
+        pub fn rdf_utf8_coalesce(parts: *const rdf_utf8_part, nparts: i32, nchunks: i64, out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
+        pub fn rdf_utf8_case_when(conds: *const *const rdf_array, values: *const rdf_utf8_part, nbranches: i32, otherwise: *const rdf_utf8_part,
+                                  nchunks: i64, out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
         // AggregateFunctions (src/functions/aggregate.rs)
         pub fn rdf_sum(a: *const rdf_array, nchunks: i64, out_scalar: *mut c_void, out_is_some: *mut i32) -> i32;
         pub fn rdf_min(a: *const rdf_array, nchunks: i64, out_scalar: *mut c_void, out_is_some: *mut i32) -> i32;

@@ -38,6 +38,10 @@ TRUNC_LEVELS = {"year": TRUNC_YEAR, "quarter": TRUNC_QUARTER, "month": TRUNC_MON
                 "hour": TRUNC_HOUR, "minute": TRUNC_MINUTE, "second": TRUNC_SECOND}
 SHIFT_DAYS, SHIFT_MONTHS, SHIFT_LAST_DAY, SHIFT_NEXT_DAY = range(4)
 DATE_SHIFTS = {"days": SHIFT_DAYS, "months": SHIFT_MONTHS, "last_day": SHIFT_LAST_DAY, "next_day": SHIFT_NEXT_DAY}
+# rdf_null_test_op, RDF_SELECT_PARTS_MAX
+IS_NULL, IS_NOT_NULL, IS_NAN = range(3)
+NULL_TESTS = {"is_null": IS_NULL, "is_not_null": IS_NOT_NULL, "is_nan": IS_NAN}
+SELECT_PARTS_MAX = 8
 
 OP_NAMES = {
     "add": OP_ADD, "subtract": OP_SUB, "multiply": OP_MUL, "divide": OP_DIV, "atan2": OP_ATAN2,
@@ -115,6 +119,10 @@ class rdf_utf8_array(C.Structure):
 
 class rdf_utf8_part(C.Structure):
     _fields_ = [("utf8", C.POINTER(rdf_utf8_array)), ("literal", C.POINTER(C.c_uint8)), ("literal_bytes", C.c_int64)]
+
+
+class rdf_value_part(C.Structure):
+    _fields_ = [("column", C.POINTER(rdf_array)), ("literal_bits", C.c_uint64), ("literal_is_null", C.c_int32)]
 
 
 class rdf_sort_key(C.Structure):
@@ -892,6 +900,115 @@ class Api:
         self._check(self._dt_fn("date_diff")(_flat([end], n), C.c_int32(end_unit), _flat([start], n), C.c_int32(start_unit), C.c_int64(n), carr))
         return self._finish(outs, carr)
 
+    # ---- conditional and NULL functions (ScalarFunctions::coalesce / greatest / least / nanv1 / when: declared by the reference, empty there)
+    @staticmethod
+    def _is_chunks(p) -> bool:
+        return isinstance(p, (list, tuple))
+
+    def _value_parts(self, parts: Sequence):
+        """parts: chunk lists, Python scalars or None (the NULL literal) -> (rdf_value_part array, dtype, the first column, objects to keep alive)."""
+        first = next((p for p in parts if self._is_chunks(p)), None)
+        if first is None:
+            raise ValueError("at least one part must be a column")
+        n = len(first)
+        dt = first[0].dtype if n else F64
+        arr = (rdf_value_part * max(1, len(parts)))()
+        keep = []
+        for i, p in enumerate(parts):
+            if self._is_chunks(p):
+                if len(p) != n:
+                    raise ValueError("chunk lists differ in length")
+                ca = _flat([p], n)
+                keep.append(ca)
+                arr[i] = rdf_value_part(C.cast(ca, C.POINTER(rdf_array)), 0, 0)
+            elif p is None:
+                arr[i] = rdf_value_part(None, 0, 1)
+            else:
+                npdt = np.dtype(NP_OF[dt])
+                bits = int(np.array([p], dtype=npdt).view(f"u{npdt.itemsize}")[0])
+                arr[i] = rdf_value_part(None, bits, 0)
+        return arr, dt, first, keep
+
+    @staticmethod
+    def _never_null(p, c: int) -> bool:
+        return p[c].validity is None if Api._is_chunks(p) else p is not None
+
+    def null_test(self, op, a: Sequence, outs=None):
+        """rdf_null_test: is_null / is_not_null / is_nan (a name of NULL_TESTS or its code) -> RDF_BOOL chunks, never NULL.  A Utf8
+        column is tested through its offsets array's validity, row offset and row count."""
+        code = NULL_TESTS[op] if isinstance(op, str) else int(op)
+        n = len(a)
+        arr = (rdf_array * max(1, n))()
+        for i, x in enumerate(a):
+            if isinstance(x, (HostUtf8, DeviceUtf8)):
+                o = x.c_struct().offsets
+                arr[i] = rdf_array(None, o.validity, o.offset, x.length, o.null_count, I32, o.mem)
+            else:
+                arr[i] = x.c_struct(getattr(x, "_unknown_nc", False))
+        if outs is None:
+            device = any(isinstance(x, (DeviceArray, DeviceUtf8)) for x in a)
+            outs = [self._window_out(BOOL, x.length, device, False) for x in a]
+        carr = (rdf_out * max(1, n))(*[o.out_struct() for o in outs])
+        self._check(self._dt_fn("null_test")(C.c_int32(code), arr, C.c_int64(n), carr))
+        return self._finish(outs, carr)
+
+    def coalesce(self, parts: Sequence, outs=None):
+        """rdf_coalesce: per row the first part that is not NULL.  parts: 1..8 chunk lists of one dtype, Python scalars or None."""
+        arr, dt, first, keep = self._value_parts(parts)
+        n = len(first)
+        if outs is None:
+            outs, carr = self._dt_outs(dt, first, [not any(self._never_null(p, c) for p in parts) for c in range(n)])
+        else:
+            carr = (rdf_out * max(1, n))(*[o.out_struct() for o in outs])
+        self._check(self._dt_fn("coalesce")(arr, C.c_int32(len(parts)), C.c_int64(n), carr))
+        return self._finish(outs, carr)
+
+    def case_when(self, conds: Sequence, values: Sequence, otherwise=None, outs=None):
+        """rdf_case_when: conds[k] (RDF_BOOL chunk lists) choose values[k]; rows no condition holds for take `otherwise` (None: NULL).
+        values / otherwise: chunk lists of one dtype, Python scalars or None."""
+        if len(conds) != len(values):
+            raise ValueError("one value per condition")
+        arr, dt, first, keep = self._value_parts(list(values) + [otherwise])
+        n = len(first)
+        cc = [_flat([c], n) for c in conds]
+        cptr = (C.POINTER(rdf_array) * max(1, len(cc)))(*[C.cast(c, C.POINTER(rdf_array)) for c in cc])
+        if outs is None:
+            every = list(values) + [otherwise]
+            outs, carr = self._dt_outs(dt, first, [not all(self._never_null(p, c) for p in every) for c in range(n)])
+        else:
+            carr = (rdf_out * max(1, n))(*[o.out_struct() for o in outs])
+        other = None if otherwise is None else C.byref(arr, len(values) * C.sizeof(rdf_value_part))
+        self._check(self._dt_fn("case_when")(cptr, arr, C.c_int32(len(values)), other, C.c_int64(n), carr))
+        return self._finish(outs, carr)
+
+    def extremum(self, greatest: bool, parts: Sequence, outs=None):
+        """rdf_extremum: greatest / least of 2..8 parts under Spark's ordering; NULL parts are skipped."""
+        arr, dt, first, keep = self._value_parts(parts)
+        n = len(first)
+        if outs is None:
+            outs, carr = self._dt_outs(dt, first, [not any(self._never_null(p, c) for p in parts) for c in range(n)])
+        else:
+            carr = (rdf_out * max(1, n))(*[o.out_struct() for o in outs])
+        self._check(self._dt_fn("extremum")(C.c_int32(1 if greatest else 0), arr, C.c_int32(len(parts)), C.c_int64(n), carr))
+        return self._finish(outs, carr)
+
+    def greatest(self, parts: Sequence, outs=None):
+        return self.extremum(True, parts, outs)
+
+    def least(self, parts: Sequence, outs=None):
+        return self.extremum(False, parts, outs)
+
+    def nanvl(self, a, b, outs=None):
+        """rdf_nanvl: a where it is not NaN, else b (Float32 / Float64; chunk lists, Python scalars or None)."""
+        arr, dt, first, keep = self._value_parts([a, b])
+        n = len(first)
+        if outs is None:
+            outs, carr = self._dt_outs(dt, first, [not (self._never_null(a, c) and self._never_null(b, c)) for c in range(n)])
+        else:
+            carr = (rdf_out * max(1, n))(*[o.out_struct() for o in outs])
+        self._check(self._dt_fn("nanvl")(C.byref(arr, 0), C.byref(arr, C.sizeof(rdf_value_part)), C.c_int64(n), carr))
+        return self._finish(outs, carr)
+
     # ---- aggregates (AggregateFunctions, src/functions/aggregate.rs)
     def _agg(self, name: str, a: Sequence):
         n = len(a)
@@ -1535,6 +1652,56 @@ class Api:
     def utf8_concat(self, parts: Sequence, sep=None, as_arrow=False):
         """concat (sep is None) / concat_ws of chunk lists and str / bytes literals."""
         return self.utf8_build("concat", None, parts, as_arrow=as_arrow) if sep is None else self.utf8_build("concat_ws", None, parts, sep, as_arrow=as_arrow)
+
+    # ---- coalesce / case_when over text (rdf_utf8_coalesce / rdf_utf8_case_when)
+    def utf8_select_call(self, parts: Sequence, conds=None):
+        """-> (call(out_offsets, out_data) -> status, the first column part, nullable per chunk) of one rdf_utf8_coalesce
+        (conds is None) or rdf_utf8_case_when call (parts = the branches' values, then `otherwise`, None for an absent one).
+        parts: chunk lists, str / bytes literals, None for the NULL literal."""
+        cols = [p for p in parts if isinstance(p, (list, tuple))]
+        if not cols:
+            raise ValueError("at least one part must be a column")
+        n = len(cols[0])
+        keep, cparts = [], (rdf_utf8_part * max(1, len(parts)))()
+        for k, p in enumerate(parts):
+            if p is None:
+                cparts[k] = rdf_utf8_part(None, None, 0)
+            elif isinstance(p, (str, bytes, bytearray)):
+                lraw, lp = self._utf8_pattern(p)
+                keep.append(lp)
+                cparts[k] = rdf_utf8_part(None, C.cast(lp, C.POINTER(C.c_uint8)), len(lraw))
+            else:
+                if len(p) != n:
+                    raise ValueError("chunk lists differ in length")
+                carr = (rdf_utf8_array * max(1, n))(*[c.c_struct() for c in p])
+                keep.append(carr)
+                cparts[k] = rdf_utf8_part(carr, None, 0)
+        can_be_null = lambda p, i: p is None or (isinstance(p, (list, tuple)) and self._utf8_nullable(p[i]))  # noqa: E731
+        if conds is None:
+            fn = self._utf8_fn("utf8_coalesce")
+            call = lambda co, cd, keep=keep: fn(cparts, C.c_int32(len(parts)), C.c_int64(n), co, cd)  # noqa: E731
+            nullable = [all(can_be_null(p, i) for p in parts) for i in range(n)]
+        else:
+            nb = len(parts) - 1
+            if len(conds) != nb:
+                raise ValueError("one value per condition")
+            cc = [_flat([c], n) for c in conds]
+            cptr = (C.POINTER(rdf_array) * max(1, nb))(*[C.cast(c, C.POINTER(rdf_array)) for c in cc])
+            other = None if parts[nb] is None else C.byref(cparts, nb * C.sizeof(rdf_utf8_part))
+            fn = self._utf8_fn("utf8_case_when")
+            call = lambda co, cd, keep=(keep, cc): fn(cptr, cparts, C.c_int32(nb), other, C.c_int64(n), co, cd)  # noqa: E731
+            nullable = [any(can_be_null(p, i) for p in parts) for i in range(n)]
+        return call, cols[0], nullable
+
+    def utf8_coalesce(self, parts: Sequence, as_arrow=False):
+        """rdf_utf8_coalesce: per row the first part that is not NULL (chunk lists, str / bytes literals, None): one result per chunk."""
+        call, shape, nullable = self.utf8_select_call(parts)
+        return self._utf8_run(call, shape, [c.length for c in shape], nullable, as_arrow)
+
+    def utf8_case_when(self, conds: Sequence, values: Sequence, otherwise=None, as_arrow=False):
+        """rdf_utf8_case_when: conds[k] (RDF_BOOL chunk lists) choose values[k]; rows no condition holds for take `otherwise` (None: NULL)."""
+        call, shape, nullable = self.utf8_select_call(list(values) + [otherwise], conds)
+        return self._utf8_run(call, shape, [c.length for c in shape], nullable, as_arrow)
 
     # ---- row hashes and digests (rdf_hash_columns / rdf_utf8_digest / rdf_utf8_crc32)
     def hash_columns(self, kind, cols: Sequence[Sequence], seed: int = 42, outs=None):

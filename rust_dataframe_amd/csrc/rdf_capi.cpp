@@ -35,6 +35,7 @@
 #include "rdf_group_sorted.h"
 #include "rdf_collect.h"
 #include "rdf_datetime.h"
+#include "rdf_select.h"
 #include "rdf_utf8_pattern.h"
 #include "rdf_utf8_build.h"
 #include "rdf_digest.h"
@@ -2876,6 +2877,7 @@ rdf_status groupby_sum_fallback(const rdf_array* keys, const rdf_array* values, 
 #include "rdf_capi_utf8_pred.inc"
 #include "rdf_capi_utf8_build.inc"
 #include "rdf_capi_digest.inc"
+#include "rdf_capi_select.inc"
 
 extern "C" {
 

@@ -1,4 +1,4 @@
-// rdf_capi_utf8_build.inc — host side of rdf_utf8_concat / _pad / _repeat / _reverse / _substring_index (kernels:
+// rdf_capi_utf8_build.inc — host side of rdf_utf8_concat / _pad / _repeat / _reverse / _substring_index / _coalesce / _case_when (kernels:
 // rdf_utf8_build.hip, what is decided about one row: rdf_utf8_build.h); textually included by rdf_capi.cpp (it uses that
 // file's per-thread context, arena and staging helpers, utf8_value_ranges and lexsort_keys_to_device).
 //
@@ -22,6 +22,8 @@ struct Utf8BuildCall {
     int64_t param;                 // pad: len, repeat: times, substring_index: count
     rdf_out* out_offsets;
     rdf_out* out_data;
+    const rdf_array* const* conds = nullptr;   // utf8_case_when: nconds lists of nchunks RDF_BOOL chunks; parts[nconds] is `otherwise`
+    int nconds = 0;
 };
 
 rdf_status utf8_build_check_literal(const char* fn, const char* what, const uint8_t* p, int64_t bytes) {
@@ -35,8 +37,9 @@ rdf_status utf8_build_check_literal(const char* fn, const char* what, const uint
 rdf_status utf8_build_run(const Utf8BuildCall& q) {
     const char* fn = q.fn;
     const int64_t nchunks = q.nchunks;
-    const rdf_utf8_array* cols[kUtf8PartsMax];
-    int col_of[kUtf8PartsMax];
+    const bool select = q.op == U8B_COALESCE || q.op == U8B_CASE_WHEN;   // (a part with neither pointer is the NULL literal)
+    const rdf_utf8_array* cols[kUtf8SelectSlots];
+    int col_of[kUtf8SelectSlots];
     int ncols = 0;
     for (int k = 0; k < q.nparts; ++k) {
         col_of[k] = -1;
@@ -59,6 +62,7 @@ rdf_status utf8_build_run(const Utf8BuildCall& q) {
             RDF_TRY(check_mem(&cols[k][c].offsets, 1, &mem));
             RDF_TRY(check_mem(&cols[k][c].data, 1, &mem));
         }
+    for (int k = 0; k < q.nconds; ++k) RDF_TRY(check_mem(q.conds[k], nchunks, &mem));
     if (nchunks > 0) {
         RDF_TRY(check_out_mem(q.out_offsets, nchunks, mem));
         RDF_TRY(check_out_mem(q.out_data, nchunks, mem));
@@ -68,7 +72,15 @@ rdf_status utf8_build_run(const Utf8BuildCall& q) {
         if (q.out_data[c].capacity < 0 || (q.out_data[c].capacity > 0 && !q.out_data[c].values))
             return fail(RDF_INVALID_ARGUMENT, "%s: output %lld: data capacity without a buffer", fn, (long long)c);
         bool nullable = false;
-        if (q.op != U8B_CONCAT_WS)
+        if (select) {   // coalesce: no part is never-NULL in the chunk; case_when: any value (an absent `otherwise` is the NULL literal) can be NULL
+            bool any = false, all = true;
+            for (int k = 0; k < q.nparts; ++k) {
+                const bool n = q.parts[k].utf8 ? q.parts[k].utf8[c].offsets.validity != nullptr : q.parts[k].literal == nullptr;
+                any |= n;
+                all &= n;
+            }
+            nullable = q.op == U8B_COALESCE ? all : any;
+        } else if (q.op != U8B_CONCAT_WS)
             for (int k = 0; k < ncols; ++k) nullable |= cols[k][c].offsets.validity != nullptr;
         if (nullable && !q.out_offsets[c].validity) return fail(RDF_INVALID_ARGUMENT, "%s: output %lld needs a validity buffer", fn, (long long)c);
     }
@@ -76,6 +88,10 @@ rdf_status utf8_build_run(const Utf8BuildCall& q) {
         for (int64_t c = 0; c < nchunks; ++c)
             if (cols[k][c].offsets.length != cols[0][c].offsets.length)
                 return fail(RDF_COMPUTE_ERROR, "%s: chunk %lld: the parts' chunk lengths differ", fn, (long long)c);
+    for (int k = 0; k < q.nconds; ++k)
+        for (int64_t c = 0; c < nchunks; ++c)
+            if (q.conds[k][c].length != cols[0][c].offsets.length - 1)
+                return fail(RDF_COMPUTE_ERROR, "%s: chunk %lld: a condition's row count differs", fn, (long long)c);
     std::vector<int64_t> row_start((size_t)nchunks + 1, 0);
     for (int64_t c = 0; c < nchunks; ++c) {
         const int64_t rows = cols[0][c].offsets.length - 1;
@@ -92,21 +108,23 @@ rdf_status utf8_build_run(const Utf8BuildCall& q) {
     const int64_t n = row_start[(size_t)nchunks];
 
     // ---- the column parts on the device: the value ranges checked, host arrays staged, the Utf8Chunk tables built
-    rdf_sort_key keys[kUtf8PartsMax];
+    rdf_sort_key keys[kUtf8SelectSlots + kUtf8PartsMax];   // the column parts, then case_when's conditions (Boolean chunks staged alongside)
     memset(keys, 0, sizeof keys);
     for (int k = 0; k < ncols; ++k) keys[k].utf8 = cols[k];
+    for (int k = 0; k < q.nconds; ++k) keys[ncols + k].values = q.conds[k];
     size_t pin_off = 0;
     LexKeysOnDevice d;
-    RDF_TRY(lexsort_keys_to_device(keys, ncols, nchunks, mem, row_start, fn, pin_off, d));
+    RDF_TRY(lexsort_keys_to_device(keys, ncols + q.nconds, nchunks, mem, row_start, fn, pin_off, d));
 
     // ---- the tile prefix of the size pass, the parts, and every literal's bytes: one upload
     size_t lit_total = (size_t)q.lit_bytes;
     for (int k = 0; k < q.nparts; ++k)
-        if (!q.parts[k].utf8) lit_total += (size_t)q.parts[k].literal_bytes;
+        if (!q.parts[k].utf8 && q.parts[k].literal) lit_total += (size_t)q.parts[k].literal_bytes;
     TableBuilder tb;
     const size_t o_ts = tb.reserve(sizeof(int64_t) * ((size_t)nchunks + 1));
     const size_t o_parts = tb.reserve(sizeof(Utf8BuildPart) * (size_t)q.nparts);
     const size_t o_lit = tb.reserve(lit_total + 16);
+    const size_t o_conds = tb.reserve(sizeof(Utf8BuildCond) * (size_t)q.nconds * (size_t)nchunks);
     RDF_TRY(tb.bind(pin_off));
     RDF_TRY(tb.alloc());
     int64_t* hts = tb.at<int64_t>(o_ts);
@@ -119,10 +137,16 @@ rdf_status utf8_build_run(const Utf8BuildCall& q) {
     for (int k = 0; k < q.nparts; ++k) {
         memset(&hparts[k], 0, sizeof(Utf8BuildPart));
         if (q.parts[k].utf8) { hparts[k].col = d.ucols[col_of[k]].d_chunks; continue; }
+        if (select && !q.parts[k].literal) { hparts[k].lit_bytes = -1; continue; }
         if (q.parts[k].literal_bytes > 0) memcpy(hlit + lit_at, q.parts[k].literal, (size_t)q.parts[k].literal_bytes);
         hparts[k].lit = tb.dev_at<uint8_t>(o_lit) + lit_at;
         hparts[k].lit_bytes = (int32_t)q.parts[k].literal_bytes;
         lit_at += (size_t)q.parts[k].literal_bytes;
+    }
+    Utf8BuildCond* hconds = tb.at<Utf8BuildCond>(o_conds);
+    for (size_t i = 0; i < (size_t)q.nconds * (size_t)nchunks; ++i) {
+        const DevChunkCol& cc = d.tb.at<DevChunkCol>(d.o_ch)[(size_t)ncols * (size_t)nchunks + i];
+        hconds[i] = Utf8BuildCond{(const uint8_t*)cc.values, cc.validity, cc.offset};
     }
     RDF_TRY(tb.upload(pin_off));
     pin_off += (tb.size + 255) & ~(size_t)255;
@@ -148,6 +172,8 @@ rdf_status utf8_build_run(const Utf8BuildCall& q) {
     a.lit_bytes = (int32_t)q.lit_bytes;
     a.lit_cp = (int32_t)utf8_count_code_points(q.lit, q.lit_bytes);
     a.param = q.param;
+    a.conds = tb.dev_at<Utf8BuildCond>(o_conds);
+    a.nconds = q.nconds;
     a.n = n;
     a.blen = (int64_t*)pblen;
     a.aux = (uint32_t*)paux;
@@ -275,6 +301,46 @@ rdf_status rdf_utf8_concat(const rdf_utf8_part* parts, int32_t nparts, int64_t n
     if (!with_separator && sep_bytes != 0) return fail(RDF_INVALID_ARGUMENT, "%s: a separator of %lld bytes without with_separator", fn, (long long)sep_bytes);
     const Utf8BuildCall q = {fn, with_separator ? U8B_CONCAT_WS : U8B_CONCAT, parts, nparts, nchunks, sep, sep_bytes, 0, out_offsets, out_data};
     return utf8_build_run(q);
+}
+
+// rdf_utf8_coalesce / rdf_utf8_case_when: the checks of their own in the order the header lists, then the shared run.  slots:
+// the value parts in the kernel's order (case_when: the branches' values, then `otherwise`, which absent is the NULL literal).
+static rdf_status utf8_select(const char* fn, int op, const rdf_array* const* conds, const rdf_utf8_part* values, int32_t n, int lo, const rdf_utf8_part* otherwise,
+                              int64_t nchunks, rdf_out* out_offsets, rdf_out* out_data) {
+    const bool cw = op == U8B_CASE_WHEN;
+    if (n < lo || n > RDF_UTF8_PARTS_MAX) return fail(RDF_INVALID_ARGUMENT, "%s: %d %s, %d .. %d are taken", fn, n, cw ? "branches" : "parts", lo, RDF_UTF8_PARTS_MAX);
+    if (nchunks < 0) return fail(RDF_INVALID_ARGUMENT, "%s: negative nchunks", fn);
+    if (nchunks == 0) return RDF_OK;
+    if (!values || !out_offsets || !out_data || (cw && !conds)) return fail(RDF_INVALID_ARGUMENT, "%s: bad chunk lists", fn);
+    rdf_utf8_part slots[kUtf8SelectSlots];
+    int ns = 0;
+    for (int k = 0; k < n; ++k) {
+        if (cw && !conds[k]) return fail(RDF_INVALID_ARGUMENT, "%s: bad chunk lists", fn);
+        slots[ns++] = values[k];
+    }
+    if (cw) slots[ns++] = otherwise ? *otherwise : rdf_utf8_part{nullptr, nullptr, 0};
+    bool any_col = false;
+    for (int k = 0; k < ns; ++k) any_col |= slots[k].utf8 != nullptr;
+    if (!any_col) return fail(RDF_INVALID_ARGUMENT, "%s: no column part (the row count is its)", fn);
+    for (int k = 0; k < ns; ++k)
+        if (slots[k].utf8 && slots[k].literal) return fail(RDF_INVALID_ARGUMENT, "%s: part %d sets both utf8 and literal", fn, k);
+    for (int k = 0; k < ns; ++k)
+        if (slots[k].literal) RDF_TRY(utf8_build_check_literal(fn, "a literal part", slots[k].literal, slots[k].literal_bytes));
+    for (int k = 0; cw && k < n; ++k)
+        for (int64_t c = 0; c < nchunks; ++c)
+            if (conds[k][c].dtype != RDF_BOOL) return fail(RDF_INVALID_ARGUMENT, "%s: condition %d is not RDF_BOOL", fn, k);
+    Utf8BuildCall q = {fn, op, slots, ns, nchunks, nullptr, 0, 0, out_offsets, out_data};
+    q.conds = conds;
+    q.nconds = cw ? n : 0;
+    return utf8_build_run(q);
+}
+
+rdf_status rdf_utf8_coalesce(const rdf_utf8_part* parts, int32_t nparts, int64_t nchunks, rdf_out* out_offsets, rdf_out* out_data) {
+    return utf8_select("utf8_coalesce", U8B_COALESCE, nullptr, parts, nparts, 1, nullptr, nchunks, out_offsets, out_data);
+}
+rdf_status rdf_utf8_case_when(const rdf_array* const* conds, const rdf_utf8_part* values, int32_t nbranches, const rdf_utf8_part* otherwise, int64_t nchunks,
+                              rdf_out* out_offsets, rdf_out* out_data) {
+    return utf8_select("utf8_case_when", U8B_CASE_WHEN, conds, values, nbranches, 1, otherwise, nchunks, out_offsets, out_data);
 }
 
 rdf_status rdf_utf8_pad(int32_t side, const rdf_utf8_array* chunks, int64_t nchunks, int64_t len, const uint8_t* pad, int64_t pad_bytes,

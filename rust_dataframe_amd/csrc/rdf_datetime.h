@@ -325,4 +325,5 @@ hipError_t launch_dt_fields(const DtArgs& a, hipStream_t s);
 hipError_t launch_dt_trunc(const DtArgs& a, hipStream_t s);
 hipError_t launch_dt_shift(const DtArgs& a, hipStream_t s);
 hipError_t launch_dt_diff(const DtArgs& a, hipStream_t s);
+hipError_t launch_dt_nulls(const DtArgs& a, hipStream_t s);
 #endif

@@ -159,7 +159,12 @@ hipError_t launch_utf8_pred(const Utf8PredArgs& a, hipStream_t s);
 struct Utf8BuildPart {
     const Utf8Chunk* col;      // nchunks chunks of a column part, or nullptr
     const uint8_t*   lit;      // a literal part's bytes
-    int32_t          lit_bytes;
+    int32_t          lit_bytes; // (coalesce / case_when: -1 = the NULL literal)
+};
+struct Utf8BuildCond {         // one RDF_BOOL chunk of a case_when condition
+    const uint8_t* values;
+    const uint8_t* validity;   // nullptr = all valid
+    int64_t        offset;     // bit of row 0, of both
 };
 struct Utf8BuildArgs {
     const Utf8BuildPart* parts;      // device copy: nparts (1 for every op but concat)
@@ -173,13 +178,15 @@ struct Utf8BuildArgs {
     int64_t          param;          // pad: len; repeat: times (both clamped to [0, 2^31]); substring_index: count
     int64_t          n;              // rows
     int64_t*         blen;           // per row: output bytes (scanned into bscan)
-    uint32_t*        aux;            // per row: bit 31 = valid; concat: the present parts' bits; pad: kept bytes; substring_index: the span's start
+    uint32_t*        aux;            // per row: bit 31 = valid; concat: the present parts' bits; pad: kept bytes; substring_index: the span's start; coalesce / case_when: the chosen part
     const int64_t*   bscan;          // n + 1 entries
     int64_t*         tot;            // per chunk: bytes, rows
     unsigned long long* null_counts; // per chunk
     const Utf8OutChunk* outs;
     int64_t          ntiles;         // copy tiles
     int64_t*         tile_row;       // per copy tile: the row (of its chunk) that holds the tile's first byte
+    const Utf8BuildCond* conds;      // case_when: [nconds * nchunks], condition k of chunk c at k * nchunks + c; parts[nconds] is `otherwise`
+    int32_t          nconds;
 };
 hipError_t launch_utf8_build_size(const Utf8BuildArgs& a, hipStream_t s);     // blen, aux, null_counts
 hipError_t launch_utf8_build_totals(const Utf8BuildArgs& a, hipStream_t s);   // tot

@@ -18,9 +18,12 @@
 
 #include "rdf_utf8_pattern.h"
 
-enum : int { U8B_CONCAT = 0, U8B_CONCAT_WS, U8B_LPAD, U8B_RPAD, U8B_REPEAT, U8B_REVERSE, U8B_SUBSTRING_INDEX, U8B_NOPS };
+enum : int { U8B_CONCAT = 0, U8B_CONCAT_WS, U8B_LPAD, U8B_RPAD, U8B_REPEAT, U8B_REVERSE, U8B_SUBSTRING_INDEX,
+             U8B_COALESCE, U8B_CASE_WHEN,   // rdf_utf8_coalesce / rdf_utf8_case_when: a row is ONE piece, the chosen part's row or literal
+             U8B_NOPS };
 
 constexpr int kUtf8PartsMax = 8;                 // parts of one concat
+constexpr int kUtf8SelectSlots = kUtf8PartsMax + 1;   // case_when: eight branches and `otherwise`; the chosen slot is 4 bits of a row's note
 constexpr int64_t kUtf8BuildClamp = 1ll << 31;   // len / times are clamped to it, and so is one row's output length
 
 RDF_U8P_HD int64_t utf8_build_clamp(int64_t v) { return v < 0 ? 0 : (v > kUtf8BuildClamp ? kUtf8BuildClamp : v); }

@@ -5,7 +5,8 @@
 //
 //   size    the tiles of rdf_utf8_pred.hip: a block takes 256 rows of ONE chunk, a lane a row.  One read of every part's
 //           offsets and validity bit gives the row's validity, its output length and a 31-bit note for the write pass (concat:
-//           which parts are present; pad: the kept bytes of the row; substring_index: where the span starts).  Row bytes are
+//           which parts are present; pad: the kept bytes of the row; substring_index: where the span starts; coalesce /
+//           case_when (rdf_utf8_coalesce / rdf_utf8_case_when): the chosen part, O(1) per row from offsets and bitmaps).  Row bytes are
 //           read only by pad (code points) and substring_index (the search): rows up to kUtf8ShortRow bytes on their lane
 //           through rdf_utf8_build.h, longer ones by the whole wave one after the other, 16 bytes a lane and 1 KiB a step
 //           (the occurrences of a delimiter are the set bits of the lanes' 16 start positions: the count-th one is found by
@@ -171,6 +172,30 @@ __global__ __launch_bounds__(kUtf8PredThreads) void utf8_build_size_kernel(Utf8B
                     aux = present;
                     out = sum + (OP == U8B_CONCAT_WS ? utf8_concat_seps(present) * m : 0);
                 }
+            } else if (OP == U8B_COALESCE || OP == U8B_CASE_WHEN) {
+                // the chosen part (rdf_select.h's rule: the first part that can decide the row); its index is the row's note
+                int chosen = -1;
+                if (OP == U8B_COALESCE) {
+                    for (int k = 0; k < a.nparts && chosen < 0; ++k) {
+                        const Utf8BuildPart pt = a.parts[k];
+                        if (pt.col ? row_valid(pt.col[c], r) : pt.lit_bytes >= 0) chosen = k;
+                    }
+                } else {
+                    chosen = a.nconds;   // `otherwise`
+                    for (int k = 0; k < a.nconds; ++k) {
+                        const Utf8BuildCond cc = a.conds[(int64_t)k * a.nchunks + c];
+                        if ((!cc.validity || bit_at(cc.validity, cc.offset + r)) && bit_at(cc.values, cc.offset + r)) { chosen = k; break; }
+                    }
+                }
+                if (chosen >= 0) {
+                    const Utf8BuildPart pt = a.parts[chosen];
+                    valid = pt.col ? row_valid(pt.col[c], r) : pt.lit_bytes >= 0;
+                    if (valid) {
+                        aux = (uint32_t)chosen;
+                        if (pt.col) { row_span(pt.col[c], r, o0, o1); out = o1 - o0; }
+                        else out = pt.lit_bytes;
+                    }
+                }
             } else {
                 const Utf8Chunk& ch = a.parts[0].col[c];
                 valid = row_valid(ch, r);
@@ -300,6 +325,16 @@ __device__ __forceinline__ const uint8_t* row_source(const Utf8BuildArgs& a, int
             },
             2 * a.nparts, j, &k, run);
     }
+    if (OP == U8B_COALESCE || OP == U8B_CASE_WHEN) {   // one piece: the chosen part's row or literal, L bytes
+        const Utf8BuildPart pt = a.parts[aux & 15u];
+        const uint8_t* src = pt.lit;
+        if (pt.col) {
+            int32_t p0, p1;
+            row_span(pt.col[c], r, p0, p1);
+            src = pt.col[c].data + p0;
+        }
+        return utf8_piece_at([&](int) { return Utf8Piece{src, L, L > 0 ? L : 1}; }, 1, j, &k, run);
+    }
     const Utf8Chunk& ch = a.parts[0].col[c];
     int32_t o0, o1;
     row_span(ch, r, o0, o1);
@@ -387,6 +422,8 @@ unsigned grid_for(int64_t n, int threads) {
         case U8B_RPAD: hipLaunchKernelGGL((KERNEL<U8B_RPAD>), __VA_ARGS__); break;                   \
         case U8B_REPEAT: hipLaunchKernelGGL((KERNEL<U8B_REPEAT>), __VA_ARGS__); break;               \
         case U8B_REVERSE: hipLaunchKernelGGL((KERNEL<U8B_REVERSE>), __VA_ARGS__); break;             \
+        case U8B_COALESCE: hipLaunchKernelGGL((KERNEL<U8B_COALESCE>), __VA_ARGS__); break;           \
+        case U8B_CASE_WHEN: hipLaunchKernelGGL((KERNEL<U8B_CASE_WHEN>), __VA_ARGS__); break;         \
         default: hipLaunchKernelGGL((KERNEL<U8B_SUBSTRING_INDEX>), __VA_ARGS__); break;              \
     }
 
