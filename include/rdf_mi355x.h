@@ -496,7 +496,12 @@ rdf_status rdf_list_contains(const rdf_list_array* list, const void* value, rdf_
 rdf_status rdf_list_position(const rdf_list_array* list, const void* value, rdf_out* out);
 /* ArrayFunctions::array_max / array_min (array.rs:182-231): per-row extremum, NULL for a NULL list.  An EMPTY
  * list gives NULL (the reference unwraps None and panics); floats are accepted, NaN loses against any number
- * (the column aggregates' rule).  out: child dtype. */
+ * (the column aggregates' rule; a row of nothing but NaNs gives a NaN of unspecified sign and payload), and -0.0
+ * orders below +0.0 as in array_sort: max{-0.0, +0.0} is +0.0 wherever the zeros stand.  A NULL result holds 0.
+ * out: child dtype.
+ * The bitmaps rdf_list_contains / _position / _max / _min write to device memory (RDF_MEM_DEVICE: the RDF_BOOL values
+ * of array_contains and every output validity) are stored in whole 64-bit words: such a buffer holds
+ * ceil(rows / 64) * 8 bytes and is 8-byte aligned. */
 rdf_status rdf_list_max(const rdf_list_array* list, rdf_out* out);
 rdf_status rdf_list_min(const rdf_list_array* list, rdf_out* out);
 /* ArrayFunctions::array_remove (array.rs:262-292): every element equal to `value` dropped, order kept; a NULL

@@ -1111,6 +1111,8 @@ static rdf_status list_find(const rdf_list_array* l, const void* value, rdf_out*
 rdf_status ora_list_contains(const rdf_list_array* l, const void* value, rdf_out* out) { return list_find(l, value, out, 0); }
 rdf_status ora_list_position(const rdf_list_array* l, const void* value, rdf_out* out) { return list_find(l, value, out, 1); }
 
+/* -0.0 orders below +0.0, as in array_sort's total order: the extremum of a row does not depend on where its zeros stand */
+static int zero_less(double p, double q) { return p < q || (p == q && signbit(p) && !signbit(q)); }
 static int elem_less(const rdf_array* a, int64_t x, int64_t y) {   /* value order; NaN handled by the callers */
     int64_t i = a->offset + x, j = a->offset + y;
     switch (a->dtype) {
@@ -1122,8 +1124,8 @@ static int elem_less(const rdf_array* a, int64_t x, int64_t y) {   /* value orde
         case RDF_U16: return ((const uint16_t*)a->values)[i] < ((const uint16_t*)a->values)[j];
         case RDF_U32: return ((const uint32_t*)a->values)[i] < ((const uint32_t*)a->values)[j];
         case RDF_U64: return ((const uint64_t*)a->values)[i] < ((const uint64_t*)a->values)[j];
-        case RDF_F32: return ((const float*)a->values)[i] < ((const float*)a->values)[j];
-        default: return ((const double*)a->values)[i] < ((const double*)a->values)[j];
+        case RDF_F32: return zero_less(((const float*)a->values)[i], ((const float*)a->values)[j]);
+        default: return zero_less(((const double*)a->values)[i], ((const double*)a->values)[j]);
     }
 }
 static int elem_nan(const rdf_array* a, int64_t x) {

@@ -299,3 +299,60 @@ def tuple_with_hash(target, dtypes, prefix):
     last = _solve_tuple(bits + [0], len(prefix), target)
     out = [raw_bits(v, d) if d in (F64, F32) else v for v, d in zip(prefix, dtypes)]
     return tuple(out + [value_of_bits(key_bits_inv(last, dtypes[-1]), dtypes[-1])])
+
+
+# ---------------------------------------------------------------- the per-row tables of the List set functions (rdf_list.hip)
+# set_hash lives in the kernels' translation unit and runs on the device only, so unlike the two hashes above it has no host
+# test against the source: if the kernels' hash changes, the rows built from these models stop colliding on the device (they
+# stay valid inputs with the same expected results) and this restatement has to follow it.
+
+def set_hash(bits):
+    """set_hash of rdf_list.hip over the value's 64 hashed bits: a signed integer sign-extended, an unsigned one zero-extended,
+    a float's own bits (Float32: 32 of them) after v + 0.0, which turns -0.0 into +0.0."""
+    bits &= M
+    bits ^= bits >> 32
+    return ((bits * GOLD) & M) >> 32
+
+
+def set_home_lds(h, size):
+    """SetTableLds::home: the tables of list_set_block_kernel have a power of two of slots."""
+    return h & (size - 1)
+
+
+def set_home_wave(h, size):
+    """SetTable::home: the tables of list_set_wave_kernel have 2 * elements slots."""
+    return (h * size) >> 32
+
+
+def set_hashed_bits(value, np_dtype):
+    """The 64 bits set_hash sees of one numpy scalar."""
+    import numpy as np
+    dt = np.dtype(np_dtype)
+    if dt.kind == "f":
+        return int((np.asarray([value], dt) + dt.type(0)).view({4: np.uint32, 8: np.uint64}[dt.itemsize])[0])
+    return int(value) & M
+
+
+def set_colliders(np_dtype, size, slot, lds, want, seed=0, draws=1 << 21):
+    """Up to `want` distinct finite values of the dtype (no -0.0) whose home slot in a table of `size` slots is `slot`: seeded
+    draws over the whole range of the type, hashed with numpy and checked again, one by one, with the integer model."""
+    import numpy as np
+    dt = np.dtype(np_dtype)
+    rng = np.random.default_rng(seed)
+    if dt.itemsize <= 2:
+        raw = np.arange(1 << (8 * dt.itemsize), dtype=np.uint64)
+    else:
+        raw = rng.integers(0, 1 << (8 * dt.itemsize), size=draws, dtype=np.uint64, endpoint=False) if dt.itemsize < 8 else rng.integers(0, M, size=draws, dtype=np.uint64, endpoint=True)
+    vals = np.unique(raw.astype({1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}[dt.itemsize])).view(dt)
+    if dt.kind == "f":
+        vals = vals[np.isfinite(vals) & ~((vals == 0) & np.signbit(vals))]
+        bits = vals.view({4: np.uint32, 8: np.uint64}[dt.itemsize]).astype(np.uint64)
+    else:
+        bits = vals.astype(np.int64).view(np.uint64)
+    with np.errstate(over="ignore"):
+        h = ((bits ^ (bits >> np.uint64(32))) * np.uint64(GOLD)) >> np.uint64(32)
+    home = (h & np.uint64(size - 1)) if lds else ((h * np.uint64(size)) >> np.uint64(32))
+    out = vals[home == np.uint64(slot)][:want]
+    fn = set_home_lds if lds else set_home_wave
+    assert all(fn(set_hash(set_hashed_bits(v, dt)), size) == slot for v in out)
+    return out
