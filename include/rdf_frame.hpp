@@ -827,6 +827,70 @@ class Column {
         });
     }
 
+    // Text to values and back, on the device (rdf_utf8_parse / rdf_utf8_format; Spark 3's semantics as the C header states them).
+    //   utf8_parse    this Utf8 column -> Boolean / an integer type / Int32 day numbers / Int64 timestamps in `unit`; pattern null:
+    //                 the kind's CAST grammar, else to_date / to_timestamp / unix_timestamp.  A row that does not parse is NULL,
+    //                 so every result chunk carries a bitmap.
+    //   utf8_format   Boolean / integer / temporal storage chunks -> a Utf8 column carried like every text column of this mirror
+    //                 (the values are staged through the host, as text is); pattern null: CAST(x AS STRING), else date_format.
+    Column utf8_parse(rdf_text_kind kind, DataType out, int32_t unit = RDF_TIME_SECOND, const std::string* pattern = nullptr, bool on_host = false) const {
+        need_text("utf8_parse");
+        const TextChunks tc = text_chunks("utf8_parse");
+        const std::vector<bool> nullable(tc.txt.size(), true);
+        return text_result(out, tc, nullable, field_.name, on_host, [&](rdf_out* outs) {
+            check(rdf_utf8_parse(tc.txt.data(), (int64_t)tc.txt.size(), (int32_t)kind, unit, pattern ? (const uint8_t*)pattern->data() : nullptr,
+                                 pattern ? (int64_t)pattern->size() : 0, outs, nullptr));
+        });
+    }
+    static Column utf8_format(const std::vector<ArrayRef>& arr, rdf_text_kind kind, int32_t unit = RDF_TIME_SECOND, const std::string* pattern = nullptr,
+                              const std::string& name = "format") {
+        struct Staged { std::vector<uint8_t> values, valid; };
+        std::vector<Staged> keep(arr.size());
+        std::vector<rdf_array> a;
+        std::vector<bool> nullable;
+        TextChunks shape;
+        for (size_t i = 0; i < arr.size(); ++i) {
+            const Array& x = *arr[i];
+            if (x.dtype == DataType::Utf8) throw DataFrameError(DataFrameError::ComputeError, "utf8_format: the input is text already");
+            Staged& s = keep[i];
+            if (x.dtype == DataType::Boolean) s.values = pack_bits(x.bools_to_host());
+            else {
+                const int64_t es = (int64_t)type_size(x.dtype);
+                s.values.resize((size_t)(x.length * es));
+                if (x.length > 0) x.fetch(s.values.data(), (const uint8_t*)x.values->data() + x.offset * es, x.length * es);
+            }
+            s.values.resize(s.values.size() + 8, 0);
+            if (x.validity) { s.valid = pack_bits(x.valid_to_host()); s.valid.resize(s.valid.size() + 8, 0); }
+            a.push_back(rdf_array{s.values.data(), x.validity ? s.valid.data() : nullptr, 0, x.length, x.validity ? x.null_count : 0, (int32_t)x.dtype, RDF_MEM_HOST});
+            rdf_utf8_array u;
+            std::memset(&u, 0, sizeof u);
+            u.offsets.length = x.length + 1;
+            shape.txt.push_back(u);
+            nullable.push_back(x.validity != nullptr);
+        }
+        return text_build(shape, nullable, name, [&](rdf_out* oo, rdf_out* od) {
+            return rdf_utf8_format(a.data(), (int64_t)a.size(), (int32_t)kind, unit, pattern ? (const uint8_t*)pattern->data() : nullptr,
+                                   pattern ? (int64_t)pattern->size() : 0, oo, od);
+        });
+    }
+    // to_date(s, fmt) / to_timestamp(s, fmt) / unix_timestamp(s, fmt) of a Utf8 column; date_format / from_unix_time of a temporal one
+    Column to_date(const std::string& fmt) const { return utf8_parse(RDF_TEXT_DATE, DataType::Int32, RDF_TIME_SECOND, &fmt); }
+    Column to_timestamp(rdf_time_unit unit, const std::string& fmt) const { return utf8_parse(RDF_TEXT_TIMESTAMP, DataType::Int64, (int32_t)unit, &fmt); }
+    Column unix_timestamp(const std::string& fmt) const { return utf8_parse(RDF_TEXT_TIMESTAMP, DataType::Int64, RDF_TIME_SECOND, &fmt); }
+    Column date_format(rdf_time_unit unit, const std::string& fmt) const { return utf8_format(data_.chunks(), RDF_TEXT_TIMESTAMP, (int32_t)unit, &fmt, field_.name); }
+    Column from_unix_time(const std::string& fmt) const { return utf8_format(data_.chunks(), RDF_TEXT_TIMESTAMP, RDF_TIME_SECOND, &fmt, field_.name); }
+    // CAST between Utf8 and Boolean / the integer types (either direction)
+    Column cast_text(DataType to) const {
+        if (data_type() == DataType::Utf8) {
+            if (to != DataType::Boolean && !is_integer_type(to)) throw DataFrameError(DataFrameError::ComputeError, "cast: Utf8 casts to Boolean and the integer types");
+            return utf8_parse(to == DataType::Boolean ? RDF_TEXT_BOOL : RDF_TEXT_INT, to);
+        }
+        if (to != DataType::Utf8 || (data_type() != DataType::Boolean && !is_integer_type(data_type())))
+            throw DataFrameError(DataFrameError::ComputeError, "cast: Boolean and the integer types cast to Utf8");
+        return utf8_format(data_.chunks(), data_type() == DataType::Boolean ? RDF_TEXT_BOOL : RDF_TEXT_INT, RDF_TIME_SECOND, nullptr, field_.name);
+    }
+    static bool is_integer_type(DataType t) { return (int32_t)t >= RDF_I8 && (int32_t)t <= RDF_U64; }
+
     // Text columns made of more than one source, on the device (rdf_utf8_concat / _pad / _repeat / _reverse /
     // _substring_index; Spark 3's semantics, see the C header): each call runs twice under the sizing rule and returns an
     // ordinary Utf8 column with the input's chunking, carried like every text column of this mirror, so with_column,
@@ -3214,6 +3278,9 @@ struct ScalarFunctions {
         return finish(outs, ov);
     }
     static std::vector<ArrayRef> cast(const std::vector<ArrayRef>& arr, DataType to) {
+        // to and from Utf8 (Boolean and the integer types): rdf_utf8_format / rdf_utf8_parse, the text staged through the host
+        if (to == DataType::Utf8 || (!arr.empty() && arr[0]->dtype == DataType::Utf8))
+            return Column::from_arrays(arr, Field{"cast", arr.empty() ? to : arr[0]->dtype, true}).cast_text(to).data().chunks();
         std::vector<rdf_array> a;
         std::vector<std::shared_ptr<Array>> outs;
         std::vector<rdf_out> ov;
@@ -3255,6 +3322,20 @@ struct ScalarFunctions {
     }
     static std::vector<ArrayRef> like(const std::vector<ArrayRef>& arr, const std::string& pattern, int32_t escape = -1) {
         return text_column(arr, "like").utf8_predicate(RDF_UTF8_LIKE, pattern, escape).data().chunks();
+    }
+    // to_date(s, fmt) / to_timestamp / unix_timestamp / from_unix_time / date_format (src/functions/scalar.rs:459, 461, 473, 262, 209:
+    // empty bodies): Spark 3's datetime patterns on the device (rdf_utf8_parse / rdf_utf8_format).  Parsing gives Int32 day
+    // numbers / Int64 timestamps in `unit` (unix_timestamp: seconds), NULL where a row does not parse; formatting gives Utf8.
+    static std::vector<ArrayRef> to_date(const std::vector<ArrayRef>& arr, const std::string& fmt) { return text_column(arr, "to_date").to_date(fmt).data().chunks(); }
+    static std::vector<ArrayRef> to_timestamp(const std::vector<ArrayRef>& arr, rdf_time_unit unit, const std::string& fmt) {
+        return text_column(arr, "to_timestamp").to_timestamp(unit, fmt).data().chunks();
+    }
+    static std::vector<ArrayRef> unix_timestamp(const std::vector<ArrayRef>& arr, const std::string& fmt) { return text_column(arr, "unix_timestamp").unix_timestamp(fmt).data().chunks(); }
+    static std::vector<ArrayRef> from_unix_time(const std::vector<ArrayRef>& arr, const std::string& fmt) {
+        return Column::utf8_format(arr, RDF_TEXT_TIMESTAMP, RDF_TIME_SECOND, &fmt, "from_unix_time").data().chunks();
+    }
+    static std::vector<ArrayRef> date_format(const std::vector<ArrayRef>& arr, rdf_time_unit unit, const std::string& fmt) {
+        return Column::utf8_format(arr, RDF_TEXT_TIMESTAMP, (int32_t)unit, &fmt, "date_format").data().chunks();
     }
     // concat / concat_ws / lpad / rpad / repeat / reverse / substring_index over Utf8 arrays (declared with empty bodies in
     // src/functions/scalar.rs): Spark 3's semantics on the device (rdf_utf8_concat .. rdf_utf8_substring_index), Utf8 arrays

@@ -676,6 +676,59 @@ rdf_status rdf_utf8_reverse(const rdf_utf8_array* chunks, int64_t nchunks, rdf_o
 rdf_status rdf_utf8_substring_index(const rdf_utf8_array* chunks, int64_t nchunks, const uint8_t* delim, int64_t delim_bytes,
                                     int64_t count, rdf_out* out_offsets, rdf_out* out_data);
 
+/* ------------------------------------------------------------------ text to values and back
+ *
+ * ScalarFunctions::{to_date(s, fmt), to_timestamp, unix_timestamp, from_unix_time, date_format} (src/functions/scalar.rs
+ * declares them with empty bodies) and CAST between Utf8 and Boolean / integer / date / timestamp columns, with Spark 3's
+ * semantics as far as tests/textconv_ref.py (the executable model) and DESIGN.md state them; no time zones beyond a numeric
+ * offset in the text.  Inputs follow the rdf_utf8_array conventions exactly as rdf_utf8_trim takes them; temporal storage
+ * follows rdf_datetime_fields (Int32 or Int64 plus its rdf_time_unit, RDF_TIME_DAY is Int32).
+ *
+ * CAST grammars (pattern == NULL): the bytes 0x09-0x0D, 0x1C-0x1F and 0x20 are trimmed from both ends, nothing else.
+ *   INT        [+-]? digit+ ( '.' digit* )?   the fraction is checked and dropped; a value outside the dtype is NULL; for an
+ *              unsigned dtype '-0' is 0 and any other negative NULL; a text without a digit before the '.' is NULL
+ *   BOOL       t true y yes 1 / f false n no 0, ASCII letters of either case
+ *   DATE       [+-]? y{4,7} ( - m{1,2} ( - d{1,2} ( [ T] anything )? )? )?   a missing month or day is 1; a date that
+ *              does not exist, or whose day number leaves Int32, is NULL
+ *   TIMESTAMP  the date part, optionally [ T] h{1,2} : m{1,2} ( : s{1,2} ( . digit* )? )? after a full date, optionally a
+ *              zone Z, UTC or [+-] h{1,2} ( : m{1,2} )? of at most 18:00, which is subtracted; fraction digits beyond the
+ *              unit are dropped; a value the unit's Int64 cannot hold is NULL
+ * Patterns (DATE / TIMESTAMP): yyyy yy M MM MMM d dd D DDD H HH h hh a m mm s ss S..SSSSSSSSS, EEE (format only), '...'
+ * quoted text ('' a quote), any non-letter byte for itself; at most 32 tokens and 64 literal bytes.  A pattern trims nothing
+ * and has to consume the whole row.  Two-letter numeric tokens take exactly two digits, one-letter ones one or two (D up to
+ * three), greedily; absent fields are those of 1970-01-01 00:00:00; a field given twice with two values, fields that contradict
+ * each other (D against M / d, H against h a) or lie outside their range give NULL.
+ * CAST to text: shortest decimal; true / false; yyyy-MM-dd; yyyy-MM-dd HH:mm:ss plus '.' and the fraction without trailing
+ * zeros when it is not 0.  Years 0..9999 print as four digits, larger ones as '+' and the digits, negative ones as '-' and at
+ * least four digits.  parse(format(x)) == x for every integer, every Int32 day number and every timestamp of the years
+ * -999999 .. 9999999.
+ *
+ * Refused with RDF_INVALID_ARGUMENT before any device work and with nothing written: an unknown kind or unit; a pattern with
+ * BOOL / INT; a pattern that does not compile or whose output could pass 256 bytes a row (rdf_last_error() names the
+ * position); a NULL list with nchunks > 0, negative nchunks; an output of the wrong dtype; two memory kinds in one call; parse:
+ * an output without a validity buffer; format: an input with validity but an output without, Int64 storage with RDF_TIME_DAY,
+ * chunks of two storage types.  Float dtypes, and temporal storage other than Int32 / Int64, are RDF_COMPUTE_ERROR
+ * ("... does not support type").  A capacity below the rows is RDF_MEMORY_ERROR.  nchunks == 0 is RDF_OK.  Without a device
+ * a valid call returns RDF_DEVICE_ERROR (no CPU fallback). */
+typedef enum { RDF_TEXT_BOOL = 0, RDF_TEXT_INT, RDF_TEXT_DATE, RDF_TEXT_TIMESTAMP } rdf_text_kind;
+
+/* Utf8 -> Boolean / integer / Date32 day number / timestamp.  pattern == NULL: Spark 3's CAST grammar of the kind;
+ * else a datetime pattern (DATE, TIMESTAMP only): to_date(s, fmt), to_timestamp(s, fmt), unix_timestamp(s, fmt) is
+ * TIMESTAMP with RDF_TIME_SECOND.  A row that does not parse is NULL, never an error, so every output needs a validity
+ * buffer.  failed[c] (may be NULL): rows of chunk c that were not NULL and did not parse.
+ * out[c]: RDF_BOOL (BOOL), any of the eight integer dtypes taken from out[c].dtype (INT; one dtype for the call), RDF_I32
+ * (DATE), RDF_I64 in `unit`, second .. nanosecond (TIMESTAMP).  NULL rows hold 0, bitmaps are written as
+ * rdf_datetime_fields writes them, null_count is set. */
+rdf_status rdf_utf8_parse(const rdf_utf8_array* chunks, int64_t nchunks, int32_t kind, int32_t unit,
+                          const uint8_t* pattern, int64_t pattern_bytes, rdf_out* out, int64_t* failed);
+
+/* The inverse: Boolean / integer / temporal storage (+ unit, as rdf_hour takes it) -> Utf8 under the sizing rule of
+ * rdf_utf8_trim.  pattern == NULL: CAST(x AS STRING); else date_format(x, fmt), from_unix_time(x, fmt) is TIMESTAMP with
+ * RDF_TIME_SECOND.  Kind DATE prints the date of a temporal value of any unit, TIMESTAMP its date and time; with a pattern
+ * the two are the same.  NULL in gives NULL out with an empty row. */
+rdf_status rdf_utf8_format(const rdf_array* a, int64_t nchunks, int32_t kind, int32_t unit,
+                           const uint8_t* pattern, int64_t pattern_bytes, rdf_out* out_offsets, rdf_out* out_data);
+
 /* DataFrame::sort (src/dataframe.rs:194-222) whose criteria may be Utf8 columns: arrow's lexsort_to_indices over numeric
  * and StringArray columns alike.  keys[k] is criterion k (key 0 most significant) and sets exactly one of
  *   values  nchunks numeric chunks (one dtype), ordered as by rdf_sort_to_indices, or

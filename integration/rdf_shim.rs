@@ -281,6 +281,14 @@ pub mod sys {
         pub fn rdf_utf8_reverse(chunks: *const rdf_utf8_array, nchunks: i64, out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
         pub fn rdf_utf8_substring_index(chunks: *const rdf_utf8_array, nchunks: i64, delim: *const u8, delim_bytes: i64, count: i64,
                                         out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
+        // text to values and back (src/functions/scalar.rs: date_format :209, from_unix_time :262, to_date :459, to_timestamp :461,
+        // unix_timestamp :473, and CAST between Utf8 and Boolean / integer / date / timestamp): kind 0 .. 3 = bool, int, date,
+        // timestamp; pattern null = the CAST grammar, else a datetime pattern.  parse: a row that does not parse is NULL, so every
+        // output carries a validity buffer; failed (may be null) counts such rows per chunk.  format: rdf_utf8_trim's sizing rule.
+        pub fn rdf_utf8_parse(chunks: *const rdf_utf8_array, nchunks: i64, kind: i32, unit: i32, pattern: *const u8, pattern_bytes: i64,
+                              out: *mut rdf_out, failed: *mut i64) -> i32;
+        pub fn rdf_utf8_format(a: *const rdf_array, nchunks: i64, kind: i32, unit: i32, pattern: *const u8, pattern_bytes: i64,
+                               out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
         // row hashes and digests (src/functions/scalar.rs: hash :265, crc32 :205, md5 :338, sha1 :389, sha2 :390): kind 0 = Spark's
         // Murmur3_x86_32 (Int32 out, seed 42 by default), 1 = xxhash64 (Int64 out); digests 0 .. 5 = md5, sha1, sha224, sha256, sha384,
         // sha512 as lowercase hex text under the sizing rule of rdf_utf8_trim; crc32 as Int64

@@ -544,6 +544,8 @@ UTF8_PATTERN_MAX = 1024
 UTF8_PARTS_MAX = 8
 # rdf_hash_kind / rdf_digest_kind
 HASH_KINDS = {"hash": 0, "murmur3": 0, "xxhash64": 1}
+TEXT_BOOL, TEXT_INT, TEXT_DATE, TEXT_TIMESTAMP = range(4)
+TEXT_KINDS = {"bool": TEXT_BOOL, "int": TEXT_INT, "date": TEXT_DATE, "timestamp": TEXT_TIMESTAMP}
 DIGEST_KINDS = {"md5": 0, "sha1": 1, "sha224": 2, "sha256": 3, "sha384": 4, "sha512": 5}
 DIGEST_HEX_BYTES = (32, 40, 56, 64, 96, 128)
 HASH_COLS_MAX = 8
@@ -1484,7 +1486,7 @@ class Api:
     def _utf8_run(self, call, chunks, rows_out, nullable, as_arrow=False):
         """The sizing call, then the call into exactly sized buffers -> one HostUtf8 / DeviceUtf8 per output chunk
         (python lists / pyarrow arrays with as_arrow="pylist" / True)."""
-        device = any(isinstance(c, DeviceUtf8) for c in chunks)
+        device = any(isinstance(c, (DeviceUtf8, DeviceArray)) for c in chunks)   # (rdf_utf8_format: the inputs are value chunks)
         co, cd, keep = self._utf8_outs(chunks, rows_out, nullable, device)
         st = call(co, cd)
         if st not in (RDF_OK, RDF_MEMORY_ERROR):
@@ -1652,6 +1654,44 @@ class Api:
     def utf8_concat(self, parts: Sequence, sep=None, as_arrow=False):
         """concat (sep is None) / concat_ws of chunk lists and str / bytes literals."""
         return self.utf8_build("concat", None, parts, as_arrow=as_arrow) if sep is None else self.utf8_build("concat_ws", None, parts, sep, as_arrow=as_arrow)
+
+    # ---- text to values and back (rdf_utf8_parse / rdf_utf8_format)
+    @staticmethod
+    def _text_kind(kind, unit):
+        code = TEXT_KINDS[kind] if isinstance(kind, str) else int(kind)
+        return code, (TIME_SECOND if unit is None else int(unit))
+
+    def utf8_parse(self, chunks: Sequence, kind, unit=None, pattern=None, dtype=None, outs=None):
+        """rdf_utf8_parse: "bool" / "int" / "date" / "timestamp" (or the code) from text, by the kind's CAST grammar or, with
+        `pattern` (str / bytes), to_date / to_timestamp / unix_timestamp -> (one array per chunk, failed rows per chunk).
+        dtype: the integer dtype of an "int" call (default Int64); unit: of a "timestamp" call (default seconds)."""
+        code, unit = self._text_kind(kind, unit)
+        out_dt = {TEXT_BOOL: BOOL, TEXT_DATE: I32, TEXT_TIMESTAMP: I64}.get(code, I64 if dtype is None else int(dtype))
+        n = len(chunks)
+        carr = (rdf_utf8_array * max(1, n))(*[c.c_struct() for c in chunks])
+        raw, cp = self._utf8_pattern(pattern)
+        outs, co = self._utf8_pred_outs(out_dt, chunks, [True] * n, outs)
+        failed = (C.c_int64 * max(1, n))()
+        self._check(self._utf8_fn("utf8_parse")(carr, C.c_int64(n), C.c_int32(code), C.c_int32(unit), cp if pattern is not None else None,
+                                                C.c_int64(len(raw)), co, failed))
+        return self._finish(outs, co), [int(failed[i]) for i in range(n)]
+
+    def utf8_format_call(self, chunks: Sequence, kind, unit=None, pattern=None):
+        """-> (call(out_offsets, out_data) -> status, chunks, nullable per chunk) of one rdf_utf8_format call; utf8_format runs it
+        under the sizing rule, tests call it with buffers of their own."""
+        code, unit = self._text_kind(kind, unit)
+        n = len(chunks)
+        carr = _flat([chunks], n)
+        raw, cp = self._utf8_pattern(pattern)
+        fn = self._utf8_fn("utf8_format")
+        call = lambda co, cd: fn(carr, C.c_int64(n), C.c_int32(code), C.c_int32(unit), cp if pattern is not None else None, C.c_int64(len(raw)), co, cd)  # noqa: E731
+        return call, chunks, [(c.validity is not None) if isinstance(c, HostArray) else bool(c.validity_ptr) for c in chunks]
+
+    def utf8_format(self, chunks: Sequence, kind, unit=None, pattern=None, as_arrow=False):
+        """rdf_utf8_format: CAST(x AS STRING) of Boolean / integer / temporal chunks or, with `pattern`, date_format /
+        from_unix_time: one Utf8 result per chunk.  unit: the time unit of temporal storage (default seconds)."""
+        call, shape, nullable = self.utf8_format_call(chunks, kind, unit, pattern)
+        return self._utf8_run(call, shape, [c.length for c in shape], nullable, as_arrow)
 
     # ---- coalesce / case_when over text (rdf_utf8_coalesce / rdf_utf8_case_when)
     def utf8_select_call(self, parts: Sequence, conds=None):
