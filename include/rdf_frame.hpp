@@ -461,6 +461,7 @@ struct GenericVector {
 // Column (src/table.rs:134-344)
 
 struct Scalar;   // (Column::fill_null takes one; defined below)
+struct ListArray;   // (Column::split returns one; defined with the ArrayFunctions)
 class Column {
   public:
     Column() = default;
@@ -927,6 +928,37 @@ class Column {
             return rdf_utf8_substring_index(tc.txt.data(), (int64_t)tc.txt.size(), (const uint8_t*)delim.data(), (int64_t)delim.size(), count, oo, od);
         });
     }
+
+    // A row's content changed by what the row holds, on the device (rdf_utf8_replace / _translate / _initcap / _split; Spark 3's
+    // semantics, see the C header): each call runs twice under the sizing rule.  replace, translate and initcap return an
+    // ordinary Utf8 column with the input's chunking, a key for group_aggregate, joins and sort like any other.
+    //   replace(search, replacement)   every non-overlapping occurrence from the left; an empty search changes nothing
+    //   translate(matching, replace)   code point i of matching becomes code point i of replace, or is dropped
+    //   initcap()                      lower-cased; the first code point of the row and after every ' ' title-cased
+    //   split(delim, limit)            a LITERAL delimiter -> ONE ListArray over all chunks with a Utf8 child (text stays on the
+    //                                  host in this mirror), which ScalarFunctions::explode takes; defined below ListArray
+    Column replace(const std::string& search, const std::string& replacement) const {
+        need_text("replace");
+        const TextChunks tc = text_chunks("replace");
+        return text_build(tc, chunk_nullable(), field_.name, [&](rdf_out* oo, rdf_out* od) {
+            return rdf_utf8_replace(tc.txt.data(), (int64_t)tc.txt.size(), (const uint8_t*)search.data(), (int64_t)search.size(),
+                                    (const uint8_t*)replacement.data(), (int64_t)replacement.size(), oo, od);
+        });
+    }
+    Column translate(const std::string& matching, const std::string& replace) const {
+        need_text("translate");
+        const TextChunks tc = text_chunks("translate");
+        return text_build(tc, chunk_nullable(), field_.name, [&](rdf_out* oo, rdf_out* od) {
+            return rdf_utf8_translate(tc.txt.data(), (int64_t)tc.txt.size(), (const uint8_t*)matching.data(), (int64_t)matching.size(),
+                                      (const uint8_t*)replace.data(), (int64_t)replace.size(), oo, od);
+        });
+    }
+    Column initcap() const {
+        need_text("initcap");
+        const TextChunks tc = text_chunks("initcap");
+        return text_build(tc, chunk_nullable(), field_.name, [&](rdf_out* oo, rdf_out* od) { return rdf_utf8_initcap(tc.txt.data(), (int64_t)tc.txt.size(), oo, od); });
+    }
+    inline ListArray split(const std::string& delim, int64_t limit = -1) const;
 
     // Row hashes and digests, on the device (rdf_hash_columns / rdf_utf8_digest / rdf_utf8_crc32; Spark 3's semantics, see the
     // C header).
@@ -3370,6 +3402,17 @@ struct ScalarFunctions {
     static std::vector<ArrayRef> substring_index(const std::vector<ArrayRef>& arr, const std::string& delim, int64_t count) {
         return text_column(arr, "substring_index").substring_index(delim, count).data().chunks();
     }
+    // replace / translate / initcap / split over Utf8 arrays (initcap, translate and split are declared with empty bodies in
+    // src/functions/scalar.rs): Spark 3's semantics on the device (rdf_utf8_replace .. rdf_utf8_split).  split takes a LITERAL
+    // delimiter and returns ONE ListArray over all chunks whose child is a Utf8 array, so explode() above takes it as it is.
+    static std::vector<ArrayRef> replace(const std::vector<ArrayRef>& arr, const std::string& search, const std::string& replacement) {
+        return text_column(arr, "replace").replace(search, replacement).data().chunks();
+    }
+    static std::vector<ArrayRef> translate(const std::vector<ArrayRef>& arr, const std::string& matching, const std::string& replace) {
+        return text_column(arr, "translate").translate(matching, replace).data().chunks();
+    }
+    static std::vector<ArrayRef> initcap(const std::vector<ArrayRef>& arr) { return text_column(arr, "initcap").initcap().data().chunks(); }
+    static inline ListArray split(const std::vector<ArrayRef>& arr, const std::string& delim, int64_t limit = -1);
     // hash / xxhash64 / crc32 / md5 / sha1 / sha2 (declared with empty bodies, src/functions/scalar.rs:205, :265, :338, :389, :390):
     // Spark 3's semantics on the device (rdf_hash_columns / rdf_utf8_crc32 / rdf_utf8_digest).  hash and xxhash64 take the columns
     // as chunk lists of one chunking, numeric, Boolean or Utf8, and return Int32 / Int64 arrays that are never NULL; the digests
@@ -3803,7 +3846,16 @@ struct ListArray {
     int64_t len() const { return offsets->length - 1; }
     ArrayRef values() const { return child; }
     DataType value_type() const { return child->dtype; }
-    rdf_list_array view() const { rdf_list_array l; l.offsets = offsets->view(); l.values = child->view(); return l; }
+    rdf_list_array view() const {
+        rdf_list_array l;
+        l.offsets = offsets->view();
+        if (child->dtype == DataType::Utf8) {   // text stays on the host in this mirror: rdf_list_explode, which reads the offsets only, is the one call such a list goes to
+            std::memset(&l.values, 0, sizeof l.values);
+            l.values.dtype = RDF_U8;
+            l.values.mem = l.offsets.mem;
+        } else l.values = child->view();
+        return l;
+    }
     std::vector<int32_t> value_offsets() const { return offsets->values_to_host<int32_t>(); }
     int32_t value_offset(int64_t i) const { return offsets->value<int32_t>(i); }
     int32_t value_length(int64_t i) const { return offsets->value<int32_t>(i + 1) - offsets->value<int32_t>(i); }
@@ -3836,6 +3888,59 @@ struct ListArray {
         return out;
     }
 };
+
+// Column::split / ScalarFunctions::split (rdf_utf8_split): the sizing call, then the call into exactly sized host buffers; the
+// chunks' lists are joined into one ListArray whose child is one Utf8 array.
+inline ListArray Column::split(const std::string& delim, int64_t limit) const {
+    need_text("split");
+    const TextChunks tc = text_chunks("split");
+    const size_t n = tc.txt.size();
+    std::vector<std::vector<int32_t>> lo(n), eo(n);
+    std::vector<std::vector<uint8_t>> valid(n), data(n);
+    std::vector<rdf_out> ol(n), oe(n), od(n);
+    const std::vector<bool> nullable = chunk_nullable();
+    for (size_t i = 0; i < n; ++i) {
+        const int64_t rows = tc.txt[i].offsets.length - 1;
+        lo[i].assign((size_t)rows + 1, 0);
+        if (nullable[i]) valid[i].assign((size_t)((rows + 63) / 64 * 8 + 8), 0);
+        ol[i] = rdf_out{lo[i].data(), nullable[i] ? valid[i].data() : nullptr, rows + 1, 0, 0, RDF_I32, RDF_MEM_HOST};
+        oe[i] = rdf_out{nullptr, nullptr, 0, 0, 0, RDF_I32, RDF_MEM_HOST};
+        od[i] = rdf_out{nullptr, nullptr, 0, 0, 0, RDF_U8, RDF_MEM_HOST};
+    }
+    auto call = [&] {
+        return rdf_utf8_split(tc.txt.data(), (int64_t)n, (const uint8_t*)delim.data(), (int64_t)delim.size(), limit, ol.data(), oe.data(), od.data());
+    };
+    rdf_status st = call();
+    if (st == RDF_MEMORY_ERROR && n > 0 && oe[0].length > 0) {
+        for (size_t i = 0; i < n; ++i) {
+            eo[i].assign((size_t)oe[i].length, 0);
+            oe[i].values = eo[i].data();
+            oe[i].capacity = oe[i].length;
+            data[i].assign((size_t)od[i].length + 8, 0);
+            od[i].values = data[i].data();
+            od[i].capacity = od[i].length;
+        }
+        st = call();
+    }
+    check(st);
+    std::vector<int32_t> offsets{0};
+    std::vector<std::string> strs;
+    std::vector<bool> ok;
+    bool any_null = false;
+    for (size_t i = 0; i < n; ++i) {
+        const int64_t rows = ol[i].length - 1;
+        for (int64_t r = 0; r < rows; ++r) {
+            const bool bit = !nullable[i] || ((valid[i][(size_t)(r >> 3)] >> (r & 7)) & 1);
+            ok.push_back(bit);
+            any_null |= !bit;
+            for (int32_t e = lo[i][(size_t)r]; e < lo[i][(size_t)r + 1]; ++e)
+                strs.emplace_back((const char*)data[i].data() + eo[i][(size_t)e], (size_t)(eo[i][(size_t)e + 1] - eo[i][(size_t)e]));
+            offsets.push_back((int32_t)strs.size());
+        }
+    }
+    return ListArray::from_parts(offsets, Array::from_strings(std::move(strs)), any_null ? &ok : nullptr);
+}
+inline ListArray ScalarFunctions::split(const std::vector<ArrayRef>& arr, const std::string& delim, int64_t limit) { return text_column(arr, "split").split(delim, limit); }
 
 struct ArrayFunctions {
     // array.rs:15-37: NULL list -> NULL, else whether the row's slice holds `val`

@@ -676,6 +676,54 @@ rdf_status rdf_utf8_reverse(const rdf_utf8_array* chunks, int64_t nchunks, rdf_o
 rdf_status rdf_utf8_substring_index(const rdf_utf8_array* chunks, int64_t nchunks, const uint8_t* delim, int64_t delim_bytes,
                                     int64_t count, rdf_out* out_offsets, rdf_out* out_data);
 
+/* ------------------------------------------------------------------ Utf8 rewrites */
+
+/* A row's content changed by what the row holds: replace(phone, '-', ''), translate(s, 'áé', 'ae'), initcap(city) before a
+ * GROUP BY; split(tags, ',') -> rdf_list_explode -> rdf_utf8_take to turn a delimited cell into rows.  The reference declares
+ * initcap, translate and split with empty bodies (src/functions/scalar.rs), so these follow Spark 3; the executable model,
+ * with every rule below spelled out, is tests/utf8_rewrite_ref.py (Spark itself was not run).
+ * Inputs are taken exactly as rdf_utf8_trim takes them (row `offset`, value offsets that need not start at 0, validity at
+ * any bit offset, host or device memory, all one kind).  Outputs are chunked like the inputs under the one sizing rule of
+ * rdf_utf8_filter .. _upper (values == NULL, capacity == 0 is the sizing call; a capacity that is too small gives
+ * RDF_MEMORY_ERROR with every length set and nothing written; an output chunk above 2^31-1 bytes is RDF_COMPUTE_ERROR).  A
+ * NULL row gives a NULL row of zero bytes; an output whose rows can be NULL needs out_offsets[i].validity (split:
+ * out_list_offsets[i].validity); null_count is set.  Bytes are not validated and nothing outside a row is read.
+ *   replace    occurrences of `search` are found byte-wise from the left, each search resuming at the END of the previous hit
+ *              ('aaaaa', 'aa', 'b' -> 'bba'); every hit is replaced.  An empty search gives the row unchanged
+ *              (UTF8String.replace); an empty replacement deletes.
+ *   translate  both arguments are cut into units (a unit begins at every byte that is not a continuation byte and runs over
+ *              the continuation bytes after it; on valid UTF-8: the code points).  A unit of the row equal to unit i of
+ *              `matching` becomes unit i of `replace`, and is dropped when `replace` has no unit i; the first position of a
+ *              unit in `matching` decides; units of `replace` beyond matching's count are ignored.  A unit whose length is
+ *              not what its first byte announces (a stray continuation byte, a lead byte with too few or too many of them)
+ *              never matches and is copied.
+ *   initcap    title_words(lower(row)): lower is rdf_utf8_lower's mapping (one-to-many mappings, Final_Sigma); a word
+ *              begins at the first byte of the row and after every byte 0x20, and at no other white space
+ *              (UTF8String.toTitleCase); a word's first code point takes its SIMPLE title mapping (one code point: 'ǆ' ->
+ *              'ǅ', 'ß' stays).  Units that are not well-formed are copied.
+ *   split      `delim` is a LITERAL (Spark takes a regular expression; a delimiter without metacharacters means the same).
+ *              Hits are found as in replace.  limit > 0: only the first limit - 1 hits split, so the last element holds the
+ *              rest; limit <= 0: every hit splits.  Trailing empty strings are kept ('a,b,,c,' -> 5 elements), the empty row
+ *              gives [''], a NULL row a NULL list.  The result is a List<Utf8>: out_list_offsets[i] is RDF_I32, rows + 1
+ *              entries from 0, with the rows' validity: the `offsets` member of an rdf_list_array, as rdf_list_explode
+ *              takes it; out_offsets[i] (RDF_I32, elements + 1 entries, no validity) and out_data[i] are the child Utf8
+ *              chunk, as rdf_utf8_take takes it.  On return the lengths of all three are set; a capacity of out_offsets or
+ *              out_data that is too small, or a NULL `values` there, is RDF_MEMORY_ERROR: all lengths set, nothing written.
+ * Errors, all before any device work, in this order, RDF_INVALID_ARGUMENT unless said otherwise: a literal (search,
+ * replacement, matching, replace, delim; in argument order) whose length is negative, or above RDF_UTF8_PATTERN_MAX, or a
+ * NULL pointer with a positive length; an empty delim; negative nchunks or a NULL list with nchunks > 0 (nchunks == 0 is
+ * RDF_OK here); offsets / data of the wrong dtype; outputs of the wrong dtype; mixed memory kinds; a row-offsets output
+ * without a buffer, a negative capacity, a data capacity without a buffer (not for split, where that is the sizing call); a
+ * missing validity buffer; a row-offsets capacity below rows + 1: RDF_MEMORY_ERROR with that length set; no device:
+ * RDF_DEVICE_ERROR. */
+rdf_status rdf_utf8_replace(const rdf_utf8_array* chunks, int64_t nchunks, const uint8_t* search, int64_t search_bytes,
+                            const uint8_t* replacement, int64_t replacement_bytes, rdf_out* out_offsets, rdf_out* out_data);
+rdf_status rdf_utf8_translate(const rdf_utf8_array* chunks, int64_t nchunks, const uint8_t* matching, int64_t matching_bytes,
+                              const uint8_t* replace, int64_t replace_bytes, rdf_out* out_offsets, rdf_out* out_data);
+rdf_status rdf_utf8_initcap(const rdf_utf8_array* chunks, int64_t nchunks, rdf_out* out_offsets, rdf_out* out_data);
+rdf_status rdf_utf8_split(const rdf_utf8_array* chunks, int64_t nchunks, const uint8_t* delim, int64_t delim_bytes, int64_t limit,
+                          rdf_out* out_list_offsets, rdf_out* out_offsets, rdf_out* out_data);
+
 /* ------------------------------------------------------------------ text to values and back
  *
  * ScalarFunctions::{to_date(s, fmt), to_timestamp, unix_timestamp, from_unix_time, date_format} (src/functions/scalar.rs

@@ -281,6 +281,16 @@ pub mod sys {
         pub fn rdf_utf8_reverse(chunks: *const rdf_utf8_array, nchunks: i64, out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
         pub fn rdf_utf8_substring_index(chunks: *const rdf_utf8_array, nchunks: i64, delim: *const u8, delim_bytes: i64, count: i64,
                                         out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
+        // Utf8 rewrites (ScalarFunctions::initcap / translate / split, declared with empty bodies, and replace): the sizing rule of
+        // rdf_utf8_trim.  split takes a LITERAL delimiter and returns a List<Utf8>: out_list_offsets (rows + 1 entries, with the rows'
+        // validity) is the `offsets` member of an rdf_list_array; out_offsets / out_data are the child Utf8 chunk, both sized in two calls.
+        pub fn rdf_utf8_replace(chunks: *const rdf_utf8_array, nchunks: i64, search: *const u8, search_bytes: i64,
+                                replacement: *const u8, replacement_bytes: i64, out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
+        pub fn rdf_utf8_translate(chunks: *const rdf_utf8_array, nchunks: i64, matching: *const u8, matching_bytes: i64,
+                                  replace: *const u8, replace_bytes: i64, out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
+        pub fn rdf_utf8_initcap(chunks: *const rdf_utf8_array, nchunks: i64, out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
+        pub fn rdf_utf8_split(chunks: *const rdf_utf8_array, nchunks: i64, delim: *const u8, delim_bytes: i64, limit: i64,
+                              out_list_offsets: *mut rdf_out, out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
         // text to values and back (src/functions/scalar.rs: date_format :209, from_unix_time :262, to_date :459, to_timestamp :461,
         // unix_timestamp :473, and CAST between Utf8 and Boolean / integer / date / timestamp): kind 0 .. 3 = bool, int, date,
         // timestamp; pattern null = the CAST grammar, else a datetime pattern.  parse: a row that does not parse is NULL, so every

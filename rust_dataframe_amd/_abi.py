@@ -1655,6 +1655,107 @@ class Api:
         """concat (sep is None) / concat_ws of chunk lists and str / bytes literals."""
         return self.utf8_build("concat", None, parts, as_arrow=as_arrow) if sep is None else self.utf8_build("concat_ws", None, parts, sep, as_arrow=as_arrow)
 
+    # ---- Utf8 rewrites: a row's content changed by what it holds (rdf_utf8_replace / _translate / _initcap / _split)
+    def _utf8_rewrite_call(self, name, chunks, lits, tail=()):
+        n = len(chunks)
+        carr = (rdf_utf8_array * max(1, n))(*[c.c_struct() for c in chunks])
+        args = []
+        for lit in lits:
+            raw, cp = self._utf8_pattern(lit)
+            args += [cp, C.c_int64(len(raw))]
+        fn = self._utf8_fn(name)
+        call = lambda *outs, keep=(carr, args): fn(carr, C.c_int64(n), *args, *tail, *outs)  # noqa: E731
+        return call, chunks, [self._utf8_nullable(c) for c in chunks]
+
+    def utf8_replace_call(self, chunks: Sequence, search, replacement):
+        """-> (call(out_offsets, out_data) -> status, chunks, nullable per chunk), as utf8_build_call returns them."""
+        return self._utf8_rewrite_call("utf8_replace", chunks, [search, replacement])
+
+    def utf8_translate_call(self, chunks: Sequence, matching, replace):
+        return self._utf8_rewrite_call("utf8_translate", chunks, [matching, replace])
+
+    def utf8_initcap_call(self, chunks: Sequence):
+        return self._utf8_rewrite_call("utf8_initcap", chunks, [])
+
+    def utf8_split_call(self, chunks: Sequence, delim, limit: int = -1):
+        """-> (call(out_list_offsets, out_offsets, out_data) -> status, chunks, nullable per chunk)"""
+        return self._utf8_rewrite_call("utf8_split", chunks, [delim], (C.c_int64(int(limit)),))
+
+    def utf8_replace(self, chunks: Sequence, search, replacement, as_arrow=False):
+        """replace(row, search, replacement): every non-overlapping occurrence from the left; one result per chunk."""
+        call, shape, nullable = self.utf8_replace_call(chunks, search, replacement)
+        return self._utf8_run(call, shape, [c.length for c in shape], nullable, as_arrow)
+
+    def utf8_translate(self, chunks: Sequence, matching, replace, as_arrow=False):
+        """translate(row, matching, replace): code point i of matching becomes code point i of replace, or is dropped."""
+        call, shape, nullable = self.utf8_translate_call(chunks, matching, replace)
+        return self._utf8_run(call, shape, [c.length for c in shape], nullable, as_arrow)
+
+    def utf8_initcap(self, chunks: Sequence, as_arrow=False):
+        """initcap(row): lower-cased, the first code point after every space (and the first of the row) title-cased."""
+        call, shape, nullable = self.utf8_initcap_call(chunks)
+        return self._utf8_run(call, shape, [c.length for c in shape], nullable, as_arrow)
+
+    def utf8_split(self, chunks: Sequence, delim, limit: int = -1, as_arrow=False):
+        """split(row, delim, limit) with a literal delimiter -> per chunk a List<Utf8> as (list, child): a HostList /
+        DeviceList that holds the list offsets and validity (rdf_list_explode takes it as it is; its `values` member is the
+        child's Int32 offsets array, which that call never reads) and the child HostUtf8 / DeviceUtf8 with one row per
+        element (rdf_utf8_take takes it).  as_arrow=True: pyarrow ListArrays of strings ("pylist": python lists).  The
+        sizing call, then the call into exactly sized buffers."""
+        call, shape, nullable = self.utf8_split_call(chunks, delim, limit)
+        device = any(isinstance(c, DeviceUtf8) for c in chunks)
+        rows = [c.length for c in shape]
+
+        def outs(ecaps, dcaps):
+            lists = [self._window_out(I32, r + 1, device, nl) for r, nl in zip(rows, nullable)]
+            offs = [self._window_out(I32, e, device, False) if e else None for e in ecaps]
+            co, cd, keep = self._utf8_outs(shape, rows, [False] * len(rows), device, dcaps)
+            mem = MEM_DEVICE if device else MEM_HOST
+            cl = (rdf_out * max(1, len(rows)))(*[x.out_struct() for x in lists])
+            ce = (rdf_out * max(1, len(rows)))(*[x.out_struct() if x is not None else rdf_out(None, None, 0, 0, 0, I32, mem) for x in offs])
+            return cl, ce, cd, lists, offs, keep
+
+        n = len(rows)
+        cl, ce, cd, lists, offs, keep = outs([0] * n, [0] * n)
+        st = call(cl, ce, cd)
+        if st != RDF_MEMORY_ERROR:
+            self._check(st)
+        if n and st == RDF_MEMORY_ERROR:
+            cl, ce, cd, lists, offs, keep = outs([ce[i].length for i in range(n)], [cd[i].length for i in range(n)])
+            self._check(call(cl, ce, cd))
+        res = []
+        for i in range(n):
+            elems = ce[i].length - 1
+            lists[i].length = rows[i] + 1
+            lists[i].null_count = cl[i].null_count
+            offs[i].length = elems + 1
+            if device:
+                import torch
+                _, dt, _ = keep[i]
+                lst = DeviceList(lists[i].values_ptr, rows[i], offs[i], lists[i].validity_ptr if nullable[i] else None, 0, keep=lists[i].keep)
+                child = DeviceUtf8(offs[i].values_ptr, dt.data_ptr() if dt is not None else 0, cd[i].length, elems, None, 0, 0, 0,
+                                   keep=(offs[i].keep[0].view(torch.int32), dt, None))
+            else:
+                _, db, _ = keep[i]
+                lst = HostList(lists[i].values, offs[i], lists[i].validity if nullable[i] else None, 0, rows[i])
+                child = HostUtf8(offs[i].values, db if db is not None else np.zeros(8, dtype=np.uint8), None, 0, elems, 0, 0)
+            if as_arrow:
+                hl = lst if not device else HostList(lst.keep[0].cpu().numpy().view(np.int32).copy(), None,
+                                                    lst.keep[1].cpu().numpy().copy() if nullable[i] else None, 0, rows[i])
+                hc = child.to_host() if device else child
+                lo = hl.offsets[:rows[i] + 1]
+                valid = unpack_bits(hl.validity, 0, rows[i]) if hl.validity is not None else np.ones(rows[i], dtype=bool)
+                if as_arrow == "pylist":
+                    flat = hc.to_pylist()
+                    res.append([flat[lo[r]:lo[r + 1]] if valid[r] else None for r in range(rows[i])])
+                else:
+                    import pyarrow as pa
+                    mask = pa.array(~valid) if hl.validity is not None else None
+                    res.append(pa.ListArray.from_arrays(pa.array(lo, type=pa.int32()), hc.to_arrow(), mask=mask))
+            else:
+                res.append((lst, child))
+        return res
+
     # ---- text to values and back (rdf_utf8_parse / rdf_utf8_format)
     @staticmethod
     def _text_kind(kind, unit):

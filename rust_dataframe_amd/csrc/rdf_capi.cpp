@@ -39,6 +39,8 @@
 #include "rdf_textconv.h"
 #include "rdf_utf8_pattern.h"
 #include "rdf_utf8_build.h"
+#define RDF_UTF8_REWRITE_NO_CASE   // the compiler of the translate table is all the host side needs
+#include "rdf_utf8_rewrite.h"
 #include "rdf_digest.h"
 #include "rdf_digest_kernels.h"
 
@@ -2878,6 +2880,7 @@ rdf_status groupby_sum_fallback(const rdf_array* keys, const rdf_array* values, 
 #include "rdf_capi_datetime.inc"
 #include "rdf_capi_utf8_pred.inc"
 #include "rdf_capi_utf8_build.inc"
+#include "rdf_capi_utf8_rewrite.inc"
 #include "rdf_capi_digest.inc"
 #include "rdf_capi_select.inc"
 #include "rdf_capi_textconv.inc"

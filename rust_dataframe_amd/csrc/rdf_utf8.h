@@ -191,3 +191,43 @@ struct Utf8BuildArgs {
 hipError_t launch_utf8_build_size(const Utf8BuildArgs& a, hipStream_t s);     // blen, aux, null_counts
 hipError_t launch_utf8_build_totals(const Utf8BuildArgs& a, hipStream_t s);   // tot
 hipError_t launch_utf8_build_write(const Utf8BuildArgs& a, hipStream_t s);    // offsets, validity, the bytes
+
+// ---- rewrites of Utf8 columns by their content: replace, translate, initcap, split (rdf_utf8_rewrite.hip; host side:
+// rdf_capi_utf8_rewrite.inc; what is decided about one row: rdf_utf8_rewrite.h).  Size pass in the tiles of the predicates,
+// the scans, and a SOURCE-driven write pass: a block assembles the output of a run of rows in an LDS image of
+// kUtf8RewriteImage bytes and streams it out in aligned 16-byte stores.  Output chunk c has the rows of input chunk c; for
+// split it is the child Utf8 chunk (one row per element) and list_offs are the list's offsets.
+struct Utf8TranslateTable;
+constexpr int kUtf8RewriteImage = 16384;
+struct Utf8RewriteOut {
+    int32_t* offs;        // rows + 1 entries (split: elems + 1)
+    uint8_t* valid;       // validity of the rows, nullptr = not requested
+    uint8_t* data;
+    int32_t* list_offs;   // split: rows + 1 entries
+    int64_t  row_start, rows;
+    int64_t  byte_start, bytes;   // in the scan of the row lengths
+    int64_t  elem_start, elems;   // in the scan of the rows' element counts (split)
+};
+struct Utf8RewriteArgs {
+    const Utf8Chunk* chunks;
+    int64_t          nchunks;
+    const int64_t*   tile_start;   // nchunks + 1 entries, tiles of kUtf8PredThreads rows
+    int64_t          ntiles;
+    int32_t          op;           // U8R_*
+    const uint8_t*   lit;          // search / delimiter (device copy)
+    const uint8_t*   rep;          // replacement
+    int32_t          lit_bytes, rep_bytes;
+    const Utf8TranslateTable* table;   // translate (device copy)
+    int64_t          maxhits;      // split: the hits that split; replace: all
+    int64_t          n;            // rows
+    int64_t*         blen;         // per row: output bytes (scanned into bscan)
+    int64_t*         elen;         // split: per row: elements (scanned into escan)
+    const int64_t*   bscan;        // n + 1 entries
+    const int64_t*   escan;
+    int64_t*         tot;          // per chunk: bytes, rows, elements
+    unsigned long long* null_counts;   // per chunk
+    const Utf8RewriteOut* outs;
+};
+hipError_t launch_utf8_rewrite_size(const Utf8RewriteArgs& a, hipStream_t s);     // blen, elen, null_counts
+hipError_t launch_utf8_rewrite_totals(const Utf8RewriteArgs& a, hipStream_t s);   // tot
+hipError_t launch_utf8_rewrite_write(const Utf8RewriteArgs& a, hipStream_t s);    // offsets, validity, the bytes
