@@ -960,6 +960,47 @@ class Column {
     }
     inline ListArray split(const std::string& delim, int64_t limit = -1) const;
 
+    // Regular expressions, on the device (rdf_utf8_regexp_match / _count / _extract / _replace / _split; java.util.regex's
+    // leftmost-first matching over the accepted syntax, see the C header): a pattern outside it, or past a size cap, throws
+    // before any device work.  A NULL row gives NULL.
+    //   rlike(pattern)                  a match exists anywhere in the row                                      -> Boolean
+    //   regexp_count(pattern)           the matches Matcher.find finds                                          -> Int32
+    //   regexp_extract(pattern, 0)      the first match, or "" (group != 0 throws: capture groups are not built) -> Utf8
+    //   regexp_replace(pattern, rep)    every match replaced; `\x` in rep stands for x, an unescaped `$` throws -> Utf8
+    //   split_regexp(pattern, limit)    String.split(regex, limit) -> ONE ListArray as split() returns it; defined below ListArray
+    Column rlike(const std::string& pattern, bool on_host = false) const {
+        need_text("rlike");
+        const TextChunks tc = text_chunks("rlike");
+        return text_result(DataType::Boolean, tc, chunk_nullable(), "bool_filter", on_host, [&](rdf_out* outs) {
+            check(rdf_utf8_regexp_match(tc.txt.data(), (int64_t)tc.txt.size(), (const uint8_t*)pattern.data(), (int64_t)pattern.size(), outs));
+        });
+    }
+    Column regexp_count(const std::string& pattern, bool on_host = false) const {
+        need_text("regexp_count");
+        const TextChunks tc = text_chunks("regexp_count");
+        return text_result(DataType::Int32, tc, chunk_nullable(), field_.name, on_host, [&](rdf_out* outs) {
+            check(rdf_utf8_regexp_count(tc.txt.data(), (int64_t)tc.txt.size(), (const uint8_t*)pattern.data(), (int64_t)pattern.size(), outs));
+        });
+    }
+    Column regexp_extract(const std::string& pattern, int32_t group = 0) const {
+        need_text("regexp_extract");
+        const TextChunks tc = text_chunks("regexp_extract");
+        return text_build(tc, chunk_nullable(), field_.name, [&](rdf_out* oo, rdf_out* od) {
+            return rdf_utf8_regexp_extract(tc.txt.data(), (int64_t)tc.txt.size(), (const uint8_t*)pattern.data(), (int64_t)pattern.size(), group, oo, od);
+        });
+    }
+    Column regexp_replace(const std::string& pattern, const std::string& replacement) const {
+        need_text("regexp_replace");
+        const TextChunks tc = text_chunks("regexp_replace");
+        return text_build(tc, chunk_nullable(), field_.name, [&](rdf_out* oo, rdf_out* od) {
+            return rdf_utf8_regexp_replace(tc.txt.data(), (int64_t)tc.txt.size(), (const uint8_t*)pattern.data(), (int64_t)pattern.size(),
+                                           (const uint8_t*)replacement.data(), (int64_t)replacement.size(), oo, od);
+        });
+    }
+    inline ListArray split_regexp(const std::string& pattern, int64_t limit = -1) const;
+    // split() and split_regexp(): `call(chunks, nchunks, list offsets, element offsets, data)` run twice under the sizing rule
+    template <class Call> inline ListArray split_lists(const char* what, Call call) const;
+
     // Row hashes and digests, on the device (rdf_hash_columns / rdf_utf8_digest / rdf_utf8_crc32; Spark 3's semantics, see the
     // C header).
     //   hash / xxhash64   Spark's Murmur3_x86_32 / XXH64 over the columns in order with a seed (42 is Spark's), NULLs skipped:
@@ -1140,7 +1181,7 @@ struct Scalar {
 struct BooleanFilter;
 using FilterRef = std::shared_ptr<const BooleanFilter>;
 struct BooleanFilter {
-    enum Kind { InputScalar, InputColumn, Not, And, Or, Gt, Ge, Eq, Ne, Lt, Le, StartsWith, EndsWith, Contains, Like } kind;
+    enum Kind { InputScalar, InputColumn, Not, And, Or, Gt, Ge, Eq, Ne, Lt, Le, StartsWith, EndsWith, Contains, Like, RLike } kind;
     Scalar scalar_v;
     std::string column_name;
     int32_t escape = -1;   // Like: -1 = none, or one ASCII byte
@@ -1164,6 +1205,8 @@ struct BooleanFilter {
     static FilterRef like(FilterRef a, FilterRef b, int32_t escape = -1) {
         auto f = std::make_shared<BooleanFilter>(); f->kind = Like; f->l = std::move(a); f->r = std::move(b); f->escape = escape; return f;
     }
+    // RLIKE: the String scalar is a regular expression (rdf_utf8_regexp_match), true where a match exists anywhere in the row
+    static FilterRef rlike(FilterRef a, FilterRef b) { return make(RLike, a, b); }
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -1192,8 +1235,8 @@ inline ExprRef filter_to_expr(const FilterRef& f, const std::function<ExprRef(co
         case BooleanFilter::InputScalar:
             if (f->scalar_v.kind == Scalar::String) throw DataFrameError(DataFrameError::ComputeError, "a String scalar compares with Utf8 columns only");
             return Expr::literal(f->scalar_v, f->scalar_v.rdf_type());
-        case BooleanFilter::StartsWith: case BooleanFilter::EndsWith: case BooleanFilter::Contains: case BooleanFilter::Like:
-            throw DataFrameError(DataFrameError::ComputeError, "starts_with / ends_with / contains / like take a Utf8 column and a String scalar");
+        case BooleanFilter::StartsWith: case BooleanFilter::EndsWith: case BooleanFilter::Contains: case BooleanFilter::Like: case BooleanFilter::RLike:
+            throw DataFrameError(DataFrameError::ComputeError, "starts_with / ends_with / contains / like / rlike take a Utf8 column and a String scalar");
         case BooleanFilter::InputColumn: return resolve(f->column_name);
         case BooleanFilter::Not: return Expr::make(RDF_OP_NOT, filter_to_expr(f->l, resolve));
         default: break;
@@ -2489,7 +2532,7 @@ class DataFrame {
 
     // evaluate_boolean_filter (:612-624): one BooleanArray mask per RecordBatch, computed in ONE launch
     Column evaluate_boolean_filter(const FilterRef& filter) const {
-        // The text leaves — a comparison or starts_with / ends_with / contains / like over a Utf8 column and a String scalar,
+        // The text leaves — a comparison or starts_with / ends_with / contains / like / rlike over a Utf8 column and a String scalar,
         // or a comparison of two Utf8 columns — are evaluated on their own (rdf_utf8_predicate / rdf_utf8_compare) into Boolean
         // columns that stand in for them, under private names, in what rdf_predicate then evaluates.
         std::vector<std::pair<std::string, Column>> leaves;
@@ -2526,6 +2569,7 @@ class DataFrame {
             case BooleanFilter::EndsWith: op = RDF_UTF8_ENDS_WITH; comparison = false; break;
             case BooleanFilter::Contains: op = RDF_UTF8_CONTAINS; comparison = false; break;
             case BooleanFilter::Like: op = RDF_UTF8_LIKE; comparison = false; break;
+            case BooleanFilter::RLike: comparison = false; break;   // op stays -1: rdf_utf8_regexp_match, not rdf_utf8_predicate
             case BooleanFilter::Not: case BooleanFilter::And: case BooleanFilter::Or: {
                 auto g = std::make_shared<BooleanFilter>(*f);
                 g->l = lower_text_leaves(f->l, leaves);
@@ -2536,7 +2580,10 @@ class DataFrame {
         }
         const bool on_host = is_host();
         Column mask;
-        if (is_text_column(f->l) && is_text_scalar(f->r)) {
+        if (f->kind == BooleanFilter::RLike) {
+            if (!is_text_column(f->l) || !is_text_scalar(f->r)) return f;
+            mask = column_by_name(f->l->column_name).rlike(f->r->scalar_v.s, on_host);
+        } else if (is_text_column(f->l) && is_text_scalar(f->r)) {
             mask = column_by_name(f->l->column_name).utf8_predicate(op, f->r->scalar_v.s, f->escape, on_host);
         } else if (comparison && is_text_scalar(f->l) && is_text_column(f->r)) {   // 'x' < col  is  col > 'x'
             static const int32_t flipped[6] = {RDF_UTF8_EQ, RDF_UTF8_NE, RDF_UTF8_GT, RDF_UTF8_GE, RDF_UTF8_LT, RDF_UTF8_LE};
@@ -3413,6 +3460,20 @@ struct ScalarFunctions {
     }
     static std::vector<ArrayRef> initcap(const std::vector<ArrayRef>& arr) { return text_column(arr, "initcap").initcap().data().chunks(); }
     static inline ListArray split(const std::vector<ArrayRef>& arr, const std::string& delim, int64_t limit = -1);
+    // rlike / regexp_count / regexp_extract / regexp_replace / split_regexp over Utf8 arrays (regexp_extract and regexp_replace are
+    // declared with empty bodies in src/functions/scalar.rs): java.util.regex's leftmost-first matching on the device
+    // (rdf_utf8_regexp_match .. rdf_utf8_regexp_split) -> Boolean / Int32 / Utf8 arrays, and ONE ListArray as split returns it.
+    static std::vector<ArrayRef> rlike(const std::vector<ArrayRef>& arr, const std::string& pattern) { return text_column(arr, "rlike").rlike(pattern).data().chunks(); }
+    static std::vector<ArrayRef> regexp_count(const std::vector<ArrayRef>& arr, const std::string& pattern) {
+        return text_column(arr, "regexp_count").regexp_count(pattern).data().chunks();
+    }
+    static std::vector<ArrayRef> regexp_extract(const std::vector<ArrayRef>& arr, const std::string& pattern, int32_t group = 0) {
+        return text_column(arr, "regexp_extract").regexp_extract(pattern, group).data().chunks();
+    }
+    static std::vector<ArrayRef> regexp_replace(const std::vector<ArrayRef>& arr, const std::string& pattern, const std::string& replacement) {
+        return text_column(arr, "regexp_replace").regexp_replace(pattern, replacement).data().chunks();
+    }
+    static inline ListArray split_regexp(const std::vector<ArrayRef>& arr, const std::string& pattern, int64_t limit = -1);
     // hash / xxhash64 / crc32 / md5 / sha1 / sha2 (declared with empty bodies, src/functions/scalar.rs:205, :265, :338, :389, :390):
     // Spark 3's semantics on the device (rdf_hash_columns / rdf_utf8_crc32 / rdf_utf8_digest).  hash and xxhash64 take the columns
     // as chunk lists of one chunking, numeric, Boolean or Utf8, and return Int32 / Int64 arrays that are never NULL; the digests
@@ -3889,11 +3950,11 @@ struct ListArray {
     }
 };
 
-// Column::split / ScalarFunctions::split (rdf_utf8_split): the sizing call, then the call into exactly sized host buffers; the
-// chunks' lists are joined into one ListArray whose child is one Utf8 array.
-inline ListArray Column::split(const std::string& delim, int64_t limit) const {
-    need_text("split");
-    const TextChunks tc = text_chunks("split");
+// Column::split / split_regexp and their ScalarFunctions (rdf_utf8_split / rdf_utf8_regexp_split): the sizing call, then the call
+// into exactly sized host buffers; the chunks' lists are joined into one ListArray whose child is one Utf8 array.
+template <class Call> inline ListArray Column::split_lists(const char* what, Call split_call) const {
+    need_text(what);
+    const TextChunks tc = text_chunks(what);
     const size_t n = tc.txt.size();
     std::vector<std::vector<int32_t>> lo(n), eo(n);
     std::vector<std::vector<uint8_t>> valid(n), data(n);
@@ -3907,9 +3968,7 @@ inline ListArray Column::split(const std::string& delim, int64_t limit) const {
         oe[i] = rdf_out{nullptr, nullptr, 0, 0, 0, RDF_I32, RDF_MEM_HOST};
         od[i] = rdf_out{nullptr, nullptr, 0, 0, 0, RDF_U8, RDF_MEM_HOST};
     }
-    auto call = [&] {
-        return rdf_utf8_split(tc.txt.data(), (int64_t)n, (const uint8_t*)delim.data(), (int64_t)delim.size(), limit, ol.data(), oe.data(), od.data());
-    };
+    auto call = [&] { return split_call(tc.txt.data(), (int64_t)n, ol.data(), oe.data(), od.data()); };
     rdf_status st = call();
     if (st == RDF_MEMORY_ERROR && n > 0 && oe[0].length > 0) {
         for (size_t i = 0; i < n; ++i) {
@@ -3940,7 +3999,20 @@ inline ListArray Column::split(const std::string& delim, int64_t limit) const {
     }
     return ListArray::from_parts(offsets, Array::from_strings(std::move(strs)), any_null ? &ok : nullptr);
 }
+inline ListArray Column::split(const std::string& delim, int64_t limit) const {
+    return split_lists("split", [&](const rdf_utf8_array* c, int64_t n, rdf_out* ol, rdf_out* oe, rdf_out* od) {
+        return rdf_utf8_split(c, n, (const uint8_t*)delim.data(), (int64_t)delim.size(), limit, ol, oe, od);
+    });
+}
+inline ListArray Column::split_regexp(const std::string& pattern, int64_t limit) const {
+    return split_lists("split_regexp", [&](const rdf_utf8_array* c, int64_t n, rdf_out* ol, rdf_out* oe, rdf_out* od) {
+        return rdf_utf8_regexp_split(c, n, (const uint8_t*)pattern.data(), (int64_t)pattern.size(), limit, ol, oe, od);
+    });
+}
 inline ListArray ScalarFunctions::split(const std::vector<ArrayRef>& arr, const std::string& delim, int64_t limit) { return text_column(arr, "split").split(delim, limit); }
+inline ListArray ScalarFunctions::split_regexp(const std::vector<ArrayRef>& arr, const std::string& pattern, int64_t limit) {
+    return text_column(arr, "split_regexp").split_regexp(pattern, limit);
+}
 
 struct ArrayFunctions {
     // array.rs:15-37: NULL list -> NULL, else whether the row's slice holds `val`

@@ -724,6 +724,63 @@ rdf_status rdf_utf8_initcap(const rdf_utf8_array* chunks, int64_t nchunks, rdf_o
 rdf_status rdf_utf8_split(const rdf_utf8_array* chunks, int64_t nchunks, const uint8_t* delim, int64_t delim_bytes, int64_t limit,
                           rdf_out* out_list_offsets, rdf_out* out_offsets, rdf_out* out_data);
 
+/* ------------------------------------------------------------------ regular expressions over Utf8
+ *
+ * Spark 3's rlike, regexp_count, regexp_extract(s, p, 0), regexp_replace and split(s, regex, limit): java.util.regex, that is
+ * LEFTMOST-FIRST matching (a|ab on "ab" matches "a").  The pattern compiles once per call, on the host, into two small DFAs
+ * (the forward one finds where the leftmost-first match ends, the reverse one where it starts); the device walks them, a
+ * class look-up and a table entry per row byte, a lane a row.  There is no backtracking: a pattern cannot make a kernel run long.
+ *
+ * accepted: literals; \ \. \t \n \r \f \xhh \uhhhh and a backslash before ASCII punctuation; `.` (every code point but \n \r
+ *   U+0085 U+2028 U+2029); classes [abc] [a-z] [^..] with \d \w \s inside; \d \D \w \W \s \S (ASCII definitions, \s is
+ *   [ \t\n\x0B\f\r]); ( ) and (?: ), which both only group; |; * + ? {n} {n,} {n,m}, greedy and lazy; ^ \A (row start) and
+ *   $ \z (row end); one leading (?i) (?s) (?is) (?si); (?i) folds ASCII letters only.
+ * refused with RDF_INVALID_ARGUMENT, rdf_last_error() naming the construct and its byte in the pattern: backreferences,
+ *   look-ahead and look-behind, atomic and named groups, possessive quantifiers, \b \B \G \Z \R \X \h \v, \p{..}, POSIX classes,
+ *   && and a nested [ in a class, a ] or ^] that opens a class, \Q..\E, octal escapes, flags anywhere but at the front, the
+ *   flags m x u d U, a dangling {, a quantifier without an operand, {n,m} with n > m or a count above 1000, counted repetition
+ *   past 1000 expanded leaves; and, because their Java meaning is not certain, a quantifier on a quantifier, a quantifier on
+ *   an anchor and a quantifier that may repeat more than once over an operand that can match the empty string.  A pattern
+ *   whose program passes 4096 instructions, whose DFAs pass 2048 states each or whose tables pass 256 KiB is refused with
+ *   the count in the message; it is never run wrong.
+ * KNOWN DIFFERENCE FROM SPARK: `$` is Java's \z; Java's `$` also matches before a final line terminator.  After an empty
+ *   match the search moves on by a code point, where Java moves by a UTF-16 unit.
+ * bytes: rows are not validated; the pattern must be UTF-8.  Every consuming element matches one well-formed UTF-8 sequence
+ *   (RFC 3629) and nothing else: a stray or truncated byte is matched by no element, not by `.` and not by [^a].  A match,
+ *   the empty one included, begins only at a byte that is not a continuation byte, or at the row's end.
+ * matches are found as Matcher.find finds them: from byte 0; after a non-empty match from its end; after an empty match at p
+ *   from the next allowed start after p; ^ holds at byte 0 only.  A NULL row gives NULL.
+ *
+ *   rdf_utf8_regexp_match    rlike: a match exists.  RDF_BOOL masks under the conventions of rdf_utf8_predicate.
+ *   rdf_utf8_regexp_count    the matches.  RDF_I32 under the conventions of rdf_utf8_measure.
+ *   rdf_utf8_regexp_extract  the first match's bytes, '' when there is none.  group must be 0 ("capture groups are not
+ *                            built"); the ABI does not change when they are.  Outputs as rdf_utf8_replace's.
+ *   rdf_utf8_regexp_replace  every match replaced.  In the replacement \x stands for x; a trailing backslash and any
+ *                            unescaped $ are refused.  Outputs as rdf_utf8_replace's, under the one sizing rule.
+ *   rdf_utf8_regexp_split    String.split(regex, limit) as Spark 3 calls it: a zero-width match at byte 0 never splits;
+ *                            limit > 0: only the first limit - 1 hits split; limit <= 0: every hit; trailing empty strings
+ *                            are kept; the empty row gives ['']; an empty pattern is valid.  Outputs as rdf_utf8_split's.
+ *   rdf_utf8_regexp_info     host only, needs no device: the counts the caps are defined on.
+ *
+ * Order of the checks: pattern_bytes outside 0 .. RDF_UTF8_PATTERN_MAX, a null pattern with bytes; the pattern compiled
+ * (syntax, then the caps); group != 0; the replacement's length and pointer, then its escapes; then the checks of
+ * rdf_utf8_predicate (match, count) or of rdf_utf8_replace / rdf_utf8_split in their order, nchunks == 0 being RDF_OK
+ * there; no device: RDF_DEVICE_ERROR.  Every refusal of the pattern, group or replacement comes before any device work. */
+typedef struct {
+    int32_t program_len, forward_states, reverse_states, classes;
+    int64_t table_bytes;
+    int32_t can_match_empty, anchored_start;
+} rdf_regexp_info;
+rdf_status rdf_utf8_regexp_info(const uint8_t* pattern, int64_t pattern_bytes, rdf_regexp_info* out);
+rdf_status rdf_utf8_regexp_match(const rdf_utf8_array* chunks, int64_t nchunks, const uint8_t* pattern, int64_t pattern_bytes, rdf_out* mask);
+rdf_status rdf_utf8_regexp_count(const rdf_utf8_array* chunks, int64_t nchunks, const uint8_t* pattern, int64_t pattern_bytes, rdf_out* out);
+rdf_status rdf_utf8_regexp_extract(const rdf_utf8_array* chunks, int64_t nchunks, const uint8_t* pattern, int64_t pattern_bytes, int32_t group,
+                                   rdf_out* out_offsets, rdf_out* out_data);
+rdf_status rdf_utf8_regexp_replace(const rdf_utf8_array* chunks, int64_t nchunks, const uint8_t* pattern, int64_t pattern_bytes,
+                                   const uint8_t* replacement, int64_t replacement_bytes, rdf_out* out_offsets, rdf_out* out_data);
+rdf_status rdf_utf8_regexp_split(const rdf_utf8_array* chunks, int64_t nchunks, const uint8_t* pattern, int64_t pattern_bytes, int64_t limit,
+                                 rdf_out* out_list_offsets, rdf_out* out_offsets, rdf_out* out_data);
+
 /* ------------------------------------------------------------------ text to values and back
  *
  * ScalarFunctions::{to_date(s, fmt), to_timestamp, unix_timestamp, from_unix_time, date_format} (src/functions/scalar.rs

@@ -62,6 +62,10 @@ pub mod sys {
     #[repr(C)] #[derive(Clone, Copy)]
     pub struct rdf_utf8_part { pub utf8: *const rdf_utf8_array, pub literal: *const u8, pub literal_bytes: i64 }
     pub const RDF_UTF8_PARTS_MAX: i32 = 8;
+    // what rdf_utf8_regexp_info reports of a compiled pattern: the counts the size caps are defined on
+    #[repr(C)] #[derive(Clone, Copy)]
+    pub struct rdf_regexp_info { pub program_len: i32, pub forward_states: i32, pub reverse_states: i32, pub classes: i32,
+                                 pub table_bytes: i64, pub can_match_empty: i32, pub anchored_start: i32 }
     // one criterion of rdf_lexsort_to_indices: exactly one of values / utf8 points at nchunks chunks
     #[repr(C)] #[derive(Clone, Copy)]
     pub struct rdf_sort_key { pub values: *const rdf_array, pub utf8: *const rdf_utf8_array, pub options: rdf_sort_options }
@@ -291,6 +295,18 @@ pub mod sys {
         pub fn rdf_utf8_initcap(chunks: *const rdf_utf8_array, nchunks: i64, out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
         pub fn rdf_utf8_split(chunks: *const rdf_utf8_array, nchunks: i64, delim: *const u8, delim_bytes: i64, limit: i64,
                               out_list_offsets: *mut rdf_out, out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
+        // regular expressions (src/functions/scalar.rs declares regexp_extract and regexp_replace next to split, with empty bodies):
+        // java.util.regex's leftmost-first matching, compiled per call into two DFAs on the host; a pattern the library does not
+        // take is RDF_INVALID_ARGUMENT with the construct and its byte in rdf_last_error().
+        pub fn rdf_utf8_regexp_info(pattern: *const u8, pattern_bytes: i64, out: *mut rdf_regexp_info) -> i32;
+        pub fn rdf_utf8_regexp_match(chunks: *const rdf_utf8_array, nchunks: i64, pattern: *const u8, pattern_bytes: i64, mask: *mut rdf_out) -> i32;
+        pub fn rdf_utf8_regexp_count(chunks: *const rdf_utf8_array, nchunks: i64, pattern: *const u8, pattern_bytes: i64, out: *mut rdf_out) -> i32;
+        pub fn rdf_utf8_regexp_extract(chunks: *const rdf_utf8_array, nchunks: i64, pattern: *const u8, pattern_bytes: i64, group: i32,
+                                       out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
+        pub fn rdf_utf8_regexp_replace(chunks: *const rdf_utf8_array, nchunks: i64, pattern: *const u8, pattern_bytes: i64,
+                                       replacement: *const u8, replacement_bytes: i64, out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
+        pub fn rdf_utf8_regexp_split(chunks: *const rdf_utf8_array, nchunks: i64, pattern: *const u8, pattern_bytes: i64, limit: i64,
+                                     out_list_offsets: *mut rdf_out, out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
         // text to values and back (src/functions/scalar.rs: date_format :209, from_unix_time :262, to_date :459, to_timestamp :461,
         // unix_timestamp :473, and CAST between Utf8 and Boolean / integer / date / timestamp): kind 0 .. 3 = bool, int, date,
         // timestamp; pattern null = the CAST grammar, else a datetime pattern.  parse: a row that does not parse is NULL, so every

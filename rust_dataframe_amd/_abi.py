@@ -117,6 +117,11 @@ class rdf_utf8_array(C.Structure):
     _fields_ = [("offsets", rdf_array), ("data", rdf_array)]
 
 
+class rdf_regexp_info(C.Structure):
+    _fields_ = [("program_len", C.c_int32), ("forward_states", C.c_int32), ("reverse_states", C.c_int32), ("classes", C.c_int32),
+                ("table_bytes", C.c_int64), ("can_match_empty", C.c_int32), ("anchored_start", C.c_int32)]
+
+
 class rdf_utf8_part(C.Structure):
     _fields_ = [("utf8", C.POINTER(rdf_utf8_array)), ("literal", C.POINTER(C.c_uint8)), ("literal_bytes", C.c_int64)]
 
@@ -1655,6 +1660,55 @@ class Api:
         """concat (sep is None) / concat_ws of chunk lists and str / bytes literals."""
         return self.utf8_build("concat", None, parts, as_arrow=as_arrow) if sep is None else self.utf8_build("concat_ws", None, parts, sep, as_arrow=as_arrow)
 
+    # ---- regular expressions over Utf8 (rdf_utf8_regexp_info / _match / _count / _extract / _replace / _split): Spark 3's
+    # rlike, regexp_count, regexp_extract(s, p, 0), regexp_replace and split with a regular expression.  `pattern` is str
+    # (encoded as UTF-8) or bytes; a pattern the library does not take raises with the construct and its byte position.
+    def utf8_regexp_info(self, pattern) -> dict:
+        """rdf_utf8_regexp_info (host only, needs no device): the sizes the caps are defined on."""
+        raw, cp = self._utf8_pattern(pattern)
+        info = rdf_regexp_info()
+        self._check(self._utf8_fn("utf8_regexp_info")(cp, C.c_int64(len(raw)), C.byref(info)))
+        return {k: int(getattr(info, k)) for k, _ in rdf_regexp_info._fields_}
+
+    def _utf8_regexp_measure(self, name, dtype, chunks, pattern, outs):
+        n = len(chunks)
+        carr = (rdf_utf8_array * max(1, n))(*[c.c_struct() for c in chunks])
+        raw, cp = self._utf8_pattern(pattern)
+        outs, co = self._utf8_pred_outs(dtype, chunks, [self._utf8_nullable(c) for c in chunks], outs)
+        self._check(self._utf8_fn(name)(carr, C.c_int64(n), cp, C.c_int64(len(raw)), co))
+        return self._finish(outs, co)
+
+    def utf8_regexp_match(self, chunks: Sequence, pattern, outs=None):
+        """rlike: a match exists anywhere in the row -> one Boolean array per chunk."""
+        return self._utf8_regexp_measure("utf8_regexp_match", BOOL, chunks, pattern, outs)
+
+    def utf8_regexp_count(self, chunks: Sequence, pattern, outs=None):
+        """regexp_count: the matches Matcher.find finds -> one Int32 array per chunk."""
+        return self._utf8_regexp_measure("utf8_regexp_count", I32, chunks, pattern, outs)
+
+    def utf8_regexp_extract_call(self, chunks: Sequence, pattern, group: int = 0):
+        return self._utf8_rewrite_call("utf8_regexp_extract", chunks, [pattern], (C.c_int32(int(group)),))
+
+    def utf8_regexp_replace_call(self, chunks: Sequence, pattern, replacement):
+        return self._utf8_rewrite_call("utf8_regexp_replace", chunks, [pattern, replacement])
+
+    def utf8_regexp_split_call(self, chunks: Sequence, pattern, limit: int = -1):
+        return self._utf8_rewrite_call("utf8_regexp_split", chunks, [pattern], (C.c_int64(int(limit)),))
+
+    def utf8_regexp_extract(self, chunks: Sequence, pattern, group: int = 0, as_arrow=False):
+        """regexp_extract(row, pattern, 0): the first match's bytes, '' when there is none; group != 0 is refused."""
+        call, shape, nullable = self.utf8_regexp_extract_call(chunks, pattern, group)
+        return self._utf8_run(call, shape, [c.length for c in shape], nullable, as_arrow)
+
+    def utf8_regexp_replace(self, chunks: Sequence, pattern, replacement, as_arrow=False):
+        """regexp_replace(row, pattern, replacement): every match replaced; in the replacement \\x stands for x."""
+        call, shape, nullable = self.utf8_regexp_replace_call(chunks, pattern, replacement)
+        return self._utf8_run(call, shape, [c.length for c in shape], nullable, as_arrow)
+
+    def utf8_regexp_split(self, chunks: Sequence, pattern, limit: int = -1, as_arrow=False):
+        """split(row, regex, limit) as String.split -> what utf8_split returns."""
+        return self._utf8_split_run(self.utf8_regexp_split_call(chunks, pattern, limit), chunks, as_arrow)
+
     # ---- Utf8 rewrites: a row's content changed by what it holds (rdf_utf8_replace / _translate / _initcap / _split)
     def _utf8_rewrite_call(self, name, chunks, lits, tail=()):
         n = len(chunks)
@@ -1702,7 +1756,11 @@ class Api:
         child's Int32 offsets array, which that call never reads) and the child HostUtf8 / DeviceUtf8 with one row per
         element (rdf_utf8_take takes it).  as_arrow=True: pyarrow ListArrays of strings ("pylist": python lists).  The
         sizing call, then the call into exactly sized buffers."""
-        call, shape, nullable = self.utf8_split_call(chunks, delim, limit)
+        return self._utf8_split_run(self.utf8_split_call(chunks, delim, limit), chunks, as_arrow)
+
+    def _utf8_split_run(self, split_call, chunks, as_arrow):
+        """utf8_split's and utf8_regexp_split's shared tail: one *_split_call under the sizing rule -> what utf8_split returns"""
+        call, shape, nullable = split_call
         device = any(isinstance(c, DeviceUtf8) for c in chunks)
         rows = [c.length for c in shape]
 

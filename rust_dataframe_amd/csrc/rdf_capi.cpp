@@ -41,6 +41,7 @@
 #include "rdf_utf8_build.h"
 #define RDF_UTF8_REWRITE_NO_CASE   // the compiler of the translate table is all the host side needs
 #include "rdf_utf8_rewrite.h"
+#include "rdf_utf8_regex.h"
 #include "rdf_digest.h"
 #include "rdf_digest_kernels.h"
 
@@ -2881,6 +2882,7 @@ rdf_status groupby_sum_fallback(const rdf_array* keys, const rdf_array* values, 
 #include "rdf_capi_utf8_pred.inc"
 #include "rdf_capi_utf8_build.inc"
 #include "rdf_capi_utf8_rewrite.inc"
+#include "rdf_capi_utf8_regex.inc"
 #include "rdf_capi_digest.inc"
 #include "rdf_capi_select.inc"
 #include "rdf_capi_textconv.inc"

@@ -22,6 +22,8 @@ struct Utf8PredCall {
     int64_t nchunks;
     const Utf8Pattern* pattern;   // compiled, or nullptr
     rdf_out* outs;
+    const uint8_t* regex;         // rdf_capi_utf8_regex.inc: a compiled regular expression's image instead of a pattern
+    int64_t regex_bytes;
 };
 
 // the literal / pattern of a call, checked and compiled
@@ -128,7 +130,7 @@ rdf_status utf8_pred_run(const Utf8PredCall& q) {
     const size_t o_ts = tb.reserve(sizeof(int64_t) * ((size_t)nchunks + 1));
     const size_t o_out = tb.reserve(sizeof(Utf8PredOut) * (size_t)nchunks);
     const size_t o_nulls = tb.reserve(sizeof(unsigned long long) * (size_t)nchunks);
-    const size_t o_pat = tb.reserve(q.pattern ? sizeof(Utf8Pattern) : 0);
+    const size_t o_pat = tb.reserve(q.pattern ? sizeof(Utf8Pattern) : q.regex ? (size_t)q.regex_bytes : 0);
     RDF_TRY(tb.bind(pin_off));
     int64_t* hts = tb.at<int64_t>(o_ts);
     Utf8PredOut* hout = tb.at<Utf8PredOut>(o_out);
@@ -146,6 +148,7 @@ rdf_status utf8_pred_run(const Utf8PredCall& q) {
     }
     memset(tb.at<char>(o_nulls), 0, sizeof(unsigned long long) * (size_t)nchunks);
     if (q.pattern) memcpy(tb.at<char>(o_pat), q.pattern, sizeof(Utf8Pattern));
+    if (q.regex) memcpy(tb.at<char>(o_pat), q.regex, (size_t)q.regex_bytes);
     RDF_TRY(tb.alloc());
     RDF_TRY(tb.upload(pin_off));
 
@@ -161,8 +164,10 @@ rdf_status utf8_pred_run(const Utf8PredCall& q) {
     a.family = q.family; a.measure = q.measure; a.op = q.op; a.pos = q.pos;
     a.nulls = counting ? tb.dev_at<unsigned long long>(o_nulls) : nullptr;
     KernelTimer kt;
-    ctx.last_kernel = "utf8_pred_kernel";
-    HIP_TRY(launch_utf8_pred(a, ctx.stream));
+    a.regex = q.regex ? tb.dev_at<uint8_t>(o_pat) : nullptr;
+    ctx.last_kernel = q.regex ? "utf8_regex_measure_kernel" : "utf8_pred_kernel";
+    if (q.regex) HIP_TRY(launch_utf8_regex_measure(a, q.regex_bytes, ctx.stream));
+    else HIP_TRY(launch_utf8_pred(a, ctx.stream));
     kt.stop();
     if (counting) HIP_TRY(hipMemcpyAsync(tb.at<char>(o_nulls), a.nulls, sizeof(unsigned long long) * (size_t)nchunks, hipMemcpyDeviceToHost, ctx.stream));
     HIP_TRY(hipStreamSynchronize(ctx.stream));

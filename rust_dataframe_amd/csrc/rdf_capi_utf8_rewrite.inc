@@ -22,6 +22,9 @@ struct Utf8RewriteCall {
     rdf_out* out_list;             // split: the list offsets (and the rows' validity)
     rdf_out* out_offsets;          // the rows' offsets (split: the child's)
     rdf_out* out_data;
+    const uint8_t* regex;          // rdf_capi_utf8_regex.inc: a compiled regular expression's image; lit is unused then
+    int64_t regex_bytes;
+    int regex_op;                  // U8X_EXTRACT / _REPLACE / _SPLIT
 };
 
 rdf_status utf8_rewrite_run(const Utf8RewriteCall& q) {
@@ -85,7 +88,7 @@ rdf_status utf8_rewrite_run(const Utf8RewriteCall& q) {
     const size_t o_ts = tb.reserve(sizeof(int64_t) * ((size_t)nchunks + 1));
     const size_t o_lit = tb.reserve((size_t)q.lit_bytes + 16);
     const size_t o_rep = tb.reserve((size_t)q.rep_bytes + 16);
-    const size_t o_tab = tb.reserve(q.op == U8R_TRANSLATE ? sizeof(Utf8TranslateTable) : 16);
+    const size_t o_tab = tb.reserve(q.op == U8R_TRANSLATE ? sizeof(Utf8TranslateTable) : q.regex ? (size_t)q.regex_bytes : 16);
     RDF_TRY(tb.bind(pin_off));
     RDF_TRY(tb.alloc());
     int64_t* hts = tb.at<int64_t>(o_ts);
@@ -96,6 +99,7 @@ rdf_status utf8_rewrite_run(const Utf8RewriteCall& q) {
         if (q.lit_bytes > 0) memcpy(tb.at<uint8_t>(o_lit), q.lit, (size_t)q.lit_bytes);
         if (q.rep_bytes > 0) memcpy(tb.at<uint8_t>(o_rep), q.rep, (size_t)q.rep_bytes);
     }
+    if (q.regex) memcpy(tb.at<uint8_t>(o_tab), q.regex, (size_t)q.regex_bytes);
     RDF_TRY(tb.upload(pin_off));
     pin_off += (tb.size + 255) & ~(size_t)255;
 
@@ -131,8 +135,11 @@ rdf_status utf8_rewrite_run(const Utf8RewriteCall& q) {
     a.tot = (int64_t*)ptot;
     a.null_counts = (unsigned long long*)pnulls;
     KernelTimer kt;
-    ctx.last_kernel = "utf8_rewrite_size_kernel + utf8_rewrite_write_kernel";
-    HIP_TRY(launch_utf8_rewrite_size(a, ctx.stream));
+    a.regex = q.regex ? tb.dev_at<uint8_t>(o_tab) : nullptr;
+    a.regex_op = q.regex_op;
+    ctx.last_kernel = q.regex ? "utf8_regex_size_kernel + utf8_regex_write_kernel" : "utf8_rewrite_size_kernel + utf8_rewrite_write_kernel";
+    if (q.regex) HIP_TRY(launch_utf8_regex_size(a, q.regex_bytes, ctx.stream));
+    else HIP_TRY(launch_utf8_rewrite_size(a, ctx.stream));
     HIP_TRY(launch_scan(a.blen, (int64_t*)pbscan, n, (int64_t*)pbscan + n + 1, ctx.stream));
     if (split) HIP_TRY(launch_scan(a.elen, (int64_t*)pescan, n, (int64_t*)pescan + n + 1, ctx.stream));
     HIP_TRY(launch_utf8_rewrite_totals(a, ctx.stream));
@@ -216,7 +223,8 @@ rdf_status utf8_rewrite_run(const Utf8RewriteCall& q) {
     }
     RDF_TRY(to.upload(pin_off));
     a.outs = to.dev_at<Utf8RewriteOut>(o_outs);
-    HIP_TRY(launch_utf8_rewrite_write(a, ctx.stream));
+    if (q.regex) HIP_TRY(launch_utf8_regex_write(a, q.regex_bytes, ctx.stream));
+    else HIP_TRY(launch_utf8_rewrite_write(a, ctx.stream));
     kt.stop();
     HIP_TRY(hipStreamSynchronize(ctx.stream));
     if (mem == RDF_MEM_HOST) {

@@ -149,6 +149,7 @@ struct Utf8PredArgs {
     int32_t             op;           // compare: U8P_EQ .. U8P_GE; measure: U8M_*; predicate: the pattern's kind decides
     int32_t             pos;          // locate
     unsigned long long* nulls;        // per chunk: NULL rows added up (nullptr: the host knows them)
+    const uint8_t*      regex;        // rdf_utf8_regex.hip: the compiled pattern's image (device copy, 16-byte aligned)
 };
 hipError_t launch_utf8_pred(const Utf8PredArgs& a, hipStream_t s);
 
@@ -227,7 +228,18 @@ struct Utf8RewriteArgs {
     int64_t*         tot;          // per chunk: bytes, rows, elements
     unsigned long long* null_counts;   // per chunk
     const Utf8RewriteOut* outs;
+    const uint8_t*   regex;        // rdf_utf8_regex.hip: the compiled pattern's image (device copy, 16-byte aligned)
+    int32_t          regex_op;     // U8X_EXTRACT / _REPLACE / _SPLIT
 };
 hipError_t launch_utf8_rewrite_size(const Utf8RewriteArgs& a, hipStream_t s);     // blen, elen, null_counts
 hipError_t launch_utf8_rewrite_totals(const Utf8RewriteArgs& a, hipStream_t s);   // tot
 hipError_t launch_utf8_rewrite_write(const Utf8RewriteArgs& a, hipStream_t s);    // offsets, validity, the bytes
+
+// ---- regular expressions over Utf8 (rdf_utf8_regex.hip; host side: rdf_capi_utf8_regex.inc; the compiler and what is decided
+// about one row: rdf_utf8_regex.h).  rlike and regexp_count are ONE kernel in the tiles and with the outputs of the
+// predicates (measure != 0: the count); extract, replace and split are the three steps of the rewrites with the rewrites'
+// scans, totals kernel and outputs.  Every block copies the pattern's tables into LDS when they fit kUtf8RegexLdsBytes; a
+// row stays on one lane, and a tile's rows beyond kUtf8ShortRow are dealt over the block's four waves.
+hipError_t launch_utf8_regex_measure(const Utf8PredArgs& a, int64_t image_bytes, hipStream_t s);
+hipError_t launch_utf8_regex_size(const Utf8RewriteArgs& a, int64_t image_bytes, hipStream_t s);    // blen, elen, null_counts
+hipError_t launch_utf8_regex_write(const Utf8RewriteArgs& a, int64_t image_bytes, hipStream_t s);   // offsets, validity, the bytes
