@@ -959,6 +959,10 @@ class Column {
         return text_build(tc, chunk_nullable(), field_.name, [&](rdf_out* oo, rdf_out* od) { return rdf_utf8_initcap(tc.txt.data(), (int64_t)tc.txt.size(), oo, od); });
     }
     inline ListArray split(const std::string& delim, int64_t limit = -1) const;
+    // The median and the p-quantile (Spark's `percentile`: linear between the two nearest ranks) of a numeric column over its
+    // non-NULL rows, none for a column without one: AggregateFunctions::median / percentile (rdf_groupby_percentile).
+    inline std::optional<double> median() const;
+    inline std::optional<double> quantile(double p) const;
 
     // Regular expressions, on the device (rdf_utf8_regexp_match / _count / _extract / _replace / _split; java.util.regex's
     // leftmost-first matching over the accepted syntax, see the C header): a pattern outside it, or past a size cap, throws
@@ -2909,6 +2913,42 @@ class DataFrame {
         }
         return r;
     }
+    // rdf_groupby_percentile over columns of this frame: `groups` (0 .. 4 names) are the grouping columns, `value` the ONE
+    // column the calls read.  -> the group count, the UInt32 row index of every group's first row (groups in ascending key
+    // order, NULL last), one array per call — Float64 for RDF_PCT_CONT, UInt32 row indices into `value` for RDF_PCT_DISC, NULL
+    // for a group without a non-NULL value — and the Int64 count of non-NULL values per group.  A capacity of the rows always
+    // suffices (of one row without grouping columns): one call.  Without grouping columns a numeric column is answered by the radix select, no sort.
+    struct PercentileGroups { int64_t groups = 0; ArrayRef group_rows, counts; std::vector<ArrayRef> outs; };
+    PercentileGroups percentile_groups(const std::vector<std::string>& groups, const std::string& value, const std::vector<rdf_percentile_call>& calls) const {
+        const bool host = numeric_columns_on_host();
+        std::vector<SortCriteria> crit;
+        for (auto& g : groups) crit.push_back(SortCriteria{g, false, false});
+        crit.push_back(SortCriteria{value, false, false});
+        const SortKeys sk = sort_keys(crit, host);
+        const int64_t cap = groups.empty() ? std::min<int64_t>(1, (int64_t)num_rows()) : (int64_t)num_rows();   // no grouping columns: one row
+        auto rows = Array::make_out(DataType::UInt32, cap, false, host), counts = Array::make_out(DataType::Int64, cap, false, host);
+        rdf_out orow = rows->out_view(cap), ocnt = counts->out_view(cap);
+        std::vector<std::shared_ptr<Array>> outs;
+        std::vector<rdf_out> ov;
+        for (auto& c : calls) {
+            outs.push_back(Array::make_out(c.kind == RDF_PCT_CONT ? DataType::Float64 : DataType::UInt32, cap, true, host));
+            ov.push_back(outs.back()->out_view(cap));
+        }
+        PercentileGroups r;
+        check(rdf_groupby_percentile(groups.empty() ? nullptr : sk.keys.data(), (int32_t)groups.size(), &sk.keys[groups.size()], (int64_t)num_chunks(),
+                                     calls.empty() ? nullptr : calls.data(), (int32_t)calls.size(), &orow, calls.empty() ? nullptr : ov.data(), &ocnt, &r.groups));
+        rows->length = orow.length;
+        counts->length = ocnt.length;
+        r.group_rows = rows;
+        r.counts = counts;
+        for (size_t c = 0; c < outs.size(); ++c) {
+            outs[c]->length = ov[c].length;
+            outs[c]->null_count = ov[c].null_count;
+            if (ov[c].null_count == 0) outs[c]->validity = nullptr;
+            r.outs.push_back(outs[c]);
+        }
+        return r;
+    }
     // rdf_groupby_collect over columns of this frame: `groups` (0 .. 4 names) are the grouping columns, `value` the ONE column
     // collected, kind RDF_COLLECT_LIST / RDF_COLLECT_SET.  -> the group and element counts, the UInt32 row index of every
     // group's first row (groups in ascending key order, NULL last), the Int32 offsets (groups + 1 entries), the UInt32 row
@@ -3882,6 +3922,41 @@ struct AggregateFunctions {  // src/functions/aggregate.rs:12-93
     static std::optional<Column> first(const Column& c, bool ignore_nulls = false) { return first_or_last(c, RDF_GRP_FIRST, ignore_nulls); }
     static std::optional<Column> last(const Column& c, bool ignore_nulls = false) { return first_or_last(c, RDF_GRP_LAST, ignore_nulls); }
 
+    // percentile / median / percentile_disc of a whole column over its non-NULL rows (Spark's aggregates of those names;
+    // aggregate.rs stops before them): rdf_groupby_percentile with no grouping columns, which answers a numeric column by a
+    // radix select instead of a sort.  p outside [0, 1] is refused.
+    //   percentile(c, p)       Spark 3's `percentile`: pos = (m - 1) * p over the m sorted values, linear between the values at
+    //                          floor(pos) and ceil(pos); numeric columns only.  none for an empty or all-NULL column
+    //   percentiles(c, {p..})  up to 8 of them from one call, in the order given
+    //   median(c)              percentile(c, 0.5)
+    //   percentile_disc(c, p)  SQL's percentile_disc: the row holding the value at sorted position max(0, ceil(p * m) - 1), as
+    //                          a ONE-row column typed like the input (numeric or Utf8), or none
+    static std::vector<std::optional<double>> percentiles(const Column& c, const std::vector<double>& ps) {
+        const DataType dt = c.data_type();
+        if (!(is_integer(dt) || is_float(dt))) throw DataFrameError(DataFrameError::ComputeError, "Aggregating column must be numeric");
+        if (ps.size() > RDF_PERCENTILE_MAX_CALLS) throw DataFrameError(DataFrameError::ComputeError, "percentiles: at most " + std::to_string(RDF_PERCENTILE_MAX_CALLS) + " per call");
+        std::vector<rdf_percentile_call> calls;
+        for (double p : ps) {
+            if (!(p >= 0.0 && p <= 1.0)) throw DataFrameError(DataFrameError::ComputeError, "percentile: p must lie in [0, 1]");
+            calls.push_back(rdf_percentile_call{RDF_PCT_CONT, 0, p});
+        }
+        std::vector<std::optional<double>> out(ps.size());
+        if (c.num_rows() == 0 || ps.empty()) return out;
+        const DataFrame::PercentileGroups g = DataFrame::from_columns({c}).percentile_groups({}, c.name(), calls);
+        for (size_t i = 0; i < ps.size() && g.groups; ++i)
+            if (g.outs[i]->null_count == 0) out[i] = g.outs[i]->values_to_host<double>()[0];
+        return out;
+    }
+    static std::optional<double> percentile(const Column& c, double p) { return percentiles(c, {p})[0]; }
+    static std::optional<double> median(const Column& c) { return percentile(c, 0.5); }
+    static std::optional<Column> percentile_disc(const Column& c, double p) {
+        if (!(p >= 0.0 && p <= 1.0)) throw DataFrameError(DataFrameError::ComputeError, "percentile_disc: p must lie in [0, 1]");
+        if (c.num_rows() == 0) return std::nullopt;
+        const DataFrame::PercentileGroups g = DataFrame::from_columns({c}).percentile_groups({}, c.name(), {rdf_percentile_call{RDF_PCT_DISC, 0, p}});
+        if (!g.groups || g.outs[0]->null_count > 0) return std::nullopt;
+        return c.take(g.outs[0], 4096);
+    }
+
   private:
     static std::optional<Column> first_or_last(const Column& c, int32_t fn, bool ignore_nulls) {
         if (c.num_rows() == 0) return std::nullopt;
@@ -3896,6 +3971,9 @@ struct AggregateFunctions {  // src/functions/aggregate.rs:12-93
         return mask->views();
     }
 };
+
+inline std::optional<double> Column::median() const { return AggregateFunctions::median(*this); }
+inline std::optional<double> Column::quantile(double p) const { return AggregateFunctions::percentile(*this, p); }
 
 // ------------------------------------------------------------------------------------------------
 // ListArray over a primitive child + ArrayFunctions (src/functions/array.rs:15-399)
@@ -4205,6 +4283,35 @@ class Evaluate {
         Column child = g.values ? Column::from_arrays({g.values}, Field{column, vc.data_type(), true})
                                 : Column::from_arrays(vc.take(g.child_rows, 4096).data().chunks(), Field{column, vc.data_type(), true});
         return GroupedLists{DataFrame::from_columns(std::move(keys)), g.offsets, std::move(child)};
+    }
+    // Percentiles per group, eager (the planner's AggregateFunction enum has no percentile): the grouping columns — 0 .. 4 of
+    // them, integer, float or Utf8, gathered through the groups' first rows — then one column per call.  A continuous call
+    // {RDF_PCT_CONT, 0, p} gives the Float64 column "percentile(x, p)" ("median(x)" for p = 0.5), a discrete one
+    // {RDF_PCT_DISC, 0, p} the column "percentile_disc(x, p)" typed like x (numeric or Utf8), taken by the row indices the call
+    // returns.  Rows ordered by the grouping columns, the NULL group last; a group without a non-NULL x has NULL in every column.
+    static DataFrame group_percentile(const DataFrame& frame, const std::vector<std::string>& groups, const std::string& value,
+                                      const std::vector<rdf_percentile_call>& calls) {
+        if (groups.size() > RDF_MAX_GROUP_KEYS) throw DataFrameError(DataFrameError::ComputeError, "group_percentile: at most " + std::to_string(RDF_MAX_GROUP_KEYS) + " grouping columns");
+        if (calls.empty() || calls.size() > RDF_PERCENTILE_MAX_CALLS) throw DataFrameError(DataFrameError::ComputeError, "group_percentile: 1.." + std::to_string(RDF_PERCENTILE_MAX_CALLS) + " calls");
+        const Column& vc = frame.column_by_name(value);
+        const DataFrame::PercentileGroups g = frame.percentile_groups(groups, value, calls);
+        std::vector<Column> out_cols;
+        for (auto& n : groups) {
+            const Column& kc = frame.column_by_name(n);
+            out_cols.push_back(Column::from_arrays(kc.take(g.group_rows, 4096).data().chunks(), Field{n, kc.data_type(), true}));
+        }
+        auto p_text = [](double p) { std::ostringstream o; o << p; return o.str(); };
+        for (size_t c = 0; c < calls.size(); ++c) {
+            if (calls[c].kind == RDF_PCT_CONT) {
+                const std::string name = calls[c].p == 0.5 ? "median(" + value + ")" : "percentile(" + value + ", " + p_text(calls[c].p) + ")";
+                out_cols.push_back(Column::from_arrays({g.outs[c]}, Field{name, DataType::Float64, true}));
+                continue;
+            }
+            // the value column taken by the calls' row indices; where the call is NULL the index is 0, and the row is masked
+            Column taken = vc.take(g.outs[c], 4096);
+            out_cols.push_back(Column::from_arrays(taken.data().chunks(), Field{"percentile_disc(" + value + ", " + p_text(calls[c].p) + ")", vc.data_type(), true}));
+        }
+        return DataFrame::from_columns(std::move(out_cols));
     }
     // GROUP BY, eager, over 1..4 grouping columns of which each is an integer or a Utf8 column: the grouping columns, then one
     // column per (aggregation, input column), named and typed as Dataset::try_aggregate plans them; rows ordered by the

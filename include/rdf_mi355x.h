@@ -1045,6 +1045,56 @@ rdf_status rdf_groupby_sorted(const rdf_sort_key* group_by, int32_t ngroup, cons
                               const rdf_group_call* calls, int32_t ncalls, rdf_out* out_group_rows, rdf_out* outs,
                               int64_t* out_groups);
 
+/* ------------------------------------------------------------------ percentiles and median per group */
+
+/* Up to 8 percentiles of ONE value column per group of 0 .. 4 grouping keys, all from ONE sort over (grouping keys, value).
+ * The reference's aggregate.rs stops before percentiles; the semantics are Spark 3's `percentile` (its formula restated) for
+ * RDF_PCT_CONT and SQL's percentile_disc for RDF_PCT_DISC, and tests/percentile_ref.py is their executable definition.
+ * `median` is {RDF_PCT_CONT, 0, 0.5}.
+ *
+ * Keys, value, groups, their order (ascending, NULL last), out_group_rows, memory kinds, the row limit, the sizing rule and
+ * the count-only call (out_group_rows == NULL, ncalls == 0, out_counts == NULL) are rdf_groupby_sorted's.  value is NULL
+ * exactly when ncalls == 0 and out_counts == NULL.
+ *   - A group's non-NULL values are taken in the sort's order: NaN after +inf, -0.0 and +0.0 peers, Utf8 by unsigned bytes.
+ *     m is their count.  out_counts (optional) is ONE RDF_I64 array of m per group.
+ *   - m == 0 gives NULL for every call: every outs[c] needs a validity bitmap when any value chunk carries validity; a
+ *     bitmap is written wherever one is given, and null_count is set.  The value under a NULL is 0.
+ *   - RDF_PCT_CONT: output RDF_F64, numeric values only.  d(v) = (double)v: Float32 widened, integers rounded to nearest
+ *     even, -0.0 read as +0.0, every NaN the quiet NaN 0x7FF8000000000000.  pos = (double)(m - 1) * p, lo = floor(pos),
+ *     hi = ceil(pos).  If lo == hi or the values at sorted positions lo and hi are peers the result is d(v_lo); otherwise
+ *     (hi - pos) * d(v_lo) + (pos - lo) * d(v_hi), two multiplies and one add, each rounded (no FMA).  IEEE otherwise: a
+ *     -inf / +inf pair gives NaN.  A NaN result is 0x7FF8000000000000.
+ *   - RDF_PCT_DISC: output RDF_U32 ROW INDICES (the FIRST / LAST / LAG convention; gather with rdf_take / rdf_utf8_take), any
+ *     value type.  k = max(0, (int64)ceil(p * (double)m) - 1); the result is the smallest row index of the group whose value
+ *     is a peer of the k-th sorted value.
+ *   - The result is a function of the multiset of rows alone: chunking, offsets, memory kind and repetition change no byte;
+ *     shuffling the rows changes only the DISC indices, which map back to the same values.
+ * Errors, all before any device work, in this order: null out_groups; a bad key count or key list; a bad call count or call
+ * list; a value column missing or unasked for; an unknown kind; p outside [0, 1] or NaN; then the keys' and value's own
+ * rules (rdf_groupby_sorted's); CONT of a Utf8 column; a wrong output dtype; a missing validity bitmap; a wrong out_counts
+ * or out_group_rows dtype; mixed memory kinds: RDF_INVALID_ARGUMENT.
+ * Routes.  The SORTED route serves every call: rdf_window's front over (grouping keys, value), then one thread per (group,
+ * call).  The SELECT route serves ngroup == 0 with a numeric value and runs no sort: a radix select over the values' ordered
+ * unsigned images, RDF_PCT_SELECT_BITS per pass, candidates re-read under a prefix test until at most RDF_PCT_SELECT_FINISH
+ * of them are left (one block sorts those in LDS) or the key's bits are used up — at most ceil(key bits / digit bits) counting
+ * reads plus one collecting read, whatever the values hold.  Both routes give the same bytes.
+ * Under auto the select route takes every call it can serve: it measured faster for every dtype, size and distribution
+ * tried.
+ * rdf_set_option("percentile_route", 0 auto | 1 sorted | 2 select); 2 on a call the select route cannot serve is
+ * RDF_INVALID_ARGUMENT (refused after the kinds and p, before the keys are looked at); rdf_last_kernel names the route taken.
+ * RDF_PERCENTILE_PICK_BLOCK is the block of the kernel that answers one (group, call) per thread, RDF_PCT_SELECT_TILE the
+ * rows of one block tile of the select route's streaming passes: tests place group counts and row counts around them. */
+#define RDF_PERCENTILE_MAX_CALLS 8
+#define RDF_PERCENTILE_PICK_BLOCK 256
+#define RDF_PCT_SELECT_BITS 8
+#define RDF_PCT_SELECT_TILE 4096
+#define RDF_PCT_SELECT_FINISH 2048
+typedef enum { RDF_PCT_CONT = 0, RDF_PCT_DISC = 1 } rdf_percentile_kind;
+typedef struct { int32_t kind; int32_t reserved; double p; } rdf_percentile_call;
+rdf_status rdf_groupby_percentile(const rdf_sort_key* group_by, int32_t ngroup, const rdf_sort_key* value, int64_t nchunks,
+                                  const rdf_percentile_call* calls, int32_t ncalls, rdf_out* out_group_rows, rdf_out* outs,
+                                  rdf_out* out_counts, int64_t* out_groups);
+
 /* ------------------------------------------------------------------ collect per group and explode: collect_list, collect_set, explode */
 
 /* The three operations that connect rows with lists: ArrayFunction::CollectList / CollectSet (src/expression.rs:691-692,

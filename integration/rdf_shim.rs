@@ -90,6 +90,9 @@ pub mod sys {
     #[repr(C)] #[derive(Clone, Copy)] pub struct rdf_group_call { pub fn_: i32, pub ignore_nulls: i32 }
     pub const RDF_GRP_COUNT_DISTINCT: i32 = 0; pub const RDF_GRP_SUM_DISTINCT: i32 = 1; pub const RDF_GRP_FIRST: i32 = 2; pub const RDF_GRP_LAST: i32 = 3;
     pub const RDF_GROUP_MAX_CALLS: i32 = 8;
+    // one call of rdf_groupby_percentile: kind = RDF_PCT_*, p in [0, 1]; the median is { RDF_PCT_CONT, 0, 0.5 }
+    #[repr(C)] #[derive(Clone, Copy)] pub struct rdf_percentile_call { pub kind: i32, pub reserved: i32, pub p: f64 }
+    pub const RDF_PCT_CONT: i32 = 0; pub const RDF_PCT_DISC: i32 = 1; pub const RDF_PERCENTILE_MAX_CALLS: i32 = 8;
     // rdf_groupby_collect's kind, and the tile of its compaction / of explode's expansion
     pub const RDF_COLLECT_LIST: i32 = 0; pub const RDF_COLLECT_SET: i32 = 1; pub const RDF_COLLECT_TILE: i32 = 1024;
     // the state of rdf_moments / rdf_comoments: count, the mean(s) as two doubles each, the central sums
@@ -197,6 +200,10 @@ pub mod sys {
         pub fn rdf_groupby_sorted(group_by: *const rdf_sort_key, ngroup: i32, value: *const rdf_sort_key, nchunks: i64,
                                   calls: *const rdf_group_call, ncalls: i32, out_group_rows: *mut rdf_out, outs: *mut rdf_out,
                                   out_groups: *mut i64) -> i32;
+        // percentile / median / percentile_disc per group (Spark's aggregates; aggregate.rs stops before them)
+        pub fn rdf_groupby_percentile(group_by: *const rdf_sort_key, ngroup: i32, value: *const rdf_sort_key, nchunks: i64,
+                                      calls: *const rdf_percentile_call, ncalls: i32, out_group_rows: *mut rdf_out, outs: *mut rdf_out,
+                                      out_counts: *mut rdf_out, out_groups: *mut i64) -> i32;
         // ArrayFunction::CollectList / CollectSet (expression.rs:691-692; collect_list() / collect_set(), array.rs:404-405) per group,
         // and ScalarFunctions::explode (scalar.rs:237): all declared with empty bodies
         pub fn rdf_groupby_collect(group_by: *const rdf_sort_key, ngroup: i32, value: *const rdf_sort_key, nchunks: i64, kind: i32,
@@ -756,6 +763,43 @@ pub fn groupby_sorted(group_by: &[Vec<&dyn Array>], value: Option<&Vec<&dyn Arra
                                        if ccalls.is_empty() { std::ptr::null() } else { ccalls.as_ptr() }, ccalls.len() as i32,
                                        &mut rout, if outs.is_empty() { std::ptr::null_mut() } else { outs.as_mut_ptr() }, &mut groups) })?;
     Ok((rbuf.finish(&rout), bufs.into_iter().zip(outs.iter()).map(|(b, o)| b.finish(o)).collect()))
+}
+
+/// percentile / median / percentile_disc (Spark's aggregates; aggregate.rs stops before them) per group of 0 .. 4 grouping
+/// columns over ONE value column: `calls` = (RDF_PCT_CONT | RDF_PCT_DISC, p), the median is (RDF_PCT_CONT, 0.5).  -> (row index
+/// of every group's first row, groups in ascending key order with the NULL group last; one array per call: Float64Array for
+/// CONT, UInt32Array of ROW INDICES into the value column for DISC, NULL where the group has no non-NULL value; Int64Array of
+/// the non-NULL values per group).  Without grouping columns a numeric column is answered by a radix select, no sort.
+pub fn groupby_percentile(group_by: &[Vec<&dyn Array>], value: &Vec<&dyn Array>, calls: &[(i32, f64)]) -> Result<(ArrayRef, Vec<ArrayRef>, ArrayRef), ArrowError> {
+    let cols: Vec<&Vec<&dyn Array>> = group_by.iter().chain(std::iter::once(value)).collect();
+    let nchunks = value.len();
+    let rows: usize = value.iter().map(|a| a.len()).sum();
+    let mut num: Vec<Vec<rdf_array>> = Vec::new();
+    let mut txt: Vec<Vec<rdf_utf8_array>> = Vec::new();
+    for chunks in &cols {
+        match chunks.first().map(|a| a.data_type()) {
+            Some(DataType::Utf8) => { txt.push(chunks.iter().map(|a| utf8_view(a.as_any().downcast_ref::<StringArray>().unwrap())).collect()); num.push(Vec::new()); }
+            _ => { num.push(chunks.iter().map(|a| view(*a)).collect()); txt.push(Vec::new()); }
+        }
+    }
+    let keys: Vec<rdf_sort_key> = (0..cols.len()).map(|k| rdf_sort_key {
+        values: if num[k].is_empty() { std::ptr::null() } else { num[k].as_ptr() },
+        utf8: if txt[k].is_empty() { std::ptr::null() } else { txt[k].as_ptr() },
+        options: rdf_sort_options { descending: 0, nulls_first: 0 },
+    }).collect();
+    let ng = group_by.len();
+    let ccalls: Vec<rdf_percentile_call> = calls.iter().map(|(k, p)| rdf_percentile_call { kind: *k, reserved: 0, p: *p }).collect();
+    let mut bufs: Vec<OutBuf> = calls.iter().map(|(k, _)| OutBuf::new(if *k == RDF_PCT_CONT { DataType::Float64 } else { DataType::UInt32 }, rows, true)).collect();
+    let mut outs: Vec<rdf_out> = bufs.iter_mut().map(|b| b.as_out()).collect();
+    let mut rbuf = OutBuf::new(DataType::UInt32, rows, false);
+    let mut rout = rbuf.as_out();
+    let mut cbuf = OutBuf::new(DataType::Int64, rows, false);
+    let mut cout = cbuf.as_out();
+    let mut groups = 0i64;
+    status(unsafe { rdf_groupby_percentile(if ng > 0 { keys.as_ptr() } else { std::ptr::null() }, ng as i32, keys[ng..].as_ptr(), nchunks as i64,
+                                           if ccalls.is_empty() { std::ptr::null() } else { ccalls.as_ptr() }, ccalls.len() as i32,
+                                           &mut rout, if outs.is_empty() { std::ptr::null_mut() } else { outs.as_mut_ptr() }, &mut cout, &mut groups) })?;
+    Ok((rbuf.finish(&rout), bufs.into_iter().zip(outs.iter()).map(|(b, o)| b.finish(o)).collect(), cbuf.finish(&cout)))
 }
 
 /// collect_list() / collect_set() (src/functions/array.rs:404-405, ArrayFunction::CollectList / CollectSet, empty there) per

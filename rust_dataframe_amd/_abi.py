@@ -164,6 +164,31 @@ GROUP_MAX_CALLS = 8
 GROUP_SORTED_TILE = 256   # RDF_GROUP_SORTED_TILE: the fold's tile over the distinct (group, value) pairs
 
 
+class rdf_percentile_call(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("p", C.c_double)]
+
+
+PCT_CONT, PCT_DISC = 0, 1
+PERCENTILE_KINDS = {"cont": PCT_CONT, "disc": PCT_DISC}
+PERCENTILE_MAX_CALLS = 8
+PERCENTILE_PICK_BLOCK = 256   # RDF_PERCENTILE_PICK_BLOCK: one (group, call) per thread of the pick kernel
+PCT_SELECT_BITS, PCT_SELECT_TILE, PCT_SELECT_FINISH = 8, 4096, 2048   # RDF_PCT_SELECT_*: digit bits, rows per block tile, candidates of the LDS finish
+
+
+def percentile_calls(calls: Sequence):
+    """[("cont", p) | ("disc", p) | "median" | (kind number, p), ...] -> [(kind, p), ...]"""
+    out = []
+    for c in calls:
+        if isinstance(c, str):
+            if c != "median":
+                raise ValueError(f"unknown percentile call {c!r}")
+            out.append((PCT_CONT, 0.5))
+        else:
+            kind, p = c
+            out.append((PERCENTILE_KINDS[kind] if isinstance(kind, str) else int(kind), float(p)))
+    return out
+
+
 def group_sorted_out_dtype(fn: int, value_dtype: int = I64) -> int:
     if fn == GRP_COUNT_DISTINCT:
         return I64
@@ -2146,6 +2171,52 @@ class Api:
             return groups.value, rows_out, outs
         rows = self.window_to_numpy(rows_out)[0] if rows_out is not None else None
         return groups.value, rows, [self.window_to_numpy(o) for o in outs]
+
+    # ---- percentiles and median per group
+    def groupby_percentile(self, group_by: Sequence, value, calls: Sequence, group_rows: bool = True, counts: bool = False,
+                           outs=None, rows_out=None, counts_out=None, raw: bool = False):
+        """rdf_groupby_percentile: group_by = [chunks, ...] (0 .. 4 numeric or Utf8 columns), value = chunks of ONE numeric or
+        Utf8 column (None with no calls and no counts), calls = [("cont", p) | ("disc", p) | "median", ...].  Groups come in
+        ascending key order, NULL last.  -> (groups, group_rows, results, counts): the number of groups, the UInt32 row index
+        of every group's first row (None with group_rows=False), per call the pair (values, valid) — Float64 for "cont", UInt32
+        row indices for "disc" — and the Int64 count of non-NULL values per group (None with counts=False).  Without `outs` /
+        `rows_out` / `counts_out` the buffers hold one entry per row, which always suffices, and every call gets a validity
+        bitmap; raw=True returns the output arrays as they are."""
+        cols = list(group_by) + ([value] if value is not None else [])
+        gk, keep_g = self._sort_keys(group_by)
+        vk, keep_v = self._sort_keys([value] if value is not None else [])
+        nchunks = len(cols[0]) if cols else 0
+        n = sum(c.length for c in cols[0]) if cols else 0
+        device = any(isinstance(c, (DeviceArray, DeviceUtf8)) for k in cols for c in k)
+        kp = percentile_calls(calls)
+        cc = (rdf_percentile_call * max(1, len(kp)))()
+        for i, (kind, p) in enumerate(kp):
+            cc[i] = rdf_percentile_call(kind, 0, p)
+        if outs is None:
+            outs = [self._window_out(F64 if kind == PCT_CONT else U32, n, device, True) for kind, _ in kp]
+        if rows_out is None and group_rows:
+            rows_out = self._window_out(U32, n, device, False)
+        if counts_out is None and counts:
+            counts_out = self._window_out(I64, n, device, False)
+        carr = (rdf_out * max(1, len(outs)))(*[o.out_struct() for o in outs])
+        crow = (rdf_out * 1)(rows_out.out_struct()) if rows_out is not None else None
+        ccnt = (rdf_out * 1)(counts_out.out_struct()) if counts_out is not None else None
+        groups = C.c_int64(-1)
+        fn = self._fn("groupby_percentile")
+        fn.restype = C.c_int
+        try:
+            self._check(fn(gk if group_by else None, C.c_int32(len(group_by)), vk if value is not None else None, C.c_int64(nchunks),
+                           cc if kp else None, C.c_int32(len(kp)), crow, carr if kp else None, ccnt, C.byref(groups)))
+        finally:
+            self._finish(outs, carr)
+            if rows_out is not None:
+                self._finish([rows_out], crow)
+            if counts_out is not None:
+                self._finish([counts_out], ccnt)
+            self.last_groups = groups.value
+        if raw:
+            return groups.value, rows_out, outs, counts_out
+        return (groups.value, self._out_values(rows_out), [self.window_agg_to_numpy(o) for o in outs], self._out_values(counts_out))
 
     # ---- collect per group and explode: collect_list / collect_set / explode
     @staticmethod

@@ -33,6 +33,7 @@
 #include "rdf_window_agg.h"
 #include "rdf_moments.h"
 #include "rdf_group_sorted.h"
+#include "rdf_percentile.h"
 #include "rdf_collect.h"
 #include "rdf_datetime.h"
 #include "rdf_select.h"
@@ -100,6 +101,7 @@ struct Ctx {
     int    opt_gb_hot = 1;          // skewed keys: 1 = heavy-hitter split (the hot hash classes through gb2_stream_kernel, the scatter path over the rest), default; 0 = capacity plan / first-generation path as in round 3 (A/B)
     int    opt_gb_bucket = 0;       // partition tables of the aggregate pass: 4 = four keys per 32-byte bucket, 1 = one key per probe, 0 = by the sampled key range (default: one key per probe for keys packed into <= 4 x max_groups values, buckets otherwise)
     int    opt_uniques_route = 0;     // rdf_uniques / rdf_utf8_uniques: 0 = the hash route while its table holds the keys, else the sort route (default); 1 = always the sort (exact) route (tests, A/B)
+    int    opt_percentile_route = 0;  // rdf_groupby_percentile: 0 = by the call (the select route where it is eligible and measured faster), 1 = always the sorted route, 2 = the select route or a refusal (tests, A/B)
     int    opt_uniques_table_bits = 24;   // ... log2 of the most slots the hash route's table may have (8 bytes each, + 4 for Utf8); it is filled to half, so 2^23 distinct values fit by default
     int    opt_gb_partition = 3;    // hash GROUP BY: 3 = second generation (rdf_groupby.hip: stream / line-aligned scatter / table by max_groups, default), 4 = its partition path whatever max_groups says, 1 = rdf_groupby_sum on the first-generation histogram + scatter fallback where its range holds (A/B), 0 = one table in HBM
     // kernel timing (bench.py roofline leg)
@@ -2877,6 +2879,7 @@ rdf_status groupby_sum_fallback(const rdf_array* keys, const rdf_array* values, 
 #include "rdf_capi_window_agg.inc"
 #include "rdf_capi_moments.inc"
 #include "rdf_capi_group_sorted.inc"
+#include "rdf_capi_percentile.inc"
 #include "rdf_capi_collect.inc"
 #include "rdf_capi_datetime.inc"
 #include "rdf_capi_utf8_pred.inc"
@@ -2946,6 +2949,7 @@ rdf_status rdf_set_option(const char* name, int64_t value) {
     else if (strcmp(name, "comm_max_bytes") == 0) g_ctx.opt_comm_max_bytes = value;
     else if (strcmp(name, "stream_slab_bytes") == 0) g_ctx.opt_stream_slab = value;
     else if (strcmp(name, "uniques_route") == 0) g_ctx.opt_uniques_route = value == 1 ? 1 : 0;
+    else if (strcmp(name, "percentile_route") == 0) g_ctx.opt_percentile_route = value == 1 || value == 2 ? (int)value : 0;
     else if (strcmp(name, "uniques_table_bits") == 0) g_ctx.opt_uniques_table_bits = value < 10 ? 10 : value > 32 ? 32 : (int)value;
     else return fail(RDF_INVALID_ARGUMENT, "unknown option %s", name);
     return RDF_OK;

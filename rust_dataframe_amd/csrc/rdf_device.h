@@ -706,3 +706,70 @@ hipError_t launch_fill_i64(int64_t* p, int64_t n, uint64_t seed, uint64_t col, i
 hipError_t launch_fill_validity(uint8_t* p, int64_t nbits, uint64_t seed, uint64_t col, int64_t first_row, double null_fraction, hipStream_t s);
 
 }  // namespace rdfk
+
+// ---- percentiles per group (rdf_percentile.hip; host side: rdf_capi_percentile.inc; the decisions: rdf_percentile.h) ----
+// The window front (rdf_window.h) has sorted the rows by (grouping keys, value): a group is a partition, and one thread per
+// (group, call) reads its answer through the front's tables.
+struct Utf8Chunk;
+constexpr int kPctThreads = RDF_PERCENTILE_PICK_BLOCK;
+struct PctCallOut { int32_t kind, pad; double p; void* values; uint8_t* vbytes; };
+struct PctPickArgs {
+    const int64_t*           scan;       // [n + 1] exclusive scan of the front's flags
+    const uint32_t*          pstart;     // [G + 1] first sorted position of every group, then n
+    const uint32_t*          gstart;     // [D + 1] first sorted position of every (group, value) pair, then n
+    const uint32_t*          perm;       // sorted position -> row (nullptr = identity)
+    const rdfk::DevChunkCol* vchunks;    // the value column's numeric chunks, or nullptr
+    const Utf8Chunk*         vutf8;      // the value column's Utf8 chunks (validity only is read), or nullptr
+    const int64_t*           row_start;  // [nchunks + 1]
+    int64_t                  nchunks;
+    int32_t                  vdtype;     // numeric value: rdf_dtype
+    int32_t                  nullable;   // some value chunk carries validity
+    int64_t                  groups;     // G
+    int64_t*                 counts;     // [G] non-NULL values per group, or nullptr
+    int32_t                  ncalls, pad;
+    PctCallOut               calls[RDF_PERCENTILE_MAX_CALLS];   // values: [G] Float64 bits (CONT) / UInt32 rows (DISC); vbytes: [G] 1 = valid, or nullptr
+    unsigned long long*      nulls;      // [RDF_PERCENTILE_MAX_CALLS], zeroed
+};
+hipError_t launch_pct_pick(const PctPickArgs& a, hipStream_t s);
+
+// ---- percentiles of one whole numeric column without a sort: the radix select (rdf_percentile.hip) ----
+// Up to 16 target ranks (8 calls x lo / hi) are narrowed digit by digit over the keys' ordered unsigned images.  A SLOT is
+// one distinct prefix some target still lies under; every pass counts, per slot, the candidates by their next digit.
+constexpr int kPctSelBits = RDF_PCT_SELECT_BITS;
+constexpr int kPctSelBuckets = 1 << kPctSelBits;
+constexpr int kPctSelTile = RDF_PCT_SELECT_TILE;          // rows of one block tile
+constexpr int kPctSelFinish = RDF_PCT_SELECT_FINISH;      // candidates the one-block finish sorts in LDS
+constexpr int kPctSelRanks = 2 * RDF_PERCENTILE_MAX_CALLS;
+constexpr int kPctSelThreads = 256;
+enum : int32_t { PCT_SEL_NARROW = 0, PCT_SEL_FINISH = 1, PCT_SEL_RESOLVED = 2 };
+struct PctSelState {                                       // device memory, zeroed before the first pass
+    uint32_t hist[kPctSelRanks][kPctSelBuckets];          // this pass: candidates per slot and next digit
+    uint64_t m;                                            // non-NULL rows
+    uint64_t prefix[kPctSelRanks];                         // per slot: the digits decided so far, right-aligned
+    uint64_t residual[kPctSelRanks];                       // per rank: its 0-based rank among its slot's candidates
+    uint64_t key[kPctSelRanks];                            // per rank: the key it resolved to
+    int32_t  slot[kPctSelRanks];                           // per rank
+    int32_t  nslots, digits_done, phase, passes;           // passes: hist passes that did read the column
+    uint32_t cand_count, finished;
+    uint32_t disc_row[RDF_PERCENTILE_MAX_CALLS];           // per call: the smallest row holding the resolved key
+    uint64_t cand[kPctSelFinish];                          // the finish's candidates, in no particular order
+};
+struct PctSelArgs {
+    PctSelState*             st;
+    const rdfk::DevChunkCol* vchunks;    // the value column's chunks
+    const int64_t*           row_start;  // [nchunks + 1]
+    int64_t                  nchunks, n;
+    int32_t                  vdtype, key_bits;
+    int32_t                  pass;       // the hist pass this launch is (digits decided before it)
+    int32_t                  ncalls;
+    PctCallOut               calls[RDF_PERCENTILE_MAX_CALLS];
+    int64_t*                 counts;     // [1] or nullptr
+    uint32_t*                group_rows; // [1] or nullptr
+    unsigned long long*      nulls;      // [RDF_PERCENTILE_MAX_CALLS], zeroed
+};
+hipError_t launch_pct_sel_hist(const PctSelArgs& a, hipStream_t s);     // one streaming pass: counts by the next digit
+hipError_t launch_pct_sel_plan(const PctSelArgs& a, hipStream_t s);     // one block: every rank's bucket, the new slots
+hipError_t launch_pct_sel_gather(const PctSelArgs& a, hipStream_t s);   // phase FINISH: the candidates' keys into st->cand
+hipError_t launch_pct_sel_finish(const PctSelArgs& a, hipStream_t s);   // phase FINISH: one block sorts them in LDS
+hipError_t launch_pct_sel_rows(const PctSelArgs& a, hipStream_t s);     // DISC: the smallest row of every resolved key
+hipError_t launch_pct_sel_emit(const PctSelArgs& a, hipStream_t s);     // values, validity bytes, count
