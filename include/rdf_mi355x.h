@@ -1400,7 +1400,11 @@ typedef struct {
  * RDF_COMPUTE_ERROR.  Averages are sum / count on the caller's side (AggregateFunctions::avg,
  * src/functions/aggregate.rs:32-65).  The reference plans this step (Dataset::try_aggregate,
  * src/expression.rs:114-221) but does not execute it (src/evaluation.rs:73 panics): semantics are SQL's,
- * parity unpinned by the reference.  f64 sums: accumulation order is not deterministic (<= 1e-6 rel).
+ * parity unpinned by the reference.  f64 sums: every addition is a correctly rounded f64 addition, their order is not
+ * deterministic, so a group of n values x_i comes back within gamma(n - 1) * sum|x_i| of the exact sum (gamma(k) =
+ * k u / (1 - k u), u = 2^-53: the bound of any order and tree of additions), products are not contracted into the
+ * sums, and inputs whose values and partial sums are all exactly representable (integer-valued or small dyadic
+ * measures) are summed exactly, bit for bit in every order (tests/group_ref.py is the executable statement).
  * Large or sparse key domains: rdf_groupby_sum. */
 rdf_status rdf_group_pipeline(const rdf_expr_node* nodes, int32_t nnodes, int32_t filter_root, int32_t group_root,
                               int32_t ngroups, const int32_t* value_roots, int32_t nvalues,

@@ -2436,8 +2436,9 @@ class Api:
 
     # ---- fused grouped aggregation over a small dense domain (TPC-H Q1 shape)
     def group_pipeline(self, expr: Expr, cols: Sequence[Sequence], value_roots: Sequence[int], group_root: int, ngroups: int,
-                       filter_root: int = -1):
-        """-> (res, rows): res[v][g] = (sum, count) of value v in group g (g == ngroups: the NULL group), rows[g] = count(*)."""
+                       filter_root: int = -1, with_some: bool = False):
+        """-> (res, rows): res[v][g] = (sum, count) of value v in group g (g == ngroups: the NULL group), rows[g] = count(*).
+        with_some: (sum, count, is_some) instead."""
         nchunks = 0 if isinstance(cols, Frame) or not cols else len(cols[0])
         nodes = expr.c_array()
         nv = len(value_roots)
@@ -2459,7 +2460,7 @@ class Api:
             row = []
             for g in range(S):
                 r = out[v * S + g]
-                row.append((r.sum_f64 if r.dtype in (F32, F64) else r.sum_i64, r.count))
+                row.append((r.sum_f64 if r.dtype in (F32, F64) else r.sum_i64, r.count) + ((r.is_some,) if with_some else ()))
             res.append(row)
         return res, [rows[g] for g in range(S)]
 
