@@ -26,6 +26,7 @@
 
 #include "rdf_device.h"
 #include "rdf_stage_copy.h"
+#include "rdf_stream_plan.h"
 #include "rdf_program_plan.h"
 #include "rdf_utf8.h"
 #include "rdf_colstats.h"
@@ -346,8 +347,6 @@ uint64_t h_normalize_int(int dt, uint64_t x) {
 // ------------------------------------------------------------------------------------------------
 // staging of RDF_MEM_HOST buffers: small items are packed through the pinned buffer and moved with
 // ONE copy; large items are copied directly.
-
-constexpr size_t kSmallCopy = 256 * 1024;
 
 struct Region {
     std::vector<StageItem> items;

@@ -7,6 +7,8 @@
 #include <thread>
 #include <vector>
 
+constexpr size_t kSmallCopy = 256 * 1024;   // items below this are packed through the staging buffer, larger ones travel by their own copy
+
 struct StageItem {
     const void* src;   // host source (H2D) — or destination (D2H)
     size_t bytes;

@@ -1,0 +1,275 @@
+"""What the streamed batch loop (rdf_capi_stream.inc) must return, in plain numpy and Python: a model of its five sinks that knows
+nothing of slabs, pieces or copy routes, and nothing of the C oracle.  A streamed call is a call: whatever the slab size, the
+result is the one the header documents for the whole batch list.
+
+Expressions are evaluated by spec_ref.evaluate over whole columns (one rounding per operation, integers wrap at the value's
+width, comparisons in f64, NULL where any input is NULL); the grouped sink is group_ref; float bounds come from exact_ref.
+
+  aggregate sink   count / min / max exact over the valid rows that pass the predicate; integer sums exact with wrap-around at the
+                   value's width; float sums against math.fsum of the selected values:
+                     f64   |got - fsum| <= gamma(count - 1) * sum|x|  — the bound of ANY order and tree of correctly rounded f64
+                           additions (exact_ref.gamma, u = 2^-53), which covers a fold in slab order one level above the kernel's.
+                     f32   The kernel accumulates f32 values in f64.  fill_agg_result (rdf_capi_program.inc) then ROUNDS each
+                           run_program result to f32 — `r->sum_f64 = dt == RDF_F32 ? (double)(float)s : s` — and a streamed call
+                           is one run_program per slab: the slab partials are rounded to f32 per slab, and agg_fold
+                           (rdf_capi_stream.inc) adds those rounded partials in f64 (`t.sum_f64 += p.sum_f64`) without rounding
+                           again.  So per slab s: |p_s - exact_s| <= n_s 2^-53 sum_s|x| (any-order f64) + ulp32(p_s) / 2, and
+                           ulp32(p) / 2 <= 2^-24 |p| for a normal p.  The slab half-ulps add up to at most
+                           2^-24 sum_s |p_s| <= 2^-24 sum|x| (1 + count 2^-53) whatever the number of slabs, the f64 additions
+                           inside and across slabs to at most gamma(count) sum|x|.  With the one-shot path's single rounding
+                           (half an f32 ulp of the result) allowed on top, so that one bound serves both paths:
+                             |got - fsum| <= ulp32(fsum) / 2 + gamma(count) sum|x| + 2^-24 sum|x| (1 + count 2^-53).
+                           Where every slab partial is an integer below 2^24 in magnitude (integer-valued f32 data with
+                           sum|x| < 2^24) nothing is rounded at all: `f32_sum_is_exact`, and the sum must be the reference itself.
+  store sinks      per batch: values at valid rows (bit for bit: integer, IEEE-exact and cast results), validity, null_count.
+                   Casts as rdf_cast documents them; numeric <-> Boolean always succeed (x != 0; 0 / 1).  A mask's value bit is
+                   0 where the mask is NULL.
+  filter sink      per batch the kept rows of every column (a NULL predicate drops the row): values, validity, length, null_count.
+  hash GROUP BY    a dict per key: (value, count).  count = valid values of the group (rows for COUNT, or without values);
+                   sum = wrapping 64-bit for integers, f64 for floats (Float32 widened), 0 for a group without a valid value;
+                   min / max = None for such a group.  Float sums are accumulated with atomics in no fixed order: group_ref's
+                   any-order bound.
+  fused grouped    group_ref.run_chunks.
+"""
+import math
+from fractions import Fraction
+
+import numpy as np
+
+from rust_dataframe_amd import _abi as A
+
+import exact_ref as X
+import group_ref as GR
+import spec_ref as S
+
+
+# ---------------------------------------------------------------- columns
+def columns(cols):
+    """cols[c] = chunk list of HostArrays -> [(dtype, values, valid)] over all rows, as spec_ref.evaluate takes them."""
+    return [(col[0].dtype, v, np.ones(len(v), dtype=bool) if valid is None else valid) for col, (v, valid) in zip(cols, GR.columns_of(cols))]
+
+
+def batches(x, lens):
+    """A vector over all rows -> one per batch."""
+    at = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    return [x[at[i]:at[i + 1]] for i in range(len(lens))]
+
+
+def lens_of(cols):
+    return [ch.length for ch in cols[0]]
+
+
+def _bits(v):
+    """The bit pattern of a numeric vector (floats compare bit for bit: -0.0 is not 0.0, a NaN is its payload)."""
+    v = np.ascontiguousarray(v)
+    return v.view({4: np.uint32, 8: np.uint64}[v.dtype.itemsize]) if v.dtype.kind == "f" else v
+
+
+# ---------------------------------------------------------------- aggregate sink
+def aggregate(expr, cols, value_roots, filter_root=-1):
+    """-> [spec_ref.Agg] (count, sum, min, max and the selected values of every value root)."""
+    return S.run_agg(expr, columns(cols), value_roots, filter_root)
+
+
+def _abs_sum(values):
+    return sum((Fraction(abs(float(t))) for t in values.tolist()), Fraction(0))
+
+
+def f64_sum_bound(agg) -> Fraction:
+    return Fraction(X.gamma(max(agg.count - 1, 0))) * _abs_sum(agg.values)
+
+
+def f32_sum_bound(agg) -> Fraction:
+    """See the module docstring: slab partials are rounded to f32 per slab and added in f64."""
+    a = _abs_sum(agg.values)
+    half_ulp = Fraction(float(X.ulp_of(np.float64(agg.sum), np.float64(0.0), np.float32))) / 2
+    return half_ulp + Fraction(X.gamma(agg.count)) * a + Fraction(1, 2 ** 24) * a * (1 + Fraction(agg.count, 2 ** 53))
+
+
+def f32_sum_is_exact(agg) -> bool:
+    """Integer-valued data whose every partial sum is an integer below 2^24: no addition and no rounding to f32 loses a bit."""
+    v = agg.values.astype(np.float64)
+    return bool(np.all(v == np.rint(v))) and _abs_sum(agg.values) < 2 ** 24
+
+
+def check_aggregate(got, model, what=""):
+    """got = Api.pipeline(...) (AggResults), model = aggregate(...)."""
+    assert len(got) == len(model), what
+    for v, (g, m) in enumerate(zip(got, model)):
+        w = f"{what}: value {v}"
+        assert g.dtype == m.dt, f"{w}: dtype {g.dtype} != {m.dt}"
+        assert g.count == m.count, f"{w}: count {g.count} != {m.count}"
+        assert bool(g.is_some) == (m.count > 0), f"{w}: is_some {g.is_some} with count {m.count}"
+        if m.count > 0:
+            assert g.min == m.min and g.max == m.max, f"{w}: min / max {g.min!r} {g.max!r} != {m.min!r} {m.max!r}"
+        if m.dt not in S.FLOATS:
+            assert g.sum == (m.sum + 2 ** 64 if m.dt == A.U64 and m.sum < 0 else m.sum), f"{w}: sum {g.sum} != {m.sum}"
+            continue
+        assert math.isfinite(m.sum), "the model's float data is finite"
+        if m.dt == A.F32 and f32_sum_is_exact(m):
+            assert g.sum == m.sum, f"{w}: f32 sum {g.sum!r} != {m.sum!r} (integer-valued: nothing is rounded)"
+            continue
+        bound = f64_sum_bound(m) if m.dt == A.F64 else f32_sum_bound(m)
+        err = abs(Fraction(g.sum) - Fraction(m.sum)) if math.isfinite(g.sum) else None
+        assert err is not None and err <= bound, f"{w}: sum {g.sum!r} vs fsum {m.sum!r} over {m.count} values: |diff| {float(err) if err is not None else 'inf'} > bound {float(bound)!r}"
+
+
+# ---------------------------------------------------------------- store sinks
+def store(expr, cols, root) -> S.Val:
+    """The value of `root` over all rows."""
+    return S.run_store(expr, columns(cols), root)
+
+
+def cast(col, to) -> S.Val:
+    """rdf_cast of one column."""
+    dt, v, valid = columns([col])[0]
+    if to == A.BOOL and dt != A.BOOL:
+        return S.Val(A.BOOL, v != 0, valid.copy())
+    if dt == A.BOOL and to != A.BOOL:
+        return S.Val(to, v.astype(A.NP_OF[to]), valid.copy())
+    return S.cast(S.Val(dt, v, valid), to)
+
+
+def unary(op, col) -> S.Val:
+    """abs / floor / sqrt of a float column: IEEE 754 defines all three exactly (sqrt is correctly rounded), and so does numpy."""
+    dt, v, valid = columns([col])[0]
+    assert dt in S.FLOATS
+    with np.errstate(all="ignore"):
+        return S.Val(dt, {"abs": np.abs, "floor": np.floor, "sqrt": np.sqrt}[op](v), valid.copy())
+
+
+def mask(expr, cols, root) -> S.Val:
+    """rdf_predicate: the value bit of a NULL slot is 0."""
+    p = store(expr, cols, root)
+    assert p.dt == A.BOOL
+    return S.Val(A.BOOL, p.v.astype(bool) & p.valid, p.valid)
+
+
+def check_store(got, val: S.Val, lens, what=""):
+    """got = one output HostArray per batch."""
+    assert len(got) == len(lens), what
+    for i, (g, v, ok) in enumerate(zip(got, batches(val.v, lens), batches(val.valid, lens))):
+        w = f"{what}: batch {i}"
+        assert g.dtype == val.dt, f"{w}: dtype {g.dtype} != {val.dt}"
+        assert g.length == len(v), f"{w}: length {g.length} != {len(v)}"
+        assert g.null_count == int((~ok).sum()), f"{w}: null_count {g.null_count} != {int((~ok).sum())}"
+        if g.validity is None:
+            assert ok.all(), f"{w}: the model has NULLs, the output no validity buffer"
+        else:
+            assert np.array_equal(g.valid_mask(), ok), f"{w}: validity differs at rows {np.flatnonzero(g.valid_mask() != ok)[:8]}"
+        gv = g.to_numpy()
+        same = _bits(gv[ok]) == _bits(np.asarray(v)[ok])
+        assert same.all(), f"{w}: values differ at valid rows {np.flatnonzero(ok)[~same][:8]}"
+
+
+def check_same_chunks(a, b, what=""):
+    """Two runs of one call (streamed, one shot): every batch equal in length, null_count, validity and value BITS at valid rows."""
+    assert len(a) == len(b), what
+    for i, (x, y) in enumerate(zip(a, b)):
+        w = f"{what}: batch {i}"
+        assert (x.dtype, x.length, x.null_count) == (y.dtype, y.length, y.null_count), f"{w}: {(x.dtype, x.length, x.null_count)} != {(y.dtype, y.length, y.null_count)}"
+        ok = x.valid_mask()
+        assert np.array_equal(ok, y.valid_mask()), f"{w}: validity differs"
+        assert np.array_equal(_bits(x.to_numpy()[ok]), _bits(y.to_numpy()[ok])), f"{w}: values differ"
+
+
+# ---------------------------------------------------------------- filter sink
+def filter_rows(expr, cols, root):
+    """-> out[c][i] = (values, valid) of the kept rows of batch i of column c."""
+    ecols = columns(cols)
+    p = S.evaluate(expr, ecols, root)
+    assert p.dt == A.BOOL
+    keep = p.valid & p.v.astype(bool)
+    lens = lens_of(cols)
+    kb = batches(keep, lens)
+    return [[(v[k], ok[k]) for v, ok, k in zip(batches(cv, lens), batches(cvalid, lens), kb)] for _, cv, cvalid in ecols]
+
+
+def check_filter(got, model, cols, what=""):
+    """got[c][i] = output HostArray of batch i of column c."""
+    assert len(got) == len(model), what
+    for c, (gcol, mcol) in enumerate(zip(got, model)):
+        assert len(gcol) == len(mcol), what
+        for i, (g, (v, ok)) in enumerate(zip(gcol, mcol)):
+            w = f"{what}: column {c} batch {i}"
+            assert g.dtype == cols[c][0].dtype, w
+            assert g.length == len(v), f"{w}: length {g.length} != {len(v)}"
+            assert g.null_count == int((~ok).sum()), f"{w}: null_count {g.null_count} != {int((~ok).sum())}"
+            if g.validity is None:
+                assert ok.all(), w
+            else:
+                gm = A.unpack_bits(g.validity, 0, g.length)
+                assert np.array_equal(gm, ok), f"{w}: validity differs at kept rows {np.flatnonzero(gm != ok)[:8]}"
+            gv = g.values[:g.length]
+            same = _bits(gv[ok]) == _bits(v[ok])
+            assert same.all(), f"{w}: values differ at kept rows {np.flatnonzero(ok)[~same][:8]}"
+
+
+# ---------------------------------------------------------------- hash GROUP BY
+ANY = object()      # a value the header leaves open
+
+
+def groupby(keys, values, agg):
+    """keys: one chunk list without NULLs; values: a chunk list or None.  -> {key: (value | None, count, valid f64 values | None)}:
+    value is ANY for COUNT and without values (rdf_groupby_agg's out_values is not specified there), None for a MIN / MAX without a valid value."""
+    k = np.concatenate([ch.to_numpy() for ch in keys])
+    assert all(ch.validity is None or ch.valid_mask().all() for ch in keys)
+    if values is not None:
+        vdt, v, ok = columns([values])[0]
+    order = np.argsort(k, kind="stable")
+    ks = k[order]
+    starts = np.flatnonzero(np.concatenate([[True], ks[1:] != ks[:-1]])) if len(ks) else np.zeros(0, dtype=np.int64)
+    ends = np.concatenate([starts[1:], [len(ks)]]).astype(np.int64)
+    out = {}
+    for s, e in zip(starts.tolist(), ends.tolist()):
+        key = int(ks[s])
+        rows = order[s:e]
+        if values is None or agg == "count":
+            out[key] = (ANY, e - s, None)
+            continue
+        x = v[rows][ok[rows]]
+        n = len(x)
+        if vdt in S.FLOATS:
+            x = x.astype(np.float64)                      # Float32 widens exactly
+            assert np.isfinite(x).all(), "the model's float data is finite"
+            val = (math.fsum(x.tolist()) if n else 0.0) if agg == "sum" else None if n == 0 else float(x.min() if agg == "min" else x.max())
+            out[key] = (val, n, x)
+        else:
+            ints = [int(t) for t in x.tolist()]
+            val = GR.wrap64(sum(ints)) if agg == "sum" else None if n == 0 else (min(ints) if agg == "min" else max(ints))
+            out[key] = (val, n, None)
+    return out
+
+
+def groups_of(keys_out, vals_out, counts_out):
+    """The three outputs of Api.groupby_agg -> {key: (value | None, count)}; a key twice is an error."""
+    ks = keys_out[0].to_pylist()
+    v, c = vals_out.to_pylist(), counts_out.to_numpy().tolist()
+    out = {}
+    for i in range(counts_out.length):
+        assert ks[i] not in out, f"group {ks[i]} twice"
+        out[ks[i]] = (v[i], c[i])
+    return out
+
+
+def check_groupby(got, model, agg, what=""):
+    """got = groups_of(...), model = groupby(...)."""
+    assert got.keys() == model.keys(), f"{what}: keys differ: {len(got)} groups vs {len(model)}; only in one: {sorted(set(got) ^ set(model))[:8]}"
+    for key, (mv, mc, x) in model.items():
+        gv, gc = got[key]
+        w = f"{what}: group {key}"
+        assert gc == mc, f"{w}: count {gc} != {mc}"
+        if mv is ANY:
+            continue
+        if mv is None:
+            assert gv is None, f"{w}: {agg} of a group without a valid value is NULL, got {gv!r}"
+        elif agg == "sum" and x is not None:
+            one = GR.Model(1, [A.F64], [[mv]], [[mc]], [mc], [[x]])
+            assert gv is not None and GR.float_sum_ok(float(gv), one, 0, 0), f"{w}: sum {gv!r} vs fsum {mv!r} over {mc} values, bound {float(GR.float_bound(one, 0, 0))!r}"
+        else:
+            assert gv == mv, f"{w}: {agg} {gv!r} != {mv!r}"
+
+
+# ---------------------------------------------------------------- fused grouped aggregation
+def grouped(expr, cols, value_roots, group_root, ngroups, filter_root=-1):
+    return GR.run_chunks(expr, cols, value_roots, group_root, ngroups, filter_root)

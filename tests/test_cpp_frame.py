@@ -57,6 +57,41 @@ def test_stage_copy_cpp():
     run(out)
 
 
+def test_stream_plan_cpp():
+    """The host logic of the streamed batch loop (csrc/rdf_stream_plan.h: the planner, DownLayout, bits_append) on the CPU: over a
+    few thousand seeded layouts the upload is emulated and every view read back — every row of every batch exactly once, in order,
+    with its value and validity bit; items disjoint, staged in front and direct behind on 256-byte boundaries; merged runs only over
+    contiguous memory; plan.max_* bound every slab.  bits_append against a per-bit loop at every phase pair."""
+    out = os.path.join(tempfile.gettempdir(), f"rdf_test_stream_plan_{os.getpid()}")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", os.path.join(ROOT, "tests", "cpp", "test_stream_plan.cpp"), "-o", out])
+    run(out)
+
+
+SANITIZE = "-fsanitize=address,undefined"
+
+
+def _sanitizer_links():
+    """Can a trivial program be linked with the sanitizers' runtimes at all?"""
+    with tempfile.TemporaryDirectory() as d:
+        src = os.path.join(d, "t.cpp")
+        with open(src, "w") as f:
+            f.write("int main() { return 0; }\n")
+        return subprocess.run(["g++", SANITIZE, src, "-o", os.path.join(d, "t")], capture_output=True).returncode == 0
+
+
+@pytest.mark.parametrize("name", ["test_stream_plan", "test_stage_copy"])
+def test_stream_host_code_under_sanitizers_cpp(name):
+    """The same stand-alone programs (their own main, no library, nothing loaded into Python) built with AddressSanitizer and
+    UndefinedBehaviorSanitizer: a byte read past a column's buffer, a copy past a staging buffer or a shift out of range ends the
+    program."""
+    if not _sanitizer_links():
+        pytest.skip("g++ cannot link a program with " + SANITIZE)
+    out = os.path.join(tempfile.gettempdir(), f"rdf_{name}_san_{os.getpid()}")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-pthread", SANITIZE, "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
+                           os.path.join(ROOT, "tests", "cpp", name + ".cpp"), "-o", out])
+    run(out)
+
+
 def test_sort_bucket_map_cpp():
     """The bucket map of Float64 sort keys (csrc/rdf_sort_map.h: the function the kernels run, under the planner the host runs) on
     the CPU: monotone over sorted columns of every shape and across every seam, inside its buckets, the fullest bucket inside the
