@@ -1557,7 +1557,9 @@ rdf_status rdf_fill_validity(uint8_t* dev_ptr, int64_t nbits, uint64_t seed, uin
  * kernels that were measured slower and removed — the table-driven block tiles, the two-launch form for frames of 8- and 4-byte columns, the
  * older look-back walks of the wave-tile kernel),
  * "join_table" (equi-join on one key column: 2 = the build side sorted by hash, the table of its distinct keys laid out by a scan,
- * default; 1 = sorted by key, table slots claimed by compare-and-swap; 0 = a bucket index over the sorted build keys),
+ * default; 0 = a bucket index over the build keys sorted by key — what joins on several key columns, build sides of 2^31 - 1 rows or
+ * more and a table whose placement overflows use in any case; 1 named the retired table with slots claimed by compare-and-swap:
+ * accepted, the planner decides as under 2),
  * "sort_msd" (keys that vary in 25 bits or more: 1 = passes over the top bits, buckets finished in LDS, default; 0 = one pass per byte),
  * "sort_gen", "sort_pipe", "sort_super" (accepted and ignored: they selected forms of the digit passes that were measured slower and removed),
  * "sort_sample" (Float64 sort keys: 1 = the value buckets of those passes are planned from a sample of the keys — the range the rows lie

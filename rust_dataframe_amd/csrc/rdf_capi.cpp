@@ -27,6 +27,7 @@
 #include "rdf_device.h"
 #include "rdf_stage_copy.h"
 #include "rdf_stream_plan.h"
+#include "rdf_join_place.h"
 #include "rdf_program_plan.h"
 #include "rdf_utf8.h"
 #include "rdf_colstats.h"
@@ -88,7 +89,7 @@ struct Ctx {
     int64_t utf8_sort_rounds = 0;   // the last sort: refinement rounds its Utf8 criteria took (round 0 included), summed
     int    opt_sort_msd = 1;        // sort keys that vary in more than 32 bits: passes over the top bits, then every bucket sorted in LDS (1, default); 0 = one pass per byte (A/B)
     int    opt_sort_sample = 1;     // doubles: value buckets planned from a sample of the keys (range without outliers, bucket bits from the densest region); 0 = [min, max] and ~500 rows per bucket (round 3, A/B)
-    int    opt_join_table = 2;      // equi-join on one key column: probe a table of the distinct build keys — 2 (default, round 5): the build side sorted by hash, the table placed by a scan (no atomics); 1: sorted by key, slots claimed by compare-and-swap (round 3); 0 = the bucket index over the sorted build keys (A/B)
+    int    opt_join_table = 2;      // equi-join on one key column: 2 (default) = probe a table of the distinct build keys: the build side sorted by hash, the table placed by a scan (no atomics); 0 = the bucket index over the build keys sorted by key (A/B; also what every join the table cannot take uses).  Read once per call (rdf_capi_join.inc), written by rdf_set_option only
     int    opt_jit = 1;             // a program shape outside the catalogs: 1 = compile spec_kernel<Prog> for it on a helper thread (the interpreter answers until the kernel is ready; a code object in the cache directory is loaded at once), default; 2 = the call waits for the compiler; 0 = always the interpreter
     int    opt_take_rows = 1;       // take over a frame through interleaved row records: 1 = when the transaction model says so (default), 0 = never, 2 = always (tests, A/B)
     int    opt_gb_skew_plan = 1;    // skewed keys: per-partition region sizes + big partitions cut into several aggregate items (1 = when the probe finds skew, default; 0 = the first-generation combining path instead, A/B; 2 = always, tests)
@@ -2320,355 +2321,7 @@ rdf_status rdf_sort_to_indices(const rdf_array* cols, int32_t ncols, int64_t nch
 
 // ---------------------------------------------------------------- join
 
-namespace {
-// Radix-sort (key bits, row) pairs already produced by sort_keys_kernel: `width` key bytes, then the nulls-last pass.
-struct SortBuffers { uint64_t* keys[2]; uint32_t* idx[2]; void* nullflags; };
-rdf_status sort_buffers_alloc(int64_t n, SortBuffers& b) {
-    void* p;
-    for (int i = 0; i < 2; ++i) { RDF_TRY(arena_alloc((size_t)n * 8 + 8, &p)); b.keys[i] = (uint64_t*)p; }
-    for (int i = 0; i < 2; ++i) { RDF_TRY(arena_alloc((size_t)n * 4 + 8, &p)); b.idx[i] = (uint32_t*)p; }
-    RDF_TRY(arena_alloc((size_t)n + 8, &b.nullflags));
-    return RDF_OK;
-}
-// keys[0] holds the unsorted key bits (identity order).  On return keys[*kcur] / idx[*icur] are sorted.
-rdf_status radix_sort_rows(const SortBuffers& b, int64_t n, int width, bool has_nulls, int* kcur_out, int* icur_out, const uint64_t* d_stats, size_t pin_off,
-                           uint64_t* kmin_out, uint64_t* kmax_out) {
-    int kcur = 0, icur = 1;
-    const uint32_t* idx_cur = nullptr;
-    uint64_t bias = 0;
-    int need = 0;
-    uint64_t kmax = 0;
-    RDF_TRY(sort_key_range(d_stats, pin_off, &bias, &need, &kmax));
-    if (kmax_out) *kmax_out = kmax;
-    *kmin_out = bias;
-    if (need == 0 && !has_nulls) need = 1;   // all keys equal: one pass still writes the identity order
-    OsScratch os;
-    RDF_TRY(os_scratch_alloc(n, os));
-    RDF_TRY(os_column_passes(os, b.keys, b.idx, (const uint8_t*)b.nullflags, n, bias, std::min(need, width), has_nulls, kcur, icur, idx_cur, kmax >= bias ? kmax - bias : ~0ull));
-    *kcur_out = kcur;
-    *icur_out = icur;
-    return RDF_OK;
-}
-}  // namespace
-
-rdf_status rdf_equijoin_indices(const rdf_array* left_keys, int64_t left_nchunks, const rdf_array* right_keys, int64_t right_nchunks,
-                                int32_t join_type, rdf_out* out_left, rdf_out* out_right, int64_t* out_rows) {
-    return rdf_equijoin_indices_multi(left_keys, left_nchunks, right_keys, right_nchunks, 1, join_type, out_left, out_right, out_rows);
-}
-
-rdf_status rdf_equijoin_indices_multi(const rdf_array* left_keys, int64_t left_nchunks, const rdf_array* right_keys, int64_t right_nchunks,
-                                      int32_t nkeys, int32_t join_type, rdf_out* out_left, rdf_out* out_right, int64_t* out_rows) {
-    if (!left_keys || !right_keys || left_nchunks < 1 || right_nchunks < 1 || !out_rows) return fail(RDF_INVALID_ARGUMENT, "join: bad arguments");
-    if (nkeys < 1 || nkeys > 4) return fail(RDF_INVALID_ARGUMENT, "join: 1 to 4 key columns per side");
-    if (join_type < RDF_JOIN_LEFT || join_type > RDF_JOIN_FULL) return fail(RDF_INVALID_ARGUMENT, "join: bad join type");
-    if ((out_left == nullptr) != (out_right == nullptr)) return fail(RDF_INVALID_ARGUMENT, "join: give both outputs or neither (count only)");
-    int32_t mem = -1;
-    RDF_TRY(check_mem(left_keys, (int64_t)nkeys * left_nchunks, &mem));
-    RDF_TRY(check_mem(right_keys, (int64_t)nkeys * right_nchunks, &mem));
-    if (out_left) { RDF_TRY(check_out_mem(out_left, 1, mem)); RDF_TRY(check_out_mem(out_right, 1, mem)); }
-    int kdt[4] = {0, 0, 0, 0};
-    int64_t nleft = 0, nright = 0;
-    bool lnulls = false, rnulls = false;
-    for (int k = 0; k < nkeys; ++k) {   // key pair k: left_keys[k * left_nchunks + c] against right_keys[k * right_nchunks + c]
-        kdt[k] = left_keys[(int64_t)k * left_nchunks].dtype;
-        if (!is_numeric(kdt[k])) return fail(RDF_INVALID_ARGUMENT, "join: numeric key columns only");
-        int64_t nl = 0, nr = 0;
-        for (int64_t c = 0; c < left_nchunks; ++c) { const rdf_array& a = left_keys[(int64_t)k * left_nchunks + c]; if (a.dtype != kdt[k]) return fail(RDF_INVALID_ARGUMENT, "join: key columns must share one dtype (cast first)"); nl += a.length; lnulls |= a.validity != nullptr; }
-        for (int64_t c = 0; c < right_nchunks; ++c) { const rdf_array& a = right_keys[(int64_t)k * right_nchunks + c]; if (a.dtype != kdt[k]) return fail(RDF_INVALID_ARGUMENT, "join: key columns must share one dtype (cast first)"); nr += a.length; rnulls |= a.validity != nullptr; }
-        if (k == 0) { nleft = nl; nright = nr; }
-        else if (nl != nleft || nr != nright) return fail(RDF_COMPUTE_ERROR, "join: key columns of one side differ in length");
-    }
-    const int dt = kdt[0];
-    if (nleft >= (int64_t)1 << 32 || nright >= (int64_t)1 << 32) return fail(RDF_INVALID_ARGUMENT, "join: UInt32 indices cap a side at 2^32-1 rows");
-    if (out_left && (out_left->dtype != RDF_U32 || out_right->dtype != RDF_U32)) return fail(RDF_INVALID_ARGUMENT, "join: indices are UInt32");
-    const bool swap = join_type == RDF_JOIN_RIGHT;  // probe = right, build = left
-    const rdf_array* pk = swap ? right_keys : left_keys;
-    const rdf_array* bk = swap ? left_keys : right_keys;
-    const int64_t pnc = swap ? right_nchunks : left_nchunks, bnc = swap ? left_nchunks : right_nchunks;
-    const int64_t np = swap ? nright : nleft, nb = swap ? nleft : nright;
-    const bool pnulls = swap ? rnulls : lnulls, bnulls = swap ? lnulls : rnulls;
-    const bool outer = join_type != RDF_JOIN_INNER;
-    const bool full = join_type == RDF_JOIN_FULL;
-    if (np == 0 && (!full || nb == 0)) {
-        *out_rows = 0;
-        if (out_left) { out_left->length = out_right->length = 0; out_left->null_count = out_right->null_count = 0; }
-        return RDF_OK;
-    }
-    RDF_TRY(ensure_ready());
-    Ctx& ctx = g_ctx;
-    arena_begin();
-    size_t pin_off = 0, used = 0;
-    InputStager in;   // staged order: probe key 0 chunks, probe key 1 chunks, ..., then the build side the same way
-    for (int64_t c = 0; c < (int64_t)nkeys * pnc; ++c) in.add(&pk[c]);
-    for (int64_t c = 0; c < (int64_t)nkeys * bnc; ++c) in.add(&bk[c]);
-    RDF_TRY(in.finish(pin_off, &used));
-    pin_off += (used + 255) & ~(size_t)255;
-    std::vector<int64_t> prs((size_t)pnc + 1, 0), brs((size_t)bnc + 1, 0);
-    for (int64_t c = 0; c < pnc; ++c) prs[(size_t)c + 1] = prs[(size_t)c] + pk[c].length;
-    for (int64_t c = 0; c < bnc; ++c) brs[(size_t)c + 1] = brs[(size_t)c] + bk[c].length;
-    TableBuilder tb;
-    const size_t o_ch = tb.reserve(sizeof(DevChunkCol) * in.dev.size());
-    const size_t o_prs = tb.reserve(sizeof(int64_t) * prs.size());
-    const size_t o_brs = tb.reserve(sizeof(int64_t) * brs.size());
-    RDF_TRY(tb.bind(pin_off));
-    memcpy(tb.at<char>(o_ch), in.dev.data(), sizeof(DevChunkCol) * in.dev.size());
-    memcpy(tb.at<char>(o_prs), prs.data(), sizeof(int64_t) * prs.size());
-    memcpy(tb.at<char>(o_brs), brs.data(), sizeof(int64_t) * brs.size());
-    RDF_TRY(tb.alloc());
-    RDF_TRY(tb.upload(pin_off));
-    pin_off += (tb.size + 255) & ~(size_t)255;
-
-    // build side: key bits + null flags, sorted (NULL keys last)
-    SortBuffers sb;
-    RDF_TRY(sort_buffers_alloc(nb > 0 ? nb : 1, sb));
-    void* p;
-    RDF_TRY(arena_alloc(64, &p));
-    unsigned long long* d_cnt = (unsigned long long*)p;  // [0] build nulls, [1] append cursor
-    HIP_TRY(hipMemsetAsync(d_cnt, 0, 64, ctx.stream));
-    KernelTimer kt;
-    int kcur = 0, icur = 0;
-    uint64_t bkmin = 1, bkmax = 0;   // key range of the non-NULL build keys ([1, 0] = none)
-    // Round 5: one key column -> the build side is sorted by key * golden ratio and the table of its distinct keys is laid out by a
-    // scan (JoinPlaceArgs) — join_table_kernel's compare-and-swap per distinct key on a random line was 8.6 of the 18.9 ms of a
-    // 1e8 x 1e8 join.  Equal keys stay adjacent and in row order (the sort is stable), so the pairs come out as before.
-    const bool hashed = nkeys == 1 && ctx.opt_join_table == 2 && nb > 0 && nb < ((int64_t)1 << 31) - 1;
-    void* pstats;
-    RDF_TRY(arena_alloc(128, &pstats));
-    uint64_t* d_bstats = (uint64_t*)pstats;
-    uint64_t* d_pstats = d_bstats + 4;
-    uint64_t* d_ostats = d_bstats + 8;     // (hashed build) the build keys' own [min, max]
-    const uint64_t* pbits[4] = {nullptr, nullptr, nullptr, nullptr};
-    const uint64_t* bbits[4] = {nullptr, nullptr, nullptr, nullptr};
-    // One column per side: the order-preserving key bits ARE the join key.  Several: the key is a 64-bit hash of the
-    // tuple's key bits (candidates are verified column by column in the probe kernels), NULL in any column = NULL key.
-    auto side_keys = [&](bool build, int64_t n, int64_t nch, size_t chunk0, const int64_t* d_row_start, bool has_nulls, uint64_t* out_keys,
-                         uint8_t* nullflags, uint64_t* d_stats, const uint64_t** bits_out) -> rdf_status {
-        if (nkeys > 1 && has_nulls) HIP_TRY(hipMemsetAsync(nullflags, 0, (size_t)n, ctx.stream));
-        JoinCombineArgs ca;
-        memset(&ca, 0, sizeof ca);
-        for (int k = 0; k < nkeys; ++k) {
-            SortKeyArgs ka;
-            memset(&ka, 0, sizeof ka);
-            ka.chunks = tb.dev_at<DevChunkCol>(o_ch) + chunk0 + (size_t)k * (size_t)nch;
-            ka.chunk_row_start = d_row_start;
-            ka.nchunks = nch;
-            ka.n = n;
-            ka.nullflags = has_nulls ? nullflags : nullptr;
-            ka.dtype = kdt[k];
-            if (nkeys == 1) { ka.keys = out_keys; ka.bit_stats = d_stats; if (build && hashed) { ka.hash_mul = 0x9E3779B97F4A7C15ull; ka.raw_stats = d_ostats; } }   // (the key range stays what the probe's early-out compares against; the sort sees the hashed keys' range)
-            else {
-                void* pb;
-                RDF_TRY(arena_alloc((size_t)n * 8 + 8, &pb));
-                ka.keys = (uint64_t*)pb;
-                ka.null_or = 1;
-                bits_out[k] = ca.bits[k] = (const uint64_t*)pb;
-            }
-            HIP_TRY(launch_sort_keys(ka, ctx.stream));
-        }
-        if (nkeys > 1) {
-            ca.nkeys = nkeys; ca.n = n; ca.nullflags = has_nulls ? nullflags : nullptr; ca.out = out_keys; ca.bit_stats = d_stats;
-            HIP_TRY(launch_join_combine(ca, ctx.stream));
-        }
-        return RDF_OK;
-    };
-    RDF_TRY(sort_stats_reset(d_bstats));
-    RDF_TRY(sort_stats_reset(d_pstats));
-    RDF_TRY(sort_stats_reset(d_ostats));
-    if (nb > 0) {
-        RDF_TRY(side_keys(true, nb, bnc, (size_t)nkeys * (size_t)pnc, tb.dev_at<int64_t>(o_brs), bnulls, sb.keys[0], (uint8_t*)sb.nullflags, d_bstats, bbits));
-        if (bnulls) HIP_TRY(launch_count_bytes((const uint8_t*)sb.nullflags, nb, d_cnt, ctx.stream));
-        RDF_TRY(radix_sort_rows(sb, nb, nkeys == 1 && !hashed ? dtype_size(dt) : 8, bnulls, &kcur, &icur, d_bstats, pin_off, &bkmin, &bkmax));
-    }
-    // probe side: key bits + null flags in row order
-    void *ppk, *ppn, *pcounts, *poffs;
-    RDF_TRY(arena_alloc((size_t)(np > 0 ? np : 1) * 8, &ppk));
-    RDF_TRY(arena_alloc((size_t)(np > 0 ? np : 1) + 8, &ppn));
-    RDF_TRY(arena_alloc((size_t)(np + 1) * 8, &pcounts));
-    RDF_TRY(arena_alloc((size_t)(np + 2 + scan_scratch_words(np)) * 8, &poffs));
-    if (np > 0) RDF_TRY(side_keys(false, np, pnc, 0, tb.dev_at<int64_t>(o_prs), pnulls, (uint64_t*)ppk, (uint8_t*)ppn, d_pstats, pbits));
-    RDF_TRY(pinned_reserve(pin_off + 256));
-    HIP_TRY(hipMemcpyAsync(ctx.pinned + pin_off, d_cnt, 8, hipMemcpyDeviceToHost, ctx.stream));
-    if (hashed) HIP_TRY(hipMemcpyAsync(ctx.pinned + pin_off + 8, d_ostats, 16, hipMemcpyDeviceToHost, ctx.stream));
-    HIP_TRY(hipStreamSynchronize(ctx.stream));
-    unsigned long long bnull_count = 0;
-    memcpy(&bnull_count, ctx.pinned + pin_off, 8);
-    if (hashed) {
-        uint64_t st[2];
-        memcpy(st, ctx.pinned + pin_off + 8, 16);
-        if (st[0] > st[1]) { bkmin = 1; bkmax = 0; } else { bkmin = st[0]; bkmax = st[1]; }
-    }
-    const int64_t nrv = nb - (int64_t)bnull_count;
-
-    void* pmatched = nullptr;
-    if (full) { RDF_TRY(arena_alloc((size_t)((nb + 31) / 32 + 1) * 4, &pmatched)); HIP_TRY(hipMemsetAsync(pmatched, 0, (size_t)((nb + 31) / 32 + 1) * 4, ctx.stream)); }
-    // bucket index over the sorted build keys: about one bucket per build row, on the top bits of (key - min)
-    int64_t nbuckets = 1;
-    while (nbuckets < nrv && nbuckets < ((int64_t)1 << 24)) nbuckets <<= 1;
-    int bshift = 0;
-    if (bkmax >= bkmin) while (((bkmax - bkmin) >> bshift) >= (uint64_t)nbuckets) ++bshift;
-    void *pbuckets, *pfirst;
-    RDF_TRY(arena_alloc((size_t)nbuckets * 8, &pbuckets));
-    RDF_TRY(arena_alloc((size_t)(np > 0 ? np : 1) * 4, &pfirst));
-    HIP_TRY(hipMemsetAsync(pbuckets, 0, (size_t)nbuckets * 8, ctx.stream));
-    // one key column: a table of the distinct build keys at load <= 0.5 instead — one random transaction per probe row, where the
-    // bucket index costs three (bucket, sorted keys, build row)
-    const bool use_table = nkeys == 1 && nrv > 0 && nb < ((int64_t)1 << 31) - 1 && ctx.opt_join_table;
-    void* ptable = nullptr;
-    int tbits = 10;
-    if (use_table && hashed) {
-        // the table holds the DISTINCT build keys: no more of them than rows, and no more than the key range spans — a build side of
-        // 1e8 rows over a few dozen dictionary codes gets a table of 1024 slots, not 2e8 whose empty stretches a few lanes would
-        // have to write one slot after another (the placement fills the gaps in front of its keys itself)
-        int64_t nd = nrv;
-        if (bkmax >= bkmin && bkmax - bkmin < (uint64_t)nrv) nd = (int64_t)(bkmax - bkmin) + 1;
-        else if (nrv >= 65536) {
-            // ... and a few keys spread over a WIDE range (hashed identifiers, 37 of them over 3e6 rows): the sorted build side is
-            // read once more to COUNT its distinct keys (equal keys are neighbours; 8 B/row at the read rate, 0.1 ms per 1e8 rows,
-            // and a wait) — sized from the rows, the few lanes in front of such keys wrote millions of empty slots one by one
-            HIP_TRY(hipMemsetAsync(d_cnt + 3, 0, 8, ctx.stream));
-            HIP_TRY(launch_join_distinct(sb.keys[kcur], nrv, (unsigned long long*)(d_cnt + 3), ctx.stream));
-            unsigned long long distinct = 0;
-            HIP_TRY(hipMemcpyAsync(ctx.pinned + pin_off, d_cnt + 3, 8, hipMemcpyDeviceToHost, ctx.stream));
-            HIP_TRY(hipStreamSynchronize(ctx.stream));
-            memcpy(&distinct, ctx.pinned + pin_off, 8);
-            HIP_TRY(hipMemsetAsync(d_cnt + 3, 0, 8, ctx.stream));          // (the placement's overflow flag lives in the same word)
-            if (distinct > 0 && (int64_t)distinct < nd) nd = (int64_t)distinct;
-        }
-        while (((int64_t)1 << tbits) < 2 * nd) ++tbits;
-        const int64_t cap = ((int64_t)1 << tbits) + (1 << 16);      // no wrap-around: the last home slot's cluster runs into the margin
-        RDF_TRY(arena_alloc((size_t)cap * 16 + 64, &ptable));      // (not cleared: the placement writes every slot, the empty ones included)
-        JoinPlaceArgs pa;
-        memset(&pa, 0, sizeof pa);
-        pa.rkeys = sb.keys[kcur]; pa.ridx = sb.idx[icur]; pa.nrv = nrv; pa.table = (uint64_t*)ptable; pa.cap = cap; pa.tshift = 64 - tbits;
-        pa.ntiles = (nrv + kJoinPlaceTile - 1) / kJoinPlaceTile;
-        void* ptiles;
-        RDF_TRY(arena_alloc((size_t)pa.ntiles * 16 + 16, &ptiles));
-        pa.tiles = (int64_t*)ptiles;
-        pa.flags = d_cnt + 3;
-        HIP_TRY(launch_join_place(pa, ctx.stream));
-        // The table is not cleared: a placement that overflowed (a cluster ran past the margin) leaves the slots behind the last
-        // key it placed unwritten, and a probe would walk them.  Look at the flag BEFORE anything probes (one 8-byte copy and a wait:
-        // microseconds against the milliseconds of a join this size); the round-3 table takes the call if it is set.
-        unsigned long long overflow = 0;
-        HIP_TRY(hipMemcpyAsync(ctx.pinned + pin_off, d_cnt + 3, 8, hipMemcpyDeviceToHost, ctx.stream));
-        HIP_TRY(hipStreamSynchronize(ctx.stream));
-        memcpy(&overflow, ctx.pinned + pin_off, 8);
-        if (overflow) {
-            kt.stop();
-            ctx.opt_join_table = 1;
-            const rdf_status st = rdf_equijoin_indices_multi(left_keys, left_nchunks, right_keys, right_nchunks, nkeys, join_type, out_left, out_right, out_rows);
-            ctx.opt_join_table = 2;
-            return st;
-        }
-    } else if (use_table) {
-        while (((int64_t)1 << tbits) < 2 * nrv) ++tbits;
-        RDF_TRY(arena_alloc(((size_t)16 << tbits) + 64, &ptable));
-        HIP_TRY(hipMemsetAsync(ptable, 0, (size_t)16 << tbits, ctx.stream));
-        JoinTableArgs ta;
-        memset(&ta, 0, sizeof ta);
-        ta.rkeys = sb.keys[kcur]; ta.ridx = sb.idx[icur]; ta.nrv = nrv; ta.table = (uint64_t*)ptable; ta.tmask = ((uint64_t)1 << tbits) - 1; ta.tshift = 64 - tbits;
-        HIP_TRY(launch_join_table(ta, ctx.stream));
-    } else if (nrv > 0) {
-        JoinBucketArgs ba;
-        memset(&ba, 0, sizeof ba);
-        ba.rkeys = sb.keys[kcur]; ba.nrv = nrv; ba.buckets = (uint32_t*)pbuckets; ba.kmin = bkmin; ba.bucket_shift = bshift;
-        HIP_TRY(launch_join_buckets(ba, ctx.stream));
-    }
-    JoinProbeArgs ja;
-    memset(&ja, 0, sizeof ja);
-    ja.buckets = (const uint32_t*)pbuckets;
-    ja.kmin = bkmin; ja.kmax = bkmax; ja.bucket_shift = bshift;
-    ja.first = (uint32_t*)pfirst;
-    if (use_table) { ja.table = (const uint64_t*)ptable; ja.tmask = hashed ? ~0ull : ((uint64_t)1 << tbits) - 1; ja.tshift = 64 - tbits; ja.hashed = hashed ? 1 : 0; }
-    ja.nkeys = nkeys;
-    for (int k = 0; k < 4; ++k) { ja.pbits[k] = pbits[k]; ja.bbits[k] = bbits[k]; }
-    ja.lkeys = (const uint64_t*)ppk;
-    ja.lnull = pnulls ? (const uint8_t*)ppn : nullptr;
-    ja.rkeys = sb.keys[kcur];
-    ja.ridx = sb.idx[icur];
-    ja.nl = np;
-    ja.nrv = nrv;
-    ja.outer = outer;
-    ja.counts = (int64_t*)pcounts;
-    ja.matched = (uint32_t*)pmatched;
-    ja.unmatched = d_cnt + 2;
-    HIP_TRY(launch_join_count(ja, ctx.stream));
-    HIP_TRY(launch_scan((const int64_t*)pcounts, (int64_t*)poffs, np, (int64_t*)poffs + np + 1, ctx.stream));
-    JoinAppendArgs aa;
-    memset(&aa, 0, sizeof aa);
-    if (full) {
-        aa.ridx = sb.idx[icur];
-        aa.matched = (const uint32_t*)pmatched;
-        aa.nr = nb;
-        aa.nrv = nrv;
-        aa.cursor = d_cnt + 1;
-        aa.count_only = 1;
-        HIP_TRY(launch_join_append(aa, ctx.stream));
-    }
-    HIP_TRY(hipMemcpyAsync(ctx.pinned + pin_off, (int64_t*)poffs + np, 8, hipMemcpyDeviceToHost, ctx.stream));
-    HIP_TRY(hipMemcpyAsync(ctx.pinned + pin_off + 8, d_cnt + 1, 24, hipMemcpyDeviceToHost, ctx.stream));
-    HIP_TRY(hipStreamSynchronize(ctx.stream));
-    int64_t probe_rows = 0;
-    unsigned long long appended = 0, unmatched = 0, place_overflow = 0;
-    memcpy(&probe_rows, ctx.pinned + pin_off, 8);
-    memcpy(&appended, ctx.pinned + pin_off + 8, 8);
-    memcpy(&unmatched, ctx.pinned + pin_off + 16, 8);
-    memcpy(&place_overflow, ctx.pinned + pin_off + 24, 8);
-    if (hashed && place_overflow) {     // a cluster ran past the table's margin (keys that crowd on the last slots): the round-3 table takes the call
-        kt.stop();
-        ctx.opt_join_table = 1;
-        const rdf_status st = rdf_equijoin_indices_multi(left_keys, left_nchunks, right_keys, right_nchunks, nkeys, join_type, out_left, out_right, out_rows);
-        ctx.opt_join_table = 2;
-        return st;
-    }
-    const int64_t total = probe_rows + (int64_t)appended;
-    *out_rows = total;
-    if (!out_left) { kt.stop(); return RDF_OK; }
-    if (out_left->capacity < total || out_right->capacity < total) return fail(RDF_MEMORY_ERROR, "join: output capacity too small (need %lld rows)", (long long)total);
-    rdf_out* out_probe = swap ? out_right : out_left;
-    rdf_out* out_build = swap ? out_left : out_right;
-    if ((outer && !out_build->validity) || (full && !out_probe->validity)) return fail(RDF_INVALID_ARGUMENT, "output validity buffer required");
-    // device outputs
-    const size_t words = (size_t)((total + 31) / 32 + 2);
-    void *dop, *dob, *dvp, *dvb;
-    RDF_TRY(arena_alloc((size_t)(total + 1) * 4, &dop));
-    RDF_TRY(arena_alloc((size_t)(total + 1) * 4, &dob));
-    RDF_TRY(arena_alloc(words * 4, &dvp));
-    RDF_TRY(arena_alloc(words * 4, &dvb));
-    HIP_TRY(hipMemsetAsync(dvp, 0xFF, words * 4, ctx.stream));
-    HIP_TRY(hipMemsetAsync(dvb, 0xFF, words * 4, ctx.stream));
-    ja.offsets = (const int64_t*)poffs;
-    ja.out_probe = (uint32_t*)dop;
-    ja.out_build = (uint32_t*)dob;
-    ja.out_build_validity = (uint32_t*)dvb;
-    ja.matched = nullptr;
-    HIP_TRY(launch_join_write(ja, ctx.stream));
-    if (full) {
-        unsigned long long start = (unsigned long long)probe_rows;
-        HIP_TRY(hipMemcpyAsync(d_cnt + 1, &start, 8, hipMemcpyHostToDevice, ctx.stream));
-        HIP_TRY(hipStreamSynchronize(ctx.stream));
-        aa.count_only = 0;
-        aa.out_probe = (uint32_t*)dop;
-        aa.out_build = (uint32_t*)dob;
-        aa.out_probe_validity = (uint32_t*)dvp;
-        HIP_TRY(launch_join_append(aa, ctx.stream));
-    }
-    kt.stop();
-    ctx.last_kernel = "join_write_kernel";
-    const hipMemcpyKind kind = mem == RDF_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    if (total > 0) {
-        HIP_TRY(hipMemcpyAsync(out_probe->values, dop, (size_t)total * 4, kind, ctx.stream));
-        HIP_TRY(hipMemcpyAsync(out_build->values, dob, (size_t)total * 4, kind, ctx.stream));
-        if (out_probe->validity) HIP_TRY(hipMemcpyAsync(out_probe->validity, dvp, (size_t)((total + 7) / 8), kind, ctx.stream));
-        if (out_build->validity) HIP_TRY(hipMemcpyAsync(out_build->validity, dvb, (size_t)((total + 7) / 8), kind, ctx.stream));
-    }
-    // null counts: build-side NULLs = probe rows without a partner; probe-side NULLs = appended rows
-    HIP_TRY(hipStreamSynchronize(ctx.stream));
-    out_probe->length = out_build->length = total;
-    out_probe->null_count = (int64_t)appended;
-    out_build->null_count = (int64_t)unmatched;
-    return RDF_OK;
-}
+#include "rdf_capi_join.inc"
 
 // ---------------------------------------------------------------- group-by
 
@@ -2926,7 +2579,7 @@ rdf_status rdf_set_option(const char* name, int64_t value) {
     else if (strcmp(name, "sort_sample") == 0) g_ctx.opt_sort_sample = (int)value;
     else if (strcmp(name, "stream_table_kernel") == 0) g_ctx.opt_stream_table_kernel = value != 0;
     else if (strcmp(name, "textconv_stage") == 0) g_ctx.opt_textconv_stage = value != 0;
-    else if (strcmp(name, "join_table") == 0) g_ctx.opt_join_table = value < 0 || value > 2 ? 2 : (int)value;
+    else if (strcmp(name, "join_table") == 0) g_ctx.opt_join_table = value == 0 ? 0 : 2;   // (1 named the retired compare-and-swap table: accepted, the planner decides as under 2)
     else if (strcmp(name, "jit") == 0) g_ctx.opt_jit = (int)value;
     else if (strcmp(name, "gb_skew_plan") == 0) g_ctx.opt_gb_skew_plan = (int)value;
     else if (strcmp(name, "gb_compact") == 0) g_ctx.opt_gb_compact = (int)value;

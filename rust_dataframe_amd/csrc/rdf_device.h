@@ -338,21 +338,19 @@ struct JoinProbeArgs {
     const uint64_t* pbits[4];  // [nkeys][nl] key bits of the probe side, row order
     const uint64_t* bbits[4];  // [nkeys][nr] key bits of the build side, ROW order (indexed through ridx)
     // one key column, fewer than 2^31 build rows: an open-addressing table over the DISTINCT build keys, 16 bytes per slot:
-    // {key bits, first sorted position << 32 | info}, info = the key's build rows (>= 2) or 1 << 31 | the build row of a key that
-    // occurs once, 0 = empty slot.  A probe is ONE random memory transaction: the count phase leaves the build row itself in
-    // `first` (bit 31 set) for such keys and the write phase never touches ridx.
-    const uint64_t* table;     // [2 * (tmask + 1)] or nullptr: the bucket index above
-    uint64_t        tmask;
+    // {key bits * golden ratio, first sorted position << 32 | info}, info = the key's build rows (>= 2) or 1 << 31 | the build row of
+    // a key that occurs once, 0 = empty slot.  A probe is ONE random memory transaction: the count phase leaves the build row itself
+    // in `first` (bit 31 set) for such keys and the write phase never touches ridx.
+    const uint64_t* table;     // [2 * cap] in slot order, placed by a scan (JoinPlaceArgs): no wrap-around; or nullptr: the bucket index above
     int32_t         tshift;    // slot = (key * golden ratio) >> tshift
-    int32_t         hashed;    // the table holds key * golden ratio (a bijection) in slot order, placed by a scan: no wrap-around (tmask = ~0)
+    int32_t         pad3;
 };
-struct JoinTableArgs { const uint64_t* rkeys; const uint32_t* ridx; int64_t nrv; uint64_t* table; uint64_t tmask; int32_t tshift, pad; };
-// Round 5: the same table WITHOUT atomics.  The build side is sorted by h = key * golden ratio (odd multiplier: a bijection on 64 bits),
+// The table is built WITHOUT atomics.  The build side is sorted by h = key * golden ratio (odd multiplier: a bijection on 64 bits),
 // so the distinct keys arrive in slot order and linear probing's layout is a scan: slot(r) = max(home(r), slot(r - 1) + 1) = r +
 // max over q <= r of (home(q) - q) for the r-th distinct key.  Phase 0: per tile of 2048 sorted rows {distinct keys, max(home - local
 // index)}; phase 1 (one block): their exclusive prefixes under (cA, mA) + (cB, mB) = (cA + cB, max(mA, mB - cA)); phase 2: every tile
 // places its keys — near-sequential 16-byte stores instead of 1e8 compare-and-swaps on random lines.  No wrap-around: the table has
-// `cap` slots >= 2^tbits + a margin, a slot beyond it raises flags[0] and the host falls back to join_table_kernel.
+// `cap` slots >= 2^tbits + a margin, a slot beyond it raises flags[0] and the host answers the call with the bucket index instead.
 struct JoinPlaceArgs { const uint64_t* rkeys; const uint32_t* ridx; int64_t nrv; uint64_t* table; int64_t cap; int64_t* tiles; int64_t ntiles;
                        unsigned long long* flags; int32_t tshift, phase; };
 struct JoinCombineArgs { const uint64_t* bits[4]; int32_t nkeys, pad; int64_t n; const uint8_t* nullflags; uint64_t* out; uint64_t* bit_stats; };
@@ -688,7 +686,6 @@ hipError_t launch_take(const TakeArgs& a, hipStream_t s);
 hipError_t launch_sort_keys(const SortKeyArgs& a, hipStream_t s);
 hipError_t launch_join_buckets(const JoinBucketArgs& a, hipStream_t s);
 hipError_t launch_copy_small(const void* src_pinned, void* dst_dev, size_t bytes, hipStream_t s);   // src: page-locked, device-mapped host memory
-hipError_t launch_join_table(const JoinTableArgs& a, hipStream_t s);
 hipError_t launch_join_place(JoinPlaceArgs a, hipStream_t s);     // the three phases
 hipError_t launch_join_distinct(const uint64_t* sorted_keys, int64_t n, unsigned long long* out, hipStream_t s);     // distinct values of a sorted array, added to *out
 constexpr int kJoinPlaceTile = 2048;

@@ -1,7 +1,7 @@
 // rdf_hash.h — the functions that DEFINE the 64-bit hashes rows are matched by before their keys are compared:
 //   Utf8 rows   rdf_colstats.hip: cs_utf8_hash_kernel -> cs_utf8_verify_kernel / cs_dict_rep_kernel (rdf_utf8_uniques,
 //               rdf_utf8_dictionary_encode and, through the encoder, GROUP BY and join on text keys)
-//   key tuples  rdf_kernels.hip: join_combine_kernel -> join_verify (rdf_equijoin_indices_multi on 2..4 key columns)
+//   key tuples  rdf_join.hip: join_combine_kernel -> join_verify (rdf_equijoin_indices_multi on 2..4 key columns)
 // Shared by the kernels and a CPU program (tests/cpp/test_hash.cpp) that the Python models of tests/hash_models.py are held to:
 // every mixer in here is a bijection of 64-bit words, so keys that really collide can be constructed, and the tests run the
 // "hash equal, keys different" branches on them.  The kernels call these functions; the loops in here are the sequential

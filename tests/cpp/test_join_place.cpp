@@ -113,4 +113,75 @@ TEST(a_probe_finds_every_key_by_walking_from_its_home) {
     }
 }
 
+// The sizes the host gives the two lookups.  Every expected value follows from the rules, none is measured: distinct keys nd =
+// min(rows, key range + 1, counted distinct); tbits = the smallest value >= 10 with 2^tbits >= 2 nd; cap = 2^tbits + 2^16.
+TEST(the_table_is_sized_from_the_distinct_keys) {
+    // 3e6 rows over 37 dictionary codes: the range bounds the keys, nobody counts
+    CHECK(join_range_bounds_keys(3000000, 100, 136) && !join_table_counts_keys(3000000, 100, 136));
+    JoinTablePlan p = join_table_plan(3000000, 100, 136, 0);
+    CHECK(p.nd == 37 && p.tbits == 10 && p.cap == 66560);
+    // 37 hashed identifiers over 3e6 rows: the range says nothing (>= rows), the count does
+    CHECK(!join_range_bounds_keys(3000000, 5, 5 + 3000000ull) && join_table_counts_keys(3000000, 5, 5 + 3000000ull));
+    p = join_table_plan(3000000, 5, 5 + 3000000ull, 37);
+    CHECK(p.nd == 37 && p.tbits == 10 && p.cap == 66560);
+    p = join_table_plan(3000000, 0, ~0ull, 37);
+    CHECK(p.nd == 37 && p.tbits == 10 && p.cap == 66560);
+    // a range of exactly rows - 1 still bounds (rows keys at most either way)
+    CHECK(join_range_bounds_keys(3000000, 0, 2999999) && !join_range_bounds_keys(3000000, 0, 3000000));
+    // below 65 536 rows a wide range is not counted: sized from the rows
+    CHECK(!join_table_counts_keys(65535, 0, ~0ull) && join_table_counts_keys(65536, 0, ~0ull));
+    p = join_table_plan(65535, 0, ~0ull, 0);
+    CHECK(p.nd == 65535 && p.tbits == 17 && p.cap == (1ll << 17) + 65536);
+    // a count that is not below the rows changes nothing; a count of 0 means "not counted"
+    p = join_table_plan(6000000, 0, ~0ull, 6000000);
+    CHECK(p.nd == 6000000 && p.tbits == 24 && p.cap == (1ll << 24) + 65536);      // 2^23 < 1.2e7 <= 2^24
+    p = join_table_plan(6000000, 0, ~0ull, 0);
+    CHECK(p.nd == 6000000 && p.tbits == 24);
+    // load <= 0.5 exactly at the power of two, one more bit one key later; never below 10 bits
+    p = join_table_plan(512, 0, ~0ull, 0);
+    CHECK(p.nd == 512 && p.tbits == 10 && p.cap == 1024 + 65536);
+    p = join_table_plan(513, 0, ~0ull, 0);
+    CHECK(p.nd == 513 && p.tbits == 11 && p.cap == 2048 + 65536);
+    p = join_table_plan(1, 7, 7, 0);
+    CHECK(p.nd == 1 && p.tbits == 10);
+    // no keys at all (kmax < kmin): the range bounds nothing
+    CHECK(!join_range_bounds_keys(10, 1, 0));
+}
+
+TEST(the_bucket_index_has_a_bucket_per_row_on_the_top_bits_of_the_range) {
+    // nbuckets = the smallest power of two >= rows, 2^24 at most; shift = the smallest with (kmax - kmin) >> shift < nbuckets
+    JoinBucketPlan b = join_bucket_plan(1, 42, 42);
+    CHECK(b.nbuckets == 1 && b.shift == 0);
+    b = join_bucket_plan(0, 1, 0);                      // no rows, an empty key range
+    CHECK(b.nbuckets == 1 && b.shift == 0);
+    b = join_bucket_plan(1000, 1, 0);                   // an empty key range, whatever the rows
+    CHECK(b.nbuckets == 1024 && b.shift == 0);
+    b = join_bucket_plan(1ll << 25, 0, (1ull << 25) - 1);
+    CHECK(b.nbuckets == (1ll << 24) && b.shift == 1);
+    b = join_bucket_plan(3, 10, 13);                    // range 3 < 4 buckets
+    CHECK(b.nbuckets == 4 && b.shift == 0);
+    b = join_bucket_plan(4, 10, 14);                    // range 4: one shift
+    CHECK(b.nbuckets == 4 && b.shift == 1);
+    b = join_bucket_plan(5, 10, 14);
+    CHECK(b.nbuckets == 8 && b.shift == 0);
+    b = join_bucket_plan(2, 0, ~0ull);                  // the whole 64-bit range over two buckets: the top bit
+    CHECK(b.nbuckets == 2 && b.shift == 63);
+    b = join_bucket_plan(1ll << 30, 0, ~0ull);
+    CHECK(b.nbuckets == (1ll << 24) && b.shift == 40);
+    // one bucket over the whole 64-bit range: the rule's answer is 64, reached without ever shifting by 64 (the loop this replaces
+    // went on to evaluate range >> 64).  The host cannot ask for it: one bucket means one key at most, a range of 0.
+    b = join_bucket_plan(1, 0, ~0ull);
+    CHECK(b.nbuckets == 1 && b.shift == 64);
+    // every plan keeps the largest key's bucket inside the array
+    std::mt19937_64 g(4);
+    for (int it = 0; it < 20000; ++it) {
+        const long long rows = 1 + (long long)(g() % (1ull << (1 + g() % 27)));
+        const uint64_t lo = g() >> (g() % 64), span = g() >> (g() % 64), hi = lo + span < lo ? ~0ull : lo + span;
+        if (rows == 1 && hi != lo) continue;
+        b = join_bucket_plan(rows, lo, hi);
+        CHECK(b.shift < 64 && ((hi - lo) >> b.shift) < (uint64_t)b.nbuckets);
+        if (b.shift > 0) CHECK(((hi - lo) >> (b.shift - 1)) >= (uint64_t)b.nbuckets);
+    }
+}
+
 int main() { return run_all(); }

@@ -413,7 +413,7 @@ def order_inputs(dtype, shape):
 def test_pair_order_of_a_single_key_join(api, ora, dtype, shape, how):
     (_, lch, lkeys), (_, rch, rkeys) = order_inputs(dtype, shape)
     ora_pairs = pairs_of(*ora.equijoin_indices(lch, rch, how))
-    for table in (2, 1, 0):
+    for table in (2, 0):
         lib.set_option("join_table", table)
         try:
             pairs = pairs_of(*api.equijoin_indices(lch, rch, how))
@@ -423,6 +423,24 @@ def test_pair_order_of_a_single_key_join(api, ora, dtype, shape, how):
             check_numeric_join(pairs, ora_pairs, [lkeys], [rkeys], how)
         except AssertionError as e:
             raise AssertionError(f"join_table {table}: {e}") from e
+
+
+@pytest.mark.parametrize("how", HOWS)
+def test_the_retired_join_table_value_means_the_default(api, how):
+    """join_table = 1 named the table whose slots were claimed by compare-and-swap: the value is still accepted and the call takes
+    the default route — the same index arrays and validity as under 2 (FULL's tail of unmatched build rows is written through an
+    atomic cursor, so it is the same rows in any order: the contract above)."""
+    (_, lch, lkeys), (_, rch, rkeys) = order_inputs(H.I64, (4097, 4095))
+    got = {}
+    for table in (2, 1):
+        lib.set_option("join_table", table)
+        try:
+            got[table] = pairs_of(*api.equijoin_indices(lch, rch, how))
+        finally:
+            lib.set_option("join_table", 2)
+    n = R.full_probe_rows([lkeys], [rkeys]) if how == "full" else len(got[2])
+    assert len(got[1]) == len(got[2]) and got[1][:n] == got[2][:n]
+    assert sorted(got[1][n:], key=lambda p: p[1]) == sorted(got[2][n:], key=lambda p: p[1])
 
 
 # ---------------------------------------------------------------- float keys are bits
@@ -458,7 +476,7 @@ def test_float_keys_join_on_their_bits(api, ora, dtype, how):
     zero_rows = [i for i, v in enumerate(left) if v == sp[1]]
     assert zero_rows and all(right[j] == sp[1] for i in zero_rows for (a, j) in exp if a == i)
     ora_pairs = pairs_of(*ora.equijoin_indices(lch, rch, how))
-    for table in (2, 1, 0):
+    for table in (2, 0):
         lib.set_option("join_table", table)
         try:
             pairs = pairs_of(*api.equijoin_indices(lch, rch, how))

@@ -1304,9 +1304,9 @@ def test_equijoin_bucket_index_edge_cases(gpu, ora, how):
     from rust_dataframe_amd import lib
     for lk, rk in cases:
         el, er = ora.equijoin_indices(lk, rk, how)
-        # the table of distinct build keys — laid out by a scan over the hash-ordered build side (2, default) or claimed slot by slot
-        # with compare-and-swap (1, round 3) — and the bucket index over the sorted build keys (0)
-        for table in (2, 1, 0):
+        # the table of distinct build keys, laid out by a scan over the hash-ordered build side (2, default), and the bucket index
+        # over the sorted build keys (0)
+        for table in (2, 0):
             lib.set_option("join_table", table)
             try:
                 gl, gr = gpu.equijoin_indices(lk, rk, how)
@@ -1319,12 +1319,13 @@ def test_equijoin_bucket_index_edge_cases(gpu, ora, how):
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape", ["distinct", "duplicates", "few_keys", "few_keys_wide_range", "crowded_slots"])
 def test_equijoin_table_placed_by_scan(gpu, shape):
-    """Round 5: the table of distinct build keys is laid out without atomics — the build side sorted by key * golden ratio, slot(r) =
+    """The table of distinct build keys is laid out without atomics — the build side sorted by key * golden ratio, slot(r) =
     r + prefix-max(home - r) over the distinct keys (three kernels: per-tile aggregates, one block scanning them, placement).  Sizes
-    that span thousands of 4096-row tiles (the one-block scan handles several tiles per thread), against the compare-and-swap table
-    of round 3: identical index arrays (the probe rows' order and, inside a probe row, the build rows' order do not depend on how the
-    table was built), pair counts against numpy.  `crowded_slots`: keys whose hashes pile onto the table's last home slot, far beyond its
-    margin — the placement flags it and the call falls back to the round-3 table."""
+    that span thousands of 2048-row tiles (the one-block scan handles several tiles per thread).  Both routes — the table (2) and the
+    bucket index over the build keys sorted by key (0) — are held to an exact numpy model of the pair order: probe rows ascending and,
+    inside a probe row, its build rows ascending (the build sort is stable), one NULL build entry for a probe row without partners
+    under `left`.  `crowded_slots`: keys whose hashes pile onto the table's last home slot, far beyond its margin — the placement flags
+    it and the bucket index answers the call, so both routes end there."""
     from rust_dataframe_amd import lib
     rng = np.random.default_rng(515)
     if shape == "distinct":
@@ -1361,21 +1362,32 @@ def test_equijoin_table_placed_by_scan(gpu, shape):
     pos = np.searchsorted(uniq, pk)
     hit = (pos < len(uniq)) & (uniq[np.minimum(pos, len(uniq) - 1)] == pk)
     inner_rows = int(cnt[pos[hit]].sum())
+    # the model: equal build keys in row order (stable sort), the probe rows in theirs
+    order = np.argsort(bk, kind="stable")
+    sorted_bk = bk[order]
+    lo, hi = np.searchsorted(sorted_bk, pk, side="left"), np.searchsorted(sorted_bk, pk, side="right")
     for how, rows in (("inner", inner_rows), ("left", inner_rows + int((~hit).sum()))):
-        got = {}
-        for table in (2, 1):
+        per_row = hi - lo if how == "inner" else np.maximum(hi - lo, 1)           # output rows of every probe row
+        first = np.cumsum(per_row) - per_row
+        exp_probe = np.repeat(np.arange(npb), per_row)
+        exp_valid = np.repeat(hi > lo, per_row)
+        within = np.arange(int(per_row.sum())) - np.repeat(first, per_row)
+        exp_build = order[np.where(exp_valid, np.repeat(lo, per_row) + within, 0)]
+        assert len(exp_probe) == rows, (shape, how)
+        for table in (2, 0):
             lib.set_option("join_table", table)
             try:
                 gl, gr = gpu.equijoin_indices(L, R, how)
             finally:
                 lib.set_option("join_table", 2)
             assert gl.length == rows, (shape, how, table)
-            got[table] = (gl.to_numpy(), gr.to_numpy(), gr.null_count)
-        assert np.array_equal(got[2][0], got[1][0]) and got[2][2] == got[1][2], (shape, how)
-        m = got[1][1] if how == "inner" else None
-        if how == "inner":
-            assert np.array_equal(got[2][1], m), shape
-            assert np.array_equal(pk[got[2][0]], bk[got[2][1]]), shape          # every pair joins equal keys
+            got_probe, got_build, got_valid = gl.to_numpy(), gr.to_numpy(), gr.valid_mask()
+            assert np.array_equal(got_probe, exp_probe), (shape, how, table)
+            assert gl.null_count == 0 and gr.null_count == int((~exp_valid).sum()), (shape, how, table)
+            assert np.array_equal(got_valid, exp_valid), (shape, how, table)
+            assert np.array_equal(got_build[exp_valid], exp_build[exp_valid]), (shape, how, table)
+            if how == "inner":
+                assert np.array_equal(pk[got_probe], bk[got_build]), shape          # every pair joins equal keys
 
 
 @pytest.mark.parametrize("val_dtype", [A.F64, A.I64, A.F32, None])

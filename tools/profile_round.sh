@@ -116,8 +116,8 @@ RDF_LIB_PATH="$REPO/rust_dataframe_amd/librdf_base_r04.so" python "$REPO/tools/b
 python "$REPO/tools/exp_gb_window.py" --windows 8,32,64,128,256 --reps 2 2>> "$OUT/kernels.err" > "$OUT/gb_window.jsonl"
 grep '"probe"' "$OUT/stream_sinks.err" | head -1 > "$OUT/link_probe.jsonl"       # each direction alone, both at once (bench_stream_sinks.py prints it first)
 # (rdf_filter_frame on long batches: step 3f)
-# equi-join: the scan-placed table (default) against the compare-and-swap table
-python "$REPO/tools/bench_kernels.py" --rows 1000000000 --steps 3 --only join_inner_1e8_x_1e7,join_inner_1e8_x_1e7_cas_table,join_inner_1e8_x_1e8,join_inner_1e8_x_1e8_cas_table 2>> "$OUT/kernels.err" | grep kernel_ms > "$OUT/join_table_ab.jsonl"
+# equi-join: the scan-placed table (default) against the bucket index
+python "$REPO/tools/bench_kernels.py" --rows 1000000000 --steps 3 --only join_inner_1e8_x_1e7,join_inner_1e8_x_1e7_bucket_index,join_inner_1e8_x_1e8 2>> "$OUT/kernels.err" | grep kernel_ms > "$OUT/join_table_ab.jsonl"
 if [ -x "$REPO/tools/ubench_streams.bin" ]; then timeout 300 "$REPO/tools/ubench_streams.bin" > "$OUT/ubench_streams.txt" 2>&1; fi
 fi
 # 3f. round 6: the one-pass filter on block tiles (rdf_bfilter.hip) against the wave-tile kernel by batch length, its HBM counters on ONE
