@@ -446,8 +446,8 @@ typedef enum { RDF_AGG_SUM = 0, RDF_AGG_MIN = 1, RDF_AGG_MAX = 2, RDF_AGG_COUNT 
  *   MIN / MAX of a group without a non-NULL value is NULL (validity required when the value column is nullable);
  *   NaN never wins a MIN / MAX unless every value of the group is NaN (the column aggregates' rule, rdf_min / rdf_max);
  * out_counts: Int64.  Capacities >= min(max_groups, rows) + 2; group order unspecified.  More than max_groups distinct key
- * tuples -> RDF_MEMORY_ERROR.  Several grouping columns are packed into one 64-bit key after range compression
- * (bits(max - min) per column, + 1 code for NULL); when the ranges together pass 64 bits (several sparse columns) the
+ * tuples (the NULL tuple is one of them) -> RDF_MEMORY_ERROR; exactly max_groups succeed.  Several grouping columns are
+ * packed into one 64-bit key after range compression (bits(max - min) per column, + 1 code for NULL); when the ranges together pass 64 bits (several sparse columns) the
  * widest columns are dictionary-coded instead (rank among the column's distinct values, found by a count-only GROUP BY
  * of that column).  Tuples needing more than 64 bits either way -> RDF_INVALID_ARGUMENT.
  * f64 sums are accumulated with hardware atomics: the rounding order is not deterministic (<= 1e-6 relative). */
@@ -971,7 +971,10 @@ typedef struct { rdf_out* values; rdf_out* utf8_offsets; rdf_out* utf8_data; } r
  * (nchunks integer chunks) or `utf8` (nchunks Utf8 chunks); its `options` are ignored.  Everything rdf_groupby_agg
  * documents holds: a NULL key is a group of its own, NULL values are skipped, the output dtypes, the capacities
  * (>= min(max_groups, rows) + 2 for every numeric output), RDF_MEMORY_ERROR beyond max_groups groups, unspecified group
- * order.  A Utf8 grouping column comes back as one Utf8 chunk whose row g belongs to out_values[g] / out_counts[g]; it is
+ * order.  One difference, kept because callers size max_groups by their non-NULL keys: with a Utf8 key among the grouping
+ * columns the two groups the kernels set aside — the NULL tuple, and the tuple whose packed code hashes to the LDS free
+ * marker — do not count against max_groups, so up to max_groups + 2 groups come back (the capacities above hold them).
+ * A Utf8 grouping column comes back as one Utf8 chunk whose row g belongs to out_values[g] / out_counts[g]; it is
  * NULL for the NULL group (validity required when the key carries a validity buffer) and sizes like every Utf8 output:
  * lengths reported, RDF_MEMORY_ERROR and nothing written when short; groups + 1 offsets and the key column's input bytes
  * always suffice.  Utf8 keys are dictionary-encoded (rdf_utf8_dictionary_encode), the codes grouped next to the numeric

@@ -1519,6 +1519,7 @@ rdf_status ora_groupby_sum(const rdf_array* keys, const rdf_array* values, int64
             gcnt[g]++;
         }
     }
+    if (st == RDF_OK && ng > max_groups) { st = RDF_MEMORY_ERROR; snprintf(g_err, sizeof g_err, "groupby: more than max_groups distinct keys"); }   /* the NULL key counted */
     if (st == RDF_OK && (out_keys->capacity < ng || out_sums->capacity < ng || out_counts->capacity < ng)) { st = RDF_MEMORY_ERROR; snprintf(g_err, sizeof g_err, "output capacity too small"); }
     if (st == RDF_OK && null_group >= 0 && !out_keys->validity) { st = RDF_INVALID_ARGUMENT; snprintf(g_err, sizeof g_err, "output validity buffer required"); }
     if (st == RDF_OK) {
@@ -1542,7 +1543,7 @@ rdf_status ora_groupby_sum(const rdf_array* keys, const rdf_array* values, int64
  * sequential scan: a NULL in a grouping column is a value of its own, NULL values are skipped, MIN / MAX of a group
  * without a non-NULL value is NULL, NaN loses against every number (the rule of ora_min / ora_max).  Groups in first-seen order. */
 static rdf_status groupby_generic(const rdf_array* keys, int32_t nkeys, const rdf_array* values, const rdf_array* weights,
-                                  int64_t nchunks, int32_t agg, int64_t max_groups,
+                                  int64_t nchunks, int32_t agg, int64_t max_groups, int64_t slack,
                                   rdf_out* out_keys, rdf_out* out_values, rdf_out* out_counts) {
     if (nchunks < 1) FAIL(RDF_INVALID_ARGUMENT, "groupby: a column has at least one chunk");
     if (nkeys < 1 || nkeys > RDF_MAX_GROUP_KEYS) FAIL(RDF_INVALID_ARGUMENT, "groupby: 1..4 grouping columns");
@@ -1610,7 +1611,7 @@ static rdf_status groupby_generic(const rdf_array* keys, int32_t nkeys, const rd
             } else if (fval) {
                 double v = arr_f64(&values[c], i);
                 if (v != v) continue;
-                if (!ghas[g] || (agg == RDF_AGG_MIN ? v < gf[g] : v > gf[g])) gf[g] = v;
+                if (!ghas[g] || (agg == RDF_AGG_MIN ? zero_less(v, gf[g]) : zero_less(gf[g], v))) gf[g] = v;   /* -0.0 below +0.0, as ora_min / ora_max */
                 ghas[g] = 1;
             } else if (uval) {
                 uint64_t v = ((const uint64_t*)values[c].values)[values[c].offset + i];
@@ -1623,7 +1624,7 @@ static rdf_status groupby_generic(const rdf_array* keys, int32_t nkeys, const rd
             }
         }
     }
-    if (st == RDF_OK && ng > max_groups + 2) { st = RDF_MEMORY_ERROR; snprintf(g_err, sizeof g_err, "groupby: more than max_groups distinct keys"); }
+    if (st == RDF_OK && ng > max_groups + slack) { st = RDF_MEMORY_ERROR; snprintf(g_err, sizeof g_err, "groupby: more than max_groups distinct keys"); }
     for (int k = 0; k < nkeys && st == RDF_OK; k++) if (out_keys[k].capacity < ng) { st = RDF_MEMORY_ERROR; snprintf(g_err, sizeof g_err, "output capacity too small"); }
     if (st == RDF_OK && (out_values->capacity < ng || out_counts->capacity < ng)) { st = RDF_MEMORY_ERROR; snprintf(g_err, sizeof g_err, "output capacity too small"); }
     if (st == RDF_OK) {
@@ -1657,14 +1658,15 @@ static rdf_status groupby_generic(const rdf_array* keys, int32_t nkeys, const rd
 }
 rdf_status ora_groupby_agg(const rdf_array* keys, int32_t nkeys, const rdf_array* values, int64_t nchunks, int32_t agg, int64_t max_groups,
                            rdf_out* out_keys, rdf_out* out_values, rdf_out* out_counts) {
-    return groupby_generic(keys, nkeys, values, NULL, nchunks, agg, max_groups, out_keys, out_values, out_counts);
+    /* the header's promise: more than max_groups distinct key tuples, the NULL tuple counted, are RDF_MEMORY_ERROR */
+    return groupby_generic(keys, nkeys, values, NULL, nchunks, agg, max_groups, 0, out_keys, out_values, out_counts);
 }
 /* merge of partial groups: the same scan with the partial's count as the row's weight (a partial with count 0 only
  * contributes its key) */
 rdf_status ora_groupby_merge(const rdf_array* keys, const rdf_array* partial, const rdf_array* counts, int32_t agg, int64_t max_groups,
                              rdf_out* out_keys, rdf_out* out_values, rdf_out* out_counts) {
     if (!counts || counts->dtype != RDF_I64) FAIL(RDF_INVALID_ARGUMENT, "groupby_merge: counts are Int64");
-    return groupby_generic(keys, 1, partial, counts, 1, partial ? agg : RDF_AGG_COUNT, max_groups, out_keys, out_values, out_counts);
+    return groupby_generic(keys, 1, partial, counts, 1, partial ? agg : RDF_AGG_COUNT, max_groups, 2, out_keys, out_values, out_counts);
 }
 
 /* ------------------------------------------------------------------ synthetic data

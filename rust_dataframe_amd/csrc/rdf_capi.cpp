@@ -2336,7 +2336,7 @@ static_assert(kG2MaxGroups <= kGbMaxGroups, "whatever max_groups the second gene
 bool gb_fallback_in_range(int64_t max_groups, int64_t nrows) { return max_groups > 1024 && max_groups <= kGbMaxGroups && nrows > 0; }
 
 rdf_status groupby_sum_fallback(const rdf_array* keys, const rdf_array* values, int64_t nchunks, int64_t max_groups,
-                                rdf_out* out_keys, rdf_out* out_sums, rdf_out* out_counts) {
+                                rdf_out* out_keys, rdf_out* out_sums, rdf_out* out_counts, int64_t slack /* groups beyond max_groups the caller accepts */) {
     if (nchunks < 1 || !keys) return fail(RDF_INVALID_ARGUMENT, "groupby: a column has at least one chunk");
     if (!out_keys || !out_sums || !out_counts) return fail(RDF_INVALID_ARGUMENT, "groupby: null output");
     if (max_groups < 1) return fail(RDF_INVALID_ARGUMENT, "groupby: max_groups must be positive");
@@ -2492,7 +2492,7 @@ rdf_status groupby_sum_fallback(const rdf_array* keys, const rdf_array* values, 
         RDF_TRY(put(z, hs[0], hs[2]));
     }
     if (hf[1]) { null_idx = ng; RDF_TRY(put(0, hs[1], hs[3])); }
-    if (ng > out_keys->capacity || ng > out_sums->capacity || ng > out_counts->capacity)
+    if (ng > max_groups + slack || ng > out_keys->capacity || ng > out_sums->capacity || ng > out_counts->capacity)   // (the two special groups count against max_groups too)
         return fail(RDF_MEMORY_ERROR, "groupby: more than max_groups (%lld) distinct keys", (long long)max_groups);
     const hipMemcpyKind kind = mem == RDF_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     if (ng > 0) {

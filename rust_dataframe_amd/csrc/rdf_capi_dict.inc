@@ -427,7 +427,8 @@ rdf_status rdf_groupby_agg_keys(const rdf_sort_key* keys, int32_t nkeys, const r
         ok[k].validity = out_keys[k].values->validity ? (uint8_t*)tkeys[k].p + ((vb + 255) & ~(size_t)255) : nullptr;
         ok[k].capacity = cap_needed;
     }
-    RDF_TRY(rdf_groupby_agg(flat.data(), nkeys, values, nchunks, agg, max_groups, ok, &tv, &tc));
+    // (over Utf8 keys the NULL group and the code whose hash is the LDS free marker never counted against max_groups: kept)
+    RDF_TRY(groupby_agg_impl(flat.data(), nkeys, values, nchunks, agg, max_groups, ok, &tv, &tc, 2));
     const std::string gb_kernels = g_ctx.last_kernel;
     const int64_t groups = tc.length;
 

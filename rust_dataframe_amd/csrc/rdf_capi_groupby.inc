@@ -510,6 +510,7 @@ rdf_status gb_engine(const GbInput& in, int op, int64_t max_groups, int force_pa
         ga.recs_k = (const uint32_t*)preck;
         ga.key_base = key_base;
         ga.compact = a.compact | ((ctx.opt_gb_bucket == 1 || (ctx.opt_gb_bucket == 0 && dense_keys)) ? 256 : 0);   // bit 8: one key per probe in the partition tables
+        if (getenv("RDF_DEBUG")) fprintf(stderr, "[rdf] gb2 aggregate pass: %s\n", (ga.compact & 256) ? "one key per probe" : "buckets of four");
         ga.nlines = (const uint32_t*)pnl;
         ga.nb = nb;
         ga.cap_lines = cap_lines;
@@ -555,7 +556,7 @@ rdf_status gb_engine(const GbInput& in, int op, int64_t max_groups, int force_pa
             for (uint32_t x : nl) { tot += x; mx = std::max(mx, x); }
             fprintf(stderr, "[rdf] gb2 partition path: rows=%lld nb=%d cap_lines=%lld flags=0x%x lines total=%llu max=%u ng=%lld\n", (long long)nrows, nb, (long long)cap_lines, flags, (unsigned long long)tot, mx, (long long)d.ng);
         }
-        if (hot && (flags & (128u | 16u | 32u))) {   // more keys in the hot classes than the LDS table takes, or the others were not as even as sampled: without the split
+        if (hot && (flags & (128u | 16u | 32u))) {   // the others were not as even as sampled (16, 32); 128, a full table of hot keys, cannot happen with at most 100 of them (rdf_groupby.hip) and is kept as a guard: without the split
             if (getenv("RDF_DEBUG")) fprintf(stderr, "[rdf] gb2: the heavy-hitter split gave up (flags 0x%x), re-running without it\n", flags);
             return gb_engine(in, op, max_groups, force_path, sc, d, pin_off, skewed, lds_full, allow_compact, false);
         }
@@ -585,6 +586,7 @@ rdf_status gb_engine(const GbInput& in, int op, int64_t max_groups, int force_pa
             while (r < 5 && (int64_t)prime_slots[r + 1] >= 2 * max_groups + 2) ++r;
             a.replicas = 1 << r;
             a.sub_slots = prime_slots[r];
+            if (getenv("RDF_DEBUG")) fprintf(stderr, "[rdf] gb2 stream path: %d sub-tables of %d slots for max_groups %lld\n", a.replicas, a.sub_slots, (long long)max_groups);
             constexpr int TPI = 2;
             int grid = (int)std::max<int64_t>(1, std::min<int64_t>((ntiles + TPI - 1) / TPI, 2 * (int64_t)ncu));
             HIP_TRY(launch_gb2_stream(a, grid, ctx.stream));
@@ -619,14 +621,13 @@ rdf_status gb_engine(const GbInput& in, int op, int64_t max_groups, int force_pa
 // the first-generation histogram / combining scatter / aggregate path (rdf_capi.cpp): sums and counts of one integer key column
 bool gb_fallback_in_range(int64_t max_groups, int64_t nrows);
 rdf_status groupby_sum_fallback(const rdf_array* keys, const rdf_array* values, int64_t nchunks, int64_t max_groups,
-                                rdf_out* out_keys, rdf_out* out_sums, rdf_out* out_counts);
+                                rdf_out* out_keys, rdf_out* out_sums, rdf_out* out_counts, int64_t slack);
 
-}  // namespace
-
-extern "C" {
-
-rdf_status rdf_groupby_agg(const rdf_array* keys, int32_t nkeys, const rdf_array* values, int64_t nchunks, int32_t agg, int64_t max_groups,
-                           rdf_out* out_keys, rdf_out* out_values, rdf_out* out_counts) {
+// rdf_groupby_agg.  slack: groups beyond max_groups the caller accepts — 0 for the public entries, whose promise counts every
+// group; 2 for rdf_groupby_agg_keys over Utf8 keys, where the up to two set-aside groups (the NULL key; the code whose hash is
+// the LDS free marker) never counted
+rdf_status groupby_agg_impl(const rdf_array* keys, int32_t nkeys, const rdf_array* values, int64_t nchunks, int32_t agg, int64_t max_groups,
+                            rdf_out* out_keys, rdf_out* out_values, rdf_out* out_counts, int64_t slack) {
     if (nchunks < 1 || !keys) return fail(RDF_INVALID_ARGUMENT, "groupby: a column has at least one chunk");
     if (nkeys < 1 || nkeys > kMaxKeyCols) return fail(RDF_INVALID_ARGUMENT, "groupby: 1..%d grouping columns", kMaxKeyCols);
     if (!out_keys || !out_values || !out_counts) return fail(RDF_INVALID_ARGUMENT, "groupby: null output");
@@ -679,7 +680,7 @@ rdf_status rdf_groupby_agg(const rdf_array* keys, int32_t nkeys, const rdf_array
     if (mem == RDF_MEM_HOST && nkeys == 1 && !knullable[0] && (kdt[0] == RDF_I64 || kdt[0] == RDF_U64) && g_ctx.opt_stream_slab >= 0 && !g_ctx.in_stream) {
         int64_t bytes = host_input_bytes(keys, 1, nchunks);
         if (values) bytes += host_input_bytes(values, 1, nchunks);
-        if (bytes > stream_slab_bytes()) return groupby_stream(keys, values, nchunks, agg, max_groups, out_keys, out_values, out_counts);
+        if (bytes > stream_slab_bytes()) return groupby_stream(keys, values, nchunks, agg, max_groups, out_keys, out_values, out_counts, slack);
     }
 
     // several grouping columns: the tuple is packed into ONE 64-bit key, every column range-compressed to
@@ -814,6 +815,7 @@ rdf_status rdf_groupby_agg(const rdf_array* keys, int32_t nkeys, const rdf_array
                 total_bits += bits;
             }
             if (total_bits > 64) return fail(RDF_INVALID_ARGUMENT, "groupby: the grouping columns need %d bits after range / dictionary coding; at most 64 are supported", total_bits);
+            if (getenv("RDF_DEBUG")) for (int k = 0; k < nkeys; ++k) fprintf(stderr, "[rdf] groupby key column %d: %s\n", k, use_dict[k] ? "dictionary-coded" : "range-packed");
             HIP_TRY(launch_key_pack(kp, ctx.stream));
             in.kdt = RDF_U64;
             in.keys.resize((size_t)nchunks);
@@ -836,11 +838,13 @@ rdf_status rdf_groupby_agg(const rdf_array* keys, int32_t nkeys, const rdf_array
             // heavily skewed keys overflowed a scatter region: sums of a single key column take the first-generation
             // histogram + combining path (built for exactly this) where its tables hold max_groups, everything else the HBM table
             if (op == AGG_SUM && nkeys == 1 && ctx.opt_gb_partition != 4 && gb_fallback_in_range(max_groups, nrows))
-                return groupby_sum_fallback(keys, values, nchunks, max_groups, out_keys, out_values, out_counts);
+                return groupby_sum_fallback(keys, values, nchunks, max_groups, out_keys, out_values, out_counts, slack);
             continue;
         }
         const int64_t ng = d.ng;
-        if (ng > cap_needed) return fail(RDF_MEMORY_ERROR, "groupby: more than max_groups (%lld) distinct keys", (long long)max_groups);
+        // the header's promise counts every group: gb_collect appends the up to two set-aside groups (the NULL key; the key whose hash
+        // is the LDS free marker) to as many as max_groups others, and the engine's other callers (the dictionary build) rely on that slack
+        if (ng > max_groups + slack) return fail(RDF_MEMORY_ERROR, "groupby: more than max_groups (%lld) distinct keys", (long long)max_groups);
         if (nkeys == 1) {
             RDF_TRY(gb_copy_out(d.keys, (size_t)ng * (size_t)dtype_size(kdt[0]), out_keys->values, mem));
             if (out_keys->validity) RDF_TRY(gb_copy_out(d.kvalid, (size_t)((ng + 7) / 8), out_keys->validity, mem));
@@ -898,12 +902,21 @@ rdf_status rdf_groupby_agg(const rdf_array* keys, int32_t nkeys, const rdf_array
     return fail(RDF_COMPUTE_ERROR, "groupby: no path completed");
 }
 
+}  // namespace
+
+extern "C" {
+
+rdf_status rdf_groupby_agg(const rdf_array* keys, int32_t nkeys, const rdf_array* values, int64_t nchunks, int32_t agg, int64_t max_groups,
+                           rdf_out* out_keys, rdf_out* out_values, rdf_out* out_counts) {
+    return groupby_agg_impl(keys, nkeys, values, nchunks, agg, max_groups, out_keys, out_values, out_counts, 0);
+}
+
 rdf_status rdf_groupby_sum(const rdf_array* keys, const rdf_array* values, int64_t nchunks, int64_t max_groups,
                            rdf_out* out_keys, rdf_out* out_sums, rdf_out* out_counts) {
     if ((g_ctx.opt_gb_partition == 1 || g_ctx.opt_gb_debug == 3) && keys && nchunks >= 1) {   // A/B, tests: the first-generation fallback where its range holds
         int64_t nrows = 0;
         for (int64_t c = 0; c < nchunks; ++c) nrows += keys[c].length;
-        if (gb_fallback_in_range(max_groups, nrows)) return groupby_sum_fallback(keys, values, nchunks, max_groups, out_keys, out_sums, out_counts);
+        if (gb_fallback_in_range(max_groups, nrows)) return groupby_sum_fallback(keys, values, nchunks, max_groups, out_keys, out_sums, out_counts, 0);
     }
     return rdf_groupby_agg(keys, 1, values, nchunks, values ? RDF_AGG_SUM : RDF_AGG_COUNT, max_groups, out_keys, out_sums, out_counts);
 }

@@ -1359,7 +1359,7 @@ rdf_status pipeline_stream_store(const ProgramSpec& ps, const rdf_array* cols, i
 rdf_status group_pipeline_stream(const ProgramSpec& ps, const rdf_array* cols, int32_t ncols, int64_t nchunks, const char* msg);
 rdf_status filter_stream(const rdf_expr_node* nodes, int32_t nnodes, int32_t root, const rdf_array* cols, int32_t ncols, int64_t nchunks, rdf_out* outs);
 rdf_status groupby_stream(const rdf_array* keys, const rdf_array* values, int64_t nchunks, int32_t agg, int64_t max_groups,
-                          rdf_out* out_keys, rdf_out* out_values, rdf_out* out_counts);
+                          rdf_out* out_keys, rdf_out* out_values, rdf_out* out_counts, int64_t slack);
 
 // Every entry point that takes chunk lists comes through here.  Host-resident batches beyond one slab are streamed (slab k + 1
 // crosses the link while the kernel runs over slab k, and — for sinks that materialise on the host — slab k - 1's results

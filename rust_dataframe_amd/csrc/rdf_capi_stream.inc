@@ -617,7 +617,7 @@ rdf_status filter_stream(const rdf_expr_node* nodes, int32_t nnodes, int32_t roo
 // carried across slabs, never more than (max_groups + a slab's groups) rows of them.  One grouping column, Int64 / UInt64,
 // no NULL keys (what the merge takes); anything else keeps the one-shot path.
 rdf_status groupby_stream(const rdf_array* keys, const rdf_array* values, int64_t nchunks, int32_t agg, int64_t max_groups,
-                          rdf_out* out_keys, rdf_out* out_values, rdf_out* out_counts) {
+                          rdf_out* out_keys, rdf_out* out_values, rdf_out* out_counts, int64_t slack) {
     RDF_TRY(ensure_ready());
     Ctx& ctx = g_ctx;
     const char* msg = "groupby: key and value chunks differ in length";
@@ -672,6 +672,7 @@ rdf_status groupby_stream(const rdf_array* keys, const rdf_array* values, int64_
         value_nulls = mv.null_count;
         return RDF_OK;
     }));
+    if (nA > max_groups + slack) return fail(RDF_MEMORY_ERROR, "groupby: more than max_groups (%lld) distinct keys", (long long)max_groups);   // (the merge keeps the engine's slack of two; the call's promise does not)
     if (nA > out_keys->capacity || nA > out_values->capacity || nA > out_counts->capacity) return fail(RDF_MEMORY_ERROR, "output capacity too small (need max_groups + 2)");
     HIP_TRY(hipMemcpyAsync(out_keys->values, K(cur), (size_t)nA * 8, hipMemcpyDeviceToHost, ctx.stream));
     HIP_TRY(hipMemcpyAsync(out_values->values, V(cur), (size_t)nA * 8, hipMemcpyDeviceToHost, ctx.stream));

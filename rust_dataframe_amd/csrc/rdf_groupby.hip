@@ -1092,9 +1092,9 @@ __global__ __launch_bounds__(kBlock) void gb2_finish_kernel(const Gb2FinishArgs 
             else if (a.op != AGG_SUM) { valid = c > 0; v = valid ? unord_bits(a.vcls, v) : 0; }
             a.acc[i] = v;
         }
-        const uint64_t vb = __ballot(valid);
+        const uint64_t vb = __ballot(valid), ib = __ballot(in);   // (both by the whole wave: a ballot under `lane == 0` sees lane 0 alone)
         if (a.validity && !a.native_in && lane == 0 && i < a.n) ((uint64_t*)a.validity)[i >> 6] = vb;
-        if (lane == 0 && !a.native_in) nulls += (unsigned long long)__popcll(__ballot(in) & ~vb);
+        if (lane == 0 && !a.native_in) nulls += (unsigned long long)__popcll(ib & ~vb);
     }
     if (lane == 0 && nulls && a.nulls) atomicAdd(a.nulls, nulls);
 }
@@ -1200,10 +1200,10 @@ __global__ __launch_bounds__(kBlock) void key_unpack_kernel(const KeyPackArgs a)
                 case 2: ((uint16_t*)a.out_values[k])[i] = (uint16_t)ob; break;
                 default: ((uint8_t*)a.out_values[k])[i] = (uint8_t)ob; break;
             }
-            const uint64_t vb = __ballot(valid);
+            const uint64_t vb = __ballot(valid), ib = __ballot(in);   // (both by the whole wave: a ballot under `lane == 0` sees lane 0 alone)
             if (lane == 0 && i < a.n) {
                 if (a.out_validity[k]) ((uint64_t*)a.out_validity[k])[i >> 6] = vb;
-                nulls[k] += (unsigned long long)__popcll(__ballot(in) & ~vb);
+                nulls[k] += (unsigned long long)__popcll(ib & ~vb);
             }
         }
     }

@@ -356,3 +356,42 @@ def set_colliders(np_dtype, size, slot, lds, want, seed=0, draws=1 << 21):
     fn = set_home_lds if lds else set_home_wave
     assert all(fn(set_hash(set_hashed_bits(v, dt)), size) == slot for v in out)
     return out
+
+
+# ---------------------------------------------------------------- the hash of the second-generation GROUP BY (rdf_groupby.hip)
+# g2_hash runs on the device only; gb_collect (rdf_capi_groupby.inc) spells out its inverse to name the key whose hash is the
+# LDS free marker.  tests/test_groupby_ref.py holds both constants to each other, to that key and to the two source lines.
+
+G2_MUL = GOLD
+G2_MUL_INV = 0xF1DE83E19937733D
+G2_PART_BITS = 8                     # kG2PartBits: a key's scatter partition is the top 8 bits of its hash
+G2_FREE_KEY = 7406324358081711299    # g2_hash(key) == 2^64 - 1, the free marker of the LDS tables
+
+
+def g2_hash(x):
+    x &= M
+    x ^= x >> 32
+    x = (x * G2_MUL) & M
+    return x ^ (x >> 32)
+
+
+def g2_hash_inv(z):
+    z &= M
+    z ^= z >> 32
+    z = (z * G2_MUL_INV) & M
+    return z ^ (z >> 32)
+
+
+def g2_partition(key):
+    return g2_hash(key) >> (64 - G2_PART_BITS)
+
+
+def g2_keys_in_partition(p, count, seed=0):
+    """`count` distinct keys (as unsigned 64-bit integers) whose hash has the top 8 bits `p`; none is the free-marker key."""
+    rng = random.Random(seed)
+    out = set()
+    while len(out) < count:
+        h = (p << (64 - G2_PART_BITS)) | rng.getrandbits(64 - G2_PART_BITS)
+        if h != M:
+            out.add(g2_hash_inv(h))
+    return sorted(out)

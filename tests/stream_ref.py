@@ -25,10 +25,8 @@ width, comparisons in f64, NULL where any input is NULL); the grouped sink is gr
                    Casts as rdf_cast documents them; numeric <-> Boolean always succeed (x != 0; 0 / 1).  A mask's value bit is
                    0 where the mask is NULL.
   filter sink      per batch the kept rows of every column (a NULL predicate drops the row): values, validity, length, null_count.
-  hash GROUP BY    a dict per key: (value, count).  count = valid values of the group (rows for COUNT, or without values);
-                   sum = wrapping 64-bit for integers, f64 for floats (Float32 widened), 0 for a group without a valid value;
-                   min / max = None for such a group.  Float sums are accumulated with atomics in no fixed order: group_ref's
-                   any-order bound.
+  hash GROUP BY    groupby_ref (groupby / groups_of / check_groupby are its functions): a streamed call answers as rdf_groupby_agg
+                   is defined, float sums within group_ref's any-order bound.
   fused grouped    group_ref.run_chunks.
 """
 import math
@@ -41,6 +39,7 @@ from rust_dataframe_amd import _abi as A
 import exact_ref as X
 import group_ref as GR
 import spec_ref as S
+from groupby_ref import ANY, check_groupby, groupby, groups_of  # noqa: F401  (the hash GROUP BY's model: asserted in one place)
 
 
 # ---------------------------------------------------------------- columns
@@ -206,68 +205,7 @@ def check_filter(got, model, cols, what=""):
 
 
 # ---------------------------------------------------------------- hash GROUP BY
-ANY = object()      # a value the header leaves open
-
-
-def groupby(keys, values, agg):
-    """keys: one chunk list without NULLs; values: a chunk list or None.  -> {key: (value | None, count, valid f64 values | None)}:
-    value is ANY for COUNT and without values (rdf_groupby_agg's out_values is not specified there), None for a MIN / MAX without a valid value."""
-    k = np.concatenate([ch.to_numpy() for ch in keys])
-    assert all(ch.validity is None or ch.valid_mask().all() for ch in keys)
-    if values is not None:
-        vdt, v, ok = columns([values])[0]
-    order = np.argsort(k, kind="stable")
-    ks = k[order]
-    starts = np.flatnonzero(np.concatenate([[True], ks[1:] != ks[:-1]])) if len(ks) else np.zeros(0, dtype=np.int64)
-    ends = np.concatenate([starts[1:], [len(ks)]]).astype(np.int64)
-    out = {}
-    for s, e in zip(starts.tolist(), ends.tolist()):
-        key = int(ks[s])
-        rows = order[s:e]
-        if values is None or agg == "count":
-            out[key] = (ANY, e - s, None)
-            continue
-        x = v[rows][ok[rows]]
-        n = len(x)
-        if vdt in S.FLOATS:
-            x = x.astype(np.float64)                      # Float32 widens exactly
-            assert np.isfinite(x).all(), "the model's float data is finite"
-            val = (math.fsum(x.tolist()) if n else 0.0) if agg == "sum" else None if n == 0 else float(x.min() if agg == "min" else x.max())
-            out[key] = (val, n, x)
-        else:
-            ints = [int(t) for t in x.tolist()]
-            val = GR.wrap64(sum(ints)) if agg == "sum" else None if n == 0 else (min(ints) if agg == "min" else max(ints))
-            out[key] = (val, n, None)
-    return out
-
-
-def groups_of(keys_out, vals_out, counts_out):
-    """The three outputs of Api.groupby_agg -> {key: (value | None, count)}; a key twice is an error."""
-    ks = keys_out[0].to_pylist()
-    v, c = vals_out.to_pylist(), counts_out.to_numpy().tolist()
-    out = {}
-    for i in range(counts_out.length):
-        assert ks[i] not in out, f"group {ks[i]} twice"
-        out[ks[i]] = (v[i], c[i])
-    return out
-
-
-def check_groupby(got, model, agg, what=""):
-    """got = groups_of(...), model = groupby(...)."""
-    assert got.keys() == model.keys(), f"{what}: keys differ: {len(got)} groups vs {len(model)}; only in one: {sorted(set(got) ^ set(model))[:8]}"
-    for key, (mv, mc, x) in model.items():
-        gv, gc = got[key]
-        w = f"{what}: group {key}"
-        assert gc == mc, f"{w}: count {gc} != {mc}"
-        if mv is ANY:
-            continue
-        if mv is None:
-            assert gv is None, f"{w}: {agg} of a group without a valid value is NULL, got {gv!r}"
-        elif agg == "sum" and x is not None:
-            one = GR.Model(1, [A.F64], [[mv]], [[mc]], [mc], [[x]])
-            assert gv is not None and GR.float_sum_ok(float(gv), one, 0, 0), f"{w}: sum {gv!r} vs fsum {mv!r} over {mc} values, bound {float(GR.float_bound(one, 0, 0))!r}"
-        else:
-            assert gv == mv, f"{w}: {agg} {gv!r} != {mv!r}"
+# groupby / groups_of / check_groupby: groupby_ref (imported above), the one definition of rdf_groupby_agg.
 
 
 # ---------------------------------------------------------------- fused grouped aggregation
