@@ -4483,6 +4483,145 @@ class Evaluate {
         out_cols.push_back(Column::from_arrays(vc.take(g.outs[0], 4096).data().chunks(), Field{std::string(fn == AF::First ? "first(" : "last(") + col + ")", vc.data_type(), true}));
     }
 
+    // A step with two or more hash aggregations (Sum / Min / Max / Count / Avg) over a device-resident frame: ONE
+    // rdf_groupby_multi call — the keys prepared and hashed once, every aggregate folded into one table, all outputs in one
+    // group order — and ONE sort of the groups for all columns, instead of a hash GROUP BY and a sort per aggregation.  Avg
+    // comes from the sum and the count of its call; Sum and Avg of one column share a call.  The promise is
+    // rdf_groupby_multi_capacity(ncalls), what the one-pass route holds.  -> false, with out_cols untouched, when the step is
+    // not of that shape (one hash aggregation, host-resident columns, more than 8 calls or value columns) or holds more groups
+    // than the promise: the per-aggregation path then answers as before (the table route for large group counts has not been
+    // measured against it).  CountDistinct / First / Last of the same step keep their sorted path; its groups come
+    // in the same order.  Same column names, dtypes, order and values as the per-aggregation path.
+    static bool group_aggregate_multi(const DataFrame& f, const plan::Transformation& t, const std::vector<const Column*>& kcs, bool on_host,
+                                      std::vector<Column>& out_cols) {
+        using AF = plan::AggregateFunction;
+        auto hashed = [](AF fn) { return fn == AF::Sum || fn == AF::Min || fn == AF::Max || fn == AF::Count || fn == AF::Avg; };
+        struct Entry { int32_t agg; std::string col; int value; DataType vdt, sdt; bool val_nulls; };
+        std::vector<Entry> entries;
+        std::vector<std::string> vcols;
+        size_t nhash = 0;
+        auto entry_of = [&](int32_t agg, const std::string& col) -> int {
+            for (size_t i = 0; i < entries.size(); ++i) if (entries[i].agg == agg && entries[i].col == col) return (int)i;
+            return -1;
+        };
+        for (auto& a : t.aggregations)
+            for (auto& c : a.columns) {
+                if (!hashed(a.function)) {
+                    if (a.function != AF::CountDistinct && a.function != AF::First && a.function != AF::Last) return false;
+                    continue;
+                }
+                ++nhash;
+                const Column& vc = f.column_by_name(c);
+                const DataType vdt = vc.data_type();
+                if (!(is_integer(vdt) || is_float(vdt))) return false;   // (the per-aggregation path words the refusal)
+                const int32_t agg = a.function == AF::Min ? RDF_AGG_MIN : a.function == AF::Max ? RDF_AGG_MAX : a.function == AF::Count ? RDF_AGG_COUNT : RDF_AGG_SUM;
+                if (entry_of(agg, c) >= 0) continue;
+                size_t v = 0;
+                while (v < vcols.size() && vcols[v] != c) ++v;
+                if (v == vcols.size()) vcols.push_back(c);
+                bool val_nulls = false;
+                for (auto& ch : vc.data().chunks()) val_nulls |= ch->validity != nullptr;
+                const bool extremum = agg == RDF_AGG_MIN || agg == RDF_AGG_MAX;
+                const DataType sdt = agg == RDF_AGG_COUNT ? DataType::Int64 : is_float(vdt) ? DataType::Float64 : (extremum && vdt == DataType::UInt64) ? DataType::UInt64 : DataType::Int64;
+                entries.push_back(Entry{agg, c, (int)v, vdt, sdt, val_nulls});
+            }
+        const int64_t nrows = (int64_t)f.num_rows();
+        if (nhash < 2 || on_host || nrows == 0 || entries.size() > RDF_MULTI_MAX_CALLS || vcols.size() > RDF_MULTI_MAX_VALUES) return false;
+        const size_t nk = kcs.size(), nch = kcs[0]->data().num_chunks(), nc = entries.size();
+        std::vector<DataFrame::SortCriteria> crit;
+        for (auto& n : t.names) crit.push_back(DataFrame::SortCriteria{n, false, false});
+        const DataFrame::SortKeys sk = f.sort_keys(crit, false);
+        std::vector<bool> key_nulls(nk, false);
+        std::vector<int64_t> key_bytes(nk, 0);
+        for (size_t k = 0; k < nk; ++k) {
+            for (auto& a : kcs[k]->data().chunks()) if (a->validity != nullptr) key_nulls[k] = true;
+            for (auto& u : sk.txt[k]) key_bytes[k] += u.data.length;
+        }
+        std::vector<std::vector<rdf_array>> vals(vcols.size());
+        std::vector<const rdf_array*> vptr(vcols.size());
+        for (size_t v = 0; v < vcols.size(); ++v) {
+            for (auto& a : f.column_by_name(vcols[v]).data().chunks()) vals[v].push_back(a->view());
+            vptr[v] = vals[v].data();
+        }
+        std::vector<rdf_multi_agg_call> calls(nc);
+        for (size_t c = 0; c < nc; ++c) calls[c] = rdf_multi_agg_call{entries[c].agg, entries[c].value};
+        const int64_t mg = std::max<int64_t>(1, std::min<int64_t>(nrows, rdf_groupby_multi_capacity((int32_t)nc)));
+        std::vector<std::shared_ptr<Array>> num(nk), offs(nk), data(nk), os(nc), oc(nc);
+        std::vector<rdf_out> vk(nk), vo(nk), vd(nk), vs(nc), vcn(nc);
+        std::vector<rdf_key_out> ko(nk);
+        for (size_t k = 0; k < nk; ++k) {
+            if (kcs[k]->data_type() == DataType::Utf8) {
+                offs[k] = Array::make_out(DataType::Int32, mg + 3, true, false);
+                data[k] = Array::make_out(DataType::UInt8, key_bytes[k] + 8, false, false);
+                vo[k] = offs[k]->out_view(mg + 3);
+                vd[k] = data[k]->out_view(key_bytes[k] + 8);
+                ko[k] = rdf_key_out{nullptr, &vo[k], &vd[k]};
+            } else {
+                num[k] = Array::make_out(kcs[k]->data_type(), mg + 2, key_nulls[k], false);
+                vk[k] = num[k]->out_view(mg + 2);
+                ko[k] = rdf_key_out{&vk[k], nullptr, nullptr};
+            }
+        }
+        for (size_t c = 0; c < nc; ++c) {
+            const bool extremum = entries[c].agg == RDF_AGG_MIN || entries[c].agg == RDF_AGG_MAX;
+            os[c] = Array::make_out(entries[c].sdt, mg + 2, extremum && entries[c].val_nulls, false);
+            oc[c] = Array::make_out(DataType::Int64, mg + 2, false, false);
+            vs[c] = os[c]->out_view(mg + 2);
+            vcn[c] = oc[c]->out_view(mg + 2);
+        }
+        int64_t groups = 0;
+        const rdf_status st = rdf_groupby_multi(sk.keys.data(), (int32_t)nk, vptr.data(), (int32_t)vcols.size(), (int64_t)nch, calls.data(), (int32_t)nc, mg,
+                                                ko.data(), vs.data(), vcn.data(), nullptr, &groups);
+        if (st == RDF_MEMORY_ERROR && mg < nrows) return false;   // more groups than the one-pass route holds
+        check(st);
+        std::vector<ArrayRef> ok(nk);
+        for (size_t k = 0; k < nk; ++k) {
+            if (num[k]) { num[k]->length = vk[k].length; num[k]->null_count = vk[k].null_count; ok[k] = num[k]; continue; }
+            offs[k]->length = groups + 1;
+            data[k]->length = vd[k].length;
+            const std::vector<int32_t> o = offs[k]->values_to_host<int32_t>();
+            const std::vector<uint8_t> bytes = data[k]->values_to_host<uint8_t>();
+            offs[k]->length = groups;
+            const std::vector<bool> valid = offs[k]->valid_to_host();
+            std::vector<std::string> rows((size_t)groups);
+            for (int64_t g = 0; g < groups; ++g) rows[(size_t)g].assign((const char*)bytes.data() + o[(size_t)g], (size_t)(o[(size_t)g + 1] - o[(size_t)g]));
+            auto a = std::const_pointer_cast<Array>(Array::from_strings(std::move(rows)));
+            if (vo[k].null_count > 0) {
+                const auto bits = pack_bits(valid);
+                a->validity = std::make_shared<DeviceBuffer>((int64_t)bits.size());
+                check(rdf_copy_h2d(a->validity->data(), bits.data(), (int64_t)bits.size()));
+                a->null_count = vo[k].null_count;
+            }
+            ok[k] = a;
+        }
+        std::vector<Column> gc;
+        std::vector<DataFrame::SortCriteria> order;
+        for (size_t k = 0; k < nk; ++k) {
+            gc.push_back(Column::from_arrays({ok[k]}, Field{"k" + std::to_string(k), kcs[k]->data_type(), true}));
+            order.push_back(DataFrame::SortCriteria{"k" + std::to_string(k), false, false});
+        }
+        for (size_t c = 0; c < nc; ++c) {
+            os[c]->length = oc[c]->length = vs[c].length;
+            os[c]->null_count = vs[c].null_count;
+            gc.push_back(Column::from_arrays({os[c]}, Field{"s" + std::to_string(c), entries[c].sdt, true}));
+            gc.push_back(Column::from_arrays({oc[c]}, Field{"c" + std::to_string(c), DataType::Int64, false}));
+        }
+        const DataFrame g = DataFrame::from_columns(gc).sort(order);   // the one sort every column of the step shares
+        std::vector<Column> cols;
+        for (auto& a : t.aggregations)
+            for (auto& c : a.columns) {
+                if (!hashed(a.function)) { append_sorted_aggregate(f, t.names, a.function, c, cols); continue; }
+                if (cols.empty())
+                    for (size_t k = 0; k < nk; ++k) cols.push_back(Column::from_arrays(g.column_by_name("k" + std::to_string(k)).data().chunks(), Field{t.names[k], kcs[k]->data_type(), true}));
+                const int32_t agg = a.function == AF::Min ? RDF_AGG_MIN : a.function == AF::Max ? RDF_AGG_MAX : a.function == AF::Count ? RDF_AGG_COUNT : RDF_AGG_SUM;
+                const int e = entry_of(agg, c);
+                append_aggregate_column(a.function, c, entries[(size_t)e].vdt, entries[(size_t)e].sdt, g.column_by_name("s" + std::to_string(e)).data().chunks(),
+                                        g.column_by_name("c" + std::to_string(e)).data().chunks(), cols);
+            }
+        out_cols = std::move(cols);
+        return true;
+    }
+
     // GroupAggregate whose grouping columns include Utf8 ones: one rdf_groupby_agg_keys per aggregation (the text keys are
     // dictionary-encoded on the device, the codes grouped next to the integer keys, the dictionary taken by the result's code
     // column); results ordered by the grouping columns — text in byte order, the NULL group last.
@@ -4507,6 +4646,7 @@ class Evaluate {
             for (auto& u : sk.txt[k]) key_bytes[k] += u.data.length;   // the key column's input bytes always suffice
         }
         std::vector<Column> out_cols;
+        if (group_aggregate_multi(f, t, kcs, on_host, out_cols)) return DataFrame::from_columns(out_cols);   // two or more hash aggregations: one call, one sort
         auto one = [&](AF fn, const std::string& col) {
             if (fn == AF::CountDistinct || fn == AF::First || fn == AF::Last) { append_sorted_aggregate(f, t.names, fn, col, out_cols); return; }
             if (fn != AF::Sum && fn != AF::Count && fn != AF::Avg && fn != AF::Min && fn != AF::Max) throw DataFrameError(DataFrameError::ComputeError, "Aggregation not yet supported");
@@ -4607,6 +4747,7 @@ class Evaluate {
         const int64_t nrows = (int64_t)f.num_rows();
         std::vector<Column> out_cols;
         if (nk == 1 && dense_group_aggregate(f, *kcs[0], t, out_cols)) { reset(DataFrame::from_columns(out_cols)); return; }
+        if (group_aggregate_multi(f, t, kcs, f.is_host(), out_cols)) { reset(DataFrame::from_columns(out_cols)); return; }   // two or more hash aggregations: one call, one sort
         // Sparse or NULL-holding keys: one rdf_groupby_agg per aggregation (hash GROUP BY; several grouping columns are
         // range-compressed into one 64-bit key on the device), results ordered by the grouping columns
         auto one = [&](AF fn, const std::string& col) {

@@ -985,6 +985,48 @@ rdf_status rdf_groupby_agg_keys(const rdf_sort_key* keys, int32_t nkeys, const r
                                 int32_t agg, int64_t max_groups, rdf_key_out* out_keys, rdf_out* out_values,
                                 rdf_out* out_counts);
 
+/* Hash GROUP BY with several aggregates from ONE pass over the keys: groupby(k).agg(sum(a), min(b), max(b), count(d), ...)
+ * as one call.  The grouping columns are prepared and hashed once (Utf8 keys dictionary-encoded, several keys packed into
+ * one 64-bit key exactly as in rdf_groupby_agg_keys), up to RDF_MULTI_MAX_CALLS aggregates over up to
+ * RDF_MULTI_MAX_VALUES value columns are folded into one table, and row g of EVERY output belongs to the same group.
+ *   keys / out_keys      as rdf_groupby_agg_keys: 1..RDF_MAX_GROUP_KEYS keys, each integer or Utf8; a NULL key is a group of
+ *                        its own; validity required in the key output of a nullable key.
+ *   values[v]            nchunks chunks of value column v (numeric, one dtype per column), nvalues in 0..8.
+ *   calls[c]             {agg (rdf_agg_fn), value}: value indexes `values`; -1 (COUNT only) counts the group's rows.  Two calls
+ *                        may name one column.  Avg stays on the caller's side: sum / count of the same call.
+ *   outs[c]              the dtype rdf_groupby_agg gives for (agg, dtype of the column): Float64 for float values, UInt64 for
+ *                        MIN / MAX of UInt64, Int64 otherwise (integer sums wrap); NULL values are skipped per value column;
+ *                        MIN / MAX of a group without a non-NULL value is NULL (validity required when that column is
+ *                        nullable); NaN never wins a MIN / MAX unless every value of the group is NaN.  For COUNT the values
+ *                        are unspecified (Int64).
+ *   out_counts[c]        Int64: the non-NULL values of call c's column in the group; the group's rows when value == -1.
+ *   out_group_rows       Int64 rows of the group (may be NULL: not wanted).
+ *   *out_groups          the number of groups; 0 rows is a valid call with 0 groups.
+ * Group order is unspecified.  Capacities >= min(max_groups, rows) + 2 for every numeric output; more than max_groups groups
+ * -> RDF_MEMORY_ERROR and nothing is written (exactly max_groups succeed; with a Utf8 key among the keys the two set-aside
+ * groups — the NULL tuple and the tuple whose packed code hashes to the free marker — do not count, as in
+ * rdf_groupby_agg_keys); Utf8 key outputs size as there.  f64 sums are accumulated with hardware atomics in any order: a
+ * group of n values comes back within gamma(n - 1) * sum|x_i| of the exact sum (the bound stated for rdf_group_pipeline),
+ * and inputs whose partial sums are all exactly representable are summed exactly, bit for bit.
+ * Routes (rdf_groupby_multi_plan.h): while max_groups <= rdf_groupby_multi_capacity(ncalls) every block folds its rows into
+ * a table of hashed keys in LDS — a row finds its slot once and adds into the slot's accumulators — and merges its groups
+ * into one table in HBM at the end; beyond that rows go straight to the table in HBM.  rdf_set_option("groupby_multi_route",
+ * 0 planned | 1 LDS route | 2 HBM table) forces one (the LDS route hands over to the table when a block's table fills up
+ * under a promise beyond its capacity); rdf_set_option("groupby_multi_slots", n) shrinks the LDS table (0 = planned).
+ * Before any device work, with the outputs untouched: ncalls outside 1..8, nvalues outside 0..8, an unknown agg, a value
+ * index out of range, value == -1 with SUM / MIN / MAX, a non-numeric value dtype, mixed memory kinds, a key or key output
+ * in both forms or in neither, a missing validity buffer where one is required -> RDF_INVALID_ARGUMENT; chunk row counts
+ * that differ between columns -> RDF_COMPUTE_ERROR.  Host-memory inputs are copied in whole (no streamed slabs). */
+typedef struct { int32_t agg; int32_t value; } rdf_multi_agg_call;   /* agg: rdf_agg_fn; value: index into values, -1 = count rows */
+#define RDF_MULTI_MAX_CALLS  8
+#define RDF_MULTI_MAX_VALUES 8
+rdf_status rdf_groupby_multi(const rdf_sort_key* keys, int32_t nkeys, const rdf_array* const* values, int32_t nvalues,
+                             int64_t nchunks, const rdf_multi_agg_call* calls, int32_t ncalls, int64_t max_groups,
+                             rdf_key_out* out_keys, rdf_out* outs, rdf_out* out_counts, rdf_out* out_group_rows,
+                             int64_t* out_groups);
+/* The most groups the one-pass LDS route holds for this many calls (table load <= 0.5); 0 for ncalls outside 1..8. */
+int64_t rdf_groupby_multi_capacity(int32_t ncalls);
+
 /* rdf_equijoin_indices_multi over 1..4 key pairs of which each is Utf8 on both sides or numeric of one dtype on both
  * sides (anything else: RDF_INVALID_ARGUMENT).  left_keys[k] / right_keys[k] hold left_nchunks / right_nchunks chunks.  A
  * Utf8 pair is encoded against one shared dictionary (the left chunks followed by the right chunks in one

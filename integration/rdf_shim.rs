@@ -72,6 +72,8 @@ pub mod sys {
     // one key column of rdf_groupby_agg_keys' result: `values` for a numeric key, the (utf8_offsets, utf8_data) pair for a Utf8 one
     #[repr(C)] #[derive(Clone, Copy)]
     pub struct rdf_key_out { pub values: *mut rdf_out, pub utf8_offsets: *mut rdf_out, pub utf8_data: *mut rdf_out }
+    // one call of rdf_groupby_multi: agg = RDF_AGG_*, value = index into `values` (-1: COUNT of the group's rows)
+    #[repr(C)] #[derive(Clone, Copy)] pub struct rdf_multi_agg_call { pub agg: i32, pub value: i32 }
     // one call of rdf_window: fn = RDF_WIN_*, param = ntile buckets / lag, lead offset
     #[repr(C)] #[derive(Clone, Copy)] pub struct rdf_window_call { pub fn_: i32, pub pad: i32, pub param: i64 }
     pub const RDF_WIN_ROW_NUMBER: i32 = 0; pub const RDF_WIN_RANK: i32 = 1; pub const RDF_WIN_DENSE_RANK: i32 = 2;
@@ -196,6 +198,11 @@ pub mod sys {
         pub fn rdf_equijoin_indices_keys(left_keys: *const rdf_sort_key, left_nchunks: i64, right_keys: *const rdf_sort_key,
                                          right_nchunks: i64, nkeys: i32, join_type: i32, out_left: *mut rdf_out,
                                          out_right: *mut rdf_out, out_rows: *mut i64) -> i32;
+        // several aggregates of one GROUP BY from one pass over the keys; row g of every output is one group
+        pub fn rdf_groupby_multi(keys: *const rdf_sort_key, nkeys: i32, values: *const *const rdf_array, nvalues: i32, nchunks: i64,
+                                 calls: *const rdf_multi_agg_call, ncalls: i32, max_groups: i64, out_keys: *mut rdf_key_out,
+                                 outs: *mut rdf_out, out_counts: *mut rdf_out, out_group_rows: *mut rdf_out, out_groups: *mut i64) -> i32;
+        pub fn rdf_groupby_multi_capacity(ncalls: i32) -> i64;
         // AggregateFunctions::count_distinct / sum_distinct / first / last (aggregate.rs, declared with empty bodies) per group
         pub fn rdf_groupby_sorted(group_by: *const rdf_sort_key, ngroup: i32, value: *const rdf_sort_key, nchunks: i64,
                                   calls: *const rdf_group_call, ncalls: i32, out_group_rows: *mut rdf_out, outs: *mut rdf_out,

@@ -138,6 +138,13 @@ class rdf_key_out(C.Structure):
     _fields_ = [("values", C.POINTER(rdf_out)), ("utf8_offsets", C.POINTER(rdf_out)), ("utf8_data", C.POINTER(rdf_out))]
 
 
+class rdf_multi_agg_call(C.Structure):
+    _fields_ = [("agg", C.c_int32), ("value", C.c_int32)]
+
+
+MULTI_MAX_CALLS, MULTI_MAX_VALUES = 8, 8
+
+
 class rdf_window_call(C.Structure):
     _fields_ = [("fn", C.c_int32), ("pad", C.c_int32), ("param", C.c_int64)]
 
@@ -2404,6 +2411,64 @@ class Api:
         self._finish([ov], cv)
         self._finish([oc], ccnt)
         return keys, ov, oc
+
+    def groupby_multi_capacity(self, ncalls: int) -> int:
+        """rdf_groupby_multi_capacity: the most groups the one-pass LDS route of rdf_groupby_multi holds for this many calls."""
+        fn = self._fn("groupby_multi_capacity")
+        fn.restype = C.c_int64
+        return int(fn(C.c_int32(ncalls)))
+
+    def groupby_multi(self, key_cols: Sequence[Sequence], values: Sequence[Sequence], calls: Sequence, max_groups: int, with_rows: bool = True):
+        """rdf_groupby_multi: GROUP BY over 1..4 grouping columns (numeric or Utf8 chunk lists) with several aggregates from one
+        pass: values[v] = the chunks of value column v, calls = [(agg, value index | -1)].
+        -> ([key column], [outs[c]], [counts[c]], group rows | None), one chunk each; row g of every output is one group."""
+        calls = [((self.AGGS[a] if isinstance(a, str) else int(a)), int(v)) for a, v in calls]
+        nk, n, nv, nc = len(key_cols), len(key_cols[0]), len(values), len(calls)
+        ck, keep_k = self._sort_keys(list(key_cols))
+        device = any(isinstance(c, (DeviceArray, DeviceUtf8)) for col in key_cols for c in col)
+        cap = max_groups + 2
+        kouts = (rdf_key_out * max(1, nk))()
+        holders = []
+        for k, col in enumerate(key_cols):
+            nullable = any((c.validity is not None) if isinstance(c, (HostArray, HostUtf8)) else bool(c.validity_ptr) for c in col)
+            if self._is_utf8(col):
+                co, cd, keep = self._utf8_outs(col, [cap], [nullable], device, [max(1, self._utf8_bytes(col))])
+                kouts[k] = rdf_key_out(None, C.cast(co, C.POINTER(rdf_out)), C.cast(cd, C.POINTER(rdf_out)))
+                holders.append(("utf8", co, cd, keep, nullable))
+            else:
+                o = self._window_out(col[0].dtype, cap, device, nullable)
+                co = (rdf_out * 1)(o.out_struct())
+                kouts[k] = rdf_key_out(C.cast(co, C.POINTER(rdf_out)), None, None)
+                holders.append(("num", o, co))
+        carrs = [_flat([v], n) for v in values]
+        cvals = (C.POINTER(rdf_array) * max(1, nv))(*[C.cast(a, C.POINTER(rdf_array)) for a in carrs])
+        ccalls = (rdf_multi_agg_call * max(1, nc))(*[rdf_multi_agg_call(a, v) for a, v in calls])
+        ovs, ocs = [], []
+        for a, v in calls:
+            vdt = values[v][0].dtype if (a != 3 and 0 <= v < nv) else None
+            ovs.append(self._window_out(self._agg_out_dtype(a, vdt), cap, device, True))
+            ocs.append(self._window_out(I64, cap, device, False))
+        cv = (rdf_out * max(1, nc))(*[o.out_struct() for o in ovs])
+        cc = (rdf_out * max(1, nc))(*[o.out_struct() for o in ocs])
+        orow = self._window_out(I64, cap, device, False) if with_rows else None
+        crow = (rdf_out * 1)(orow.out_struct()) if with_rows else None
+        groups = C.c_int64(-1)
+        fn = self._fn("groupby_multi")
+        fn.restype = C.c_int
+        self._check(fn(ck, C.c_int32(nk), cvals, C.c_int32(nv), C.c_int64(n), ccalls, C.c_int32(nc), C.c_int64(max_groups),
+                       kouts, cv, cc, crow, C.byref(groups)))
+        keys = []
+        for h in holders:
+            if h[0] == "utf8":
+                keys.append(self._utf8_result(h[1], h[2], h[3], device, h[4]))
+            else:
+                keys.append(self._finish([h[1]], h[2])[0])
+        self._finish(ovs, cv)
+        self._finish(ocs, cc)
+        if with_rows:
+            self._finish([orow], crow)
+        assert groups.value == ocs[0].length
+        return keys, ovs, ocs, orow
 
     def equijoin_indices_keys(self, left_cols: Sequence[Sequence], right_cols: Sequence[Sequence], how: str, count_only: bool = False, outs=None):
         """rdf_equijoin_indices_keys: left_cols[k] pairs with right_cols[k]; a pair is Utf8 on both sides or numeric of one

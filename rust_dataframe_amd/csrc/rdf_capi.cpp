@@ -29,6 +29,7 @@
 #include "rdf_stream_plan.h"
 #include "rdf_join_place.h"
 #include "rdf_program_plan.h"
+#include "rdf_groupby_multi_plan.h"
 #include "rdf_utf8.h"
 #include "rdf_colstats.h"
 #include "rdf_window.h"
@@ -84,6 +85,8 @@ struct Ctx {
     int    opt_filter_short = 1;    // batches / chunks no longer than a block tile on the block kernel's short-batch mode (round 6; default); 0 = the wave-tile kernels (A/B)
     int    opt_filter_block_rows = 8192;    // ... for frames whose mean batch length is at least this many rows (one block tile of a single 8-byte column; measured ahead of the wave-tile kernel from 8192-row batches up: profiles/r06_filter_frame_batch_length_sweep.jsonl)
     int    opt_filter_fused = 1;    // rdf_filter_frame: `col CMP literal [AND|OR col CMP literal]` predicates evaluated inside the compaction kernel, one pass (1, default); 0 = predicate -> mask, count, compact (A/B)
+    int    opt_gbm_route = 0;       // rdf_groupby_multi: 0 = planned (rdf_groupby_multi_plan.h), 1 = the one-pass LDS route, 2 = the HBM table route
+    int64_t opt_gbm_slots = 0;      // rdf_groupby_multi: slots of the block table (tests reach the capacity boundary with a few groups); 0 = planned
     int    opt_gb_debug = 0;        // 3 = rdf_groupby_sum takes the first-generation fallback (where its range holds) with the combining scatter forced (tests); nothing else is stored
     bool   sort_used_local = false; // the last sort finished at least one column with os_local_kernel
     int64_t utf8_sort_rounds = 0;   // the last sort: refinement rounds its Utf8 criteria took (round 0 included), summed
@@ -2527,6 +2530,7 @@ rdf_status groupby_sum_fallback(const rdf_array* keys, const rdf_array* values, 
 #include "rdf_capi_sort_utf8.inc"
 #include "rdf_capi_colstats.inc"
 #include "rdf_capi_dict.inc"
+#include "rdf_capi_groupby_multi.inc"
 #include "rdf_capi_window.inc"
 #include "rdf_capi_window_agg.inc"
 #include "rdf_capi_moments.inc"
@@ -2572,6 +2576,8 @@ rdf_status rdf_set_option(const char* name, int64_t value) {
     else if (strcmp(name, "fast_filter") == 0) g_ctx.opt_fast_filter = value != 0;
     else if (strcmp(name, "vec_bitmap") == 0) g_ctx.opt_vec_bitmap = value != 0;
     else if (strcmp(name, "gb_partition") == 0) g_ctx.opt_gb_partition = value == 2 ? 3 : (int)value;   // (2 named the retired radix-sort partitioning: accepted, the planner decides as under 3)
+    else if (strcmp(name, "groupby_multi_route") == 0) g_ctx.opt_gbm_route = value >= 0 && value <= 2 ? (int)value : 0;
+    else if (strcmp(name, "groupby_multi_slots") == 0) g_ctx.opt_gbm_slots = value > 0 ? value : 0;
     else if (strcmp(name, "gb_debug") == 0) g_ctx.opt_gb_debug = value == 3 ? 3 : 0;   // (every other value named a retired ablation of the kernels: accepted and ignored)
     else if (strcmp(name, "take_rows") == 0) g_ctx.opt_take_rows = (int)value;
     else if (strcmp(name, "sort_gen") == 0 || strcmp(name, "sort_pipe") == 0 || strcmp(name, "sort_super") == 0) {}   // retired forms of the digit pass (rdf_sort.hip): accepted and ignored, so that callers that still set them keep running

@@ -623,6 +623,168 @@ bool gb_fallback_in_range(int64_t max_groups, int64_t nrows);
 rdf_status groupby_sum_fallback(const rdf_array* keys, const rdf_array* values, int64_t nchunks, int64_t max_groups,
                                 rdf_out* out_keys, rdf_out* out_sums, rdf_out* out_counts, int64_t slack);
 
+// Several grouping columns <-> ONE packed 64-bit key, shared by rdf_groupby_agg and rdf_groupby_multi (and through them the
+// Utf8 compositions): every column range-compressed to bits(max - min) (+ a code for NULL), one min / max pass per column
+// decides the layout.  Columns whose ranges together need more than 64 bits (several sparse keys) are dictionary-coded
+// instead: a count-only GROUP BY of the column alone gives its distinct values (at most max_groups of them), their sorted
+// order is the code
+struct GbKeyPack {
+    KeyPackArgs kp;
+    int range_bits[kMaxKeyCols] = {0, 0, 0, 0};
+    bool use_dict[kMaxKeyCols] = {false, false, false, false};
+    std::vector<uint64_t> hdict[kMaxKeyCols];
+    GbKeyPack() { memset(&kp, 0, sizeof kp); }
+
+    // the field layout: one min / max pass per column (nkeys > 1; one column is grouped as it is)
+    rdf_status plan(const rdf_array* keys, int32_t nkeys, int64_t nchunks, const int* kdt, const bool* knullable, int64_t max_groups, int64_t nrows) {
+        if (nkeys > 1) {
+            int total_bits = 0;
+            for (int k = 0; k < nkeys; ++k) {
+                rdf_agg_result r;
+                RDF_TRY(agg_column(keys + (int64_t)k * nchunks, nchunks, false, &r));
+                const bool sgn = is_signed_int(kdt[k]);
+                uint64_t lo = 0, hi = 0;
+                if (r.is_some) {
+                    lo = sgn ? ((uint64_t)r.min_i64 ^ 0x8000000000000000ull) : h_normalize_int(kdt[k], (uint64_t)r.min_i64);
+                    hi = sgn ? ((uint64_t)r.max_i64 ^ 0x8000000000000000ull) : h_normalize_int(kdt[k], (uint64_t)r.max_i64);
+                }
+                uint64_t span = hi - lo;                       // largest field code before the NULL shift
+                int bits = 0;
+                if (knullable[k] && span == ~0ull) bits = 65;  // a full-range nullable column has no spare code: dictionary only
+                else {
+                    if (knullable[k]) ++span;
+                    while (bits < 64 && (span >> bits) != 0) ++bits;
+                    if (bits == 0) bits = 1;
+                }
+                kp.dtype[k] = kdt[k];
+                kp.nullable[k] = knullable[k] ? 1 : 0;
+                kp.bias[k] = lo;
+                range_bits[k] = bits;
+                total_bits += bits;
+            }
+            if (total_bits > 64) {
+                // widest columns first, until the tuple fits with every dictionary column priced at bits(max_groups + 1)
+                const int64_t dmax = std::min<int64_t>(max_groups, std::max<int64_t>(nrows, 1)) + 1;
+                int dbits = 1;
+                while (dbits < 63 && ((uint64_t)dmax >> dbits) != 0) ++dbits;
+                while (total_bits > 64) {
+                    int w = -1;
+                    for (int k = 0; k < nkeys; ++k) if (!use_dict[k] && range_bits[k] > dbits && (w < 0 || range_bits[k] > range_bits[w])) w = k;
+                    if (w < 0) return fail(RDF_INVALID_ARGUMENT, "groupby: the grouping columns need %d bits even dictionary-coded; at most 64 are supported", total_bits);
+                    use_dict[w] = true;
+                    total_bits -= range_bits[w] - dbits;
+                }
+            }
+        }
+        return RDF_OK;
+    }
+
+    // one attempt's packed key column (in the arena) -> in.keys / in.kdt; dev: the staged chunks, the key columns first
+    rdf_status pack(const std::vector<DevChunkCol>& dev, const int* kdt, const bool* knullable, int32_t nkeys, int64_t nchunks, int64_t nrows,
+                    const std::vector<int64_t>& clen, const std::vector<int64_t>& row_start, int64_t max_groups, size_t& pin_off, GbInput& in) {
+        Ctx& ctx = g_ctx;
+        TableBuilder ktb;
+        size_t o_cols = 0, o_rs = 0;
+        void* ppk = nullptr;
+        RDF_TRY(arena_alloc((size_t)std::max<int64_t>(nrows, 1) * 8 + 64, &ppk));
+        o_cols = ktb.reserve(sizeof(DevChunkCol) * (size_t)nkeys * (size_t)nchunks);
+        o_rs = ktb.reserve(sizeof(int64_t) * row_start.size());
+        RDF_TRY(ktb.bind(pin_off));
+        memcpy(ktb.at<char>(o_cols), dev.data(), sizeof(DevChunkCol) * (size_t)nkeys * (size_t)nchunks);
+        memcpy(ktb.at<char>(o_rs), row_start.data(), sizeof(int64_t) * row_start.size());
+        RDF_TRY(ktb.alloc());
+        RDF_TRY(ktb.upload(pin_off));
+        pin_off += (ktb.size + 255) & ~(size_t)255;
+        kp.cols = ktb.dev_at<DevChunkCol>(o_cols);
+        kp.chunk_row_start = ktb.dev_at<int64_t>(o_rs);
+        kp.nchunks = nchunks; kp.n = nrows; kp.nkeys = nkeys;
+        kp.packed = (uint64_t*)ppk;
+        // dictionaries of the sparse columns (built once, uploaded per attempt), then the field layout
+        int total_bits = 0;
+        for (int k = 0; k < nkeys; ++k) {
+            int bits = range_bits[k];
+            kp.dict[k] = nullptr; kp.dict_n[k] = 0;
+            if (use_dict[k] && nrows > 0) {
+                if (hdict[k].empty()) {
+                    GbInput din;
+                    din.clen = clen; din.kdt = kdt[k]; din.vdt = -1;
+                    din.keys.assign(dev.begin() + (size_t)k * (size_t)nchunks, dev.begin() + (size_t)(k + 1) * (size_t)nchunks);
+                    GbScratch dsc; GbDense dd; bool dskew = false;
+                    bool dfull = false;
+                    RDF_TRY(gb_engine(din, AGG_SUM, max_groups, ctx.opt_gb_partition == 0 ? 0 : -1, dsc, dd, pin_off, &dskew, &dfull));
+                    if (dskew) RDF_TRY(gb_engine(din, AGG_SUM, max_groups, 0, dsc, dd, pin_off, &dskew, &dfull));
+                    const size_t es = (size_t)dtype_size(kdt[k]);
+                    std::vector<char> hk((size_t)dd.ng * es);
+                    std::vector<uint8_t> hv((size_t)((dd.ng + 7) / 8), 0xFF);
+                    if (dd.ng) HIP_TRY(hipMemcpyAsync(hk.data(), dd.keys, hk.size(), hipMemcpyDeviceToHost, ctx.stream));
+                    if (dd.ng && knullable[k]) HIP_TRY(hipMemcpyAsync(hv.data(), dd.kvalid, hv.size(), hipMemcpyDeviceToHost, ctx.stream));
+                    HIP_TRY(hipStreamSynchronize(ctx.stream));
+                    hdict[k].reserve((size_t)dd.ng);
+                    for (int64_t i = 0; i < dd.ng; ++i) {
+                        if (!((hv[(size_t)(i >> 3)] >> (i & 7)) & 1)) continue;
+                        uint64_t raw = 0;
+                        memcpy(&raw, hk.data() + (size_t)i * es, es);
+                        const uint64_t nv = h_normalize_int(kdt[k], raw);
+                        hdict[k].push_back(is_signed_int(kdt[k]) ? nv ^ 0x8000000000000000ull : nv);
+                    }
+                    std::sort(hdict[k].begin(), hdict[k].end());
+                    if (hdict[k].empty()) hdict[k].push_back(0);   // an all-NULL column: one unused code
+                }
+                void* pd = nullptr;
+                RDF_TRY(arena_alloc(hdict[k].size() * 8 + 64, &pd));
+                HIP_TRY(hipMemcpyAsync(pd, hdict[k].data(), hdict[k].size() * 8, hipMemcpyHostToDevice, ctx.stream));
+                HIP_TRY(hipStreamSynchronize(ctx.stream));
+                kp.dict[k] = (const uint64_t*)pd;
+                kp.dict_n[k] = (int64_t)hdict[k].size();
+                uint64_t span = (uint64_t)hdict[k].size() - 1 + (knullable[k] ? 1 : 0);
+                bits = 0;
+                while (bits < 64 && (span >> bits) != 0) ++bits;
+                if (bits == 0) bits = 1;
+            }
+            kp.shift[k] = total_bits;
+            kp.mask[k] = bits >= 64 ? ~0ull : ((1ull << bits) - 1);
+            total_bits += bits;
+        }
+        if (total_bits > 64) return fail(RDF_INVALID_ARGUMENT, "groupby: the grouping columns need %d bits after range / dictionary coding; at most 64 are supported", total_bits);
+        if (getenv("RDF_DEBUG")) for (int k = 0; k < nkeys; ++k) fprintf(stderr, "[rdf] groupby key column %d: %s\n", k, use_dict[k] ? "dictionary-coded" : "range-packed");
+        HIP_TRY(launch_key_pack(kp, ctx.stream));
+        in.kdt = RDF_U64;
+        in.keys.resize((size_t)nchunks);
+        for (int64_t c = 0; c < nchunks; ++c) in.keys[(size_t)c] = DevChunkCol{ppk, nullptr, row_start[(size_t)c]};
+        return RDF_OK;
+    }
+
+    // the dense packed keys of ng groups -> one array per grouping column, copied out with validity and null counts
+    rdf_status unpack(const void* packed, int64_t ng, const int* kdt, int32_t nkeys, unsigned long long* key_nulls, rdf_out* out_keys, int32_t mem, size_t pin_off) {
+        Ctx& ctx = g_ctx;
+        // unpack the tuple into one dense array per grouping column
+        void* pouts[kMaxKeyCols]; void* pval[kMaxKeyCols];
+        for (int k = 0; k < nkeys; ++k) {
+            RDF_TRY(arena_alloc((size_t)std::max<int64_t>(ng, 1) * (size_t)dtype_size(kdt[k]) + 64, &pouts[k]));
+            RDF_TRY(arena_alloc((size_t)((ng + 63) / 64 * 8) + 8, &pval[k]));
+            kp.out_values[k] = pouts[k];
+            kp.out_validity[k] = (uint8_t*)pval[k];
+        }
+        kp.packed = (uint64_t*)packed;
+        kp.n = ng;
+        kp.out_nulls = key_nulls;
+        HIP_TRY(hipMemsetAsync(key_nulls, 0, 32, ctx.stream));
+        HIP_TRY(launch_key_unpack(kp, ctx.stream));
+        RDF_TRY(pinned_reserve(pin_off + 64));
+        HIP_TRY(hipMemcpyAsync(ctx.pinned + pin_off, key_nulls, 32, hipMemcpyDeviceToHost, ctx.stream));
+        HIP_TRY(hipStreamSynchronize(ctx.stream));
+        unsigned long long kn[4];
+        memcpy(kn, ctx.pinned + pin_off, 32);
+        for (int k = 0; k < nkeys; ++k) {
+            RDF_TRY(gb_copy_out(pouts[k], (size_t)ng * (size_t)dtype_size(kdt[k]), out_keys[k].values, mem));
+            if (out_keys[k].validity) RDF_TRY(gb_copy_out(pval[k], (size_t)((ng + 7) / 8), out_keys[k].validity, mem));
+            out_keys[k].length = ng;
+            out_keys[k].null_count = (int64_t)kn[k];
+        }
+        return RDF_OK;
+    }
+};
+
 // rdf_groupby_agg.  slack: groups beyond max_groups the caller accepts — 0 for the public entries, whose promise counts every
 // group; 2 for rdf_groupby_agg_keys over Utf8 keys, where the up to two set-aside groups (the NULL key; the code whose hash is
 // the LDS free marker) never counted
@@ -683,54 +845,8 @@ rdf_status groupby_agg_impl(const rdf_array* keys, int32_t nkeys, const rdf_arra
         if (bytes > stream_slab_bytes()) return groupby_stream(keys, values, nchunks, agg, max_groups, out_keys, out_values, out_counts, slack);
     }
 
-    // several grouping columns: the tuple is packed into ONE 64-bit key, every column range-compressed to
-    // bits(max - min) (+ a code for NULL): one min / max pass per column decides the layout.  Columns whose ranges
-    // together need more than 64 bits (several sparse keys) are dictionary-coded instead: a count-only GROUP BY of
-    // the column alone gives its distinct values (at most max_groups of them), their sorted order is the code
-    KeyPackArgs kp;
-    memset(&kp, 0, sizeof kp);
-    int range_bits[kMaxKeyCols] = {0, 0, 0, 0};
-    bool use_dict[kMaxKeyCols] = {false, false, false, false};
-    std::vector<uint64_t> hdict[kMaxKeyCols];
-    if (nkeys > 1) {
-        int total_bits = 0;
-        for (int k = 0; k < nkeys; ++k) {
-            rdf_agg_result r;
-            RDF_TRY(agg_column(keys + (int64_t)k * nchunks, nchunks, false, &r));
-            const bool sgn = is_signed_int(kdt[k]);
-            uint64_t lo = 0, hi = 0;
-            if (r.is_some) {
-                lo = sgn ? ((uint64_t)r.min_i64 ^ 0x8000000000000000ull) : h_normalize_int(kdt[k], (uint64_t)r.min_i64);
-                hi = sgn ? ((uint64_t)r.max_i64 ^ 0x8000000000000000ull) : h_normalize_int(kdt[k], (uint64_t)r.max_i64);
-            }
-            uint64_t span = hi - lo;                       // largest field code before the NULL shift
-            int bits = 0;
-            if (knullable[k] && span == ~0ull) bits = 65;  // a full-range nullable column has no spare code: dictionary only
-            else {
-                if (knullable[k]) ++span;
-                while (bits < 64 && (span >> bits) != 0) ++bits;
-                if (bits == 0) bits = 1;
-            }
-            kp.dtype[k] = kdt[k];
-            kp.nullable[k] = knullable[k] ? 1 : 0;
-            kp.bias[k] = lo;
-            range_bits[k] = bits;
-            total_bits += bits;
-        }
-        if (total_bits > 64) {
-            // widest columns first, until the tuple fits with every dictionary column priced at bits(max_groups + 1)
-            const int64_t dmax = std::min<int64_t>(max_groups, std::max<int64_t>(nrows, 1)) + 1;
-            int dbits = 1;
-            while (dbits < 63 && ((uint64_t)dmax >> dbits) != 0) ++dbits;
-            while (total_bits > 64) {
-                int w = -1;
-                for (int k = 0; k < nkeys; ++k) if (!use_dict[k] && range_bits[k] > dbits && (w < 0 || range_bits[k] > range_bits[w])) w = k;
-                if (w < 0) return fail(RDF_INVALID_ARGUMENT, "groupby: the grouping columns need %d bits even dictionary-coded; at most 64 are supported", total_bits);
-                use_dict[w] = true;
-                total_bits -= range_bits[w] - dbits;
-            }
-        }
-    }
+    GbKeyPack pk;
+    RDF_TRY(pk.plan(keys, nkeys, nchunks, kdt, knullable, max_groups, nrows));
 
     RDF_TRY(ensure_ready());
     Ctx& ctx = g_ctx;
@@ -748,78 +864,11 @@ rdf_status groupby_agg_impl(const rdf_array* keys, int32_t nkeys, const rdf_arra
         for (int64_t c = 0; c < nchunks; ++c) { in.clen[(size_t)c] = keys[c].length; row_start[(size_t)c + 1] = row_start[(size_t)c] + keys[c].length; }
         in.vdt = vdt;
         if (values) in.values.assign(st.dev.begin() + (size_t)nkeys * (size_t)nchunks, st.dev.end());
-        TableBuilder ktb;
-        size_t o_cols = 0, o_rs = 0;
         if (nkeys == 1) {
             in.kdt = kdt[0];
             in.keys.assign(st.dev.begin(), st.dev.begin() + (size_t)nchunks);
         } else {
-            void* ppk = nullptr;
-            RDF_TRY(arena_alloc((size_t)std::max<int64_t>(nrows, 1) * 8 + 64, &ppk));
-            o_cols = ktb.reserve(sizeof(DevChunkCol) * (size_t)nkeys * (size_t)nchunks);
-            o_rs = ktb.reserve(sizeof(int64_t) * row_start.size());
-            RDF_TRY(ktb.bind(pin_off));
-            memcpy(ktb.at<char>(o_cols), st.dev.data(), sizeof(DevChunkCol) * (size_t)nkeys * (size_t)nchunks);
-            memcpy(ktb.at<char>(o_rs), row_start.data(), sizeof(int64_t) * row_start.size());
-            RDF_TRY(ktb.alloc());
-            RDF_TRY(ktb.upload(pin_off));
-            pin_off += (ktb.size + 255) & ~(size_t)255;
-            kp.cols = ktb.dev_at<DevChunkCol>(o_cols);
-            kp.chunk_row_start = ktb.dev_at<int64_t>(o_rs);
-            kp.nchunks = nchunks; kp.n = nrows; kp.nkeys = nkeys;
-            kp.packed = (uint64_t*)ppk;
-            // dictionaries of the sparse columns (built once, uploaded per attempt), then the field layout
-            int total_bits = 0;
-            for (int k = 0; k < nkeys; ++k) {
-                int bits = range_bits[k];
-                kp.dict[k] = nullptr; kp.dict_n[k] = 0;
-                if (use_dict[k] && nrows > 0) {
-                    if (hdict[k].empty()) {
-                        GbInput din;
-                        din.clen = in.clen; din.kdt = kdt[k]; din.vdt = -1;
-                        din.keys.assign(st.dev.begin() + (size_t)k * (size_t)nchunks, st.dev.begin() + (size_t)(k + 1) * (size_t)nchunks);
-                        GbScratch dsc; GbDense dd; bool dskew = false;
-                        bool dfull = false;
-                        RDF_TRY(gb_engine(din, AGG_SUM, max_groups, ctx.opt_gb_partition == 0 ? 0 : -1, dsc, dd, pin_off, &dskew, &dfull));
-                        if (dskew) RDF_TRY(gb_engine(din, AGG_SUM, max_groups, 0, dsc, dd, pin_off, &dskew, &dfull));
-                        const size_t es = (size_t)dtype_size(kdt[k]);
-                        std::vector<char> hk((size_t)dd.ng * es);
-                        std::vector<uint8_t> hv((size_t)((dd.ng + 7) / 8), 0xFF);
-                        if (dd.ng) HIP_TRY(hipMemcpyAsync(hk.data(), dd.keys, hk.size(), hipMemcpyDeviceToHost, ctx.stream));
-                        if (dd.ng && knullable[k]) HIP_TRY(hipMemcpyAsync(hv.data(), dd.kvalid, hv.size(), hipMemcpyDeviceToHost, ctx.stream));
-                        HIP_TRY(hipStreamSynchronize(ctx.stream));
-                        hdict[k].reserve((size_t)dd.ng);
-                        for (int64_t i = 0; i < dd.ng; ++i) {
-                            if (!((hv[(size_t)(i >> 3)] >> (i & 7)) & 1)) continue;
-                            uint64_t raw = 0;
-                            memcpy(&raw, hk.data() + (size_t)i * es, es);
-                            const uint64_t nv = h_normalize_int(kdt[k], raw);
-                            hdict[k].push_back(is_signed_int(kdt[k]) ? nv ^ 0x8000000000000000ull : nv);
-                        }
-                        std::sort(hdict[k].begin(), hdict[k].end());
-                        if (hdict[k].empty()) hdict[k].push_back(0);   // an all-NULL column: one unused code
-                    }
-                    void* pd = nullptr;
-                    RDF_TRY(arena_alloc(hdict[k].size() * 8 + 64, &pd));
-                    HIP_TRY(hipMemcpyAsync(pd, hdict[k].data(), hdict[k].size() * 8, hipMemcpyHostToDevice, ctx.stream));
-                    HIP_TRY(hipStreamSynchronize(ctx.stream));
-                    kp.dict[k] = (const uint64_t*)pd;
-                    kp.dict_n[k] = (int64_t)hdict[k].size();
-                    uint64_t span = (uint64_t)hdict[k].size() - 1 + (knullable[k] ? 1 : 0);
-                    bits = 0;
-                    while (bits < 64 && (span >> bits) != 0) ++bits;
-                    if (bits == 0) bits = 1;
-                }
-                kp.shift[k] = total_bits;
-                kp.mask[k] = bits >= 64 ? ~0ull : ((1ull << bits) - 1);
-                total_bits += bits;
-            }
-            if (total_bits > 64) return fail(RDF_INVALID_ARGUMENT, "groupby: the grouping columns need %d bits after range / dictionary coding; at most 64 are supported", total_bits);
-            if (getenv("RDF_DEBUG")) for (int k = 0; k < nkeys; ++k) fprintf(stderr, "[rdf] groupby key column %d: %s\n", k, use_dict[k] ? "dictionary-coded" : "range-packed");
-            HIP_TRY(launch_key_pack(kp, ctx.stream));
-            in.kdt = RDF_U64;
-            in.keys.resize((size_t)nchunks);
-            for (int64_t c = 0; c < nchunks; ++c) in.keys[(size_t)c] = DevChunkCol{ppk, nullptr, row_start[(size_t)c]};
+            RDF_TRY(pk.pack(st.dev, kdt, knullable, nkeys, nchunks, nrows, in.clen, row_start, max_groups, pin_off, in));
         }
         GbScratch sc;
         GbDense d;
@@ -863,30 +912,7 @@ rdf_status groupby_agg_impl(const rdf_array* keys, int32_t nkeys, const rdf_arra
             }
             out_keys->length = ng;
         } else {
-            // unpack the tuple into one dense array per grouping column
-            void* pouts[kMaxKeyCols]; void* pval[kMaxKeyCols];
-            for (int k = 0; k < nkeys; ++k) {
-                RDF_TRY(arena_alloc((size_t)std::max<int64_t>(ng, 1) * (size_t)dtype_size(kdt[k]) + 64, &pouts[k]));
-                RDF_TRY(arena_alloc((size_t)((ng + 63) / 64 * 8) + 8, &pval[k]));
-                kp.out_values[k] = pouts[k];
-                kp.out_validity[k] = (uint8_t*)pval[k];
-            }
-            kp.packed = (uint64_t*)d.keys;
-            kp.n = ng;
-            kp.out_nulls = sc.key_nulls();
-            HIP_TRY(hipMemsetAsync(sc.key_nulls(), 0, 32, ctx.stream));
-            HIP_TRY(launch_key_unpack(kp, ctx.stream));
-            RDF_TRY(pinned_reserve(pin_off + 64));
-            HIP_TRY(hipMemcpyAsync(ctx.pinned + pin_off, sc.key_nulls(), 32, hipMemcpyDeviceToHost, ctx.stream));
-            HIP_TRY(hipStreamSynchronize(ctx.stream));
-            unsigned long long kn[4];
-            memcpy(kn, ctx.pinned + pin_off, 32);
-            for (int k = 0; k < nkeys; ++k) {
-                RDF_TRY(gb_copy_out(pouts[k], (size_t)ng * (size_t)dtype_size(kdt[k]), out_keys[k].values, mem));
-                if (out_keys[k].validity) RDF_TRY(gb_copy_out(pval[k], (size_t)((ng + 7) / 8), out_keys[k].validity, mem));
-                out_keys[k].length = ng;
-                out_keys[k].null_count = (int64_t)kn[k];
-            }
+            RDF_TRY(pk.unpack(d.keys, ng, kdt, nkeys, sc.key_nulls(), out_keys, mem, pin_off));
         }
         RDF_TRY(gb_copy_out(d.acc, (size_t)ng * 8, out_values->values, mem));
         RDF_TRY(gb_copy_out(d.counts, (size_t)ng * 8, out_counts->values, mem));

@@ -559,6 +559,61 @@ hipError_t launch_key_pack(const KeyPackArgs& a, hipStream_t s);
 hipError_t launch_key_unpack(const KeyPackArgs& a, hipStream_t s);
 size_t gb2_scatter_lds_bytes(bool compact);
 
+// ---- hash GROUP BY with several aggregates folded into one table (rdf_groupby_multi.hip; layout and route: rdf_groupby_multi_plan.h) ----
+// One table in HBM, open addressing over HASHED keys (g2_hash is invertible; ~0 = free), entries = capacity + 2: entry
+// `capacity` is the key whose hash is the free marker, `capacity + 1` the NULL key; either exists when its rows > 0.
+struct GbmTable {
+    unsigned long long* keys;      // [entries]
+    unsigned long long* rows;      // [entries] rows of the group
+    unsigned long long* acc;       // [ncalls][entries] f64 bits / wrapping i64 / order-preserving image (MIN, MAX)
+    unsigned long long* cnt;       // [ncalls][entries] non-NULL values of the call's column
+    unsigned int*       head;      // [0] distinct keys in the table proper, [1] flags (bit 2: table full, bit 3: a block table full), [2] emit cursor
+    int64_t             capacity;  // power of two
+    int64_t             entries;
+};
+constexpr int kGbmSub = 512;       // rows of a sub-tile: row t of a sub-tile belongs to thread t; a sub-tile lies inside one chunk
+constexpr int32_t GBM_COUNT = 3;   // a call that only counts (next to AGG_SUM / AGG_MIN / AGG_MAX)
+struct GbmArgs {
+    const DevChunkCol* keys;             // [nchunks]
+    const DevChunkCol* values;           // [nvalues * nchunks]
+    const int64_t*     chunk_sub_start;  // [nchunks + 1], sub-tiles of kGbmSub rows
+    const int64_t*     chunk_len;
+    int64_t            nchunks, nsubs;
+    DevChunkCol        key0, val0[8];    // nchunks == 1: descriptors inline
+    int64_t            len0;
+    int32_t            key_dtype, nvalues, ncalls;
+    int32_t            value_dtype[8];
+    // the calls ordered by value column, in bit fields (a run-time index into a kernel-argument array may cost a private copy):
+    // first_bits nibble v = first order slot of value column v (nibble nvalues = their number); order_bits byte i = the call of
+    // order slot i; call_bits nibble c = op of call c (AGG_* / GBM_COUNT) | CLS_* of its accumulator << 2.  Calls that count rows
+    // (value -1) are in no slot.
+    uint64_t           first_bits, order_bits;
+    uint32_t           call_bits;
+    GbmTable           t;
+    int32_t            slots, off_acc, off_rows, off_cnt, off_tail;   // the block table (GbmPlan)
+};
+struct GbmEmitArgs {
+    GbmTable  t;
+    int32_t   ncalls, key_dtype;
+    uint32_t  rows_mask;           // bit c: call c counts rows (its count output = the group's rows)
+    int64_t   ng_main, cap_out;    // groups of the table proper (the special groups follow them); stride of the dense per-call arrays
+    void*     out_keys;  uint32_t* out_keys_validity;   // dense; validity zeroed by the host, bits set here
+    int64_t*  out_rows;
+    uint64_t* out_acc;   int64_t* out_cnt;              // [ncalls][cap_out]
+};
+struct GbmFinishArgs {
+    uint64_t* acc; const int64_t* cnt;   // [ncalls][cap_out]
+    uint64_t* validity;                  // [ncalls][words] 64-bit words, words = (cap_out + 63) / 64
+    unsigned long long* nulls;           // [ncalls]
+    int64_t   n, cap_out, words;
+    int32_t   ncalls;
+    uint32_t  call_bits;                 // as GbmArgs::call_bits
+};
+hipError_t launch_gbm_stream(const GbmArgs& a, int rows_per_thread, int grid, size_t lds_bytes, hipStream_t s);
+hipError_t launch_gbm_table(const GbmArgs& a, int rows_per_thread, hipStream_t s);
+hipError_t launch_gbm_emit(const GbmEmitArgs& a, hipStream_t s);
+hipError_t launch_gbm_finish(const GbmFinishArgs& a, hipStream_t s);
+
 struct TakeArgs {
     const DevChunkCol* chunks;           // [nchunks]
     const int64_t*     chunk_row_start;  // [nchunks + 1]

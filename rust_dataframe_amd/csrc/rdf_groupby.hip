@@ -1308,3 +1308,8 @@ hipError_t launch_key_unpack(const KeyPackArgs& a, hipStream_t s) {
 }
 
 }  // namespace rdfk
+
+// ------------------------------------------------------------------------------------------------
+// rdf_groupby_multi (several aggregates folded into one table): its kernels use this file's hash, free marker, MIN / MAX
+// images and dtype-switched loads, so they are compiled as part of this translation unit
+#include "rdf_groupby_multi.hip"
