@@ -502,6 +502,7 @@ class Column {
     inline Column greatest(const Column& other) const;          // Spark's ordering: NaN above every number, NULLs skipped
     inline Column least(const Column& other) const;
     inline Column nanvl(const Column& other) const;             // Float32 / Float64: this unless it is NaN, then other
+    inline Column is_in(const Column& set) const;                // Boolean, SQL's three-valued x IN (set): rdf_member_mask(IS_IN)
     inline Column is_null() const;                              // Boolean, never NULL; Utf8 columns by their rows' bitmap
     inline Column is_not_null() const;
     inline Column is_nan() const;
@@ -1185,9 +1186,10 @@ struct Scalar {
 struct BooleanFilter;
 using FilterRef = std::shared_ptr<const BooleanFilter>;
 struct BooleanFilter {
-    enum Kind { InputScalar, InputColumn, Not, And, Or, Gt, Ge, Eq, Ne, Lt, Le, StartsWith, EndsWith, Contains, Like, RLike } kind;
+    enum Kind { InputScalar, InputColumn, Not, And, Or, Gt, Ge, Eq, Ne, Lt, Le, StartsWith, EndsWith, Contains, Like, RLike, IsIn } kind;
     Scalar scalar_v;
     std::string column_name;
+    std::shared_ptr<const Column> set_v;   // IsIn: the values (a column of the tested column's type)
     int32_t escape = -1;   // Like: -1 = none, or one ASCII byte
     FilterRef l, r;
     static FilterRef scalar(Scalar s) { auto f = std::make_shared<BooleanFilter>(); f->kind = InputScalar; f->scalar_v = s; return f; }
@@ -1211,6 +1213,10 @@ struct BooleanFilter {
     }
     // RLIKE: the String scalar is a regular expression (rdf_utf8_regexp_match), true where a match exists anywhere in the row
     static FilterRef rlike(FilterRef a, FilterRef b) { return make(RLike, a, b); }
+    // SQL's three-valued `column IN (set)` (rdf_member_mask, IS_IN): a NULL result drops the row like FALSE; NOT IN is not_(is_in(..))
+    static FilterRef is_in(FilterRef column, const Column& set) {
+        auto f = std::make_shared<BooleanFilter>(); f->kind = IsIn; f->l = std::move(column); f->set_v = std::make_shared<const Column>(set); return f;
+    }
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -2560,6 +2566,12 @@ class DataFrame {
     static bool is_text_scalar(const FilterRef& f) { return f && f->kind == BooleanFilter::InputScalar && f->scalar_v.kind == Scalar::String; }
     FilterRef lower_text_leaves(const FilterRef& f, std::vector<std::pair<std::string, Column>>& leaves) const {
         if (!f) return f;
+        if (f->kind == BooleanFilter::IsIn) {   // a membership leaf: its mask stands in for it like a text leaf's
+            if (!f->l || f->l->kind != BooleanFilter::InputColumn || !f->set_v) throw DataFrameError(DataFrameError::ComputeError, "is_in takes a column and a column of values");
+            const std::string name = std::string("\x01is_in_") + std::to_string(leaves.size());
+            leaves.emplace_back(name, member_mask(DataFrame::from_columns({*f->set_v}), {{f->l->column_name, f->set_v->name()}}, RDF_MEMBER_IS_IN, name));
+            return BooleanFilter::column(name);
+        }
         int32_t op = -1;
         bool comparison = true;
         switch (f->kind) {
@@ -2639,7 +2651,7 @@ class DataFrame {
     DataFrame filter(const FilterRef& condition) const {
         bool all_numeric = !columns_.empty();
         for (auto& c : columns_) all_numeric = all_numeric && (is_integer(c.data_type()) || is_float(c.data_type()));
-        if (!(all_host() && all_numeric && columns_.size() <= 64)) return filter_by_mask(evaluate_boolean_filter(condition));
+        if (!(all_host() && all_numeric && columns_.size() <= 64) || has_is_in(condition)) return filter_by_mask(evaluate_boolean_filter(condition));
         Lowered low;
         const int root = low.add(filter_to_expr(condition, [this](const std::string& n) {
             if (!has_column(n)) throw DataFrameError(DataFrameError::ComputeError, "Cannot find column " + n);
@@ -2674,6 +2686,7 @@ class DataFrame {
         }
         return DataFrame(schema_, std::move(result));
     }
+    static bool has_is_in(const FilterRef& f) { return f && (f->kind == BooleanFilter::IsIn || has_is_in(f->l) || has_is_in(f->r)); }
     DataFrame filter_by_mask(const Column& mask) const {
         const size_t nch = num_chunks();
         const auto mv = mask.data().views();
@@ -2741,10 +2754,15 @@ class DataFrame {
     }
     // DataFrame::join (:626-719): equi-join indices on 1..4 key column pairs, then Column::take of every column
     // of both frames (left columns first).  JoinType as src/expression.rs:339-345.
-    enum class JoinType { LeftJoin = RDF_JOIN_LEFT, RightJoin = RDF_JOIN_RIGHT, InnerJoin = RDF_JOIN_INNER, FullJoin = RDF_JOIN_FULL };
+    // LeftSemi / LeftAnti (values beyond rdf_join_type: rdf_equijoin_indices* never sees them) keep the LEFT frame's columns only:
+    // the rows with / without a partner, through rdf_member_mask and the frame filter.
+    enum class JoinType { LeftJoin = RDF_JOIN_LEFT, RightJoin = RDF_JOIN_RIGHT, InnerJoin = RDF_JOIN_INNER, FullJoin = RDF_JOIN_FULL,
+                          LeftSemi = 100, LeftAnti = 101 };
     struct JoinCriteria { JoinType join_type; std::vector<std::pair<std::string, std::string>> criteria; };
     DataFrame join(const DataFrame& other, const JoinCriteria& jc) const {
         if (jc.criteria.empty() || jc.criteria.size() > 4) throw DataFrameError(DataFrameError::ComputeError, "join: 1 to 4 key column pairs");
+        if (jc.join_type == JoinType::LeftSemi || jc.join_type == JoinType::LeftAnti)
+            return filter_by_mask(member_mask(other, jc.criteria, jc.join_type == JoinType::LeftSemi ? RDF_MEMBER_SEMI : RDF_MEMBER_ANTI, "\x01member"));
         // key pair k: this[criteria[k].first] against other[criteria[k].second], laid out [k * nchunks + chunk]
         std::vector<rdf_array> lk, rk;
         for (auto& c : jc.criteria) {
@@ -2878,6 +2896,99 @@ class DataFrame {
         idx->length = ov.length;
         return idx;
     }
+    // ---- membership: rdf_member_mask / rdf_first_occurrence as Boolean columns of this frame's chunking, and what is built on
+    // them.  Float keys follow Spark (-0.0 == +0.0, NaN == NaN); Utf8 keys are byte strings.
+    enum class Keep { First = RDF_KEEP_FIRST, Last = RDF_KEEP_LAST, None = RDF_KEEP_NONE };
+    struct MaskOuts {   // one Boolean output per chunk
+        std::vector<std::shared_ptr<Array>> arrays;
+        std::vector<rdf_out> views;
+        MaskOuts(const std::vector<int64_t>& rows, bool with_validity, bool host) {
+            for (int64_t n : rows) { arrays.push_back(Array::make_out(DataType::Boolean, n, with_validity, host)); views.push_back(arrays.back()->out_view(n)); }
+        }
+        Column column(const std::string& name, size_t first, size_t count) {
+            std::vector<ArrayRef> chunks;
+            for (size_t i = first; i < first + count; ++i) { arrays[i]->length = views[i].length; arrays[i]->null_count = views[i].null_count; chunks.push_back(arrays[i]); }
+            return Column::from_arrays(chunks, Field{name, DataType::Boolean, true});
+        }
+    };
+    std::vector<int64_t> chunk_rows() const {
+        std::vector<int64_t> rows;
+        for (auto& a : columns_.at(0).data().chunks()) rows.push_back(a->length);
+        return rows;
+    }
+    static void check_key_count(size_t n, const char* what) {
+        if (n < 1 || n > (size_t)RDF_MEMBER_MAX_KEYS)
+            throw DataFrameError(DataFrameError::ComputeError, std::string(what) + ": 1 to 4 key columns, got " + std::to_string(n) + " (more than 4 key columns are not supported)");
+    }
+    // SEMI / ANTI / IS_IN of this frame's rows against `other`'s: criteria[k].first of this frame pairs with .second of other
+    Column member_mask(const DataFrame& other, const std::vector<std::pair<std::string, std::string>>& criteria, int32_t kind, const std::string& name) const {
+        check_key_count(criteria.size(), "membership");
+        std::vector<SortCriteria> lc, rc;
+        for (auto& c : criteria) {
+            if (column_by_name(c.first).data_type() != other.column_by_name(c.second).data_type()) throw DataFrameError(DataFrameError::ComputeError, "Join columns must have compatible types");
+            lc.push_back(SortCriteria{c.first, false, false}); rc.push_back(SortCriteria{c.second, false, false});
+        }
+        const bool host = numeric_columns_on_host() && other.numeric_columns_on_host();
+        const SortKeys lsk = sort_keys(lc, host), rsk = other.sort_keys(rc, host);
+        MaskOuts out(chunk_rows(), kind == RDF_MEMBER_IS_IN, host);
+        int64_t rows = 0;
+        check(rdf_member_mask(lsk.keys.data(), (int64_t)num_chunks(), rsk.keys.data(), (int64_t)other.num_chunks(), (int32_t)criteria.size(), kind, out.views.data(), &rows));
+        return out.column(name, 0, num_chunks());
+    }
+    // TRUE on the first / last / only row of every distinct tuple of the `subset` columns (all columns when empty)
+    Column first_occurrence(const std::vector<std::string>& subset, Keep keep, const std::string& name) const {
+        std::vector<SortCriteria> crit;
+        if (subset.empty()) for (auto& c : columns_) crit.push_back(SortCriteria{c.name(), false, false});
+        else for (auto& n : subset) crit.push_back(SortCriteria{n, false, false});
+        check_key_count(crit.size(), "drop_duplicates");
+        const bool host = numeric_columns_on_host();
+        const SortKeys sk = sort_keys(crit, host);
+        MaskOuts out(chunk_rows(), false, host);
+        int64_t rows = 0;
+        check(rdf_first_occurrence(sk.keys.data(), (int32_t)crit.size(), (int64_t)num_chunks(), (int32_t)keep, out.views.data(), &rows));
+        return out.column(name, 0, num_chunks());
+    }
+    DataFrame drop_duplicates(const std::vector<std::string>& subset = {}, Keep keep = Keep::First) const { return filter_by_mask(first_occurrence(subset, keep, "\x01first")); }
+    DataFrame distinct() const { return drop_duplicates(); }
+    // INTERSECT / EXCEPT with SQL's DISTINCT set semantics (NULL equal to NULL), columns paired by position.  KEEP_FIRST over the
+    // concatenation left-then-right marks the left rows that are the first of their tuple on the left (a); over right-then-left a
+    // left row is TRUE only when no right row holds its tuple (b).  intersect = a AND NOT b, except = a AND b.
+    DataFrame set_op(const DataFrame& other, bool intersect, const char* what) const {
+        if (num_columns() != other.num_columns()) throw DataFrameError(DataFrameError::ComputeError, std::string(what) + ": the frames differ in their number of columns");
+        check_key_count(num_columns(), what);
+        std::vector<SortCriteria> lc, rc;
+        for (size_t k = 0; k < num_columns(); ++k) {
+            if (columns_[k].data_type() != other.columns_[k].data_type()) throw DataFrameError(DataFrameError::ComputeError, std::string(what) + ": column types differ");
+            lc.push_back(SortCriteria{columns_[k].name(), false, false}); rc.push_back(SortCriteria{other.columns_[k].name(), false, false});
+        }
+        const bool host = numeric_columns_on_host() && other.numeric_columns_on_host();
+        const SortKeys lsk = sort_keys(lc, host), rsk = other.sort_keys(rc, host);
+        const size_t lnc = num_chunks(), rnc = other.num_chunks();
+        std::vector<int64_t> lrows = chunk_rows(), rrows = other.chunk_rows();
+        auto first_of = [&](bool left_first) -> Column {   // KEEP_FIRST over the two frames' chunks in the given order; -> the left part
+            const SortKeys& a = left_first ? lsk : rsk; const SortKeys& b = left_first ? rsk : lsk;
+            std::vector<std::vector<rdf_array>> num(lc.size());
+            std::vector<std::vector<rdf_utf8_array>> txt(lc.size());
+            std::vector<rdf_sort_key> keys(lc.size());
+            for (size_t k = 0; k < lc.size(); ++k) {
+                num[k] = a.num[k]; num[k].insert(num[k].end(), b.num[k].begin(), b.num[k].end());
+                txt[k] = a.txt[k]; txt[k].insert(txt[k].end(), b.txt[k].begin(), b.txt[k].end());
+                keys[k] = rdf_sort_key{num[k].empty() ? nullptr : num[k].data(), txt[k].empty() ? nullptr : txt[k].data(), rdf_sort_options{0, 0}};
+            }
+            std::vector<int64_t> rows = left_first ? lrows : rrows;
+            const std::vector<int64_t>& tail = left_first ? rrows : lrows;
+            rows.insert(rows.end(), tail.begin(), tail.end());
+            MaskOuts out(rows, false, host);
+            int64_t n = 0;
+            check(rdf_first_occurrence(keys.data(), (int32_t)keys.size(), (int64_t)(lnc + rnc), RDF_KEEP_FIRST, out.views.data(), &n));
+            return out.column(left_first ? "a" : "b", left_first ? 0 : rnc, lnc);
+        };
+        const DataFrame masks = DataFrame::from_columns({first_of(true), first_of(false)});
+        const FilterRef b = BooleanFilter::column("b");
+        return filter_by_mask(masks.evaluate_boolean_filter(BooleanFilter::and_(BooleanFilter::column("a"), intersect ? BooleanFilter::not_(b) : b)));
+    }
+    DataFrame intersect(const DataFrame& other) const { return set_op(other, true, "intersect"); }
+    DataFrame except(const DataFrame& other) const { return set_op(other, false, "except"); }
     // rdf_groupby_sorted over columns of this frame: `groups` (0 .. 4 names) are the grouping columns, `value` the ONE column
     // the calls read (nullptr with no calls).  -> the group count, the UInt32 row index of every group's first row (groups in
     // ascending key order, NULL last) and one array per call: Int64 counts / sums, Float64 sums of a float column, UInt32 row
@@ -3791,6 +3902,9 @@ inline Column Column::text_null_test(int32_t op) const {   // the rows' bitmap o
 inline Column Column::is_null() const {
     if (data_type() == DataType::Utf8) return text_null_test(RDF_IS_NULL);
     return Column::from_arrays(ScalarFunctions::is_null(data_.chunks()), Field{field_.name, DataType::Boolean, false});
+}
+inline Column Column::is_in(const Column& set) const {
+    return DataFrame::from_columns({*this}).member_mask(DataFrame::from_columns({set}), {{name(), set.name()}}, RDF_MEMBER_IS_IN, name());
 }
 inline Column Column::is_not_null() const {
     if (data_type() == DataType::Utf8) return text_null_test(RDF_IS_NOT_NULL);

@@ -1038,6 +1038,63 @@ rdf_status rdf_equijoin_indices_keys(const rdf_sort_key* left_keys, int64_t left
                                      int64_t right_nchunks, int32_t nkeys, int32_t join_type, rdf_out* out_left,
                                      rdf_out* out_right, int64_t* out_rows);
 
+/* ------------------------------------------------------------------ membership: semi / anti join, is_in, distinct rows */
+
+/* Which of my rows have a partner over there (LEFT SEMI, LEFT ANTI, x IN (...)), and which rows are the first of their kind
+ * (distinct, drop_duplicates)?  One primitive: a set of key tuples goes into a hash table, a column of tuples is streamed
+ * past it, and every row gives ONE bit.  The answer is an RDF_BOOL mask per chunk — what rdf_filter, rdf_filter_columns,
+ * rdf_filter_frame and rdf_utf8_filter take, and rdf_predicate as a Boolean input column.  A mask has no output order: the
+ * result is a function of the input alone; the executable model is tests/member_ref.py.
+ *
+ * Common to both calls.  Keys follow rdf_equijoin_indices_keys: 1..RDF_MEMBER_MAX_KEYS keys, each numeric (one of the ten
+ * fixed-width numeric dtypes, or RDF_BOOL) of one dtype on both sides, or Utf8 on both sides; `options` are ignored; the key
+ * columns of one side agree in their chunks' rows.  All inputs and outputs in host memory or all in device memory (device
+ * bitmaps start on an 8-byte boundary); the two sides together (or the one side) hold fewer than 2^32 rows.
+ *   Float keys compare as rdf_uniques and rdf_window compare them — Spark 3's rule for join and grouping keys: -0.0 == +0.0
+ *   and every NaN equals every NaN.  This KNOWINGLY DIFFERS from rdf_equijoin_indices, which matches key bits (there -0.0 and
+ *   +0.0, and NaNs of different payload, are different keys).
+ *   Utf8 keys are byte strings; the empty string is a value, not NULL.  rdf_member_mask encodes a Utf8 pair against ONE shared
+ *   dictionary (left chunks then right chunks, codes only), rdf_first_occurrence every Utf8 key against its own.
+ * out_mask[i] describes chunk i's rows: bit r = row r, output offset 0, length and null_count set.  *out_rows = the TRUE bits
+ * over all chunks, always set (0 when the call is refused).  out_mask == NULL is the count-only call, which sizes a following
+ * filter.  Zero rows on either side is a valid call.
+ * Errors, all before any device work: NULL pointers, a chunk count below 1, nkeys outside 1..4, an unknown kind / keep, IS_IN
+ * with more than one key, a key setting both pointers or neither, wrong dtypes, a Utf8 key paired with a numeric one, key
+ * dtypes that differ between the sides, mixed memory kinds, a mask that is not RDF_BOOL, a missing validity buffer (IS_IN), 2^32
+ * rows or more, "member_route" 1 on a call the LDS form cannot serve: RDF_INVALID_ARGUMENT.  Key columns of one side that differ in
+ * their chunks' rows: RDF_COMPUTE_ERROR.  A capacity below a chunk's rows: RDF_MEMORY_ERROR with every `length` set and nothing
+ * written.  Scratch that does not fit — a table that "member_table_bits" made too small for the keys included —:
+ * RDF_MEMORY_ERROR, never a partial answer.
+ *
+ * rdf_member_mask
+ *   SEMI   TRUE iff no key of the left row is NULL and some right row holds an equal tuple.  A right row with a NULL in any
+ *          key is never in the set.  The result is never NULL: validity is not required and written all-valid where given.
+ *   ANTI   the complement of SEMI, bit for bit: a left row with a NULL key is kept (Spark's LEFT ANTI).
+ *   IS_IN  SQL's three-valued x IN (right), nkeys == 1: TRUE on a match; otherwise NULL when x is NULL or the right side
+ *          holds a NULL row; otherwise FALSE.  Over an empty right side every row is FALSE, NULL rows included.  Validity is
+ *          required; the value bit of a NULL slot is 0 (rdf_predicate's rule); *out_rows counts TRUE only.  NOT IN is
+ *          rdf_predicate's NOT over this mask.
+ *   The right side is built into an open-addressing table in HBM (load <= 0.5 of the build rows); while that table fits the
+ *   LDS budget and there is one key column, every probe block copies it into LDS and probes there.
+ *   rdf_set_option("member_route", 0 planned | 1 LDS | 2 HBM), ("member_slots", n) shrinks the LDS form's table (tests),
+ *   ("member_table_bits", b) caps the table at 2^b slots (4..32, default 30).  rdf_last_kernel names the form that ran.
+ *
+ * rdf_first_occurrence
+ *   Rows are equal iff they agree on every key, NULL equal to NULL, component-wise: a NULL is a key value of its own, as in
+ *   GROUP BY.  KEEP_FIRST: TRUE on the row with the smallest index of every distinct tuple (pandas keep='first'); KEEP_LAST:
+ *   the largest index; KEEP_NONE: TRUE on tuples that occur exactly once.  For FIRST and LAST *out_rows is the number of
+ *   distinct tuples.  The result is never NULL. */
+typedef enum { RDF_MEMBER_SEMI = 0, RDF_MEMBER_ANTI = 1, RDF_MEMBER_IS_IN = 2 } rdf_member_kind;
+typedef enum { RDF_KEEP_FIRST = 0, RDF_KEEP_LAST = 1, RDF_KEEP_NONE = 2 } rdf_keep;
+#define RDF_MEMBER_MAX_KEYS 4
+
+rdf_status rdf_member_mask(const rdf_sort_key* left_keys, int64_t left_nchunks, const rdf_sort_key* right_keys,
+                           int64_t right_nchunks, int32_t nkeys, int32_t kind,
+                           rdf_out* out_mask /* left_nchunks RDF_BOOL outputs, or NULL */, int64_t* out_rows);
+
+rdf_status rdf_first_occurrence(const rdf_sort_key* keys, int32_t nkeys, int64_t nchunks, int32_t keep,
+                                rdf_out* out_mask /* nchunks RDF_BOOL outputs, or NULL */, int64_t* out_rows);
+
 /* ------------------------------------------------------------------ sorted GROUP BY: count_distinct, sum_distinct, first, last */
 
 /* The aggregations of a GROUP BY that need the rows of a group in an order: AggregateFunctions::count_distinct,
@@ -1615,7 +1672,11 @@ rdf_status rdf_fill_validity(uint8_t* dev_ptr, int64_t nbits, uint64_t seed, uin
  * "uniques_route" (rdf_uniques / rdf_utf8_uniques: 0 = the hash route while its set holds the column's distinct values, the sort /
  * exact route otherwise, default; 1 = always the sort / exact route),
  * "uniques_table_bits" (log2 of the most slots that hash set may have, 10..32, default 24: it is filled to half, so up to 2^23
- * distinct values stay on the hash route). */
+ * distinct values stay on the hash route). 
+ * "member_route" (rdf_member_mask: 0 = planned, 1 = probe a copy of the table in LDS — a call it cannot serve is refused —, 2 =
+ * probe the table in HBM), "member_slots" (slots of the LDS form's table, 0 = planned: tests), "member_table_bits" (log2 of the
+ * most slots the table of rdf_member_mask / rdf_first_occurrence may have, 4..32, 0 = the default 30; a table that then cannot
+ * hold the keys is RDF_MEMORY_ERROR). */
 rdf_status rdf_set_option(const char* name, int64_t value);
 /* Number of program shapes with a specialised kernel. */
 int32_t    rdf_spec_catalog_size(void);

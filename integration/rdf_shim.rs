@@ -198,6 +198,12 @@ pub mod sys {
         pub fn rdf_equijoin_indices_keys(left_keys: *const rdf_sort_key, left_nchunks: i64, right_keys: *const rdf_sort_key,
                                          right_nchunks: i64, nkeys: i32, join_type: i32, out_left: *mut rdf_out,
                                          out_right: *mut rdf_out, out_rows: *mut i64) -> i32;
+        // LEFT SEMI / LEFT ANTI / x IN (..) and distinct rows as one RDF_BOOL mask per chunk (kind: 0 semi, 1 anti, 2 is_in;
+        // keep: 0 first, 1 last, 2 none); out_mask NULL = count only
+        pub fn rdf_member_mask(left_keys: *const rdf_sort_key, left_nchunks: i64, right_keys: *const rdf_sort_key,
+                               right_nchunks: i64, nkeys: i32, kind: i32, out_mask: *mut rdf_out, out_rows: *mut i64) -> i32;
+        pub fn rdf_first_occurrence(keys: *const rdf_sort_key, nkeys: i32, nchunks: i64, keep: i32, out_mask: *mut rdf_out,
+                                    out_rows: *mut i64) -> i32;
         // several aggregates of one GROUP BY from one pass over the keys; row g of every output is one group
         pub fn rdf_groupby_multi(keys: *const rdf_sort_key, nkeys: i32, values: *const *const rdf_array, nvalues: i32, nchunks: i64,
                                  calls: *const rdf_multi_agg_call, ncalls: i32, max_groups: i64, out_keys: *mut rdf_key_out,

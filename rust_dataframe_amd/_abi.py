@@ -19,6 +19,10 @@ STATUS_NAMES = ["OK", "ComputeError", "DivideByZero", "InvalidArgument", "Memory
 
 I8, I16, I32, I64, U8, U16, U32, U64, F32, F64, BOOL, NULLTYPE = range(12)
 MEM_HOST, MEM_DEVICE = 0, 1
+# rdf_member_kind, rdf_keep
+MEMBER_SEMI, MEMBER_ANTI, MEMBER_IS_IN = 0, 1, 2
+KEEP_FIRST, KEEP_LAST, KEEP_NONE = 0, 1, 2
+MEMBER_MAX_KEYS = 4
 
 (OP_ADD, OP_SUB, OP_MUL, OP_DIV, OP_ATAN2, OP_HYPOT, OP_LOG, OP_ABS, OP_ACOS, OP_ASIN, OP_ATAN, OP_CBRT,
  OP_CEIL, OP_COS, OP_COSH, OP_DEGREES, OP_EXP, OP_EXPM1, OP_FLOOR, OP_LOG10, OP_LOG2, OP_RADIANS, OP_ROUND,
@@ -2498,6 +2502,54 @@ class Api:
         self._finish([ol], cl)
         self._finish([orr], cr)
         return ol, orr
+
+    # ---- membership: semi / anti join, is_in, distinct rows
+    MEMBER_KINDS = {"semi": MEMBER_SEMI, "anti": MEMBER_ANTI, "is_in": MEMBER_IS_IN}
+    KEEPS = {"first": KEEP_FIRST, "last": KEEP_LAST, "none": KEEP_NONE, False: KEEP_NONE}
+
+    @staticmethod
+    def _key_rows(col):
+        return [c.length for c in col]
+
+    def _mask_call(self, call, lens, device, with_validity, count_only, outs):
+        """call(carr | None, byref(rows)) -> status; -> the row count (count_only) or (mask outputs, TRUE rows)"""
+        rows = C.c_int64(-1)
+        if count_only:
+            self._check(call(None, C.byref(rows)))
+            return rows.value
+        if outs is None:
+            outs = [self._window_out(BOOL, n, device, with_validity) for n in lens]
+        carr = (rdf_out * max(1, len(outs)))(*[o.out_struct() for o in outs])
+        st = call(carr, C.byref(rows))
+        self._finish(outs, carr)
+        self.last_out_rows = rows.value
+        self._check(st)
+        return outs, rows.value
+
+    def member_mask(self, left_cols: Sequence[Sequence], right_cols: Sequence[Sequence], kind, count_only: bool = False, outs=None):
+        """rdf_member_mask: left_cols[k] pairs with right_cols[k] (HostArray / DeviceArray / HostUtf8 / DeviceUtf8 chunk lists);
+        kind = "semi" | "anti" | "is_in".  -> (one BOOL mask per left chunk, TRUE rows), or the TRUE rows alone."""
+        kd = self.MEMBER_KINDS[kind] if isinstance(kind, str) else int(kind)
+        lk, keep_l = self._sort_keys(list(left_cols))
+        rk, keep_r = self._sort_keys(list(right_cols))
+        nk, lnc, rnc = len(left_cols), len(left_cols[0]), len(right_cols[0])
+        device = any(isinstance(c, (DeviceArray, DeviceUtf8)) for col in list(left_cols) + list(right_cols) for c in col)
+        fn = self._fn("member_mask")
+        fn.restype = C.c_int
+        return self._mask_call(lambda carr, rows: fn(lk, C.c_int64(lnc), rk, C.c_int64(rnc), C.c_int32(nk), C.c_int32(kd), carr, rows),
+                               self._key_rows(left_cols[0]), device, kd == MEMBER_IS_IN, count_only, outs)
+
+    def first_occurrence(self, key_cols: Sequence[Sequence], keep="first", count_only: bool = False, outs=None):
+        """rdf_first_occurrence: keep = "first" | "last" | "none" (pandas' keep=False).  -> (one BOOL mask per chunk, TRUE
+        rows), or the TRUE rows alone."""
+        kp = self.KEEPS[keep] if isinstance(keep, (str, bool)) else int(keep)
+        ck, keep_k = self._sort_keys(list(key_cols))
+        nk, nc = len(key_cols), len(key_cols[0])
+        device = any(isinstance(c, (DeviceArray, DeviceUtf8)) for col in key_cols for c in col)
+        fn = self._fn("first_occurrence")
+        fn.restype = C.c_int
+        return self._mask_call(lambda carr, rows: fn(ck, C.c_int32(nk), C.c_int64(nc), C.c_int32(kp), carr, rows),
+                               self._key_rows(key_cols[0]), device, False, count_only, outs)
 
     # ---- fused grouped aggregation over a small dense domain (TPC-H Q1 shape)
     def group_pipeline(self, expr: Expr, cols: Sequence[Sequence], value_roots: Sequence[int], group_root: int, ngroups: int,

@@ -39,6 +39,7 @@
 #include "rdf_percentile.h"
 #include "rdf_collect.h"
 #include "rdf_datetime.h"
+#include "rdf_member.h"
 #include "rdf_select.h"
 #include "rdf_textconv.h"
 #include "rdf_utf8_pattern.h"
@@ -108,6 +109,9 @@ struct Ctx {
     int    opt_uniques_route = 0;     // rdf_uniques / rdf_utf8_uniques: 0 = the hash route while its table holds the keys, else the sort route (default); 1 = always the sort (exact) route (tests, A/B)
     int    opt_percentile_route = 0;  // rdf_groupby_percentile: 0 = by the call (the select route where it is eligible and measured faster), 1 = always the sorted route, 2 = the select route or a refusal (tests, A/B)
     int    opt_uniques_table_bits = 24;   // ... log2 of the most slots the hash route's table may have (8 bytes each, + 4 for Utf8); it is filled to half, so 2^23 distinct values fit by default
+    int    opt_member_route = 0;      // rdf_member_mask: 0 = planned (rdf_member_plan.h), 1 = the probe from a copy of the table in LDS (a call it cannot serve is refused), 2 = the probe of the table in HBM
+    int64_t opt_member_slots = 0;     // ... slots of the LDS form (tests reach its capacity boundary with a few dozen keys); 0 = planned
+    int    opt_member_table_bits = kMemberDefaultBits;   // rdf_member_mask / rdf_first_occurrence: log2 of the most slots the table may have (a table that then cannot hold the keys is RDF_MEMORY_ERROR)
     int    opt_gb_partition = 3;    // hash GROUP BY: 3 = second generation (rdf_groupby.hip: stream / line-aligned scatter / table by max_groups, default), 4 = its partition path whatever max_groups says, 1 = rdf_groupby_sum on the first-generation histogram + scatter fallback where its range holds (A/B), 0 = one table in HBM
     // kernel timing (bench.py roofline leg)
     bool   timing = false;
@@ -2530,6 +2534,7 @@ rdf_status groupby_sum_fallback(const rdf_array* keys, const rdf_array* values, 
 #include "rdf_capi_sort_utf8.inc"
 #include "rdf_capi_colstats.inc"
 #include "rdf_capi_dict.inc"
+#include "rdf_capi_member.inc"
 #include "rdf_capi_groupby_multi.inc"
 #include "rdf_capi_window.inc"
 #include "rdf_capi_window_agg.inc"
@@ -2608,6 +2613,9 @@ rdf_status rdf_set_option(const char* name, int64_t value) {
     else if (strcmp(name, "stream_slab_bytes") == 0) g_ctx.opt_stream_slab = value;
     else if (strcmp(name, "uniques_route") == 0) g_ctx.opt_uniques_route = value == 1 ? 1 : 0;
     else if (strcmp(name, "percentile_route") == 0) g_ctx.opt_percentile_route = value == 1 || value == 2 ? (int)value : 0;
+    else if (strcmp(name, "member_route") == 0) g_ctx.opt_member_route = value >= 0 && value <= 2 ? (int)value : 0;
+    else if (strcmp(name, "member_slots") == 0) g_ctx.opt_member_slots = value > 0 ? value : 0;
+    else if (strcmp(name, "member_table_bits") == 0) g_ctx.opt_member_table_bits = value <= 0 ? kMemberDefaultBits : member_clamp_bits(value);
     else if (strcmp(name, "uniques_table_bits") == 0) g_ctx.opt_uniques_table_bits = value < 10 ? 10 : value > 32 ? 32 : (int)value;
     else return fail(RDF_INVALID_ARGUMENT, "unknown option %s", name);
     return RDF_OK;

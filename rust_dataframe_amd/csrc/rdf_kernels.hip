@@ -369,34 +369,7 @@ __global__ __launch_bounds__(kBlock) void take_kernel(const TakeArgs a) {
 // sort to indices (DataFrame::sort -> arrow::compute::lexsort_to_indices, src/dataframe.rs:194-214): the
 // order-preserving keys of a column are made here (sort_keys_kernel); the sort's digit passes are in rdf_sort.hip.
 
-__device__ __forceinline__ uint64_t sort_key_bits(const DevChunkCol& cc, int dt, int64_t e) {
-    switch (dt) {
-        case RDF_I8: return (uint8_t)(as_global<uint8_t>(cc.values)[e] ^ 0x80u);
-        case RDF_U8: return as_global<uint8_t>(cc.values)[e];
-        case RDF_I16: return (uint16_t)(as_global<uint16_t>(cc.values)[e] ^ 0x8000u);
-        case RDF_U16: return as_global<uint16_t>(cc.values)[e];
-        case RDF_I32: return as_global<uint32_t>(cc.values)[e] ^ 0x80000000u;
-        case RDF_U32: return as_global<uint32_t>(cc.values)[e];
-        case RDF_F32: { const uint32_t b = as_global<uint32_t>(cc.values)[e]; return (b & 0x80000000u) ? (uint32_t)~b : (b ^ 0x80000000u); }
-        case RDF_I64: return as_global<uint64_t>(cc.values)[e] ^ 0x8000000000000000ull;
-        case RDF_F64: { const uint64_t b = as_global<uint64_t>(cc.values)[e]; return (b >> 63) ? ~b : (b ^ 0x8000000000000000ull); }
-        default: return as_global<uint64_t>(cc.values)[e];
-    }
-}
-
-// The window functions' float keys (SortKeyArgs::canon_float): in key space -0.0 sits one below +0.0 and the NaNs lie
-// beyond the infinities at BOTH ends (sign bit set: below -inf).  -0.0 takes +0.0's key, every NaN the quiet NaN's.
-__device__ __forceinline__ uint64_t sort_key_canon(int dt, uint64_t k) {
-    if (dt == RDF_F64) {
-        if (k > 0xFFF0000000000000ull || k < 0x000FFFFFFFFFFFFFull) return 0xFFF8000000000000ull;
-        return k == 0x7FFFFFFFFFFFFFFFull ? 0x8000000000000000ull : k;
-    }
-    if (dt == RDF_F32) {
-        if (k > 0xFF800000ull || k < 0x007FFFFFull) return 0xFFC00000ull;
-        return k == 0x7FFFFFFFull ? 0x80000000ull : k;
-    }
-    return k;
-}
+// (sort_key_bits, sort_key_canon: rdf_common.hip.h — rdf_member.hip turns its keys into the same words)
 
 __global__ __launch_bounds__(kBlock) void sort_keys_kernel(const SortKeyArgs a, uint64_t width_mask) {
     uint64_t kmin = ~0ull, kmax = 0, rmin = ~0ull, rmax = 0;
