@@ -617,7 +617,9 @@ class Column {
         const rdf_array iv = indices->view();
         bool nullable = indices->validity != nullptr;
         for (auto& c : data_.chunks()) nullable |= c->validity != nullptr;
-        auto out = Array::make_out(data_type(), indices->length, nullable);
+        bool host = indices->host;   // a host-resident column taken by host-resident indices (a grouped call's first rows): the result is host-resident too
+        for (auto& c : data_.chunks()) host &= c->host;
+        auto out = Array::make_out(data_type(), indices->length, nullable, host);
         rdf_out ov = out->out_view(indices->length);
         check(rdf_take(cv.data(), (int64_t)cv.size(), &iv, &ov));
         out->length = ov.length;
@@ -2814,11 +2816,12 @@ class DataFrame {
             if (column_by_name(c.column).data_type() == DataType::Utf8) return take(lexsort_indices(criteria));
         std::vector<rdf_array> cols;
         std::vector<rdf_sort_options> opts;
+        bool host = true;   // host-resident criteria (the groups of a GROUP BY over a host-resident frame): the indices stay beside them
         for (auto& c : criteria) {
-            for (auto& a : column_by_name(c.column).data().chunks()) cols.push_back(a->view());
+            for (auto& a : column_by_name(c.column).data().chunks()) { cols.push_back(a->view()); host &= a->host; }
             opts.push_back(rdf_sort_options{c.descending ? 1 : 0, 0});
         }
-        auto idx = Array::make_out(DataType::UInt32, num_rows(), false);
+        auto idx = Array::make_out(DataType::UInt32, num_rows(), false, host);
         rdf_out ov = idx->out_view(num_rows());
         check(rdf_sort_to_indices(cols.data(), (int32_t)criteria.size(), (int64_t)num_chunks(), opts.data(), &ov));
         idx->length = ov.length;
@@ -3048,6 +3051,44 @@ class DataFrame {
         PercentileGroups r;
         check(rdf_groupby_percentile(groups.empty() ? nullptr : sk.keys.data(), (int32_t)groups.size(), &sk.keys[groups.size()], (int64_t)num_chunks(),
                                      calls.empty() ? nullptr : calls.data(), (int32_t)calls.size(), &orow, calls.empty() ? nullptr : ov.data(), &ocnt, &r.groups));
+        rows->length = orow.length;
+        counts->length = ocnt.length;
+        r.group_rows = rows;
+        r.counts = counts;
+        for (size_t c = 0; c < outs.size(); ++c) {
+            outs[c]->length = ov[c].length;
+            outs[c]->null_count = ov[c].null_count;
+            if (ov[c].null_count == 0) outs[c]->validity = nullptr;
+            r.outs.push_back(outs[c]);
+        }
+        return r;
+    }
+    // rdf_groupby_moments over columns of this frame: `groups` (0 .. 4 names) are the grouping columns, `x` the numeric column
+    // the statistics are of — or, with `y`, the first of the pair.  calls[c].stat is an rdf_stat without y, an rdf_costat with
+    // it.  -> the group count, the UInt32 row index of every group's first row (groups in ascending key order, NULL last),
+    // one Float64 array per call — NULL where the statistic is absent: no counted row, a sample form of one row, a ratio over
+    // M2 == 0 — and the Int64 count of counted rows per group.  The sort is over the grouping columns alone; a capacity of
+    // the rows always suffices: one call.
+    struct MomentGroups { int64_t groups = 0; ArrayRef group_rows, counts; std::vector<ArrayRef> outs; };
+    MomentGroups moment_groups(const std::vector<std::string>& groups, const std::string& x, const std::string* y, const std::vector<rdf_group_stat_call>& calls) const {
+        const bool host = numeric_columns_on_host();
+        std::vector<SortCriteria> crit;
+        for (auto& g : groups) crit.push_back(SortCriteria{g, false, false});
+        const SortKeys sk = sort_keys(crit, host);
+        const std::vector<rdf_array> xv = column_by_name(x).data().views();
+        const std::vector<rdf_array> yv = y ? column_by_name(*y).data().views() : std::vector<rdf_array>();
+        const int64_t cap = groups.empty() ? std::min<int64_t>(1, (int64_t)num_rows()) : (int64_t)num_rows();   // no grouping columns: one row
+        auto rows = Array::make_out(DataType::UInt32, cap, false, host), counts = Array::make_out(DataType::Int64, cap, false, host);
+        rdf_out orow = rows->out_view(cap), ocnt = counts->out_view(cap);
+        std::vector<std::shared_ptr<Array>> outs;
+        std::vector<rdf_out> ov;
+        for (size_t c = 0; c < calls.size(); ++c) {
+            outs.push_back(Array::make_out(DataType::Float64, cap, true, host));
+            ov.push_back(outs.back()->out_view(cap));
+        }
+        MomentGroups r;
+        check(rdf_groupby_moments(groups.empty() ? nullptr : sk.keys.data(), (int32_t)groups.size(), xv.data(), y ? yv.data() : nullptr, (int64_t)num_chunks(),
+                                  calls.empty() ? nullptr : calls.data(), (int32_t)calls.size(), &orow, calls.empty() ? nullptr : ov.data(), &ocnt, nullptr, 0, &r.groups));
         rows->length = orow.length;
         counts->length = ocnt.length;
         r.group_rows = rows;
@@ -4427,6 +4468,47 @@ class Evaluate {
         }
         return DataFrame::from_columns(std::move(out_cols));
     }
+    // Variance, stddev, skewness, kurtosis (and the mean) per group, eager: the grouping columns — 0 .. 4 of them, integer,
+    // float or Utf8, gathered through the groups' first rows — then one nullable Float64 column per statistic (rdf_stat), named
+    // mean(x), var_pop(x), var_samp(x), stddev_pop(x), stddev_samp(x), skewness(x), kurtosis(x).  ONE rdf_groupby_moments call,
+    // whose sort is over the grouping columns alone.  Rows ordered by the grouping columns, the NULL group last; a statistic
+    // that is absent (no non-NULL x, a sample form of one row, skewness / kurtosis of a constant group) is NULL.
+    static DataFrame group_moments(const DataFrame& frame, const std::vector<std::string>& groups, const std::string& value, const std::vector<int32_t>& stats) {
+        static const char* names[] = {"mean", "var_pop", "var_samp", "stddev_pop", "stddev_samp", "skewness", "kurtosis"};
+        std::vector<std::string> cols;
+        for (int32_t st : stats) {
+            if (st < RDF_STAT_MEAN || st > RDF_STAT_KURTOSIS) throw DataFrameError(DataFrameError::ComputeError, "group_moments: unknown statistic " + std::to_string(st));
+            cols.push_back(std::string(names[st]) + "(" + value + ")");
+        }
+        return group_moments_frame(frame, groups, value, nullptr, stats, cols, "group_moments");
+    }
+    // covar_pop / covar_samp / corr of (x, y) per group (rdf_costat): as group_moments; a row counts when both values are not
+    // NULL.  The columns are covar_pop(x, y), covar_samp(x, y), corr(x, y).
+    static DataFrame group_comoments(const DataFrame& frame, const std::vector<std::string>& groups, const std::string& x, const std::string& y,
+                                     const std::vector<int32_t>& costats) {
+        static const char* names[] = {"covar_pop", "covar_samp", "corr"};
+        std::vector<std::string> cols;
+        for (int32_t st : costats) {
+            if (st < RDF_COSTAT_COVAR_POP || st > RDF_COSTAT_CORR) throw DataFrameError(DataFrameError::ComputeError, "group_comoments: unknown statistic " + std::to_string(st));
+            cols.push_back(std::string(names[st]) + "(" + x + ", " + y + ")");
+        }
+        return group_moments_frame(frame, groups, x, &y, costats, cols, "group_comoments");
+    }
+    static DataFrame group_moments_frame(const DataFrame& frame, const std::vector<std::string>& groups, const std::string& x, const std::string* y,
+                                         const std::vector<int32_t>& stats, const std::vector<std::string>& cols, const char* what) {
+        if (groups.size() > RDF_MAX_GROUP_KEYS) throw DataFrameError(DataFrameError::ComputeError, std::string(what) + ": at most " + std::to_string(RDF_MAX_GROUP_KEYS) + " grouping columns");
+        if (stats.empty() || stats.size() > RDF_GROUP_MOMENTS_MAX_CALLS) throw DataFrameError(DataFrameError::ComputeError, std::string(what) + ": 1.." + std::to_string(RDF_GROUP_MOMENTS_MAX_CALLS) + " statistics");
+        std::vector<rdf_group_stat_call> calls;
+        for (int32_t st : stats) calls.push_back(rdf_group_stat_call{st, 0});
+        const DataFrame::MomentGroups g = frame.moment_groups(groups, x, y, calls);
+        std::vector<Column> out_cols;
+        for (auto& n : groups) {
+            const Column& kc = frame.column_by_name(n);
+            out_cols.push_back(Column::from_arrays(kc.take(g.group_rows, 4096).data().chunks(), Field{n, kc.data_type(), true}));
+        }
+        for (size_t c = 0; c < calls.size(); ++c) out_cols.push_back(Column::from_arrays({g.outs[c]}, Field{cols[c], DataType::Float64, true}));
+        return DataFrame::from_columns(std::move(out_cols));
+    }
     // GROUP BY, eager, over 1..4 grouping columns of which each is an integer or a Utf8 column: the grouping columns, then one
     // column per (aggregation, input column), named and typed as Dataset::try_aggregate plans them; rows ordered by the
     // grouping columns, text in byte order, the NULL group last.  Integer columns only: the GroupAggregate step of a plan,
@@ -4597,6 +4679,47 @@ class Evaluate {
         out_cols.push_back(Column::from_arrays(vc.take(g.outs[0], 4096).data().chunks(), Field{std::string(fn == AF::First ? "first(" : "last(") + col + ")", vc.data_type(), true}));
     }
 
+    // Variance / StdDev / Skewness / Kurtosis of one column per group: ONE rdf_groupby_moments call per value column, carrying
+    // every such statistic the step asks of it (`done` keeps the calls made), whose groups come in ascending key order with
+    // the NULL group last — the order every other aggregate column of the step is put into, so the rows line up.  The sample
+    // forms apply, as in AggregateFunctions::variance / stddev; the columns are variance(x), stddev(x), skewness(x),
+    // kurtosis(x), Float64, NULL where the statistic is absent.
+    static bool moment_function(plan::AggregateFunction fn) {
+        using AF = plan::AggregateFunction;
+        return fn == AF::Variance || fn == AF::StdDev || fn == AF::Skewness || fn == AF::Kurtosis;
+    }
+    struct MomentCalls { std::string col; std::vector<plan::AggregateFunction> fns; DataFrame::MomentGroups g; };
+    static void append_moment_aggregate(const DataFrame& f, const plan::Transformation& t, plan::AggregateFunction fn, const std::string& col,
+                                        std::vector<MomentCalls>& done, std::vector<Column>& out_cols) {
+        using AF = plan::AggregateFunction;
+        auto stat_of = [](AF a) { return a == AF::Variance ? RDF_STAT_VAR_SAMP : a == AF::StdDev ? RDF_STAT_STDDEV_SAMP : a == AF::Skewness ? RDF_STAT_SKEWNESS : RDF_STAT_KURTOSIS; };
+        size_t at = 0;
+        while (at < done.size() && done[at].col != col) ++at;
+        if (at == done.size()) {
+            const DataType vdt = f.column_by_name(col).data_type();
+            if (!(is_integer(vdt) || is_float(vdt))) throw DataFrameError(DataFrameError::ComputeError, "Aggregating column must be numeric");
+            MomentCalls m;
+            m.col = col;
+            for (auto& a : t.aggregations)
+                if (moment_function(a.function) && std::find(a.columns.begin(), a.columns.end(), col) != a.columns.end() &&
+                    std::find(m.fns.begin(), m.fns.end(), a.function) == m.fns.end())
+                    m.fns.push_back(a.function);
+            std::vector<rdf_group_stat_call> calls;
+            for (AF a : m.fns) calls.push_back(rdf_group_stat_call{stat_of(a), 0});
+            m.g = f.moment_groups(t.names, col, nullptr, calls);
+            done.push_back(std::move(m));
+        }
+        const MomentCalls& m = done[at];
+        if (out_cols.empty())
+            for (auto& n : t.names) {
+                const Column& kc = f.column_by_name(n);
+                out_cols.push_back(Column::from_arrays(kc.take(m.g.group_rows, 4096).data().chunks(), Field{n, kc.data_type(), true}));
+            }
+        const size_t c = (size_t)(std::find(m.fns.begin(), m.fns.end(), fn) - m.fns.begin());
+        const char* name = fn == AF::Variance ? "variance(" : fn == AF::StdDev ? "stddev(" : fn == AF::Skewness ? "skewness(" : "kurtosis(";
+        out_cols.push_back(Column::from_arrays({m.g.outs[c]}, Field{std::string(name) + col + ")", DataType::Float64, true}));
+    }
+
     // A step with two or more hash aggregations (Sum / Min / Max / Count / Avg) over a device-resident frame: ONE
     // rdf_groupby_multi call — the keys prepared and hashed once, every aggregate folded into one table, all outputs in one
     // group order — and ONE sort of the groups for all columns, instead of a hash GROUP BY and a sort per aggregation.  Avg
@@ -4761,8 +4884,10 @@ class Evaluate {
         }
         std::vector<Column> out_cols;
         if (group_aggregate_multi(f, t, kcs, on_host, out_cols)) return DataFrame::from_columns(out_cols);   // two or more hash aggregations: one call, one sort
+        std::vector<MomentCalls> moment_calls;
         auto one = [&](AF fn, const std::string& col) {
             if (fn == AF::CountDistinct || fn == AF::First || fn == AF::Last) { append_sorted_aggregate(f, t.names, fn, col, out_cols); return; }
+            if (moment_function(fn)) { append_moment_aggregate(f, t, fn, col, moment_calls, out_cols); return; }
             if (fn != AF::Sum && fn != AF::Count && fn != AF::Avg && fn != AF::Min && fn != AF::Max) throw DataFrameError(DataFrameError::ComputeError, "Aggregation not yet supported");
             const Column& vc = f.column_by_name(col);
             const DataType vdt = vc.data_type();
@@ -4864,8 +4989,10 @@ class Evaluate {
         if (group_aggregate_multi(f, t, kcs, f.is_host(), out_cols)) { reset(DataFrame::from_columns(out_cols)); return; }   // two or more hash aggregations: one call, one sort
         // Sparse or NULL-holding keys: one rdf_groupby_agg per aggregation (hash GROUP BY; several grouping columns are
         // range-compressed into one 64-bit key on the device), results ordered by the grouping columns
+        std::vector<MomentCalls> moment_calls;
         auto one = [&](AF fn, const std::string& col) {
             if (fn == AF::CountDistinct || fn == AF::First || fn == AF::Last) { append_sorted_aggregate(f, t.names, fn, col, out_cols); return; }
+            if (moment_function(fn)) { append_moment_aggregate(f, t, fn, col, moment_calls, out_cols); return; }
             if (fn != AF::Sum && fn != AF::Count && fn != AF::Avg && fn != AF::Min && fn != AF::Max) throw DataFrameError(DataFrameError::ComputeError, "Aggregation not yet supported");
             const Column& vc = f.column_by_name(col);
             const DataType vdt = vc.data_type();

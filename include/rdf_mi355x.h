@@ -1147,6 +1147,53 @@ rdf_status rdf_groupby_sorted(const rdf_sort_key* group_by, int32_t ngroup, cons
                               const rdf_group_call* calls, int32_t ncalls, rdf_out* out_group_rows, rdf_out* outs,
                               int64_t* out_groups);
 
+/* ------------------------------------------------------------------ moments per group: variance, stddev, skewness, kurtosis, covar, corr */
+
+/* Up to 8 statistics of ONE value column x — or of ONE pair (x, y) — per group of 0 .. 4 grouping keys: the grouped form of
+ * rdf_moments / rdf_comoments (AggregateFunction::Variance / StdDev / Skewness / Kurtosis per group).  ONE sort over the
+ * grouping keys alone, then one moment state per group, then the statistics read off the states.
+ *
+ * Keys, groups, their order (ascending, NULL last, floats canonical), out_group_rows, memory kinds, the 2^32 row limit, the
+ * sizing rule and the count-only call (out_group_rows == NULL, ncalls == 0, out_counts == NULL, out_states == NULL) are
+ * rdf_groupby_sorted's: any given capacity below the group count is RDF_MEMORY_ERROR with nothing written and the group
+ * count in *out_groups and every length.  group_by takes 0 .. 4 keys, each numeric or Utf8; ngroup == 0 makes all rows one
+ * group.
+ *   - x is nchunks numeric chunks of any of the ten dtypes, every value converted `as f64` like rdf_moments.  y is NULL, or
+ *     nchunks numeric chunks of the same lengths; its dtype may differ from x's.  A row counts when its x is valid, and with
+ *     y given when both are valid.  There is no mask argument: a caller filters first.  x is NULL exactly when nothing but
+ *     the key tuples is asked for (ncalls == 0, out_counts == NULL, out_states == NULL).
+ *   - calls[c].stat is an rdf_stat when y == NULL and an rdf_costat otherwise.  outs[c] is RDF_F64, one entry per group, and
+ *     a validity bitmap is REQUIRED for every call: a statistic is absent without any NULL input (VAR_SAMP of one row,
+ *     SKEWNESS with M2 == 0).  "Absent" is exactly out_is_some == 0 of rdf_moments_stat / rdf_comoments_stat on the
+ *     group's state; the value under a NULL is 0 and null_count is set.
+ *   - A group whose rows all fail to count still appears: count 0, the all-zero state, every statistic NULL.  A non-finite
+ *     counted value makes every statistic of THAT group NaN (valid, not NULL); other groups are untouched.
+ *   - out_counts (optional, RDF_I64): the counted rows per group.
+ *   - out_states (optional): one rdf_moments_state (y == NULL) or rdf_comoments_state per group, in group order, in the
+ *     memory kind of the inputs; states_capacity counts states and follows the sizing rule.  They are what
+ *     rdf_moments_merge / rdf_comoments_merge combine across shards and what rdf_*_stat read.  ncalls == 0 with out_states
+ *     or out_counts given is valid.
+ *   - Accuracy: every group's state is held to rdf_moments' bound with n the GROUP's count: the per-group sums
+ *     of x and x^2 are never formed.
+ *   - Determinism: no float atomics, no block waits for another.  Chunking, offsets, memory kind and repetition change no
+ *     byte of any output.  Row order inside a group is the summation order: a shuffle of the rows may change last bits,
+ *     inside the bound, never a count.
+ * Errors, all RDF_INVALID_ARGUMENT before any device work with nothing written, in this order: null out_groups; a bad key
+ * count or key list; a bad call count or call list; x missing while anything but the key tuples is asked for, or x given
+ * with nothing asked (y without x included); an unknown stat for the form; the keys' own rules (rdf_groupby_sorted's); a
+ * non-numeric x / y or chunks of mixed dtypes; a wrong output dtype; a missing validity bitmap; a wrong out_counts /
+ * out_group_rows dtype; out_states with states_capacity < 0; mixed memory kinds.  Chunk lengths that differ between the
+ * columns are RDF_COMPUTE_ERROR.
+ * RDF_GROUP_MOMENTS_TILE is the sorted rows of one level-0 tile (rdf_group_moments.hip): tests place group boundaries
+ * around its multiples. */
+#define RDF_GROUP_MOMENTS_MAX_CALLS 8
+#define RDF_GROUP_MOMENTS_TILE 256
+typedef struct { int32_t stat; int32_t reserved; } rdf_group_stat_call;   /* rdf_stat when y == NULL, rdf_costat otherwise */
+rdf_status rdf_groupby_moments(const rdf_sort_key* group_by, int32_t ngroup, const rdf_array* x, const rdf_array* y,
+                               int64_t nchunks, const rdf_group_stat_call* calls, int32_t ncalls, rdf_out* out_group_rows,
+                               rdf_out* outs, rdf_out* out_counts, void* out_states, int64_t states_capacity,
+                               int64_t* out_groups);
+
 /* ------------------------------------------------------------------ percentiles and median per group */
 
 /* Up to 8 percentiles of ONE value column per group of 0 .. 4 grouping keys, all from ONE sort over (grouping keys, value).

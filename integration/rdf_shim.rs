@@ -92,6 +92,9 @@ pub mod sys {
     #[repr(C)] #[derive(Clone, Copy)] pub struct rdf_group_call { pub fn_: i32, pub ignore_nulls: i32 }
     pub const RDF_GRP_COUNT_DISTINCT: i32 = 0; pub const RDF_GRP_SUM_DISTINCT: i32 = 1; pub const RDF_GRP_FIRST: i32 = 2; pub const RDF_GRP_LAST: i32 = 3;
     pub const RDF_GROUP_MAX_CALLS: i32 = 8;
+    // one call of rdf_groupby_moments: stat = RDF_STAT_* without y, RDF_COSTAT_* with y
+    #[repr(C)] #[derive(Clone, Copy)] pub struct rdf_group_stat_call { pub stat: i32, pub reserved: i32 }
+    pub const RDF_GROUP_MOMENTS_MAX_CALLS: i32 = 8; pub const RDF_GROUP_MOMENTS_TILE: i32 = 256;
     // one call of rdf_groupby_percentile: kind = RDF_PCT_*, p in [0, 1]; the median is { RDF_PCT_CONT, 0, 0.5 }
     #[repr(C)] #[derive(Clone, Copy)] pub struct rdf_percentile_call { pub kind: i32, pub reserved: i32, pub p: f64 }
     pub const RDF_PCT_CONT: i32 = 0; pub const RDF_PCT_DISC: i32 = 1; pub const RDF_PERCENTILE_MAX_CALLS: i32 = 8;
@@ -213,6 +216,10 @@ pub mod sys {
         pub fn rdf_groupby_sorted(group_by: *const rdf_sort_key, ngroup: i32, value: *const rdf_sort_key, nchunks: i64,
                                   calls: *const rdf_group_call, ncalls: i32, out_group_rows: *mut rdf_out, outs: *mut rdf_out,
                                   out_groups: *mut i64) -> i32;
+        // AggregateFunction::Variance / StdDev / Skewness / Kurtosis (and covar / corr) per group: one moment state per group
+        pub fn rdf_groupby_moments(group_by: *const rdf_sort_key, ngroup: i32, x: *const rdf_array, y: *const rdf_array, nchunks: i64,
+                                   calls: *const rdf_group_stat_call, ncalls: i32, out_group_rows: *mut rdf_out, outs: *mut rdf_out,
+                                   out_counts: *mut rdf_out, out_states: *mut c_void, states_capacity: i64, out_groups: *mut i64) -> i32;
         // percentile / median / percentile_disc per group (Spark's aggregates; aggregate.rs stops before them)
         pub fn rdf_groupby_percentile(group_by: *const rdf_sort_key, ngroup: i32, value: *const rdf_sort_key, nchunks: i64,
                                       calls: *const rdf_percentile_call, ncalls: i32, out_group_rows: *mut rdf_out, outs: *mut rdf_out,

@@ -266,6 +266,14 @@ COSTAT_COVAR_POP, COSTAT_COVAR_SAMP, COSTAT_CORR = range(3)
 COSTATS = {"covar_pop": COSTAT_COVAR_POP, "covar_samp": COSTAT_COVAR_SAMP, "corr": COSTAT_CORR}
 
 
+class rdf_group_stat_call(C.Structure):
+    _fields_ = [("stat", C.c_int32), ("reserved", C.c_int32)]
+
+
+GROUP_MOMENTS_MAX_CALLS = 8
+GROUP_MOMENTS_TILE = 256   # RDF_GROUP_MOMENTS_TILE: the sorted rows of one level-0 tile of rdf_groupby_moments
+
+
 class rdf_exchange_stats(C.Structure):
     _fields_ = [("exchange", C.c_int32), ("rounds", C.c_int32), ("local_groups", C.c_int64), ("rows_sent", C.c_int64),
                 ("rows_sent_remote", C.c_int64), ("rows_received", C.c_int64), ("bytes_sent", C.c_int64),
@@ -2228,6 +2236,74 @@ class Api:
         if raw:
             return groups.value, rows_out, outs, counts_out
         return (groups.value, self._out_values(rows_out), [self.window_agg_to_numpy(o) for o in outs], self._out_values(counts_out))
+
+    # ---- moments per group: variance, stddev, skewness, kurtosis, covar, corr
+    def groupby_moments(self, group_by: Sequence, x, y=None, stats: Sequence = (), group_rows: bool = True, counts: bool = True,
+                        states: bool = False, outs=None, rows_out=None, counts_out=None, states_capacity: Optional[int] = None,
+                        raw: bool = False):
+        """rdf_groupby_moments: group_by = [chunks, ...] (0 .. 4 numeric or Utf8 columns), x = chunks of ONE numeric column
+        (None when only the key tuples are asked for), y = None or chunks of a second numeric column, stats = names of STATS
+        (without y) or COSTATS (with y), or their numbers.  Groups come in ascending key order, NULL last.
+        -> (groups, group_rows, results, counts, states): the number of groups, the UInt32 row index of every group's first
+        row (None with group_rows=False), per statistic the pair (Float64 values, valid), the Int64 count of counted rows per
+        group (None with counts=False) and, with states=True, a ctypes array of one rdf_moments_state / rdf_comoments_state
+        per group (else None).  Without `outs` / `rows_out` / `counts_out` / `states_capacity` the buffers hold one entry per
+        row, which always suffices; raw=True returns the output arrays as they are."""
+        cols = list(group_by) + [c for c in (x, y) if c is not None]
+        gk, keep_g = self._sort_keys(group_by)
+        nchunks = len(cols[0]) if cols else 0
+        n = sum(c.length for c in cols[0]) if cols else 0
+        device = any(isinstance(c, (DeviceArray, DeviceUtf8)) for k in cols for c in k)
+        names = COSTATS if y is not None else STATS
+        cc = (rdf_group_stat_call * max(1, len(stats)))()
+        for i, st in enumerate(stats):
+            cc[i] = rdf_group_stat_call(names[st] if isinstance(st, str) else int(st), 0)
+        cx = _flat([x], nchunks) if x is not None else None
+        cy = _flat([y], nchunks) if y is not None else None
+        if outs is None:
+            outs = [self._window_out(F64, n, device, True) for _ in stats]
+        if rows_out is None and group_rows:
+            rows_out = self._window_out(U32, n, device, False)
+        if counts_out is None and counts and x is not None:
+            counts_out = self._window_out(I64, n, device, False)
+        state_t = rdf_comoments_state if y is not None else rdf_moments_state
+        cap = n if states_capacity is None else int(states_capacity)
+        sbuf = sptr = None
+        if states:
+            if device:
+                import torch
+                sbuf = torch.zeros(max(1, cap) * C.sizeof(state_t), dtype=torch.uint8, device="cuda")
+                sptr = C.c_void_p(sbuf.data_ptr())
+            else:
+                sbuf = (state_t * max(1, cap))()
+                sptr = C.cast(sbuf, C.c_void_p)
+        carr = (rdf_out * max(1, len(outs)))(*[o.out_struct() for o in outs])
+        crow = (rdf_out * 1)(rows_out.out_struct()) if rows_out is not None else None
+        ccnt = (rdf_out * 1)(counts_out.out_struct()) if counts_out is not None else None
+        groups = C.c_int64(-1)
+        fn = self._fn("groupby_moments")
+        fn.restype = C.c_int
+        try:
+            self._check(fn(gk if group_by else None, C.c_int32(len(group_by)), cx, cy, C.c_int64(nchunks),
+                           cc if len(stats) else None, C.c_int32(len(stats)), crow, carr if len(stats) else None, ccnt,
+                           sptr, C.c_int64(cap if states else 0), C.byref(groups)))
+        finally:
+            self._finish(outs, carr)
+            if rows_out is not None:
+                self._finish([rows_out], crow)
+            if counts_out is not None:
+                self._finish([counts_out], ccnt)
+            self.last_groups = groups.value
+        got = None
+        if states:
+            g = groups.value
+            if device:
+                got = (state_t * g).from_buffer_copy(sbuf[:g * C.sizeof(state_t)].cpu().numpy().tobytes()) if g else (state_t * 0)()
+            else:
+                got = (state_t * g).from_buffer_copy(bytes(sbuf)[:g * C.sizeof(state_t)])
+        if raw:
+            return groups.value, rows_out, outs, counts_out, got
+        return (groups.value, self._out_values(rows_out), [self.window_agg_to_numpy(o) for o in outs], self._out_values(counts_out), got)
 
     # ---- collect per group and explode: collect_list / collect_set / explode
     @staticmethod

@@ -36,6 +36,7 @@
 #include "rdf_window_agg.h"
 #include "rdf_moments.h"
 #include "rdf_group_sorted.h"
+#include "rdf_group_moments.h"
 #include "rdf_percentile.h"
 #include "rdf_collect.h"
 #include "rdf_datetime.h"
@@ -2538,6 +2539,7 @@ rdf_status groupby_sum_fallback(const rdf_array* keys, const rdf_array* values, 
 #include "rdf_capi_groupby_multi.inc"
 #include "rdf_capi_window.inc"
 #include "rdf_capi_window_agg.inc"
+#include "rdf_capi_group_moments.inc"
 #include "rdf_capi_moments.inc"
 #include "rdf_capi_group_sorted.inc"
 #include "rdf_capi_percentile.inc"

@@ -126,37 +126,14 @@ rdf_status rdf_comoments_merge(rdf_comoments_state* into, const rdf_comoments_st
 rdf_status rdf_moments_stat(const rdf_moments_state* s, int32_t stat, double* out, int32_t* out_is_some) {
     if (!s || !out || !out_is_some) return fail(RDF_INVALID_ARGUMENT, "moments_stat: null pointer");
     if (stat < RDF_STAT_MEAN || stat > RDF_STAT_KURTOSIS) return fail(RDF_INVALID_ARGUMENT, "moments_stat: unknown statistic %d", stat);
-    *out_is_some = 0;
-    const double n = (double)s->count;
-    const bool samp = stat == RDF_STAT_VAR_SAMP || stat == RDF_STAT_STDDEV_SAMP;
-    if (s->count <= 0 || (samp && s->count < 2)) return RDF_OK;
-    if ((stat == RDF_STAT_SKEWNESS || stat == RDF_STAT_KURTOSIS) && s->m2 == 0.0) return RDF_OK;
-    switch (stat) {
-        case RDF_STAT_MEAN: *out = s->mean + s->mean_lo; break;
-        case RDF_STAT_VAR_POP: *out = s->m2 / n; break;
-        case RDF_STAT_VAR_SAMP: *out = s->m2 / (n - 1.0); break;
-        case RDF_STAT_STDDEV_POP: *out = std::sqrt(s->m2 / n); break;
-        case RDF_STAT_STDDEV_SAMP: *out = std::sqrt(s->m2 / (n - 1.0)); break;
-        case RDF_STAT_SKEWNESS: *out = std::sqrt(n) * s->m3 / (s->m2 * std::sqrt(s->m2)); break;
-        default: *out = n * s->m4 / (s->m2 * s->m2) - 3.0; break;
-    }
-    *out_is_some = 1;
+    *out_is_some = mo_stat(*s, stat, out) ? 1 : 0;
     return RDF_OK;
 }
 
 rdf_status rdf_comoments_stat(const rdf_comoments_state* s, int32_t stat, double* out, int32_t* out_is_some) {
     if (!s || !out || !out_is_some) return fail(RDF_INVALID_ARGUMENT, "comoments_stat: null pointer");
     if (stat < RDF_COSTAT_COVAR_POP || stat > RDF_COSTAT_CORR) return fail(RDF_INVALID_ARGUMENT, "comoments_stat: unknown statistic %d", stat);
-    *out_is_some = 0;
-    const double n = (double)s->count;
-    if (s->count <= 0 || (stat == RDF_COSTAT_COVAR_SAMP && s->count < 2)) return RDF_OK;
-    if (stat == RDF_COSTAT_CORR && (s->m2x == 0.0 || s->m2y == 0.0)) return RDF_OK;
-    switch (stat) {
-        case RDF_COSTAT_COVAR_POP: *out = s->cxy / n; break;
-        case RDF_COSTAT_COVAR_SAMP: *out = s->cxy / (n - 1.0); break;
-        default: *out = s->cxy / std::sqrt(s->m2x * s->m2y); break;
-    }
-    *out_is_some = 1;
+    *out_is_some = mo_costat(*s, stat, out) ? 1 : 0;
     return RDF_OK;
 }
 
