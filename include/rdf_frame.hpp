@@ -25,6 +25,7 @@
 #include <fstream>
 #include <iterator>
 #include <functional>
+#include <limits>
 #include <map>
 #include <memory>
 #include <optional>
@@ -37,6 +38,7 @@
 #include <unistd.h>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <utility>
 #include <variant>
 #include <vector>
@@ -3158,8 +3160,38 @@ class DataFrame {
         // The frame, in the reference's spelling (src/window.rs): unbounded_preceding / unbounded_following, 0 = current_row, a
         // negative number = that many rows preceding, a positive one = following.  range_between takes no offsets.
         static constexpr int64_t unbounded_preceding = INT64_MIN, current_row = 0, unbounded_following = INT64_MAX;
-        WindowSpec& rows_between(int64_t start, int64_t end) { frame_ = make_frame(RDF_FRAME_ROWS, start, end); return *this; }
-        WindowSpec& range_between(int64_t start, int64_t end) { frame_ = make_frame(RDF_FRAME_RANGE, start, end); return *this; }
+        WindowSpec& rows_between(int64_t start, int64_t end) { frame_ = make_frame(RDF_FRAME_ROWS, start, end); by_ = 0; return *this; }
+        WindowSpec& range_between(int64_t start, int64_t end) { frame_ = make_frame(RDF_FRAME_RANGE, start, end); by_ = 0; return *this; }
+        // RANGE BETWEEN with offsets in the ORDER KEY's units (Spark's rangeBetween over a numeric column): range_by(-7, 0) over a
+        // day-number column is a rolling 7-day frame.  rows_between's sign convention; the integer form is for Int32 / Int64 order
+        // columns (dates and timestamps as their storage) and takes the unbounded_* sentinels, the double form is for Float64
+        // ones: finite offsets, -infinity / +infinity = unbounded preceding / following (a double has no spare sentinel, and the
+        // C ABI itself refuses an infinite OFFSET: here an infinity is never an offset, it names the unbounded kind).  Exactly one order column; with_window_agg sends such a spec through rdf_window_range_agg.
+        WindowSpec& range_by(int64_t start, int64_t end) {
+            const rdf_window_frame f = make_frame(RDF_FRAME_RANGE, start, end);
+            range_ = rdf_window_range_frame{f.start_kind, f.end_kind, f.start, f.end, 0.0, 0.0};
+            by_ = 1;
+            return *this;
+        }
+        WindowSpec& range_by(double start, double end) {
+            auto bound = [](double b, int32_t* kind, double* off) {
+                *off = 0.0;
+                if (b == -std::numeric_limits<double>::infinity()) *kind = RDF_BOUND_UNBOUNDED_PRECEDING;
+                else if (b == std::numeric_limits<double>::infinity()) *kind = RDF_BOUND_UNBOUNDED_FOLLOWING;
+                else if (b == 0.0) *kind = RDF_BOUND_CURRENT_ROW;
+                else { *kind = b < 0.0 ? RDF_BOUND_PRECEDING : RDF_BOUND_FOLLOWING; *off = b < 0.0 ? -b : b; }   // (a NaN offset stays NaN and is refused by the library)
+            };
+            range_ = rdf_window_range_frame{0, 0, 0, 0, 0.0, 0.0};
+            bound(start, &range_.start_kind, &range_.start_f);
+            bound(end, &range_.end_kind, &range_.end_f);
+            by_ = 2;
+            return *this;
+        }
+        template <class A, class B, class = typename std::enable_if<std::is_integral<A>::value && std::is_integral<B>::value &&
+                                                                     !(std::is_same<A, int64_t>::value && std::is_same<B, int64_t>::value)>::type>
+        WindowSpec& range_by(A start, B end) { return range_by((int64_t)start, (int64_t)end); }   // (int literals: not ambiguous between the two forms)
+        int range_by_form() const { return by_; }      // 0: no range_by frame, 1: integer offsets, 2: double offsets
+        const rdf_window_range_frame& range_frame() const { return range_; }
         const std::vector<std::string>& partition() const { return partition_; }
         const std::vector<SortCriteria>& order() const { return order_; }
         // no frame set: SQL's default, RANGE BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW
@@ -3181,6 +3213,8 @@ class DataFrame {
         std::vector<std::string> partition_;
         std::vector<SortCriteria> order_;
         rdf_window_frame frame_{RDF_FRAME_RANGE, RDF_BOUND_UNBOUNDED_PRECEDING, RDF_BOUND_CURRENT_ROW, 0, 0, 0};
+        rdf_window_range_frame range_{RDF_BOUND_UNBOUNDED_PRECEDING, RDF_BOUND_CURRENT_ROW, 0, 0, 0.0, 0.0};
+        int by_ = 0;
     };
     enum class WindowAggregate : int32_t {
         Sum = RDF_WAGG_SUM, Min = RDF_WAGG_MIN, Max = RDF_WAGG_MAX, Count = RDF_WAGG_COUNT, Avg = RDF_WAGG_AVG,
@@ -3244,10 +3278,22 @@ class DataFrame {
         const bool nullable = fn != WindowAggregate::Count;
         auto out = Array::make_out(dt, num_rows(), nullable, host);
         rdf_out ov = out->out_view(num_rows());
-        const rdf_window_agg_call call{(int32_t)fn, reads ? 0 : -1, spec.frame()};
-        const bool keyed = !pk.keys.empty() || !ok.keys.empty() || reads;
-        check(rdf_window_agg(pk.keys.empty() ? nullptr : pk.keys.data(), (int32_t)pk.keys.size(), ok.keys.empty() ? nullptr : ok.keys.data(),
-                             (int32_t)ok.keys.size(), reads ? &vptr : nullptr, reads ? 1 : 0, (int64_t)num_chunks(), keyed ? 0 : num_rows(), &call, 1, &ov));
+        if (spec.range_by_form() != 0) {                    // offsets in the order key's units: one numeric order column of the form's type
+            if (spec.order().size() != 1) throw DataFrameError(DataFrameError::ComputeError, "with_window_agg: range_by needs exactly one order column");
+            const DataType kdt = column_by_name(spec.order()[0].column).data_type();
+            const bool fits = spec.range_by_form() == 1 ? (kdt == DataType::Int32 || kdt == DataType::Int64) : kdt == DataType::Float64;
+            if (!fits) throw DataFrameError(DataFrameError::ComputeError, std::string("with_window_agg: range_by with ") +
+                                            (spec.range_by_form() == 1 ? "integer offsets needs an Int32 / Int64" : "double offsets needs a Float64") +
+                                            " order column, not " + type_name(kdt));
+            const rdf_window_range_call rcall{(int32_t)fn, reads ? 0 : -1, spec.range_frame()};
+            check(rdf_window_range_agg(pk.keys.empty() ? nullptr : pk.keys.data(), (int32_t)pk.keys.size(), ok.keys.data(), 1,
+                                       reads ? &vptr : nullptr, reads ? 1 : 0, (int64_t)num_chunks(), &rcall, 1, &ov));
+        } else {
+            const rdf_window_agg_call call{(int32_t)fn, reads ? 0 : -1, spec.frame()};
+            const bool keyed = !pk.keys.empty() || !ok.keys.empty() || reads;
+            check(rdf_window_agg(pk.keys.empty() ? nullptr : pk.keys.data(), (int32_t)pk.keys.size(), ok.keys.empty() ? nullptr : ok.keys.data(),
+                                 (int32_t)ok.keys.size(), reads ? &vptr : nullptr, reads ? 1 : 0, (int64_t)num_chunks(), keyed ? 0 : num_rows(), &call, 1, &ov));
+        }
         out->length = ov.length;
         out->null_count = ov.null_count;
         ArrayRef whole = out;

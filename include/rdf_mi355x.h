@@ -1363,7 +1363,7 @@ rdf_status rdf_window(const rdf_sort_key* partition_by, int32_t npartition, cons
  *   ROWS   UNBOUNDED_PRECEDING 0;  PRECEDING s  k - s;  CURRENT_ROW k;  FOLLOWING s  k + s;  UNBOUNDED_FOLLOWING n - 1
  *   RANGE  the two unbounded kinds as above; CURRENT_ROW is f as a start and l as an end (SQL's default frame, RANGE
  *          BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW, is [0, l]).  RANGE with an offset: RDF_INVALID_ARGUMENT ("range
- *          offsets are not built").
+ *          offsets are not built"): an offset there has the order key's type, see rdf_window_range_agg below.
  * then a = max(a, 0), b = min(b, n - 1); the frame is empty when a > b.
  *
  * Results, with c = the valid (non-NULL) value rows of the frame — NULL rows are skipped:
@@ -1406,6 +1406,49 @@ typedef struct { int32_t fn; int32_t value; rdf_window_frame frame; } rdf_window
 rdf_status rdf_window_agg(const rdf_sort_key* partition_by, int32_t npartition, const rdf_sort_key* order_by, int32_t norder,
                           const rdf_array* const* values, int32_t nvalues, int64_t nchunks, int64_t nrows_if_no_keys,
                           const rdf_window_agg_call* calls, int32_t ncalls, rdf_out* outs);
+
+/* Window frames with VALUE offsets: RANGE BETWEEN s PRECEDING AND e FOLLOWING over ONE numeric order key (Spark's
+ * rangeBetween(-s, e), a rolling 7-day sum, "events within 500 us of this one").  rdf_window_agg refuses such frames; this
+ * entry point answers them, and every frame without an offset as rdf_window_agg's RANGE unit does.  Inherited unchanged:
+ * partitions (0 .. 4 keys, numeric or Utf8), peers and the float canonicalisation of the keys; chunk conventions, memory
+ * kinds, "outs[c] is one array in the original row order"; value dtypes (Int64 / Float64, up to 4 columns), up to 8 calls
+ * from ONE sort, output dtypes and validity rules; every function's result rules (NULL when no valid row, wrapping Int64
+ * sums, the double-double Float64 sum and its bound, MIN / MAX in IEEE total order, FIRST / LAST as row indices); zero
+ * rows, short capacities, the 2^32-row cap, the error codes, and "all refusals before any device work, nothing written".
+ *
+ * Order key: norder must be 1 and the key numeric, RDF_I32, RDF_I64 (dates, timestamps and times are passed as their
+ * storage) or RDF_F64; `descending` is honoured.  Anything else: RDF_INVALID_ARGUMENT.
+ * Bounds, in positions of the ordered partition of n rows (first / last peer of the row: f / l):
+ *   UNBOUNDED_PRECEDING 0;  UNBOUNDED_FOLLOWING n - 1 (the NULL and NaN rows at the partition's end included);
+ *   CURRENT_ROW f as a start, l as an end.
+ *   An offset bound of an ORDINARY row (key o not NULL and not NaN; the ordinary rows of a partition are one run of
+ *   positions: NULLs sort last, NaN after +inf, before it when descending).  With d = +1 ascending, -1 descending the bound
+ *   VALUE is v = o - d s for PRECEDING s and o + d s for FOLLOWING s.  A start is the first position of the run whose key is
+ *   not before v in the sort direction (none: one past the run's last position); an end is the last position of the run
+ *   whose key is not after v (none: one before the run's first position).  It never reaches a NULL or NaN row.
+ *     Integer keys (Int32 widens to Int64): v is the mathematical integer, no wrap; INT64_MIN with offset 2^63 - 1 is exact.
+ *     Float64 keys: v is ONE IEEE operation, fl(o - s) or fl(o + s), compared with the keys by IEEE < and > (-0.0 == +0.0):
+ *     with keys 0.1, 0.3 and offset 0.2, 0.1 lies in 0.3's frame iff 0.1 >= fl(0.3 - 0.2).  +-inf keys follow the arithmetic.
+ *   An offset bound of a NULL or NaN row: its own peer group, f as a start, l as an end (Spark's and PostgreSQL's rule).
+ * The frame is [a, b]; a > b is an empty frame: COUNT 0, the others NULL.
+ * Offsets: start_i / end_i (>= 0) are read when the order key is Int32 / Int64, start_f / end_f (finite, >= 0) when it is
+ * Float64, and only for PRECEDING / FOLLOWING.
+ * Refused with RDF_INVALID_ARGUMENT: the static frame errors of rdf_window_agg (a start of UNBOUNDED_FOLLOWING, an end of
+ * UNBOUNDED_PRECEDING, start kind > end kind, both PRECEDING with start < end, both FOLLOWING with start > end, unknown
+ * kinds), a negative integer offset, a Float64 offset that is negative, NaN or infinite, and MIN / MAX with neither side
+ * unbounded ("min / max over a range frame bounded on both sides is not built"; with one unbounded side they are the
+ * forward / backward scans' F[b] / B[a]).
+ * rdf_set_option("window_range_route", v) chooses how the bounds are searched: 0 = auto, 1 = a tile's key window is staged
+ * in LDS wherever it fits (what auto decides today as well: 0 and 1 behave alike until auto declines a window that fits),
+ * 2 = every lane searches the sorted keys in global memory; no value changes a byte of a result,
+ * and rdf_last_kernel() names wrange_bounds_lds_kernel / wrange_bounds_global_kernel as they were used. */
+typedef struct { int32_t start_kind, end_kind;      /* rdf_frame_bound */
+                 int64_t start_i, end_i;            /* offsets >= 0, read when the order key is Int32 / Int64 */
+                 double  start_f, end_f; } rdf_window_range_frame;   /* read when it is Float64; 40 bytes */
+typedef struct { int32_t fn; int32_t value; rdf_window_range_frame frame; } rdf_window_range_call;   /* rdf_window_agg_fn; 48 bytes */
+rdf_status rdf_window_range_agg(const rdf_sort_key* partition_by, int32_t npartition, const rdf_sort_key* order_by, int32_t norder,
+                                const rdf_array* const* values, int32_t nvalues, int64_t nchunks,
+                                const rdf_window_range_call* calls, int32_t ncalls, rdf_out* outs);
 
 /* ------------------------------------------------------------------ fused batch loop */
 
@@ -1681,6 +1724,8 @@ rdf_status rdf_fill_validity(uint8_t* dev_ptr, int64_t nbits, uint64_t seed, uin
  * "gb_compact" (scatter path, keys inside a window of 2^39: 1 = 4-byte records when only rows are counted, default; 2 = also
  * 12-byte records for sum / min / max; 0 = 16-byte records always), "gb_skew_plan" (1 = per-partition capacity plan when the probe finds a few heavy
  * partitions, default; 0 = the first-generation combining path instead; 2 = always),
+ * "window_range_route" (rdf_window_range_agg's bounds pass: 0 = auto, 1 = the LDS key window wherever it fits — today auto's own
+ * choice —, 2 = the global search for every tile; no value changes a result),
  * "take_rows" (rdf_take_frame / rdf_sort_frame: 1 = gather
  * interleaved row records when the index list is long and the frame wide, default; 0 = always column by column; 2 = always records),
  * "gb_hot" (skewed keys on the scatter path: 1 = the few dozen hash classes that hold the heavy hitters get a pass of their own — folded in

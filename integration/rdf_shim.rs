@@ -83,6 +83,11 @@ pub mod sys {
     #[repr(C)] #[derive(Clone, Copy)]
     pub struct rdf_window_frame { pub unit: i32, pub start_kind: i32, pub end_kind: i32, pub pad: i32, pub start: i64, pub end: i64 }
     #[repr(C)] #[derive(Clone, Copy)] pub struct rdf_window_agg_call { pub fn_: i32, pub value: i32, pub frame: rdf_window_frame }
+    // one call of rdf_window_range_agg: a RANGE frame whose offsets are in the order key's units (start_i / end_i for Int32 / Int64
+    // keys, start_f / end_f for Float64 keys; read for RDF_BOUND_PRECEDING / RDF_BOUND_FOLLOWING only)
+    #[repr(C)] #[derive(Clone, Copy)]
+    pub struct rdf_window_range_frame { pub start_kind: i32, pub end_kind: i32, pub start_i: i64, pub end_i: i64, pub start_f: f64, pub end_f: f64 }
+    #[repr(C)] #[derive(Clone, Copy)] pub struct rdf_window_range_call { pub fn_: i32, pub value: i32, pub frame: rdf_window_range_frame }
     pub const RDF_FRAME_ROWS: i32 = 0; pub const RDF_FRAME_RANGE: i32 = 1;
     pub const RDF_BOUND_UNBOUNDED_PRECEDING: i32 = 0; pub const RDF_BOUND_PRECEDING: i32 = 1; pub const RDF_BOUND_CURRENT_ROW: i32 = 2;
     pub const RDF_BOUND_FOLLOWING: i32 = 3; pub const RDF_BOUND_UNBOUNDED_FOLLOWING: i32 = 4;
@@ -238,6 +243,10 @@ pub mod sys {
         pub fn rdf_window_agg(partition_by: *const rdf_sort_key, npartition: i32, order_by: *const rdf_sort_key, norder: i32,
                               values: *const *const rdf_array, nvalues: i32, nchunks: i64, nrows_if_no_keys: i64,
                               calls: *const rdf_window_agg_call, ncalls: i32, outs: *mut rdf_out) -> i32;
+        // RANGE BETWEEN s PRECEDING AND e FOLLOWING over one Int32 / Int64 / Float64 order key (Spark's rangeBetween)
+        pub fn rdf_window_range_agg(partition_by: *const rdf_sort_key, npartition: i32, order_by: *const rdf_sort_key, norder: i32,
+                                    values: *const *const rdf_array, nvalues: i32, nchunks: i64,
+                                    calls: *const rdf_window_range_call, ncalls: i32, outs: *mut rdf_out) -> i32;
         pub fn rdf_equijoin_indices(left_keys: *const rdf_array, left_nchunks: i64, right_keys: *const rdf_array, right_nchunks: i64,
                                     join_type: i32, out_left: *mut rdf_out, out_right: *mut rdf_out, out_rows: *mut i64) -> i32;
         pub fn rdf_equijoin_indices_multi(left_keys: *const rdf_array, left_nchunks: i64, right_keys: *const rdf_array,
@@ -941,6 +950,44 @@ pub fn window_agg(partition_by: &[(Vec<&dyn Array>, bool)], order_by: &[(Vec<&dy
                                    if vptrs.is_empty() { std::ptr::null() } else { vptrs.as_ptr() }, vptrs.len() as i32,
                                    nchunks as i64, if np + no + values.len() == 0 { rows as i64 } else { 0 },
                                    ccalls.as_ptr(), ccalls.len() as i32, outs.as_mut_ptr()) })?;
+    Ok(bufs.into_iter().zip(outs.iter()).map(|(b, o)| b.finish(o)).collect())
+}
+
+/// window_agg over RANGE frames with VALUE offsets: `order_by` is ONE Int32 / Int64 (dates and timestamps as their storage) or
+/// Float64 column, `calls` are (RDF_WAGG_*, value column index or -1, frame) with the frame's offsets in that column's units — a
+/// rolling 7-day sum over a Date32 column is { RDF_BOUND_PRECEDING, RDF_BOUND_CURRENT_ROW, start_i: 7, .. }.  Results as window_agg's;
+/// MIN / MAX need one unbounded side.
+pub fn window_range_agg(partition_by: &[(Vec<&dyn Array>, bool)], order_by: &(Vec<&dyn Array>, bool), values: &[Vec<&dyn Array>], rows: usize,
+                        calls: &[(i32, i32, rdf_window_range_frame)]) -> Result<Vec<ArrayRef>, ArrowError> {
+    let nchunks = order_by.0.len();
+    let mut num: Vec<Vec<rdf_array>> = Vec::new();
+    let mut txt: Vec<Vec<rdf_utf8_array>> = Vec::new();
+    for (chunks, _) in partition_by.iter().chain(std::iter::once(order_by)) {
+        match chunks.first().map(|a| a.data_type()) {
+            Some(DataType::Utf8) => { txt.push(chunks.iter().map(|a| utf8_view(a.as_any().downcast_ref::<StringArray>().unwrap())).collect()); num.push(Vec::new()); }
+            _ => { num.push(chunks.iter().map(|a| view(*a)).collect()); txt.push(Vec::new()); }
+        }
+    }
+    let keys: Vec<rdf_sort_key> = partition_by.iter().chain(std::iter::once(order_by)).enumerate().map(|(k, (_, desc))| rdf_sort_key {
+        values: if num[k].is_empty() { std::ptr::null() } else { num[k].as_ptr() },
+        utf8: if txt[k].is_empty() { std::ptr::null() } else { txt[k].as_ptr() },
+        options: rdf_sort_options { descending: *desc as i32, nulls_first: 0 },
+    }).collect();
+    let vviews: Vec<Vec<rdf_array>> = values.iter().map(|v| v.iter().map(|a| view(*a)).collect()).collect();
+    let vptrs: Vec<*const rdf_array> = vviews.iter().map(|v| v.as_ptr()).collect();
+    let vtype = |i: i32| if i >= 0 { values[i as usize][0].data_type().clone() } else { DataType::Int64 };
+    let np = partition_by.len();
+    let ccalls: Vec<rdf_window_range_call> = calls.iter().map(|(f, v, fr)| rdf_window_range_call { fn_: *f, value: *v, frame: *fr }).collect();
+    let mut bufs: Vec<OutBuf> = calls.iter().map(|(f, v, _)| match *f {
+        RDF_WAGG_COUNT => OutBuf::new(DataType::Int64, rows, false),
+        RDF_WAGG_AVG => OutBuf::new(DataType::Float64, rows, true),
+        RDF_WAGG_FIRST_VALUE | RDF_WAGG_LAST_VALUE => OutBuf::new(DataType::UInt32, rows, true),
+        _ => OutBuf::new(vtype(*v), rows, true),
+    }).collect();
+    let mut outs: Vec<rdf_out> = bufs.iter_mut().map(|b| b.as_out()).collect();
+    status(unsafe { rdf_window_range_agg(if np > 0 { keys.as_ptr() } else { std::ptr::null() }, np as i32, keys[np..].as_ptr(), 1,
+                                         if vptrs.is_empty() { std::ptr::null() } else { vptrs.as_ptr() }, vptrs.len() as i32,
+                                         nchunks as i64, ccalls.as_ptr(), ccalls.len() as i32, outs.as_mut_ptr()) })?;
     Ok(bufs.into_iter().zip(outs.iter()).map(|(b, o)| b.finish(o)).collect())
 }
 

@@ -249,6 +249,37 @@ def window_frame(unit, start, end) -> rdf_window_frame:
     return rdf_window_frame({"rows": FRAME_ROWS, "range": FRAME_RANGE}[unit], sk, ek, 0, so, eo)
 
 
+class rdf_window_range_frame(C.Structure):
+    _fields_ = [("start_kind", C.c_int32), ("end_kind", C.c_int32), ("start_i", C.c_int64), ("end_i", C.c_int64),
+                ("start_f", C.c_double), ("end_f", C.c_double)]
+
+
+class rdf_window_range_call(C.Structure):
+    _fields_ = [("fn", C.c_int32), ("value", C.c_int32), ("frame", rdf_window_range_frame)]
+
+
+WINDOW_RANGE_TILE = 1024       # kWRangeTile of csrc/rdf_window_range.h: sorted positions per block of the bounds pass
+WINDOW_RANGE_LDS_KEYS = 4096   # kWRangeLdsKeys: the keys of a tile's window that are staged in LDS; a wider window is searched in global memory
+
+
+def window_range_frame(start, end) -> rdf_window_range_frame:
+    """(start, end) of a RANGE frame over one numeric order key: UNBOUNDED_PRECEDING / UNBOUNDED_FOLLOWING or a number in the key's
+    units, 0 = the current row, -s = s preceding, +s = s following; ints for Int32 / Int64 keys, floats for Float64 keys (both
+    fields are filled, the library reads the pair of the key's type).  A bound may also be spelled (kind, offset) with a
+    BOUND_* kind, which is how "0 PRECEDING" is said."""
+    def bound(b):
+        if isinstance(b, tuple):
+            kind, off = b
+        elif isinstance(b, str):
+            kind, off = {UNBOUNDED_PRECEDING: BOUND_UNBOUNDED_PRECEDING, UNBOUNDED_FOLLOWING: BOUND_UNBOUNDED_FOLLOWING}[b], 0
+        else:
+            kind, off = (BOUND_CURRENT_ROW, 0) if b == 0 else (BOUND_PRECEDING, -b) if b < 0 else (BOUND_FOLLOWING, b)
+        exact = isinstance(off, (int, np.integer)) or (float(off).is_integer() and abs(float(off)) < 2.0 ** 63)
+        return int(kind), (int(off) if exact else 0), float(off)
+    (sk, si, sf), (ek, ei, ef) = bound(start), bound(end)
+    return rdf_window_range_frame(sk, ek, si, ei, sf, ef)
+
+
 class rdf_moments_state(C.Structure):
     _fields_ = [("count", C.c_int64), ("mean", C.c_double), ("mean_lo", C.c_double), ("m2", C.c_double), ("m3", C.c_double), ("m4", C.c_double)]
 
@@ -2134,6 +2165,40 @@ class Api:
         self._check(fn(pk if partition_by else None, C.c_int32(len(partition_by)), ok if order_by else None, C.c_int32(len(order_by)),
                        vptr if values else None, C.c_int32(len(values)), C.c_int64(nchunks), C.c_int64(nrows),
                        cc if calls else None, C.c_int32(len(calls)), carr))
+        self._finish(outs, carr)
+        return outs if raw else [self.window_agg_to_numpy(o) for o in outs]
+
+    def window_range_agg(self, partition_by: Sequence, order_by: Sequence, values: Sequence, calls: Sequence, mem: Optional[str] = None,
+                         outs=None, raw: bool = False):
+        """rdf_window_range_agg: window_agg's functions over RANGE frames whose offsets are in the units of ONE numeric order
+        key (Int32 / Int64 / Float64): a rolling 7-day sum is ("sum", 0, (-7, 0)) over a day-number key.  calls = [(name, value
+        index, (start, end)), ...] in window_range_frame's spelling, or with an rdf_window_range_frame.  -> per call (values,
+        valid) as numpy in the original row order; raw=True returns the output arrays as they are."""
+        pk, keep_p = self._sort_keys(partition_by)
+        ok, keep_o = self._sort_keys(order_by)
+        cols = [k[0] if isinstance(k, tuple) else k for k in list(partition_by) + list(order_by)] + list(values)
+        nchunks = len(cols[0]) if cols else 0
+        n = sum(c.length for c in cols[0]) if cols else 0
+        device = mem == "device" if mem is not None else any(isinstance(c, (DeviceArray, DeviceUtf8)) for k in cols for c in k)
+        varrs = [(rdf_array * max(1, len(v)))(*[c.c_struct(getattr(c, "_unknown_nc", False)) for c in v]) for v in values]
+        vptr = (C.POINTER(rdf_array) * max(1, len(values)))(*[C.cast(a, C.POINTER(rdf_array)) for a in varrs])
+        cc = (rdf_window_range_call * max(1, len(calls)))()
+        for i, (name, value, frame) in enumerate(calls):
+            fr = frame if isinstance(frame, rdf_window_range_frame) else window_range_frame(*frame)
+            cc[i] = rdf_window_range_call(WINDOW_AGG_FNS[name] if isinstance(name, str) else int(name), int(value), fr)
+        if outs is None:
+            vdt = [v[0].dtype if len(v) else I64 for v in values]
+            outs = [self._window_out(window_agg_out_dtype(cc[i].fn, vdt[cc[i].value] if 0 <= cc[i].value < len(vdt) else I64), n, device,
+                                     cc[i].fn != WAGG_COUNT) for i in range(len(calls))]
+        carr = (rdf_out * max(1, len(outs)))(*[o.out_struct() for o in outs])
+        fn = self._fn("window_range_agg")
+        fn.restype = C.c_int
+        status = fn(pk if partition_by else None, C.c_int32(len(partition_by)), ok if order_by else None, C.c_int32(len(order_by)),
+                    vptr if values else None, C.c_int32(len(values)), C.c_int64(nchunks),
+                    cc if calls else None, C.c_int32(len(calls)), carr)
+        if status == RDF_MEMORY_ERROR:
+            self._finish(outs, carr)   # a short capacity: the lengths say how many rows the caller's outputs need
+        self._check(status)
         self._finish(outs, carr)
         return outs if raw else [self.window_agg_to_numpy(o) for o in outs]
 

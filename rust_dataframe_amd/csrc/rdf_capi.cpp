@@ -34,6 +34,7 @@
 #include "rdf_colstats.h"
 #include "rdf_window.h"
 #include "rdf_window_agg.h"
+#include "rdf_window_range.h"
 #include "rdf_moments.h"
 #include "rdf_group_sorted.h"
 #include "rdf_group_moments.h"
@@ -94,6 +95,7 @@ struct Ctx {
     int64_t utf8_sort_rounds = 0;   // the last sort: refinement rounds its Utf8 criteria took (round 0 included), summed
     int    opt_sort_msd = 1;        // sort keys that vary in more than 32 bits: passes over the top bits, then every bucket sorted in LDS (1, default); 0 = one pass per byte (A/B)
     int    opt_sort_sample = 1;     // doubles: value buckets planned from a sample of the keys (range without outliers, bucket bits from the densest region); 0 = [min, max] and ~500 rows per bucket (round 3, A/B)
+    int    opt_window_range_route = 0;   // rdf_window_range_agg's bounds pass: 0 = auto (a tile whose key window fits LDS searches there, the others search global memory), 1 = the LDS window wherever it fits, 2 = the global search for every tile (A/B, tests)
     int    opt_join_table = 2;      // equi-join on one key column: 2 (default) = probe a table of the distinct build keys: the build side sorted by hash, the table placed by a scan (no atomics); 0 = the bucket index over the build keys sorted by key (A/B; also what every join the table cannot take uses).  Read once per call (rdf_capi_join.inc), written by rdf_set_option only
     int    opt_jit = 1;             // a program shape outside the catalogs: 1 = compile spec_kernel<Prog> for it on a helper thread (the interpreter answers until the kernel is ready; a code object in the cache directory is loaded at once), default; 2 = the call waits for the compiler; 0 = always the interpreter
     int    opt_take_rows = 1;       // take over a frame through interleaved row records: 1 = when the transaction model says so (default), 0 = never, 2 = always (tests, A/B)
@@ -2539,6 +2541,7 @@ rdf_status groupby_sum_fallback(const rdf_array* keys, const rdf_array* values, 
 #include "rdf_capi_groupby_multi.inc"
 #include "rdf_capi_window.inc"
 #include "rdf_capi_window_agg.inc"
+#include "rdf_capi_window_range.inc"
 #include "rdf_capi_group_moments.inc"
 #include "rdf_capi_moments.inc"
 #include "rdf_capi_group_sorted.inc"
@@ -2615,6 +2618,7 @@ rdf_status rdf_set_option(const char* name, int64_t value) {
     else if (strcmp(name, "stream_slab_bytes") == 0) g_ctx.opt_stream_slab = value;
     else if (strcmp(name, "uniques_route") == 0) g_ctx.opt_uniques_route = value == 1 ? 1 : 0;
     else if (strcmp(name, "percentile_route") == 0) g_ctx.opt_percentile_route = value == 1 || value == 2 ? (int)value : 0;
+    else if (strcmp(name, "window_range_route") == 0) g_ctx.opt_window_range_route = value == 1 || value == 2 ? (int)value : 0;
     else if (strcmp(name, "member_route") == 0) g_ctx.opt_member_route = value >= 0 && value <= 2 ? (int)value : 0;
     else if (strcmp(name, "member_slots") == 0) g_ctx.opt_member_slots = value > 0 ? value : 0;
     else if (strcmp(name, "member_table_bits") == 0) g_ctx.opt_member_table_bits = value <= 0 ? kMemberDefaultBits : member_clamp_bits(value);

@@ -65,3 +65,11 @@ struct WaggEmitArgs {
 
 hipError_t launch_wagg_scan(int kind, const WaggScanArgs& a, hipStream_t s);   // three launches; no block waits on another
 hipError_t launch_wagg_emit(const WaggEmitArgs& a, hipStream_t s);
+
+// rdf_window_range_agg: per call, the frame's resolved ends by sorted position, relative to the partition's start
+// (rdf_window_range.hip writes them).  nullptr = that end is UNBOUNDED or CURRENT ROW and comes from n, f, l as before.
+struct WaggRangeBounds {
+    const uint32_t* start[RDF_WINDOW_MAX_CALLS];    // [n] the frame's first position
+    const uint32_t* endx[RDF_WINDOW_MAX_CALLS];     // [n] one past its last position (0: empty at the partition's start)
+};
+hipError_t launch_wagg_emit_range(const WaggEmitArgs& a, const WaggRangeBounds& rb, hipStream_t s);

@@ -275,23 +275,32 @@ template <int K> __global__ __launch_bounds__(kWaggThreads) void wagg_scan_add_k
 }
 
 // One call's answer for the row at sorted position j (k of n in its partition, peers f .. l).  -> the result is valid.
-__device__ __forceinline__ bool wagg_emit_call(const WaggEmitArgs& a, const WaggCallOut& o, int64_t ps, int64_t k, int64_t n, int64_t f, int64_t l, int64_t row) {
-    const bool range = o.unit == RDF_FRAME_RANGE;
+// kBounds: the frame's offset ends are not positions but were resolved from the order key's values into rb's arrays
+// (rdf_window_range.hip): start[j] the first position of the frame, endx[j] one past its last, both inside the partition.
+template <bool kBounds>
+__device__ __forceinline__ bool wagg_emit_call(const WaggEmitArgs& a, const WaggCallOut& o, const uint32_t* rstart, const uint32_t* rendx,
+                                               int64_t ps, int64_t k, int64_t n, int64_t f, int64_t l, int64_t row) {
     int64_t fa, fb;                                     // the frame [fa, fb] in positions of the partition
-    switch (o.start_kind) {
-        case RDF_BOUND_UNBOUNDED_PRECEDING: fa = 0; break;
-        case RDF_BOUND_PRECEDING: fa = k - o.start; break;
-        case RDF_BOUND_CURRENT_ROW: fa = range ? f : k; break;
-        default: fa = k + o.start;
+    if constexpr (kBounds) {
+        fa = rstart ? (int64_t)rstart[ps + k] : o.start_kind == RDF_BOUND_UNBOUNDED_PRECEDING ? 0 : f;
+        fb = rendx ? (int64_t)rendx[ps + k] - 1 : o.end_kind == RDF_BOUND_UNBOUNDED_FOLLOWING ? n - 1 : l;
+    } else {
+        const bool range = o.unit == RDF_FRAME_RANGE;
+        switch (o.start_kind) {
+            case RDF_BOUND_UNBOUNDED_PRECEDING: fa = 0; break;
+            case RDF_BOUND_PRECEDING: fa = k - o.start; break;
+            case RDF_BOUND_CURRENT_ROW: fa = range ? f : k; break;
+            default: fa = k + o.start;
+        }
+        switch (o.end_kind) {
+            case RDF_BOUND_UNBOUNDED_FOLLOWING: fb = n - 1; break;
+            case RDF_BOUND_PRECEDING: fb = k - o.end; break;
+            case RDF_BOUND_CURRENT_ROW: fb = range ? l : k; break;
+            default: fb = k + o.end;
+        }
+        fa = fa < 0 ? 0 : fa;
+        fb = fb > n - 1 ? n - 1 : fb;
     }
-    switch (o.end_kind) {
-        case RDF_BOUND_UNBOUNDED_FOLLOWING: fb = n - 1; break;
-        case RDF_BOUND_PRECEDING: fb = k - o.end; break;
-        case RDF_BOUND_CURRENT_ROW: fb = range ? l : k; break;
-        default: fb = k + o.end;
-    }
-    fa = fa < 0 ? 0 : fa;
-    fb = fb > n - 1 ? n - 1 : fb;
     const bool some = fa <= fb;
     const int64_t ja = (int64_t)ps + fa, jb = (int64_t)ps + fb;   // read only when `some`
     // the frame's packed counts: valid << 32 | NaN, +inf << 32 | -inf (differences of prefixes of one partition:
@@ -361,12 +370,16 @@ __device__ __forceinline__ bool wagg_emit_call(const WaggEmitArgs& a, const Wagg
     return ok;
 }
 
-template <int C> __device__ __forceinline__ void wagg_emit_calls(const WaggEmitArgs& a, int64_t ps, int64_t k, int64_t n, int64_t f, int64_t l, int64_t row,
-                                                                 unsigned int (&nulls)[RDF_WINDOW_MAX_CALLS]) {
+template <bool kBounds, int C>
+__device__ __forceinline__ void wagg_emit_calls(const WaggEmitArgs& a, const WaggRangeBounds* rb, int64_t ps, int64_t k, int64_t n, int64_t f, int64_t l,
+                                                int64_t row, unsigned int (&nulls)[RDF_WINDOW_MAX_CALLS]) {
     if constexpr (C < RDF_WINDOW_MAX_CALLS) {
         if (C >= a.ncalls) return;
-        nulls[C] += wagg_emit_call(a, a.calls[C], ps, k, n, f, l, row) ? 0u : 1u;
-        wagg_emit_calls<C + 1>(a, ps, k, n, f, l, row, nulls);
+        const uint32_t* rstart = nullptr;
+        const uint32_t* rendx = nullptr;
+        if constexpr (kBounds) { rstart = rb->start[C]; rendx = rb->endx[C]; }
+        nulls[C] += wagg_emit_call<kBounds>(a, a.calls[C], rstart, rendx, ps, k, n, f, l, row) ? 0u : 1u;
+        wagg_emit_calls<kBounds, C + 1>(a, rb, ps, k, n, f, l, row, nulls);
     }
 }
 template <int C> __device__ __forceinline__ void wagg_emit_nulls(const WaggEmitArgs& a, const unsigned int (&nulls)[RDF_WINDOW_MAX_CALLS]) {
@@ -380,7 +393,7 @@ template <int C> __device__ __forceinline__ void wagg_emit_nulls(const WaggEmitA
     }
 }
 
-__global__ __launch_bounds__(kWinThreads) void wagg_emit_kernel(const WaggEmitArgs a) {
+template <bool kBounds> __device__ __forceinline__ void wagg_emit_rows(const WaggEmitArgs& a, const WaggRangeBounds* rb) {
     unsigned int nulls[RDF_WINDOW_MAX_CALLS] = {};
     for (int64_t j = (int64_t)blockIdx.x * kWinThreads + threadIdx.x; j < a.n; j += (int64_t)gridDim.x * kWinThreads) {
         const uint64_t inc = (uint64_t)a.scan[j + 1];
@@ -388,10 +401,13 @@ __global__ __launch_bounds__(kWinThreads) void wagg_emit_kernel(const WaggEmitAr
         const uint32_t ps = a.pstart[pid], pe = a.pstart[(int64_t)pid + 1];
         const uint32_t gs = a.gstart[gid], ge = a.gstart[(int64_t)gid + 1];
         const int64_t row = a.perm ? (int64_t)a.perm[j] : j;
-        wagg_emit_calls<0>(a, (int64_t)ps, (int64_t)j - ps, (int64_t)pe - ps, (int64_t)gs - ps, (int64_t)ge - 1 - ps, row, nulls);
+        wagg_emit_calls<kBounds, 0>(a, rb, (int64_t)ps, (int64_t)j - ps, (int64_t)pe - ps, (int64_t)gs - ps, (int64_t)ge - 1 - ps, row, nulls);
     }
     wagg_emit_nulls<0>(a, nulls);
 }
+__global__ __launch_bounds__(kWinThreads) void wagg_emit_kernel(const WaggEmitArgs a) { wagg_emit_rows<false>(a, nullptr); }
+// rdf_window_range_agg's form: frames whose offset ends come from the bounds arrays
+__global__ __launch_bounds__(kWinThreads) void wagg_emit_range_kernel(const WaggEmitArgs a, const WaggRangeBounds rb) { wagg_emit_rows<true>(a, &rb); }
 
 template <int K> hipError_t launch_scan_kind(const WaggScanArgs& a, hipStream_t s) {
     const int64_t nseg = (a.n + kWaggSeg - 1) / kWaggSeg;
@@ -417,5 +433,11 @@ hipError_t launch_wagg_emit(const WaggEmitArgs& a, hipStream_t s) {
     if (a.n <= 0) return hipSuccess;
     const int64_t want = (a.n + kWinThreads - 1) / kWinThreads, lim = (int64_t)eval_grid_limit();
     hipLaunchKernelGGL(wagg_emit_kernel, dim3((unsigned)(want > lim ? lim : want)), dim3(kWinThreads), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t launch_wagg_emit_range(const WaggEmitArgs& a, const WaggRangeBounds& rb, hipStream_t s) {
+    if (a.n <= 0) return hipSuccess;
+    const int64_t want = (a.n + kWinThreads - 1) / kWinThreads, lim = (int64_t)eval_grid_limit();
+    hipLaunchKernelGGL(wagg_emit_range_kernel, dim3((unsigned)(want > lim ? lim : want)), dim3(kWinThreads), 0, s, a, rb);
     return hipGetLastError();
 }
