@@ -850,6 +850,28 @@ class Column {
     }
     static Column utf8_format(const std::vector<ArrayRef>& arr, rdf_text_kind kind, int32_t unit = RDF_TIME_SECOND, const std::string* pattern = nullptr,
                               const std::string& name = "format") {
+        return format_staged(arr, name, "utf8_format", [&](const rdf_array* a, int64_t n, rdf_out* oo, rdf_out* od) {
+            return rdf_utf8_format(a, n, (int32_t)kind, unit, pattern ? (const uint8_t*)pattern->data() : nullptr, pattern ? (int64_t)pattern->size() : 0, oo, od);
+        });
+    }
+    // Float32 / Float64 to and from text, on the device (rdf_utf8_parse_float / rdf_utf8_format_float): correctly rounded
+    // parsing, a row that does not parse is NULL; Java's Double.toString / Float.toString.
+    Column utf8_parse_float(DataType out, bool on_host = false) const {
+        need_text("utf8_parse_float");
+        const TextChunks tc = text_chunks("utf8_parse_float");
+        const std::vector<bool> nullable(tc.txt.size(), true);
+        return text_result(out, tc, nullable, field_.name, on_host, [&](rdf_out* outs) {
+            check(rdf_utf8_parse_float(tc.txt.data(), (int64_t)tc.txt.size(), outs, nullptr));
+        });
+    }
+    Column utf8_format_float() const { return utf8_format_float(data_.chunks(), field_.name); }
+    static Column utf8_format_float(const std::vector<ArrayRef>& arr, const std::string& name = "format") {
+        return format_staged(arr, name, "utf8_format_float", [&](const rdf_array* a, int64_t n, rdf_out* oo, rdf_out* od) { return rdf_utf8_format_float(a, n, oo, od); });
+    }
+  private:
+    // value chunks staged through the host (as text is), then `call` under the sizing rule -> a Utf8 column
+    template <class F>
+    static Column format_staged(const std::vector<ArrayRef>& arr, const std::string& name, const char* what, F call) {
         struct Staged { std::vector<uint8_t> values, valid; };
         std::vector<Staged> keep(arr.size());
         std::vector<rdf_array> a;
@@ -857,7 +879,7 @@ class Column {
         TextChunks shape;
         for (size_t i = 0; i < arr.size(); ++i) {
             const Array& x = *arr[i];
-            if (x.dtype == DataType::Utf8) throw DataFrameError(DataFrameError::ComputeError, "utf8_format: the input is text already");
+            if (x.dtype == DataType::Utf8) throw DataFrameError(DataFrameError::ComputeError, std::string(what) + ": the input is text already");
             Staged& s = keep[i];
             if (x.dtype == DataType::Boolean) s.values = pack_bits(x.bools_to_host());
             else {
@@ -874,25 +896,25 @@ class Column {
             shape.txt.push_back(u);
             nullable.push_back(x.validity != nullptr);
         }
-        return text_build(shape, nullable, name, [&](rdf_out* oo, rdf_out* od) {
-            return rdf_utf8_format(a.data(), (int64_t)a.size(), (int32_t)kind, unit, pattern ? (const uint8_t*)pattern->data() : nullptr,
-                                   pattern ? (int64_t)pattern->size() : 0, oo, od);
-        });
+        return text_build(shape, nullable, name, [&](rdf_out* oo, rdf_out* od) { return call(a.data(), (int64_t)a.size(), oo, od); });
     }
+  public:
     // to_date(s, fmt) / to_timestamp(s, fmt) / unix_timestamp(s, fmt) of a Utf8 column; date_format / from_unix_time of a temporal one
     Column to_date(const std::string& fmt) const { return utf8_parse(RDF_TEXT_DATE, DataType::Int32, RDF_TIME_SECOND, &fmt); }
     Column to_timestamp(rdf_time_unit unit, const std::string& fmt) const { return utf8_parse(RDF_TEXT_TIMESTAMP, DataType::Int64, (int32_t)unit, &fmt); }
     Column unix_timestamp(const std::string& fmt) const { return utf8_parse(RDF_TEXT_TIMESTAMP, DataType::Int64, RDF_TIME_SECOND, &fmt); }
     Column date_format(rdf_time_unit unit, const std::string& fmt) const { return utf8_format(data_.chunks(), RDF_TEXT_TIMESTAMP, (int32_t)unit, &fmt, field_.name); }
     Column from_unix_time(const std::string& fmt) const { return utf8_format(data_.chunks(), RDF_TEXT_TIMESTAMP, RDF_TIME_SECOND, &fmt, field_.name); }
-    // CAST between Utf8 and Boolean / the integer types (either direction)
+    // CAST between Utf8 and Boolean / the integer types / Float32 / Float64 (either direction)
     Column cast_text(DataType to) const {
         if (data_type() == DataType::Utf8) {
-            if (to != DataType::Boolean && !is_integer_type(to)) throw DataFrameError(DataFrameError::ComputeError, "cast: Utf8 casts to Boolean and the integer types");
+            if (is_float(to)) return utf8_parse_float(to);
+            if (to != DataType::Boolean && !is_integer_type(to)) throw DataFrameError(DataFrameError::ComputeError, "cast: Utf8 casts to Boolean, the integer types and the float types");
             return utf8_parse(to == DataType::Boolean ? RDF_TEXT_BOOL : RDF_TEXT_INT, to);
         }
+        if (to == DataType::Utf8 && is_float(data_type())) return utf8_format_float(data_.chunks(), field_.name);
         if (to != DataType::Utf8 || (data_type() != DataType::Boolean && !is_integer_type(data_type())))
-            throw DataFrameError(DataFrameError::ComputeError, "cast: Boolean and the integer types cast to Utf8");
+            throw DataFrameError(DataFrameError::ComputeError, "cast: Boolean, the integer types and the float types cast to Utf8");
         return utf8_format(data_.chunks(), data_type() == DataType::Boolean ? RDF_TEXT_BOOL : RDF_TEXT_INT, RDF_TIME_SECOND, nullptr, field_.name);
     }
     static bool is_integer_type(DataType t) { return (int32_t)t >= RDF_I8 && (int32_t)t <= RDF_U64; }
@@ -3595,7 +3617,7 @@ struct ScalarFunctions {
         return finish(outs, ov);
     }
     static std::vector<ArrayRef> cast(const std::vector<ArrayRef>& arr, DataType to) {
-        // to and from Utf8 (Boolean and the integer types): rdf_utf8_format / rdf_utf8_parse, the text staged through the host
+        // to and from Utf8 (Boolean, the integer types, Float32 / Float64): rdf_utf8_format / rdf_utf8_parse and their _float forms, the text staged through the host
         if (to == DataType::Utf8 || (!arr.empty() && arr[0]->dtype == DataType::Utf8))
             return Column::from_arrays(arr, Field{"cast", arr.empty() ? to : arr[0]->dtype, true}).cast_text(to).data().chunks();
         std::vector<rdf_array> a;

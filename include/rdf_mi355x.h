@@ -834,6 +834,26 @@ rdf_status rdf_utf8_parse(const rdf_utf8_array* chunks, int64_t nchunks, int32_t
 rdf_status rdf_utf8_format(const rdf_array* a, int64_t nchunks, int32_t kind, int32_t unit,
                            const uint8_t* pattern, int64_t pattern_bytes, rdf_out* out_offsets, rdf_out* out_data);
 
+/* Float32 / Float64 columns to and from text (tests/textfloat_ref.py is the executable model, DESIGN.md §30 the account).
+ * Parse: after the trim of the CAST grammars, [+-]? ( digit+ ( '.' digit* )? | '.' digit+ ) ( [eE] [+-]? digit+ )?, or in
+ * either letter case nan (no sign), [+-]? inf, [+-]? infinity; everything else (hex floats, a trailing d / f, '_') is NULL.
+ * The value is the exact decimal rounded once, to nearest and ties to even, into the target type, however many digits the row
+ * has (Float32 straight from the decimal); overflow gives an infinity, underflow a zero that keeps the sign; NaN is the
+ * canonical quiet NaN.  Format: Java's Double.toString / Float.toString as specified since JDK 19 (the shortest decimal that
+ * rounds back, the closest of that length, at least two digits chosen: 4.9E-324; plain for 10^-3 <= |x| < 10^7, else
+ * d.dddE[-]n; NaN, Infinity, -Infinity, 0.0, -0.0); at most 24 bytes a row (Float32: 15).  parse(format(x)) has the bits of x.
+ * Argument checks, memory kinds, capacities, nchunks == 0 and RDF_DEVICE_ERROR are those of rdf_utf8_parse / rdf_utf8_format;
+ * any dtype but RDF_F32 / RDF_F64 is RDF_COMPUTE_ERROR ("... does not support type").
+ * rdf_set_option("textfloat_exact", 1) sends every row through the exact (big-integer) path, for tests and measurements.
+ *
+ * Utf8 -> Float32 / Float64 (the dtype of out[c], one dtype per call): CAST(s AS FLOAT / DOUBLE).  A row that does not
+ * parse is NULL and is counted in failed[c]; NULL rows hold 0; bitmaps / null_count as rdf_utf8_parse writes them. */
+rdf_status rdf_utf8_parse_float(const rdf_utf8_array* chunks, int64_t nchunks, rdf_out* out, int64_t* failed);
+
+/* Float32 / Float64 -> Utf8: CAST(x AS STRING), under the sizing rule of rdf_utf8_trim (a first call without data
+ * buffers reports the bytes per chunk).  NULL in gives NULL out with an empty row. */
+rdf_status rdf_utf8_format_float(const rdf_array* a, int64_t nchunks, rdf_out* out_offsets, rdf_out* out_data);
+
 /* DataFrame::sort (src/dataframe.rs:194-222) whose criteria may be Utf8 columns: arrow's lexsort_to_indices over numeric
  * and StringArray columns alike.  keys[k] is criterion k (key 0 most significant) and sets exactly one of
  *   values  nchunks numeric chunks (one dtype), ordered as by rdf_sort_to_indices, or

@@ -351,6 +351,10 @@ pub mod sys {
                               out: *mut rdf_out, failed: *mut i64) -> i32;
         pub fn rdf_utf8_format(a: *const rdf_array, nchunks: i64, kind: i32, unit: i32, pattern: *const u8, pattern_bytes: i64,
                                out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
+        // CAST between Utf8 and Float32 / Float64 (the dtype of the outputs / inputs): correctly rounded parsing, a row that does not
+        // parse is NULL; Java's Double.toString / Float.toString under rdf_utf8_trim's sizing rule.
+        pub fn rdf_utf8_parse_float(chunks: *const rdf_utf8_array, nchunks: i64, out: *mut rdf_out, failed: *mut i64) -> i32;
+        pub fn rdf_utf8_format_float(a: *const rdf_array, nchunks: i64, out_offsets: *mut rdf_out, out_data: *mut rdf_out) -> i32;
         // row hashes and digests (src/functions/scalar.rs: hash :265, crc32 :205, md5 :338, sha1 :389, sha2 :390): kind 0 = Spark's
         // Murmur3_x86_32 (Int32 out, seed 42 by default), 1 = xxhash64 (Int64 out); digests 0 .. 5 = md5, sha1, sha224, sha256, sha384,
         // sha512 as lowercase hex text under the sizing rule of rdf_utf8_trim; crc32 as Int64

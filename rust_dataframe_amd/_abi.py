@@ -1927,6 +1927,39 @@ class Api:
         call, shape, nullable = self.utf8_format_call(chunks, kind, unit, pattern)
         return self._utf8_run(call, shape, [c.length for c in shape], nullable, as_arrow)
 
+    # ---- Float32 / Float64 to and from text (rdf_utf8_parse_float / rdf_utf8_format_float)
+    def _textfloat_fn(self, name):
+        fn = self._utf8_fn(name)
+        if name == "utf8_parse_float":
+            fn.argtypes = [C.POINTER(rdf_utf8_array), C.c_int64, C.POINTER(rdf_out), C.POINTER(C.c_int64)]
+        else:
+            fn.argtypes = [C.POINTER(rdf_array), C.c_int64, C.POINTER(rdf_out), C.POINTER(rdf_out)]
+        return fn
+
+    def utf8_parse_float(self, chunks: Sequence, dtype=F64, outs=None):
+        """rdf_utf8_parse_float: CAST(s AS FLOAT / DOUBLE), correctly rounded -> (one Float32 / Float64 array per chunk, failed
+        rows per chunk).  A row that does not parse is NULL."""
+        n = len(chunks)
+        carr = (rdf_utf8_array * max(1, n))(*[c.c_struct() for c in chunks])
+        outs, co = self._utf8_pred_outs(int(dtype), chunks, [True] * n, outs)
+        failed = (C.c_int64 * max(1, n))()
+        self._check(self._textfloat_fn("utf8_parse_float")(carr, C.c_int64(n), co, failed))
+        return self._finish(outs, co), [int(failed[i]) for i in range(n)]
+
+    def utf8_format_float_call(self, chunks: Sequence):
+        """-> (call(out_offsets, out_data) -> status, chunks, nullable per chunk) of one rdf_utf8_format_float call;
+        utf8_format_float runs it under the sizing rule, tests call it with buffers of their own."""
+        n = len(chunks)
+        carr = _flat([chunks], n)
+        fn = self._textfloat_fn("utf8_format_float")
+        call = lambda co, cd: fn(carr, C.c_int64(n), co, cd)  # noqa: E731
+        return call, chunks, [(c.validity is not None) if isinstance(c, HostArray) else bool(c.validity_ptr) for c in chunks]
+
+    def utf8_format_float(self, chunks: Sequence, as_arrow=False):
+        """rdf_utf8_format_float: CAST(x AS STRING) of Float32 / Float64 chunks (Java's Double.toString): one Utf8 result per chunk."""
+        call, shape, nullable = self.utf8_format_float_call(chunks)
+        return self._utf8_run(call, shape, [c.length for c in shape], nullable, as_arrow)
+
     # ---- coalesce / case_when over text (rdf_utf8_coalesce / rdf_utf8_case_when)
     def utf8_select_call(self, parts: Sequence, conds=None):
         """-> (call(out_offsets, out_data) -> status, the first column part, nullable per chunk) of one rdf_utf8_coalesce

@@ -44,6 +44,7 @@
 #include "rdf_member.h"
 #include "rdf_select.h"
 #include "rdf_textconv.h"
+#include "rdf_textfloat.h"
 #include "rdf_utf8_pattern.h"
 #include "rdf_utf8_build.h"
 #define RDF_UTF8_REWRITE_NO_CASE   // the compiler of the translate table is all the host side needs
@@ -141,6 +142,7 @@ struct Ctx {
     bool in_stream = false;          // a streamed call is running its per-slab calls on this thread (they are not streamed again)
     bool streaming = false;          // stream_run is active: slabs are in flight on the copy engines (frame_table_upload)
     int  opt_textconv_stage = 1;        // 1 = rdf_utf8_parse stages a tile's bytes in LDS when they fit (A/B: 0 = every lane reads global memory, the fallback form)
+    int  opt_textfloat_exact = 0;       // 1 = rdf_utf8_parse_float sends every number through the resolve kernel's exact path (tests, A/B)
     int  opt_stream_table_kernel = 1;   // 1 = while streaming, a frame's tables reach the device through a kernel instead of the copy engine (A/B: 0)
     char* tab_pin = nullptr; size_t tab_pin_cap = 0, tab_pin_used = 0;   // page-locked ring the tables are staged in for that kernel
     bool   agg_comm_entered = false;  // ... and this call has entered agg_dist_finish's collectives (a rank that fails before them still has to: pipeline_dist)
@@ -2595,6 +2597,7 @@ rdf_status rdf_set_option(const char* name, int64_t value) {
     else if (strcmp(name, "sort_sample") == 0) g_ctx.opt_sort_sample = (int)value;
     else if (strcmp(name, "stream_table_kernel") == 0) g_ctx.opt_stream_table_kernel = value != 0;
     else if (strcmp(name, "textconv_stage") == 0) g_ctx.opt_textconv_stage = value != 0;
+    else if (strcmp(name, "textfloat_exact") == 0) g_ctx.opt_textfloat_exact = value != 0;
     else if (strcmp(name, "join_table") == 0) g_ctx.opt_join_table = value == 0 ? 0 : 2;   // (1 named the retired compare-and-swap table: accepted, the planner decides as under 2)
     else if (strcmp(name, "jit") == 0) g_ctx.opt_jit = (int)value;
     else if (strcmp(name, "gb_skew_plan") == 0) g_ctx.opt_gb_skew_plan = (int)value;

@@ -22,31 +22,11 @@
 #include <algorithm>
 
 #include "rdf_textconv.h"
+#include "rdf_texttile.hip.h"
 
 namespace {
 
-__device__ __forceinline__ bool bit_at(const uint8_t* b, int64_t i) { return (b[i >> 3] >> (i & 7)) & 1; }
-
-// last chunk whose first tile is <= t (empty chunks share the first tile of the next one and are skipped by this rule)
-__device__ int64_t find_tile_chunk(const int64_t* ts, int64_t nch, int64_t t) {
-    int64_t lo = 0, hi = nch;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (ts[mid] <= t) lo = mid + 1; else hi = mid;
-    }
-    return lo - 1;
-}
 __device__ __forceinline__ int first_lane(uint64_t mask) { return __builtin_ctzll(mask); }
-
-// one word of a bitmap whose bit 0 is row r0 (a multiple of 64) of the chunk: the wave's nrows bits
-__device__ __forceinline__ void store_word(uint8_t* bitmap, int64_t r0, int nrows, uint64_t word, int lane) {
-    uint8_t* p = bitmap + (r0 >> 3);
-    if (nrows == 64 && ((uintptr_t)p & 7) == 0) {
-        if (lane == 0) *(uint64_t*)p = word;
-    } else if (lane < ((nrows + 7) >> 3)) {
-        p[lane] = (uint8_t)(word >> (8 * lane));
-    }
-}
 
 constexpr int kPiece = 16, kStep = 64 * kPiece;   // bytes of a row a lane / the wave takes per step
 enum : int { CLS_WS = 0, CLS_ZERO = 1, CLS_DIGIT = 2 };
@@ -78,14 +58,6 @@ __device__ int wave_last_not_ws(const uint8_t* b, int from, int to, int lane) {
         if (hits) return __shfl(at, first_lane(hits));
     }
     return from;
-}
-
-// a row's span, clamped into the bytes the host checked
-__device__ __forceinline__ void row_span(const Utf8Chunk& c, int64_t r, int32_t& o0, int32_t& o1) {
-    o0 = c.offs[r];
-    o1 = c.offs[r + 1];
-    o0 = min(max(o0, c.lo), c.hi);
-    o1 = min(max(o1, o0), c.hi);
 }
 
 // one row that a lane takes whole: [b, e) -> the value's bits

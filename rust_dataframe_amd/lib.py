@@ -19,7 +19,7 @@ EXPORTS = [
     "rdf_version", "rdf_last_error", "rdf_device_count", "rdf_set_device", "rdf_set_stream", "rdf_synchronize",
     "rdf_dev_alloc", "rdf_dev_free", "rdf_copy_h2d", "rdf_copy_d2h", "rdf_host_alloc", "rdf_host_free", "rdf_host_register", "rdf_host_unregister", "rdf_copy_h2d_async", "rdf_copy_fence",
     "rdf_binary", "rdf_unary", "rdf_cast", "rdf_hour", "rdf_sum", "rdf_min", "rdf_max", "rdf_count", "rdf_avg", "rdf_moments", "rdf_comoments", "rdf_moments_merge", "rdf_comoments_merge", "rdf_moments_stat", "rdf_comoments_stat", "rdf_groupby_sorted", "rdf_groupby_moments", "rdf_groupby_percentile", "rdf_groupby_collect", "rdf_list_explode", "rdf_datetime_fields", "rdf_datetime_trunc", "rdf_date_shift", "rdf_date_diff", "rdf_null_test", "rdf_coalesce", "rdf_case_when", "rdf_extremum", "rdf_nanvl", "rdf_utf8_coalesce", "rdf_utf8_case_when",
-    "rdf_predicate", "rdf_filter_count", "rdf_filter", "rdf_filter_columns", "rdf_filter_pipeline", "rdf_take", "rdf_list_contains", "rdf_list_position", "rdf_list_max", "rdf_list_min", "rdf_list_remove", "rdf_list_sort", "rdf_list_distinct", "rdf_list_except", "rdf_list_intersect", "rdf_list_union", "rdf_list_repeat", "rdf_utf8_filter", "rdf_utf8_take", "rdf_utf8_trim", "rdf_utf8_ltrim", "rdf_utf8_rtrim", "rdf_utf8_substring", "rdf_utf8_lower", "rdf_utf8_upper", "rdf_utf8_predicate", "rdf_utf8_compare", "rdf_utf8_measure", "rdf_utf8_concat", "rdf_utf8_pad", "rdf_utf8_repeat", "rdf_utf8_reverse", "rdf_utf8_substring_index", "rdf_utf8_replace", "rdf_utf8_translate", "rdf_utf8_initcap", "rdf_utf8_split", "rdf_utf8_regexp_info", "rdf_utf8_regexp_match", "rdf_utf8_regexp_count", "rdf_utf8_regexp_extract", "rdf_utf8_regexp_replace", "rdf_utf8_regexp_split", "rdf_utf8_parse", "rdf_utf8_format", "rdf_hash_columns", "rdf_utf8_digest", "rdf_utf8_crc32", "rdf_pipeline", "rdf_stream_stats", "rdf_frame_pin", "rdf_frame_release", "rdf_pipeline_frame", "rdf_group_pipeline_frame", "rdf_predicate_frame", "rdf_frame_info", "rdf_frame_column", "rdf_filter_frame", "rdf_take_columns", "rdf_take_frame", "rdf_sort_frame", "rdf_groupby_agg_frame", "rdf_group_pipeline", "rdf_groupby_sum", "rdf_groupby_agg", "rdf_groupby_merge", "rdf_group_exchange_pack", "rdf_group_exchange_unpack", "rdf_row_exchange_pack", "rdf_row_exchange_unpack", "rdf_sort_to_indices", "rdf_lexsort_to_indices", "rdf_hist", "rdf_uniques", "rdf_utf8_uniques", "rdf_utf8_dictionary_encode", "rdf_groupby_agg_keys", "rdf_groupby_multi", "rdf_groupby_multi_capacity", "rdf_equijoin_indices_keys", "rdf_member_mask", "rdf_first_occurrence", "rdf_window", "rdf_window_agg", "rdf_window_range_agg", "rdf_equijoin_indices", "rdf_equijoin_indices_multi",
+    "rdf_predicate", "rdf_filter_count", "rdf_filter", "rdf_filter_columns", "rdf_filter_pipeline", "rdf_take", "rdf_list_contains", "rdf_list_position", "rdf_list_max", "rdf_list_min", "rdf_list_remove", "rdf_list_sort", "rdf_list_distinct", "rdf_list_except", "rdf_list_intersect", "rdf_list_union", "rdf_list_repeat", "rdf_utf8_filter", "rdf_utf8_take", "rdf_utf8_trim", "rdf_utf8_ltrim", "rdf_utf8_rtrim", "rdf_utf8_substring", "rdf_utf8_lower", "rdf_utf8_upper", "rdf_utf8_predicate", "rdf_utf8_compare", "rdf_utf8_measure", "rdf_utf8_concat", "rdf_utf8_pad", "rdf_utf8_repeat", "rdf_utf8_reverse", "rdf_utf8_substring_index", "rdf_utf8_replace", "rdf_utf8_translate", "rdf_utf8_initcap", "rdf_utf8_split", "rdf_utf8_regexp_info", "rdf_utf8_regexp_match", "rdf_utf8_regexp_count", "rdf_utf8_regexp_extract", "rdf_utf8_regexp_replace", "rdf_utf8_regexp_split", "rdf_utf8_parse", "rdf_utf8_format", "rdf_utf8_parse_float", "rdf_utf8_format_float", "rdf_hash_columns", "rdf_utf8_digest", "rdf_utf8_crc32", "rdf_pipeline", "rdf_stream_stats", "rdf_frame_pin", "rdf_frame_release", "rdf_pipeline_frame", "rdf_group_pipeline_frame", "rdf_predicate_frame", "rdf_frame_info", "rdf_frame_column", "rdf_filter_frame", "rdf_take_columns", "rdf_take_frame", "rdf_sort_frame", "rdf_groupby_agg_frame", "rdf_group_pipeline", "rdf_groupby_sum", "rdf_groupby_agg", "rdf_groupby_merge", "rdf_group_exchange_pack", "rdf_group_exchange_unpack", "rdf_row_exchange_pack", "rdf_row_exchange_unpack", "rdf_sort_to_indices", "rdf_lexsort_to_indices", "rdf_hist", "rdf_uniques", "rdf_utf8_uniques", "rdf_utf8_dictionary_encode", "rdf_groupby_agg_keys", "rdf_groupby_multi", "rdf_groupby_multi_capacity", "rdf_equijoin_indices_keys", "rdf_member_mask", "rdf_first_occurrence", "rdf_window", "rdf_window_agg", "rdf_window_range_agg", "rdf_equijoin_indices", "rdf_equijoin_indices_multi",
     "rdf_comm_unique_id", "rdf_comm_init_rank", "rdf_comm_init_all", "rdf_comm_destroy", "rdf_comm_info", "rdf_comm_barrier", "rdf_comm_allgather",
     "rdf_agg_combine", "rdf_pipeline_dist", "rdf_pipeline_frame_dist", "rdf_group_combine", "rdf_groupby_agg_dist", "rdf_groupby_agg_frame_dist",
     "rdf_fill_uniform_f64", "rdf_fill_uniform_i64", "rdf_fill_validity",
