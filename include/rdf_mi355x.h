@@ -1797,7 +1797,26 @@ int32_t    rdf_spec_catalog_size(void);
  * RDF_JIT_CACHE=off disables it), and how many kernels were compiled / read from the cache / failed / are being compiled.
  * Without a compiler such programs run on the interpreter (same results; 1.4-2.5 x slower on its lean kernel's class, 3-20 x otherwise) unless the cache holds them. */
 const char* rdf_jit_status(void);
-/* Name of the dominant kernel the last rdf_pipeline-family call of this thread launched. */
+/* Name of the dominant kernel the last rdf_pipeline-family call of this thread launched.
+ *
+ * After rdf_sort_to_indices / rdf_sort_frame over numeric criteria the name is "os_scatter_kernel", or
+ * "os_scatter_kernel+os_local_kernel" when at least one column was finished by the LDS bucket sort, followed by a route note
+ * " (sort routes: <entry>; <entry>; ...)" with one entry per numeric column in the order the columns were SORTED (the last
+ * criterion first).  An entry is one of
+ *   none                                                            nothing varies and no row is NULL: no pass
+ *   bytes passes=P nulls=N                                          P passes over the low bytes of (key - min)
+ *   top+lds B=b top=t map=M nulls=N bucket=L lds=C                  t stable passes over the top b bits, then every bucket
+ *                                                                   sorted in LDS; C = the largest LDS class launched (rows:
+ *                                                                   the power of two >= L, at least 256)
+ *   top+bytes B=b top=t map=M bucket=L then passes=P nulls=N        the top passes ran, a bucket of L > 4096 rows turned up,
+ *                                                                   the byte passes sorted the column (the late fall-back)
+ *   crowded+bytes B=b top=t map=M digit=D then passes=P nulls=N     D rows share their top digit, more than the buckets
+ *                                                                   under it could hold: byte passes before any top pass
+ *                                                                   (the early fall-back)
+ * M names where the top bits come from: bits (the key's own bits), linear (Float64 value buckets over [min, max]:
+ * "sort_sample" 0), flat or segments (Float64 value buckets planned from a sample of the keys: one linear map between the
+ * tails, or shares per segment).  N is 1 when a NULLs-last pass ran.  L is the largest bucket the boundary search found.
+ * The words before the note keep their meaning: "os_local_kernel" appears iff some entry is top+lds. */
 const char* rdf_last_kernel(void);
 
 /* Average duration (ms) and launch count of the dominant kernel launched by this thread since the

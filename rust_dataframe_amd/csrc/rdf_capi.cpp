@@ -28,6 +28,7 @@
 #include "rdf_stage_copy.h"
 #include "rdf_stream_plan.h"
 #include "rdf_join_place.h"
+#include "rdf_sort_plan.h"
 #include "rdf_program_plan.h"
 #include "rdf_groupby_multi_plan.h"
 #include "rdf_utf8.h"
@@ -94,6 +95,7 @@ struct Ctx {
     int    opt_gb_debug = 0;        // 3 = rdf_groupby_sum takes the first-generation fallback (where its range holds) with the combining scatter forced (tests); nothing else is stored
     bool   sort_used_local = false; // the last sort finished at least one column with os_local_kernel
     int64_t utf8_sort_rounds = 0;   // the last sort: refinement rounds its Utf8 criteria took (round 0 included), summed
+    std::string* sort_note = nullptr;   // where os_column_passes writes the route of a numeric sort column (set by sort_core around its own calls only)
     int    opt_sort_msd = 1;        // sort keys that vary in more than 32 bits: passes over the top bits, then every bucket sorted in LDS (1, default); 0 = one pass per byte (A/B)
     int    opt_sort_sample = 1;     // doubles: value buckets planned from a sample of the keys (range without outliers, bucket bits from the densest region); 0 = [min, max] and ~500 rows per bucket (round 3, A/B)
     int    opt_window_range_route = 0;   // rdf_window_range_agg's bounds pass: 0 = auto (a tile whose key window fits LDS searches there, the others search global memory), 1 = the LDS window wherever it fits, 2 = the global search for every tile (A/B, tests)
@@ -1995,11 +1997,24 @@ rdf_status os_scratch_alloc(int64_t n, OsScratch& o) {
     o.seq = 0;
     return RDF_OK;
 }
+static_assert(kOsPlanLocalMax == kOsLocalMax, "rdf_sort_plan.h plans for the LDS finish of rdf_device.h");
+// One entry of the sort's route note (rdf_last_kernel, include/rdf_mi355x.h), while sort_core collects one (g_ctx.sort_note).
+__attribute__((format(printf, 1, 2))) void os_note(const char* fmt, ...) {
+    std::string* to = g_ctx.sort_note;
+    if (!to) return;
+    char buf[192];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    if (!to->empty()) *to += "; ";
+    *to += buf;
+}
 rdf_status os_column_passes(OsScratch& o, uint64_t* const keys[2], uint32_t* const idxb[2], const uint8_t* nullflags, int64_t n, uint64_t bias, int need,
                             bool null_pass, int& kcur, int& icur, const uint32_t*& idx_cur, uint64_t range = ~0ull /* max key - bias, when known */,
                             int f64_keys = 0 /* 1: the keys are the bits of doubles (2: stored inverted, descending); -1: of 4-byte floats */) {
     Ctx& ctx = g_ctx;
-    if (need == 0 && !null_pass) return RDF_OK;
+    if (need == 0 && !null_pass) { os_note("none"); return RDF_OK; }
     OsBucket fb;
     memset(&fb, 0, sizeof fb);
     // one digit pass over the first `rows` rows: digit = ((key - bias) >> shift) & mask — of the value bucket when fb.bits —, or (np) the row's NULL flag
@@ -2032,23 +2047,15 @@ rdf_status os_column_passes(OsScratch& o, uint64_t* const keys[2], uint32_t* con
     // pairs instead of 4 .. 8 passes.  NULL keys (they all carry one key value: one huge bucket) are moved behind the others
     // FIRST by the stable NULLs-last pass and stay there, in order, while the rows in front of them are sorted.  A bucket above
     // kOsLocalMax rows (keys crowded on few top-bit patterns) sends the column through the byte passes below, which sort any order.
-    int sig = 8 * need;                       // bits of (key - bias) that vary
-    if (range != ~0ull) { sig = 0; for (uint64_t r = range; r; r >>= 1) ++sig; sig = std::min(sig, 8 * need); }
+    const int sig = range != ~0ull ? os_sig_bits(range, need) : 8 * need;   // bits of (key - bias) that vary
+    const char* map_name = "bits";            // the route note's map: bits | linear | flat | segments
     // Top bits: as few passes of <= 8 bits as leave buckets the LDS finish takes, then as many bits as those passes carry for
     // free — integer keys: 2 passes (16 bits) up to ~1.2e8 rows (1e8 rows: 1526 rows per bucket on average, sorted as 2048),
     // a third pass beyond with ~500 rows per bucket; value buckets of doubles: ~500 per bucket always (a bell-shaped column's
     // densest bucket holds 4-5 x the average; measured at 5e7 rows: 800 per bucket sorts uniform doubles in 3.20 instead of
     // 3.35 ms but sends normally distributed ones to the byte passes, 5.5 instead of 4.3 ms)
-    const int per_bucket = f64_keys > 0 ? 512 : 1800;
-    int B = 12;
+    int B = os_bits_by_rows(n, f64_keys);     // rdf_sort_plan.h
     bool sampled = false;                     // the bucket bits of a column of doubles were planned from a sample
-    while ((n >> B) > 512 && B < 24) ++B;
-    if (f64_keys <= 0) {
-        int np = 1;
-        while (np < 3 && (n >> (8 * np)) > per_bucket) ++np;
-        B = std::max(12, std::min(B, 8 * np));
-        if ((n >> B) > per_bucket) B = 24;      // (no pass count fits: the condition below fails)
-    }
     if (f64_keys > 0 && range != ~0ull) {
         // doubles: sign and exponent crowd the key bits' top patterns, so the buckets are cut in VALUE space (OsBucket)
         auto value_of = [&](uint64_t stored) { const uint64_t ord = f64_keys == 2 ? ~stored : stored; const uint64_t b = (ord >> 63) ? (ord ^ 0x8000000000000000ull) : ~ord; double x; memcpy(&x, &b, 8); return x; };
@@ -2086,6 +2093,7 @@ rdf_status os_column_passes(OsScratch& o, uint64_t* const keys[2], uint32_t* con
             if (sampled) {
                 fb = plan.fb;
                 B = fb.bits;
+                map_name = fb.flat ? "flat" : "segments";
                 if (!fb.flat) {
                     void* pseg = nullptr;
                     RDF_TRY(arena_alloc(sizeof(OsSeg) * plan.segs.size(), &pseg));
@@ -2100,15 +2108,17 @@ rdf_status os_column_passes(OsScratch& o, uint64_t* const keys[2], uint32_t* con
                              sampled ? (fb.flat ? "evenly spread: one linear map between the tails" : "buckets by segment shares") : "byte passes", plan.bits);
         } else {
             const double scale = (double)((int64_t)1 << B) / (hi - lo);
-            if (std::isfinite(lo) && std::isfinite(hi) && hi > lo && std::isfinite(scale)) { fb.lo = lo; fb.scale = scale; fb.bits = B; fb.flip = f64_keys == 2; }
+            if (std::isfinite(lo) && std::isfinite(hi) && hi > lo && std::isfinite(scale)) { fb.lo = lo; fb.scale = scale; fb.bits = B; fb.flip = f64_keys == 2; map_name = "linear"; }
         }
     }
     // (f64_keys < 0: the bit patterns of 4-byte floats — sign and exponent crowd their top digit like a double's, the top-digit check below
     // would send them to the byte passes after a histogram and a host round trip, 0.17 ms per 5e7 keys; four byte passes are what a
     // value-bucket map would have to beat, and it would not: DESIGN.md 7.3)
-    if (ctx.opt_sort_msd && f64_keys >= 0 && n >= 65536 && n < ((int64_t)1 << 32) && ((n >> B) <= per_bucket || (sampled && fb.bits)) && (sig + 7) / 8 >= (B + 7) / 8 + 2 && (fb.bits || sig - B <= 52)) {
-        const int R = fb.bits ? 0 : sig - B;
-        const int npass = (B + 7) / 8;
+    const OsTopPlan tp = os_top_plan(n, sig, need, f64_keys, fb.bits, sampled, ctx.opt_sort_msd != 0);   // rdf_sort_plan.h
+    char fell[96] = "";                       // the route note of top passes that ended in the byte passes
+    if (tp.eligible) {
+        const int R = tp.R;
+        const int npass = tp.npass;
         const int nbuckets = 1 << B;
         int launched = 0;
         int64_t nv = n;                       // rows in front of the NULL keys
@@ -2130,15 +2140,10 @@ rdf_status os_column_passes(OsScratch& o, uint64_t* const keys[2], uint32_t* con
         }
         if (nv > 0) {
             ha.keys = keys[kcur]; ha.nullflags = nullptr; ha.n = nv; ha.npass = npass;
-            int sh = R;
-            for (int p = 0; p < npass; ++p) {
-                const int w = p == 0 ? B - 8 * (npass - 1) : 8;
-                ha.shift[p] = sh; ha.mask[p] = (1 << w) - 1;
-                sh += w;
-            }
+            for (int p = 0; p < npass; ++p) { ha.shift[p] = tp.shift[p]; ha.mask[p] = tp.mask[p]; }
             HIP_TRY(launch_os_hist(ha, ctx.stream));
             static const bool dbg = getenv("RDF_DEBUG_SORT") != nullptr;
-            if (!(sampled && fb.bits)) {   // the top digit's counts tell crowded keys (floats of one sign and a few exponents, ...) before any pass is spent on
+            if (tp.check_top) {   // the top digit's counts tell crowded keys (floats of one sign and a few exponents, ...) before any pass is spent on
                 // them: a top-digit value held by more rows than its share of the buckets could take at kOsLocalMax rows each
                 // (a map planned from a sample of the keys has answered that already: no host round trip for it; a plan that
                 // misjudged the column is caught by the largest bucket below, two passes later)
@@ -2146,10 +2151,11 @@ rdf_status os_column_passes(OsScratch& o, uint64_t* const keys[2], uint32_t* con
                 HIP_TRY(hipMemcpyAsync(top, o.hist + (npass - 1) * 256, 256 * 8, hipMemcpyDeviceToHost, ctx.stream));
                 HIP_TRY(hipStreamSynchronize(ctx.stream));
                 top[256] = nv;
-                const int wtop = npass == 1 ? B : 8;
+                const int wtop = tp.wtop;
                 int64_t most = 0;
                 for (int i = 0; i < (1 << wtop); ++i) most = std::max(most, top[i + 1 == (1 << wtop) ? 256 : i + 1] - top[i]);
-                if (most > ((int64_t)kOsLocalMax << (B - wtop))) {
+                if (most > tp.top_limit) {
+                    snprintf(fell, sizeof fell, "crowded+bytes B=%d top=%d map=%s digit=%lld ", B, npass, map_name, (long long)most);
                     if (dbg) fprintf(stderr, "[rdf] sort: %lld of %lld rows share their top %d bits -> byte passes\n", (long long)most, (long long)nv, wtop);
                     goto byte_passes;
                 }
@@ -2174,6 +2180,7 @@ rdf_status os_column_passes(OsScratch& o, uint64_t* const keys[2], uint32_t* con
                 while (la.lds_items < (int)maxlen) la.lds_items <<= 1;
                 HIP_TRY(launch_os_local(la, ctx.stream));
                 ctx.sort_used_local = true;
+                os_note("top+lds B=%d top=%d map=%s nulls=%d bucket=%u lds=%d", B, npass, map_name, null_pass ? 1 : 0, maxlen, la.lds_items);
                 kcur ^= 1; icur ^= 1; idx_cur = idxb[icur];
                 if (nv < n) {   // the NULL rows follow the sorted ones into the buffers that now hold the order
                     if (ks != kcur) HIP_TRY(hipMemcpyAsync(keys[kcur] + nv, keys[ks] + nv, (size_t)(n - nv) * 8, hipMemcpyDeviceToDevice, ctx.stream));
@@ -2181,8 +2188,18 @@ rdf_status os_column_passes(OsScratch& o, uint64_t* const keys[2], uint32_t* con
                 }
                 return RDF_OK;
             }
-            // (the byte passes below start from whatever order the rows are in now, NULLs-last pass included)
-        } else return RDF_OK;                 // every key is NULL: the NULLs-last pass was the whole sort
+            // The byte passes below start from whatever order the rows are in now, NULLs-last pass included — over all n rows,
+            // so the NULL tail [nv, n) must lie in the buffers that are current NOW.  The NULLs-last pass left it in (ks, is);
+            // every top pass since flipped both buffers and wrote the first nv rows only.  An even pass count (2: every integer
+            // column below 1.2e8 rows) ends in (ks, is) again; an odd one (3: a value map of 17..24 bits, 1: none today) ends in
+            // the other pair, whose tail is the order before this column or arena memory nobody wrote — row numbers the
+            // NULLs-last pass would index the NULL flags with.  Same copy as after the LDS finish above.
+            if (nv < n) {
+                if (ks != kcur) HIP_TRY(hipMemcpyAsync(keys[kcur] + nv, keys[ks] + nv, (size_t)(n - nv) * 8, hipMemcpyDeviceToDevice, ctx.stream));
+                if (is != icur) HIP_TRY(hipMemcpyAsync(idxb[icur] + nv, idxb[is] + nv, (size_t)(n - nv) * 4, hipMemcpyDeviceToDevice, ctx.stream));
+            }
+            snprintf(fell, sizeof fell, "top+bytes B=%d top=%d map=%s bucket=%u ", B, npass, map_name, maxlen);
+        } else { os_note("bytes passes=0 nulls=1"); return RDF_OK; }   // every key is NULL: the NULLs-last pass was the whole sort
     }
 byte_passes:
     memset(&fb, 0, sizeof fb);                // (a bucket map planned above is not used from here on: the passes take plain bytes)
@@ -2194,6 +2211,7 @@ byte_passes:
     int launched = 0;
     for (int p = 0; p < need; ++p) RDF_TRY(one_pass(p, 8 * p, 255, false, launched, n));
     if (null_pass) RDF_TRY(one_pass(8, 0, 255, true, launched, n));
+    os_note("%s%s passes=%d nulls=%d", fell, fell[0] ? "then" : "bytes", need, null_pass ? 1 : 0);
     return RDF_OK;
 }
 
@@ -2231,6 +2249,8 @@ rdf_status sort_core(const DevChunkCol* d_chunks, const int64_t* d_row_start, in
     bool any_utf8 = false;
     for (int k = 0; utf8 && k < ncols; ++k) any_utf8 |= utf8[k].d_chunks != nullptr;
     RDF_TRY(os_scratch_alloc(n, os));
+    std::string routes;                     // one entry per numeric column, in the order they are sorted (os_note)
+    struct NoteScope { Ctx& c; ~NoteScope() { c.sort_note = nullptr; } } note_scope{ctx};
     KernelTimer kt;
     for (int k = ncols - 1; k >= 0; --k) {  // LSD over the sort columns: least significant criterion first
         if (utf8 && utf8[k].d_chunks) {
@@ -2260,10 +2280,13 @@ rdf_status sort_core(const DevChunkCol* d_chunks, const int64_t* d_row_start, in
         uint64_t kmax = 0;
         RDF_TRY(sort_key_range(d_stats, pin_off, &bias, &need, &kmax));
         if (k == 0 && idx_cur == nullptr && need == 0 && !has_nulls) need = 1;   // all keys equal: one pass still writes the identity order
+        ctx.sort_note = &routes;
         RDF_TRY(os_column_passes(os, keys, idxb, (const uint8_t*)pnf, n, bias, std::min(need, dtype_size(dt)), has_nulls, kcur, icur, idx_cur, kmax >= bias ? kmax - bias : ~0ull, dt == RDF_F64 ? (ka.descending ? 2 : 1) : dt == RDF_F32 ? -1 : 0));
+        ctx.sort_note = nullptr;
     }
     kt.stop();
     ctx.last_kernel = ctx.sort_used_local ? "os_scatter_kernel+os_local_kernel" : "os_scatter_kernel";
+    if (!routes.empty()) ctx.last_kernel += " (sort routes: " + routes + ")";
     if (any_utf8) ctx.last_kernel = "us_keys_kernel+os_scatter_kernel (Utf8 rounds: " + std::to_string(ctx.utf8_sort_rounds) + ")";
     *idx_out = idx_cur;
     return RDF_OK;
